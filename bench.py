@@ -6,8 +6,9 @@ path over the scene already resident in HBM: camera upload, (tile ordering,) tra
 for N > 1 -- the RCCL gather of the row strips to rank 0 plus the de-interleave. Frames are
 streamed the way a recording loop submits them: 4 traces in flight (8 from N = 4), a
 frame's gather running under the next frames' traces; every frame issued in the timed region is
-complete, gathered and assembled before the clock stops; the K-step region is repeated until the
-regions add up to `--min-seconds` and the median region is reported (min / max beside it).
+complete, gathered and assembled before the clock stops. The timed region is exactly `--steps` steps and
+`ms_per_step` is its duration over K; `--min-seconds S` repeats the region until the regions add up to S
+seconds and reports the median region (min / max beside it).
 `--no-pipeline` traces one frame at a time; the `single_frame` object reports one frame alone
 (warm / cold / moving camera). The finished RGBA8 frames stay in HBM (the PCIe-inclusive rate is
 reported separately as `fps_with_readback`).
@@ -27,7 +28,10 @@ rust/all-is-cubes-hip/examples/capture.rs: tests/golden/README.md) with its reco
 
 Launch: `python bench.py --gpus 1 --steps K --warmup W`, or for N > 1
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line. `--dump-outputs DIR` writes the frame the last timed step delivered to DIR as .npy files
+(`frame_rgba`: float32, rows x columns x RGBA8 values; a frame above 32 MB as float32 is stored as a fixed, seeded sample of its
+pixels, `frame_rgba_sample` with their row-major indices in `frame_rgba_sample_index`), so that two builds can be compared output
+for output: with the same arguments the inputs are the same on every run.
 """
 from __future__ import annotations
 
@@ -38,11 +42,6 @@ import os
 import sys
 import time
 from pathlib import Path
-
-# HIP deals streams onto hardware queues in creation order, 4 by default; with four frame streams,
-# an upload stream, torch's and RCCL's own, two frame slots could end up sharing a queue and
-# serialise their kernels. Must be set before the runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = Path(__file__).resolve().parent
 if str(ROOT) not in sys.path:
@@ -139,6 +138,22 @@ def build_workload(name: str):
     return space, size, eye, target, view_distance, label
 
 
+def launch_shape(world, streamed, in_flight=0, frames_per_launch=0, frames_per_gather=0):
+    """(frames per launch, frames in flight, render slots in use, frames per gather, group slots of the gather ring) for `world` ranks; 0 = default."""
+    # traces in flight (AIC_MAX_IN_FLIGHT = 32): a rank's share of a frame shrinks with N while a ray's latency does not -- the default keeps about four
+    # frames' worth of rays on each device (profiles/r05_rank_share.txt)
+    per_launch = (frames_per_launch if frames_per_launch in (1, 2, 4, 8) else (1 if world < 4 else 8)) if streamed else 1  # frames traced by one launch (aic_render_submit_batch)
+    # (with eight shares per launch: two launches in flight at N = 4, four from N = 8 -- what the share's time stops falling at on one GPU, profiles/r06_rank_share.txt)
+    depth = max(1, min(32, in_flight if in_flight > 0 else (4 if world < 4 else ((8 if world < 8 else 16) if per_launch == 1 else (16 if world < 8 else 32)))))
+    launches = max(2, depth // per_launch) if per_launch > 1 else depth  # render slots in use (a launch occupies one)
+    if per_launch > 1:
+        depth = launches * per_launch
+    # (the frames of one launch are done together: they travel in one collective -- no frame waits for another that is not done anyway)
+    per_gather = max(1, min(depth, frames_per_gather if frames_per_gather > 0 else per_launch)) if streamed else 1
+    ring = ((depth + per_gather - 1) // per_gather + (1 if per_gather == 1 else 2)) if streamed else 1  # group slots: the groups being traced, one being gathered
+    return per_launch, depth, launches, per_gather, ring
+
+
 REPLAY: dict = {}  # --workload replay:<file>: the recorded camera matrix, exposure and options
 
 
@@ -177,7 +192,10 @@ def main() -> int:
     ap.add_argument("--light-budget", type=int, default=2048, help="relight: cube updates of the light updater per frame (one launch)")
     ap.add_argument("--blocking-light", action="store_true", help="relight: the blocking aic_evaluate_light per frame (rounds 2-5) instead of aic_evaluate_light_submit / _wait")
     ap.add_argument("--no-secondary", action="store_true", help="atrium (the default line): skip the short s256 leg reported as `secondary`")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="repeat the K-step timed region until the regions add up to this much time")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step timed region until the regions add up to this much time (default: one region of exactly --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step delivered to DIR as .npy (float32; a seeded pixel sample of a frame above 32 MB)")
     args = ap.parse_args()
     default_transparency = 0 if args.workload == "light-bench" else 1
     if args.transparency is None:
@@ -294,17 +312,7 @@ def main() -> int:
     # frame i's last rays finish) and, for N > 1, frame i-2's RCCL gather running under them.
     # --no-pipeline: one frame at a time, gathered before the next is traced.
     streamed = not args.no_pipeline
-    # traces in flight (AIC_MAX_IN_FLIGHT = 32): a rank's share of a frame shrinks with N while a ray's latency does not -- the default keeps about four
-    # frames' worth of rays on each device (profiles/r05_rank_share.txt)
-    per_launch = (args.frames_per_launch if args.frames_per_launch in (1, 2, 4, 8) else (1 if world < 4 else 8)) if streamed else 1  # frames traced by one launch (aic_render_submit_batch)
-    # (with eight shares per launch: two launches in flight at N = 4, four from N = 8 -- what the share's time stops falling at on one GPU, profiles/r06_rank_share.txt)
-    depth = max(1, min(32, args.in_flight if args.in_flight > 0 else (4 if world < 4 else ((8 if world < 8 else 16) if per_launch == 1 else (16 if world < 8 else 32)))))
-    launches = max(2, depth // per_launch) if per_launch > 1 else depth  # render slots in use (a launch occupies one)
-    if per_launch > 1:
-        depth = launches * per_launch
-    # (the frames of one launch are done together: they travel in one collective -- no frame waits for another that is not done anyway)
-    per_gather = max(1, min(depth, args.frames_per_gather if args.frames_per_gather > 0 else per_launch)) if streamed else 1
-    ring = ((depth + per_gather - 1) // per_gather + (1 if per_gather == 1 else 2)) if streamed else 1  # group slots: the groups being traced, one being gathered
+    per_launch, depth, launches, per_gather, ring = launch_shape(world, streamed, args.in_flight, args.frames_per_launch, args.frames_per_gather)
     pipe = D.StripGatherPipeline(h, w, strip, "cpu" if one_gpu_test else dev, depth=ring,
                                  wait_event=None if one_gpu_test else renderer.wait_event, frames=per_gather) if exchange else None
     n_local = depth if streamed else 1
@@ -442,9 +450,9 @@ def main() -> int:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # The region is a few tens of milliseconds at the default K, so it is repeated until the regions add up to
-    # --min-seconds of GPU time (every rank runs the same count: the first region's time is agreed on first). `value`
-    # and `ms_per_step` are those of the MEDIAN region; min / max are reported beside them.
+    # One region of exactly --steps steps; with --min-seconds it is repeated until the regions add up to that much
+    # time (every rank runs the same count: the first region's time is agreed on first). `value` and `ms_per_step`
+    # are those of the MEDIAN region; min / max are reported beside them.
     regions = [timed_region()]
     n_regions = max(1, min(5000, int(np.ceil(args.min_seconds / max(regions[0], 1e-6)))))  # (capped at 200 until round 4: a 10 ms region then summed to 2.1 s, not --min-seconds)
     region_kernel_ms = [float(np.mean(kernel_ms)) if kernel_ms else 0.0]
@@ -454,6 +462,11 @@ def main() -> int:
     order = int(np.argsort(regions)[len(regions) // 2])
     elapsed = regions[order]
     mean_kernel_ms = region_kernel_ms[order]
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed step, before the untimed extras below reuse the buffers: the assembled frame on rank 0 when the strips
+        # travel through the exchange, the rank's own (whole, at N = 1) frame otherwise
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, (frame_buf if exchange else render_target(frame_no[0] - 1)[:local_rows]).cpu().numpy())
 
     # --- untimed extras: algorithmic-byte counters, read-back rate ------------------------------
     verified = None
@@ -750,6 +763,24 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_FULL_BYTES = 32 << 20  # a frame up to this size as float32 is written whole; a larger one as a sample of this many pixels' bytes
+DUMP_SEED = 20260101
+
+
+def dump_outputs(out_dir, img) -> None:
+    """`img`: the (rows, columns, 4) uint8 frame a caller of the timed path receives. Written as float32 .npy files: whole when it fits
+    DUMP_FULL_BYTES, otherwise a fixed sample of pixels chosen by DUMP_SEED (the same pixels for the same frame size)."""
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = img.shape[:2]
+    if h * w * 4 * 4 <= DUMP_FULL_BYTES:
+        np.save(os.path.join(out_dir, "frame_rgba.npy"), img.astype(np.float32))
+        return
+    n = DUMP_FULL_BYTES // (4 * 4 + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_rgba_sample.npy"), img.reshape(h * w, 4)[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_rgba_sample_index.npy"), idx.astype(np.float64))
 
 
 class SceneLoop:

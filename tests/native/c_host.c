@@ -33,7 +33,7 @@ static void check(aic_ctx *ctx, int rc, const char *what) {
 }
 
 int main(int argc, char **argv) {
-    /* libaic_hip.so's load-time default for the HIP runtime's hardware queues is in place before main() in a host that links it */
+    /* loading libaic_hip.so leaves the HIP runtime's hardware-queue setting as the host's environment gave it */
     const char *hwq = getenv("GPU_MAX_HW_QUEUES");
     printf("GPU_MAX_HW_QUEUES=%s\n", hwq ? hwq : "(unset)");
     if (aic_abi_version() != AIC_ABI_VERSION) {

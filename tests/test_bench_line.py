@@ -127,3 +127,52 @@ def test_bench_defaults_are_one_gpu_and_short():
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     src = open(spec.origin).read()
     assert '"--gpus", type=int, default=1' in src.replace("'", '"')
+
+
+def test_steps_set_the_timed_region_and_outputs_can_be_dumped():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--dump-outputs" in out.stdout
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    # one timed region of exactly --steps steps unless a repetition is asked for
+    assert '"--min-seconds", type=float, default=0.0' in src
+
+
+def test_dump_outputs_is_whole_or_a_fixed_sample_under_the_cap(tmp_path):
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod_d", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    rng = np.random.default_rng(0)
+    small = rng.integers(0, 256, (1080, 1920, 4), dtype=np.uint8)
+    mod.dump_outputs(str(tmp_path / "small"), small)
+    got = np.load(tmp_path / "small" / "frame_rgba.npy")
+    assert got.dtype == np.float32 and (got == small).all()
+    big = rng.integers(0, 256, (2160, 3840, 4), dtype=np.uint8)
+    for d in ("big1", "big2"):
+        mod.dump_outputs(str(tmp_path / d), big)
+    total = sum(f.stat().st_size for f in (tmp_path / "big1").iterdir())
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "big1" / "frame_rgba_sample_index.npy")
+    val = np.load(tmp_path / "big1" / "frame_rgba_sample.npy")
+    assert idx.dtype == np.float64 and val.dtype == np.float32 and len(idx) == len(val) == len(np.unique(idx))
+    assert (val == big.reshape(-1, 4)[idx.astype(np.int64)]).all()
+    assert (idx == np.load(tmp_path / "big2" / "frame_rgba_sample_index.npy")).all()
+
+
+def test_launch_shape_defaults():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod_s", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    # (frames per launch, frames in flight, launches in flight, frames per gather, ring slots)
+    assert mod.launch_shape(1, True) == (1, 4, 4, 1, 5)
+    assert mod.launch_shape(2, True) == (1, 4, 4, 1, 5)
+    assert mod.launch_shape(4, True) == (8, 16, 2, 8, 4)
+    # N >= 8: a rank's shares of eight frames per launch, four launches (32 frames) in flight -- what the four-rank GPU test is launched with
+    assert mod.launch_shape(8, True) == (8, 32, 4, 8, 6)
+    assert mod.launch_shape(8, True) == mod.launch_shape(4, True, in_flight=32, frames_per_launch=8)
+    assert mod.launch_shape(8, False) == (1, 16, 16, 1, 1)

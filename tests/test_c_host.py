@@ -26,7 +26,7 @@ def build_c_host(tmp_path) -> Path:
 
 
 def clean_env():
-    return {k: v for k, v in os.environ.items() if k not in ("GPU_MAX_HW_QUEUES", "AIC_KEEP_HW_QUEUES")}
+    return {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
 
 
 def write_scene(path: Path, flat_space, options: abi.Options, frame: abi.FrameDesc, up_xyz, up_block, up_light) -> None:
@@ -60,8 +60,8 @@ def test_c_host_compiles_as_c99_and_is_refused_loudly_without_a_device(tmp_path)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=clean_env())
     assert out.returncode == 2, (out.returncode, out.stdout, out.stderr)
     assert "AIC_ERR_NO_DEVICE" in out.stdout
-    # the library's load-time default is in place before main() of a host that links it
-    assert out.stdout.splitlines()[0] == "GPU_MAX_HW_QUEUES=8"
+    # a host that links the library finds its environment as it was started: the library sets nothing
+    assert out.stdout.splitlines()[0] == "GPU_MAX_HW_QUEUES=(unset)"
 
 
 @pytest.mark.gpu
@@ -89,7 +89,7 @@ def test_c_host_draws_what_ctypes_and_the_oracle_draw(tmp_path):
     result = tmp_path / "frames.bin"
     out = subprocess.run([str(exe), str(scene), str(result)], capture_output=True, text=True, timeout=300, env=clean_env())
     assert out.returncode == 0, (out.stdout, out.stderr)
-    assert out.stdout.splitlines()[0] == "GPU_MAX_HW_QUEUES=8"
+    assert out.stdout.splitlines()[0] == "GPU_MAX_HW_QUEUES=(unset)"
     raw = result.read_bytes()
     fsz = w * h * 4 + ctypes.sizeof(abi.FrameInfo)
     assert len(raw) == 2 * fsz

@@ -30,7 +30,7 @@ class Out(ctypes.Structure):
 
 
 def build_lib():
-    so = os.path.join(tempfile.gettempdir(), "libwave_sim.so")
+    so = os.path.join(tempfile.mkdtemp(prefix="wave_sim_"), "libwave_sim.so")  # a directory of its own: no clash with another user's or run's copy
     subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(HERE, "wave_sim.cpp")])
     return ctypes.CDLL(so)
 
