@@ -464,6 +464,63 @@ def evaluate_light(flat_space, maximum_distance: int = 30, fast: bool = True, ep
     return n
 
 
+
+class LightSession:
+    """A flat space, its light and its light update queue kept across calls (orc_light_session, aic_light.inc): the
+    oracle's side of a layer whose queue the device keeps between aic_evaluate_light calls. `hb_width` as in
+    `evaluate_light`; `threads` as well (results unchanged)."""
+
+    def __init__(self, flat_space, maximum_distance: int = 30, hb_width: int = 16, threads: int = 1):
+        self.space = Space(flat_space)  # (owns the blocks, voxels and palette the session reads)
+        self.shape = tuple(int(v) for v in self.space.packed.size)
+        self.threads = threads
+        light = np.ascontiguousarray(flat_space.light, dtype=np.uint8).reshape(-1, 4)
+        f = lib().orc_light_session_create
+        f.restype = C.c_void_p
+        self._h = f(C.byref(self.space.c), C.c_int32(maximum_distance), C.c_void_p(_p(light)), C.c_int32(hb_width))
+
+    def set_cubes(self, cubes, block_index) -> None:
+        """`Mutation::set` of each cube, then `modified_cube_needs_update` (updater.rs:135-173) of each, in order: what
+        `aic_update_cubes` + `aic_light_cubes_changed` do on the device."""
+        xyz = np.ascontiguousarray(cubes, dtype=np.int32).reshape(-1, 3)
+        bi = np.ascontiguousarray(block_index, dtype=np.uint16).reshape(-1)
+        assert len(bi) == len(xyz)
+        lib().orc_light_session_set_cubes.restype = None
+        lib().orc_light_session_set_cubes(C.c_void_p(self._h), C.c_int32(len(xyz)), C.c_void_p(_p(xyz)), C.c_void_p(_p(bi)))
+
+    def evaluate(self, fast: bool = False, epsilon: int = 1, batch: int = 32, max_updates: int = 1 << 62):
+        """`fast_evaluate_light` (if `fast`) then `evaluate_light(epsilon)` continuing the session's queue, in batches of
+        `batch` until `max_updates` (checked between batches): returns (updates, summed ComputedLight::cost, queue left)."""
+        lib().orc_set_light_threads(C.c_int32(self.threads))
+        f = lib().orc_light_session_evaluate
+        f.restype = C.c_uint64
+        cost, left = C.c_uint64(0), C.c_uint64(0)
+        n = int(f(C.c_void_p(self._h), C.c_int32(1 if fast else 0), C.c_int32(epsilon), C.c_int32(batch), C.c_uint64(max_updates),
+                  C.byref(cost), C.byref(left)))
+        return n, int(cost.value), int(left.value)
+
+    def light(self) -> np.ndarray:
+        """The light volume, [x][y][z][4] texels."""
+        out = np.zeros(self.shape + (4,), np.uint8)
+        lib().orc_light_session_read_light.restype = None
+        lib().orc_light_session_read_light(C.c_void_p(self._h), C.c_void_p(_p(out)))
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().orc_light_session_free.restype = None
+            lib().orc_light_session_free(C.c_void_p(self._h))
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self) -> None:
+        self.close()
+
 # ---- axis-aligned rays and the orthographic renderer (aic_ortho.inc; SURVEY.md 8 a18 / N4) ----------
 
 def aa_raycast(origin, direction: int, bounds=None, include_exit=True, max_steps=64, sub_origin=None, zoom=None):

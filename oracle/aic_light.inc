@@ -952,9 +952,10 @@ void compute_batch(const LightSpace &ls, const std::vector<uint32_t> &cubes, std
     pool.run(ls, cubes, out);
 }
 
-uint64_t evaluate_light(LightSpace &ls, int epsilon, int batch, uint64_t max_updates) {
+// Returns the update count; `cost` (if non-null) gets the sum of their ComputedLight::cost.
+uint64_t evaluate_light(LightSpace &ls, int epsilon, int batch, uint64_t max_updates, uint64_t *cost = nullptr) {
     const int eps = priority_from_difference(epsilon);
-    uint64_t total = 0;
+    uint64_t total = 0, cost_sum = 0;
     std::vector<ComputedLight> out;
     std::vector<uint32_t> cubes;
     while (total < max_updates) {
@@ -969,9 +970,11 @@ uint64_t evaluate_light(LightSpace &ls, int epsilon, int batch, uint64_t max_upd
         compute_batch(ls, cubes, out);
         for (const ComputedLight &c : out) {
             apply_light_update(ls, c, nullptr);
+            cost_sum += c.cost;
             total++;
         }
     }
+    if (cost) *cost = cost_sum;
     return total;
 }
 
@@ -987,6 +990,66 @@ void orc_set_light_threads(int32_t n) { g_light_threads = n < 1 ? 1 : n; }
 // the capacity they would have grown to when fast_evaluate_light clears them (queue.rs:287-298; HbTable::clear keeps its buckets).
 static int g_light_build_history = 0;
 void orc_set_light_build_history(int32_t on) { g_light_build_history = on; }
+
+}  // extern "C"
+
+namespace {
+
+// modified_cube_needs_update (updater.rs:135-173) for a cube whose block has just been set: an opaque-for-light cube
+// takes PackedLight::OPAQUE and leaves the queue, any other is queued at Priority::NEWLY_VISIBLE, and so is every
+// neighbour whose face towards the cube is not opaque.
+void modified_cube_needs_update(LightSpace &ls, const I3 &cube) {
+    size_t idx;
+    if (!ls.index(cube, &idx)) return;
+    if (opaque_for_light_computation(ls.derived[ls.sp->block_index[idx]])) {
+        ls.light[idx] = PL_OPAQUE;
+        ls.queue.remove((uint32_t)idx);
+    } else {
+        ls.queue.insert((uint32_t)idx, PRIORITY_NEWLY_VISIBLE);
+    }
+    for (int f = 1; f <= 6; f++) {
+        const I3 n = face_normal(f);
+        const I3 nb = i3(cube[0] + n[0], cube[1] + n[1], cube[2] + n[2]);
+        size_t ni;
+        if (!ls.index(nb, &ni)) continue;
+        const int opposite = f > 3 ? f - 3 : f + 3;
+        if (!ls.derived[ls.sp->block_index[ni]].opaque[opposite - 1]) ls.queue.insert((uint32_t)ni, PRIORITY_NEWLY_VISIBLE);
+    }
+}
+
+// The queue that building the space cube by cube leaves (see orc_set_light_build_history): every visible cube in
+// GridAab::interior_iter order; the light texels it writes are overwritten by fast_evaluate_light.
+void replay_build_history(LightSpace &ls) {
+    const int32_t *lo = ls.sp->lo, *sz = ls.sp->size;
+    for (int32_t x = 0; x < sz[0]; x++) for (int32_t y = 0; y < sz[1]; y++) for (int32_t z = 0; z < sz[2]; z++) {
+        const I3 cube = i3(lo[0] + x, lo[1] + y, lo[2] + z);
+        size_t idx;
+        if (!ls.index(cube, &idx)) continue;
+        if (!ls.derived[ls.sp->block_index[idx]].visible) continue;  // never set(): still the AIR the space was built with
+        modified_cube_needs_update(ls, cube);
+    }
+}
+
+// A light session: a space, its light and its update queue kept across calls, as the reference's Space keeps its
+// LightUpdateQueue between Mutation::evaluate_light calls. What orc_evaluate_light does in one call can be split into
+// several -- budgeted calls, calls with different batch sizes -- and block changes can come in between.
+struct LightSession {
+    std::vector<uint16_t> block_index;  // the session's own copy: orc_light_session_set_cubes changes it
+    orc_space space;                    // the caller's space (blocks, voxels, palette: the caller keeps them alive) over that copy
+    LightSpace ls;
+    LightSession(const orc_space *s, int32_t maximum_distance, int32_t hb_width)
+        : block_index(s->block_index, s->block_index + (size_t)s->size[0] * s->size[1] * s->size[2]),
+          space(with_block_index(*s, block_index.data())),
+          ls(&space, maximum_distance, hb_width) {}
+    static orc_space with_block_index(orc_space s, const uint16_t *bi) {
+        s.block_index = bi;
+        return s;
+    }
+};
+
+}  // namespace
+
+extern "C" {
 
 // Per-block derived properties: out[n_blocks][32] floats = color rgba, 6 x face colour rgba, emission rgb,
 // then opaque[6] and visible as 0/1 floats... laid out as: [0..4) color, [4..28) faces, [28..31) emission, [31] visible,
@@ -1034,26 +1097,7 @@ uint64_t orc_evaluate_light(const orc_space *space, int32_t maximum_distance, in
     LightSpace ls(space, maximum_distance, hb_width);
     const size_t n = ls.light.size();
     if (fast) {
-        if (g_light_build_history) {
-            const int32_t *lo = space->lo, *sz = space->size;
-            for (int32_t x = 0; x < sz[0]; x++) for (int32_t y = 0; y < sz[1]; y++) for (int32_t z = 0; z < sz[2]; z++) {  // GridAab::interior_iter order
-                const I3 cube = i3(lo[0] + x, lo[1] + y, lo[2] + z);
-                size_t idx;
-                if (!ls.index(cube, &idx)) continue;
-                const Derived &ev = ls.derived[space->block_index[idx]];
-                if (!ev.visible) continue;  // never set(): still the AIR the space was built with
-                if (opaque_for_light_computation(ev)) ls.queue.remove((uint32_t)idx);
-                else ls.queue.insert((uint32_t)idx, PRIORITY_NEWLY_VISIBLE);
-                for (int f = 1; f <= 6; f++) {
-                    const I3 n = face_normal(f);
-                    const I3 nb = i3(cube[0] + n[0], cube[1] + n[1], cube[2] + n[2]);
-                    size_t ni;
-                    if (!ls.index(nb, &ni)) continue;
-                    const int opposite = f > 3 ? f - 3 : f + 3;
-                    if (!ls.derived[space->block_index[ni]].opaque[opposite - 1]) ls.queue.insert((uint32_t)ni, PRIORITY_NEWLY_VISIBLE);
-                }
-            }
-        }
+        if (g_light_build_history) replay_build_history(ls);
         fast_evaluate_light(ls);
     } else {
         for (size_t i = 0; i < n; i++) {
@@ -1068,6 +1112,50 @@ uint64_t orc_evaluate_light(const orc_space *space, int32_t maximum_distance, in
         light_inout[4 * i] = ls.light[i].r; light_inout[4 * i + 1] = ls.light[i].g; light_inout[4 * i + 2] = ls.light[i].b; light_inout[4 * i + 3] = ls.light[i].status;
     }
     return total;
+}
+
+// light [n][4]: the starting texels (ignored by a `fast` evaluation). The queue starts empty.
+orc_light_session *orc_light_session_create(const orc_space *space, int32_t maximum_distance, const uint8_t *light, int32_t hb_width) {
+    LightSession *s = new LightSession(space, maximum_distance, hb_width);
+    for (size_t i = 0; i < s->ls.light.size(); i++) s->ls.light[i] = PackedLight{light[4 * i], light[4 * i + 1], light[4 * i + 2], light[4 * i + 3]};
+    return reinterpret_cast<orc_light_session *>(s);
+}
+
+void orc_light_session_free(orc_light_session *h) { delete reinterpret_cast<LightSession *>(h); }
+
+// Mutation::set for each cube in turn, then modified_cube_needs_update for each in the same order (what aic_update_cubes
+// followed by aic_light_cubes_changed does). Cubes outside the space are skipped.
+void orc_light_session_set_cubes(orc_light_session *h, int32_t n, const int32_t *cubes, const uint16_t *block_index) {
+    LightSession *s = reinterpret_cast<LightSession *>(h);
+    for (int32_t k = 0; k < n; k++) {
+        size_t idx;
+        if (s->ls.index(i3(cubes[3 * k], cubes[3 * k + 1], cubes[3 * k + 2]), &idx)) s->block_index[idx] = block_index[k];
+    }
+    for (int32_t k = 0; k < n; k++) modified_cube_needs_update(s->ls, i3(cubes[3 * k], cubes[3 * k + 1], cubes[3 * k + 2]));
+}
+
+// fast_evaluate_light (if `fast`, which replaces the queue) and then evaluate_light(epsilon) continuing the session's
+// queue: batches of `batch` until max_updates is reached (checked between batches) or the queue's highest priority is at
+// most from_difference(epsilon). Returns the update count; *cost = their summed ComputedLight::cost, *queue_left = the
+// entries left in the queue.
+uint64_t orc_light_session_evaluate(orc_light_session *h, int32_t fast, int32_t epsilon, int32_t batch, uint64_t max_updates,
+                                    uint64_t *cost, uint64_t *queue_left) {
+    LightSession *s = reinterpret_cast<LightSession *>(h);
+    if (fast) {
+        if (g_light_build_history) replay_build_history(s->ls);
+        fast_evaluate_light(s->ls);
+    }
+    const uint64_t total = evaluate_light(s->ls, epsilon, batch, max_updates, cost);
+    if (queue_left) *queue_left = s->ls.queue.len;
+    return total;
+}
+
+void orc_light_session_read_light(const orc_light_session *h, uint8_t *light_out) {
+    const LightSession *s = reinterpret_cast<const LightSession *>(h);
+    for (size_t i = 0; i < s->ls.light.size(); i++) {
+        const PackedLight &t = s->ls.light[i];
+        light_out[4 * i] = t.r; light_out[4 * i + 1] = t.g; light_out[4 * i + 2] = t.b; light_out[4 * i + 3] = t.status;
+    }
 }
 
 }  // extern "C"

@@ -196,6 +196,14 @@ void orc_set_light_threads(int32_t n);
 uint64_t orc_evaluate_light(const orc_space *space, int32_t maximum_distance, int32_t fast, int32_t epsilon, int32_t batch,
                             uint64_t max_updates, uint8_t *light_inout, int32_t n_queue, const int32_t *queue_cubes,
                             const int32_t *queue_priorities, int32_t hb_width);
+/* a light session: the space's block indices, light and update queue kept across calls (see aic_light.inc) */
+typedef struct orc_light_session orc_light_session;
+orc_light_session *orc_light_session_create(const orc_space *space, int32_t maximum_distance, const uint8_t *light, int32_t hb_width);
+void orc_light_session_free(orc_light_session *s);
+void orc_light_session_set_cubes(orc_light_session *s, int32_t n, const int32_t *cubes, const uint16_t *block_index);
+uint64_t orc_light_session_evaluate(orc_light_session *s, int32_t fast, int32_t epsilon, int32_t batch, uint64_t max_updates,
+                                    uint64_t *cost, uint64_t *queue_left);
+void orc_light_session_read_light(const orc_light_session *s, uint8_t *light_out);
 
 /* ---- axis-aligned rays and the orthographic renderer (aic_ortho.inc) ---- */
 int32_t orc_aa_raycast(const int32_t origin[3], int32_t direction, const float *sub_origin, int32_t zoom_resolution,

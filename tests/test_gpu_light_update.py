@@ -426,11 +426,12 @@ def test_host_mirror_device_light_mode(ctx):
     assert (img_a2 != img_a).any()
 
 
-def _random_light_scene(seed):
+def _random_light_scene(seed, sizes=(3, 9)):
     """A small space with every kind of block the updater distinguishes: air, opaque and translucent atoms, an opaque
-    emitter, a translucent emitter, recursive blocks (full, partial, translucent, emissive voxels), an octant sky, at random."""
+    emitter, a translucent emitter, recursive blocks (full, partial, translucent, emissive voxels), an octant sky, at random.
+    `sizes`: the half-open range of its cubes per axis."""
     rng = np.random.default_rng(1000 + seed)
-    size = tuple(int(v) for v in rng.integers(3, 9, 3))
+    size = tuple(int(v) for v in rng.integers(sizes[0], sizes[1], 3))
     lo = tuple(int(v) for v in rng.integers(-5, 5, 3))
     sp = flat.FlatSpace(lo, size)
     if seed % 3 == 0:

@@ -1,6 +1,8 @@
 """Pins of the oracle's light updater (oracle/aic_light.inc): the reference's own light unit
 tests (all-is-cubes/src/space/light/tests.rs) and the lighting image tests of test-renderers
 (cases/src/lib.rs:501-512, 976-983, 1107-1135 over the scenes of 1354-1610), at the thresholds those cases state."""
+import copy
+
 import numpy as np
 import pytest
 
@@ -161,6 +163,88 @@ def test_compute_derived_slab():
     assert np.isclose(d["face_colors"][0][0][3], 0.25)   # NX: the 4/16 of the face the slab's side covers
     assert np.isclose(d["face_colors"][0][5][3], 1.0)    # PZ: every pixel hits the slab's top
 
+
+
+# ---- the light session (orc_light_session): the oracle side of the device's budgeted, queue-continuing calls ----------
+
+@pytest.mark.parametrize("order", [0, 16])
+@pytest.mark.parametrize("batch", [1, 32, 257, 4096])
+def test_light_session_single_call_equals_evaluate_light(batch, order):
+    sp = scenes.fog_test_space()
+    ref = copy.deepcopy(sp)
+    n_ref = oracle.evaluate_light(ref, maximum_distance=30, fast=True, epsilon=1, batch=batch, hb_width=order, threads=4)
+    with oracle.LightSession(sp, 30, hb_width=order, threads=4) as s:
+        n, cost, left = s.evaluate(fast=True, epsilon=1, batch=batch)
+        assert n == n_ref > 4096 and cost > 0 and left == 0
+        assert (s.light() == np.asarray(ref.light)).all()
+
+
+@pytest.mark.parametrize("batch,order", [(257, 0), (32, 16), (2048, 0)])
+def test_light_session_slices_add_up_to_one_call(batch, order):
+    """Calls with max_updates == batch compute one batch each; together they are the single call, update for update."""
+    sp = scenes.fog_test_space()
+    with oracle.LightSession(sp, 30, hb_width=order, threads=4) as one:
+        n_one, cost_one, _ = one.evaluate(fast=True, epsilon=1, batch=batch)
+        want = one.light()
+    with oracle.LightSession(sp, 30, hb_width=order, threads=4) as s:
+        n, cost, left = s.evaluate(fast=True, epsilon=1, batch=batch, max_updates=batch)
+        assert n == batch and left > 0
+        calls = 1
+        while True:
+            k, c, left = s.evaluate(fast=False, epsilon=1, batch=batch, max_updates=batch)
+            if k == 0:
+                break
+            assert k <= batch and calls < 100000
+            n, cost, calls = n + k, cost + c, calls + 1
+        assert (n, cost, left) == (n_one, cost_one, 0)
+        assert calls >= n_one // batch
+        assert (s.light() == want).all()
+
+
+def _air_near_centre(sp, k=0):
+    air = next(i for i, b in enumerate(sp.blocks) if b.is_air)
+    rel = np.argwhere(np.asarray(sp.block_index) == air)
+    centre = np.array(sp.size) / 2
+    pick = rel[np.argsort(np.abs(rel - centre).sum(axis=1), kind="stable")[k]]
+    return tuple(int(v) + l for v, l in zip(pick, sp.lo))
+
+
+def test_light_session_set_cubes_is_modified_cube_needs_update():
+    """set_cubes on the session's own queue equals the Python restatement of Mutation::set (set_block) handed to
+    evaluate_light: a lamp placed (queued with its neighbours), then a wall (OPAQUE, not queued)."""
+    lamp = flat.atom((1.0, 1.0, 1.0, 1.0), (4.0, 2.0, 0.5))
+    wall = flat.atom((0.8, 0.7, 0.6, 1.0))
+    base = copy.deepcopy(lit(scenes.light_spread_space))
+    c1, c2 = _air_near_centre(base, 0), _air_near_centre(base, 5)
+    ref = copy.deepcopy(base)
+    sp = copy.deepcopy(base)
+    i_lamp, i_wall = sp.add_block(lamp), sp.add_block(wall)
+    with oracle.LightSession(sp, 30, hb_width=16, threads=4) as s:
+        for cube, block, index in ((c1, lamp, i_lamp), (c2, wall, i_wall)):
+            queue = set_block(ref, cube, block)
+            n_ref = oracle.evaluate_light(ref, maximum_distance=30, fast=False, epsilon=1, batch=32, queue=queue, hb_width=16)
+            s.set_cubes([cube], [index])
+            n, _, left = s.evaluate(fast=False, epsilon=1, batch=32)
+            assert n == n_ref > 0 and left == 0
+            assert (s.light() == np.asarray(ref.light)).all()
+
+
+def test_light_session_cost_is_the_sum_of_compute_light():
+    """The summed cost of a batch is the sum of ComputedLight::cost (orc_compute_light) of the cubes it popped, each against
+    the light the batch started from: here the cube a lamp was placed at and its neighbours, all in one batch."""
+    lamp = flat.atom((1.0, 1.0, 1.0, 1.0), (4.0, 2.0, 0.5))
+    base = copy.deepcopy(lit(scenes.light_spread_space))
+    cube = _air_near_centre(base)
+    queued = [c for c, _ in set_block(copy.deepcopy(base), cube, lamp)]
+    sp = copy.deepcopy(base)
+    index = sp.add_block(lamp)
+    with oracle.LightSession(sp, 30, hb_width=0) as s:
+        s.set_cubes([cube], [index])
+        sp.set(cube, index)
+        sp.light = s.light()
+        want = sum(oracle.compute_light(oracle.Space(sp), c, 30)[1] for c in queued)
+        n, cost, _ = s.evaluate(fast=False, epsilon=1, batch=64, max_updates=1)  # one batch: everything queued
+        assert n == len(queued) > 1 and cost == want > 0
 
 # ---- the lighting image tests ----------------------------------------------------------------------
 
