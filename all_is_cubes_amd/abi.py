@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options",
     "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
-    "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf",
+    "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
     "aic_create_multi", "aic_destroy_multi", "aic_multi_device_count", "aic_multi_context", "aic_multi_last_error", "aic_multi_upload_space",
@@ -184,6 +184,7 @@ def load() -> C.CDLL:
                                           C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         lib.aic_probe_light_lut.argtypes = [C.c_void_p, C.c_void_p]
         lib.aic_probe_powf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.aic_probe_expf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.aic_evaluate_light.argtypes = [C.c_void_p, C.c_int, C.POINTER(LightParams), C.POINTER(LightInfo)]
         lib.aic_evaluate_light_submit.argtypes = [C.c_void_p, C.c_int, C.POINTER(LightParams)]
         lib.aic_evaluate_light_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(LightInfo)]
@@ -515,6 +516,13 @@ class Context:
         y = np.ascontiguousarray(y, np.float32)
         out = np.zeros(x.shape, np.float32)
         self._check(self._lib.aic_probe_powf(self._h, _ptr(x), _ptr(y), x.size, _ptr(out)))
+        return out
+
+    def probe_expf(self, x) -> np.ndarray:
+        """The device's expf (distance_fog's f32::exp) of every element of `x` (|x| < 88)."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros(x.shape, np.float32)
+        self._check(self._lib.aic_probe_expf(self._h, _ptr(x), x.size, _ptr(out)))
         return out
 
     def evaluate_light(self, layer: int, maximum_distance: int, fast: bool = True, epsilon: int = 1, batch: int = 32,

@@ -30,6 +30,7 @@ size_t trace_ray_cold_bytes(uint32_t n_cus, uint32_t *groups);
 void launch_scatter_cubes(uint16_t *grid, uint32_t *light, const int32_t *xyz, const uint16_t *bi, const uint32_t *lt,
                           uint32_t n, const int lo[3], const int size[3], const uint32_t *cls, hipStream_t stream);
 void launch_probe_powf(const float *x, const float *y, float *out, uint32_t n, hipStream_t stream);
+void launch_probe_expf(const float *x, float *out, uint32_t n, hipStream_t stream);
 void launch_order_tiles(const uint32_t *cost, uint32_t *order, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, uint32_t *queue_start,
                         hipStream_t stream, bool clear_cost = false, uint32_t *clear_words = nullptr, uint32_t n_clear_words = 0);
 // the same for the frames of a batch, one workgroup each, in ONE launch (OrderJobs: aic_device.h)
@@ -1732,6 +1733,23 @@ int aic_probe_powf(aic_ctx *c, const float *x, const float *y, uint32_t n, float
     HIP_TRY(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dy, y, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     launch_probe_powf(dx, dy, dout, n, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return AIC_OK;
+}
+
+int aic_probe_expf(aic_ctx *c, const float *x, uint32_t n, float *out) {
+    if (!c || (n && (!x || !out))) return fail(c, AIC_ERR_INVALID, "aic_probe_expf: bad argument");
+    if (!n) return AIC_OK;
+    for (uint32_t i = 0; i < n; i++)  // expf_table has no overflow / underflow handling: keep to its domain
+        if (!(std::fabs(x[i]) < 88.0f)) return fail(c, AIC_ERR_INVALID, "aic_probe_expf: x outside (-88, 88)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipError_t e = c->staging.ensure((size_t)n * 8);
+    if (e != hipSuccess) return hip_fail(c, "alloc staging", e);
+    float *dx = (float *)c->staging.p, *dout = dx + n;
+    HIP_TRY(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    launch_probe_expf(dx, dout, n, c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -483,7 +483,8 @@ AIC_DEV float powf_table(float x, float y, const double *s_pow) {
 // f32::exp as the reference's libm computes it (glibc sysdeps/ieee754/flt-32/e_expf.c, from ARM's optimized-routines; restated
 // from the published algorithm like powf_table above): x * 32/ln2 split into an integer and a remainder, 2^(k/32) from the
 // same 32-entry table as powf's exp2 step, a cubic in the remainder, all in f64, rounded to f32 once. Domain: |x| < 88 (the fog
-// term feeds it [-1.6, 0]); no overflow / underflow handling.
+// term feeds it [-1.6, 0]); no overflow / underflow handling. Pinned against the host's expf on every f32 in [-1.6, 0]
+// (aic_probe_expf; tests/test_gpu_linear_parity.py).
 AIC_DEV float expf_table(float x, const double *s_pow) {
     const double z = KC(0x1.71547652b82fep+5) * (double)x;  // InvLn2N = N / ln 2, N = 32
     double kd = z + KC(0x1.8p+52);
@@ -3032,6 +3033,16 @@ __global__ void probe_powf_kernel(const float *x, const float *y, float *out, ui
     out[i] = powf_table_domain(x[i], y[i]) ? powf_table(x[i], y[i], s_pow) : powf_exact(x[i], y[i]);
 }
 
+// aic_probe_expf: the device's expf as distance_fog uses it (expf_table; its domain, |x| < 88, is the caller's to keep)
+__global__ void probe_expf_kernel(const float *x, float *out, uint32_t n) {
+    __shared__ double s_pow[64];
+    pow_tables_to_lds(s_pow, threadIdx.x, blockDim.x);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = expf_table(x[i], s_pow);
+}
+
 // ---------------------------------------------------------------------------------------
 // host-callable launchers (used by aic_abi.cpp)
 
@@ -3126,6 +3137,11 @@ void launch_scatter_cubes(uint16_t *grid, uint32_t *light, const int32_t *xyz, c
 void launch_probe_powf(const float *x, const float *y, float *out, uint32_t n, hipStream_t stream) {
     if (!n) return;
     hipLaunchKernelGGL(probe_powf_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, x, y, out, n);
+}
+
+void launch_probe_expf(const float *x, float *out, uint32_t n, hipStream_t stream) {
+    if (!n) return;
+    hipLaunchKernelGGL(probe_expf_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, x, out, n);
 }
 
 void launch_order_tiles_jobs(const OrderJobs &jobs, uint32_t n_jobs, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, hipStream_t stream,

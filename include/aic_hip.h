@@ -368,6 +368,8 @@ int aic_probe_raycast(aic_ctx *ctx, const double origin[3], const double directi
                       aic_rc_step *out, uint32_t *n_out, int *ended);
 /* the device's f32::powf as apply_transmittance uses it (raytracer_components.rs:215-258): out[i] = x[i]^y[i] */
 int aic_probe_powf(aic_ctx *ctx, const float *x, const float *y, uint32_t n, float *out);
+/* the device's f32::exp as distance_fog uses it (sr.rs:745-768): out[i] = e^x[i]; AIC_ERR_INVALID unless every |x[i]| < 88 */
+int aic_probe_expf(aic_ctx *ctx, const float *x, uint32_t n, float *out);
 /* the device's PackedLight decode table (light/data.rs:301-354) */
 int aic_probe_light_lut(aic_ctx *ctx, float out[256]);
 

@@ -361,6 +361,14 @@ def apply_transmittance(color, thickness: float):
     return out, coeff.value
 
 
+def expf(x) -> np.ndarray:
+    """f32::exp as distance_fog calls it (the C library's expf), element by element."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    lib().orc_expf(C.c_void_p(_p(x)), C.c_uint64(x.size), C.c_void_p(_p(out)))
+    return out
+
+
 def to_srgb8(rgba) -> np.ndarray:
     c = np.ascontiguousarray(rgba, dtype=np.float32)
     out = np.zeros(4, np.uint8)

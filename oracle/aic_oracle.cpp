@@ -1951,6 +1951,10 @@ void orc_apply_transmittance(const float color[4], float thickness, float out_co
     out_color[0] = o.r; out_color[1] = o.g; out_color[2] = o.b; out_color[3] = o.a;
 }
 
+// the f32::exp of distance_fog (sr.rs:745-768), element by element: the same std::exp(float) call the fog term makes
+void orc_expf(const float *x, uint64_t n, float *out) {
+    for (uint64_t i = 0; i < n; i++) out[i] = std::exp(x[i]);
+}
 void orc_to_srgb8(const float rgba[4], uint8_t out[4]) { to_srgb8(Rgba{rgba[0], rgba[1], rgba[2], rgba[3]}, out); }
 float orc_packed_light_scalar_out(uint8_t v) { return g_light_lut[v]; }
 uint8_t orc_packed_light_scalar_in(float v) { return packed_scalar_in(v); }

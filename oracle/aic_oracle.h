@@ -171,6 +171,7 @@ void orc_unproject(const double inverse_projection_view[16], const double ndc[3]
 void orc_apply_transmittance(const float color[4], float thickness, float out_color[4],
                              float *out_coeff);
 void orc_to_srgb8(const float rgba[4], uint8_t out[4]);
+void orc_expf(const float *x, uint64_t n, float *out);
 float orc_packed_light_scalar_out(uint8_t v);
 uint8_t orc_packed_light_scalar_in(float v);
 void orc_block_sky(const orc_space *space, uint8_t out_faces_mean[7][4]);

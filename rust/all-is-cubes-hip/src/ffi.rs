@@ -236,6 +236,7 @@ unsafe extern "C" {
     pub fn aic_multi_render_wait(m: *mut aic_multi, slot: u32, info: *mut aic_frame_info) -> c_int;
     pub fn aic_probe_raycast(ctx: *mut aic_ctx, origin: *const f64, direction: *const f64, use_bounds: c_int, lo: *const i32, hi: *const i32, include_exit: c_int, max_steps: u32, out: *mut aic_rc_step, n_out: *mut u32, ended: *mut c_int) -> c_int;
     pub fn aic_probe_powf(ctx: *mut aic_ctx, x: *const f32, y: *const f32, n: u32, out: *mut f32) -> c_int;
+    pub fn aic_probe_expf(ctx: *mut aic_ctx, x: *const f32, n: u32, out: *mut f32) -> c_int;
     pub fn aic_probe_light_lut(ctx: *mut aic_ctx, out: *mut f32) -> c_int;
     // light propagation on the device (Space::evaluate_light / fast_evaluate_light)
     pub fn aic_evaluate_light(ctx: *mut aic_ctx, layer: c_int, params: *const aic_light_params, info: *mut aic_light_info) -> c_int;

@@ -2,7 +2,8 @@
 random scenes, cameras and options -- mixed block resolutions, partial voxel volumes, random light
 (all statuses), octant skies, backdrops, eyes inside and outside the space, axis-parallel views,
 narrow and wide fields of view. Same bar as tests/test_gpu_parity.py: per-pixel step counts, first
-hit (cube, voxel, face, block), f64 distance bit for bit; RGBA8 within one level."""
+hit (cube, voxel, face, block), f64 distance bit for bit; RGBA8 within one level. And the linear Rgba
+of the production variants (AIC_FRAME_OUT_LINEAR) bit for bit, as tests/test_gpu_linear_parity.py holds it."""
 import os
 
 import numpy as np
@@ -88,6 +89,9 @@ def test_random_scene_camera_options(seed):
         xt = abi.tuning(variant=abi.VARIANT_EXCHANGING)
         exchanged = ctx.render(ctx.make_frame(w, h, world_inv=inv, backdrop=backdrop, tuning=xt))
         assert fast["info"].variant == abi.VARIANT_PLAIN and exchanged["info"].variant == (abi.VARIANT_PLAIN if opt.lighting == 5 else abi.VARIANT_EXCHANGING)
+        # the linear Rgba before exposure and tone mapping, through both production variants: compared with the oracle's bits below
+        linear = [ctx.render(ctx.make_frame(w, h, world_inv=inv, backdrop=backdrop, flags=abi.FRAME_OUT_LINEAR, tuning=abi.tuning(variant=v)))["rgba8"]
+                  for v in (abi.VARIANT_PLAIN, abi.VARIANT_EXCHANGING)]
         if opt.antialiasing == 0 and opt.lighting != 5:  # (a mean of four samples / secondary rays' steps do not come back from one channel)
             was = opt.debug_pixel_cost
             opt.debug_pixel_cost = 1
@@ -101,5 +105,8 @@ def test_random_scene_camera_options(seed):
         # them): with debug_pixel_cost the pixel is rgb(0.02 n, 0.002 n, ..) and the linear float output hands it over unrounded
         counts = np.rint(cost["rgba8"][..., 1].astype(np.float64) / float(np.float32(0.002))).astype(np.int64)
         assert (counts == got["aux"]["cubes_traced"]).all(), "per-pixel step counts of the production (exchanging) variant"
-    ref = oracle.render(oracle.Space(sp), opt, oracle.make_camera(inv, w, h), backdrop=backdrop, want_aux=True)
+    ref = oracle.render(oracle.Space(sp), opt, oracle.make_camera(inv, w, h), backdrop=backdrop, want_aux=True, want_linear=True)
     assert_parity(got, ref)
+    for name, lin in zip(("plain", "exchanging"), linear):
+        bad = np.argwhere((lin.view(np.uint32) != ref["linear"].view(np.uint32)).any(axis=-1))
+        assert len(bad) == 0, f"{name} variant: {len(bad)} pixels differ in their linear bits, first {tuple(bad[0])}: {lin[tuple(bad[0])]} vs {ref['linear'][tuple(bad[0])]}"
