@@ -21,10 +21,20 @@ LAYER_WORLD, LAYER_UI = 0, 1
 MAX_IN_FLIGHT = 32  # AIC_MAX_IN_FLIGHT
 FLAW_UNSUPPORTED, FLAW_NO_BLOOM = 1, 2
 FRAME_COUNTERS, FRAME_AUX, FRAME_PIXEL_CENTERS, FRAME_OUT_LINEAR, FRAME_OUT_COLORBUF, FRAME_NO_FEEDBACK = 1, 2, 4, 8, 16, 32
+FRAME_BLOOM = 64  # AIC_FRAME_BLOOM: bloom the frame when the world options' bloom_intensity > 0 (RGBA8 output, whole frames)
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
 LIGHT_HOOK_SESSION, LIGHT_HOOK_POOL_SHIFT = 1, 8
+
+
+def bloom_geometry(width: int, height: int):
+    """(levels, (T0x, T0y)) of AIC_FRAME_BLOOM's mip chain for a width x height frame (mip_ping.rs:460-481 on the half-size request of
+    bloom.rs:50-53): R = (ceil(w / 2), ceil(h / 2)), L = min(6, ilog2(min R) + 1), T0 = R rounded up to a multiple of 2^L."""
+    rx, ry = (width + 1) // 2, (height + 1) // 2
+    levels = min(6, min(rx, ry).bit_length())
+    d = 1 << levels
+    return levels, ((rx + d - 1) // d * d, (ry + d - 1) // d * d)
 
 
 def tuning(queues=None, super_shift=None, variant=None) -> int:
@@ -44,7 +54,7 @@ ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options",
     "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
-    "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf",
+    "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
     "aic_create_multi", "aic_destroy_multi", "aic_multi_device_count", "aic_multi_context", "aic_multi_last_error", "aic_multi_upload_space",
@@ -185,6 +195,8 @@ def load() -> C.CDLL:
         lib.aic_probe_light_lut.argtypes = [C.c_void_p, C.c_void_p]
         lib.aic_probe_powf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.aic_probe_expf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.aic_probe_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.POINTER(Options), C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_uint32 * 2)]
         lib.aic_evaluate_light.argtypes = [C.c_void_p, C.c_int, C.POINTER(LightParams), C.POINTER(LightInfo)]
         lib.aic_evaluate_light_submit.argtypes = [C.c_void_p, C.c_int, C.POINTER(LightParams)]
         lib.aic_evaluate_light_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(LightInfo)]
@@ -524,6 +536,22 @@ class Context:
         out = np.zeros(x.shape, np.float32)
         self._check(self._lib.aic_probe_expf(self._h, _ptr(x), x.size, _ptr(out)))
         return out
+
+    def probe_bloom(self, colorbuf, exposure: float, options: "Options", want_mip0: bool = False):
+        """AIC_FRAME_BLOOM's post-process on a ColorBuf ([h][w][4] float32: l0, l1, l2, t) with `options`' bloom_intensity (even 0), tone mapping and
+        maximum intensity: returns the RGBA8 frame [h][w][4], and with want_mip0 also the chain's mip 0 as float16 [T0y][T0x][4]."""
+        cb = np.ascontiguousarray(colorbuf, np.float32)
+        if cb.ndim != 3 or cb.shape[2] != 4:
+            raise ValueError("colorbuf must be [h][w][4]")
+        h, w = cb.shape[:2]
+        out = np.zeros((h, w, 4), np.uint8)
+        size = (C.c_uint32 * 2)()
+        t0 = bloom_geometry(w, h)[1]
+        mip0 = np.zeros((t0[1], t0[0], 4), np.float16) if want_mip0 else None
+        self._check(self._lib.aic_probe_bloom(self._h, w, h, _ptr(cb), float(exposure), C.byref(options), _ptr(out),
+                                              _ptr(mip0) if mip0 is not None else None, C.byref(size)))
+        assert (size[0], size[1]) == t0, ((size[0], size[1]), t0)
+        return (out, mip0) if want_mip0 else out
 
     def evaluate_light(self, layer: int, maximum_distance: int, fast: bool = True, epsilon: int = 1, batch: int = 32,
                        queue_order: int = 16, queue=None, max_updates: int = 0, lanes_per_cube: int = 0, session: bool = False,

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/aic_hip.h"
+#include "aic_bloom.h"
 #include "aic_device.h"
 
 namespace aic {
@@ -184,10 +185,13 @@ struct aic_ctx {
         DevBuf<float4> acc;  // UI pre-pass accumulators
         // cost feedback: the longest ray of every tile of the sub-frame's last frame, and the tile order made from it
         DevBuf<uint32_t> tile_cost, tile_order, queue_start;
+        // AIC_FRAME_BLOOM (on the sub-frame's first bloomed frame): the trace's ColorBuf, then the bloom chain's mips (aic_bloom.h)
+        DevBuf<float4> bloom_cb;
+        DevBuf<uint2> bloom_mips;
         uint32_t cost_sig[4] = {0, 0, 0, 0};  // width, local rows, partition of the frame tile_cost describes
         double cost_cam[16] = {0};            // ... and its world camera
         void release() {
-            counters.release(); acc.release(); tile_cost.release(); tile_order.release(); queue_start.release();
+            counters.release(); acc.release(); tile_cost.release(); tile_order.release(); queue_start.release(); bloom_cb.release(); bloom_mips.release();
             if (host_counters) (void)hipHostFree(host_counters);
             host_counters = nullptr;
             counters_clean = record_ready = false; cost_clean_n = 0;
@@ -1004,6 +1008,11 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
         part.strip_rows = f->height ? f->height : 1;
     }
     if (part.part >= part.n_parts) return fail(c, AIC_ERR_INVALID, "aic_render: partition.part >= n_parts");
+    if (f->flags & AIC_FRAME_BLOOM) {  // (checked before anything is queued: the context stays as it was)
+        if (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) return fail(c, AIC_ERR_INVALID, "aic_render: AIC_FRAME_BLOOM is for RGBA8 output only");
+        if (part.n_parts > 1u) return fail(c, AIC_ERR_UNSUPPORTED, "aic_render: AIC_FRAME_BLOOM needs the whole frame (partition.n_parts = 1)");
+        if (patches || ortho_n) return fail(c, AIC_ERR_UNSUPPORTED, "AIC_FRAME_BLOOM: not for patches or orthographic views");
+    }
     const uint32_t local_rows = aic_partition_rows(f->height, &part);
     const size_t npix = (size_t)f->width * local_rows;
     for (uint32_t j = 0; j < k; j++)
@@ -1020,16 +1029,16 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     DevLayer hl[2];
     fill_dev_layer(c, c->layers[AIC_LAYER_WORLD], f->world, &hl[0], &flaws);
     fill_dev_layer(c, c->layers[AIC_LAYER_UI], f->ui, &hl[1], &flaws);
-    {
-        const aic_options &wo = c->layers[AIC_LAYER_WORLD].opt;
-        if (wo.bloom_intensity != 0.0f) flaws |= AIC_FLAW_NO_BLOOM;  // renderer.rs:293-297
-    }
+    // AIC_FRAME_BLOOM: the frame is bloomed as the reference's GPU renderer blooms it (aic_bloom.hip); at intensity 0 the flag changes nothing
+    const aic_options &bloom_opt = c->layers[AIC_LAYER_WORLD].opt;
+    const bool bloom = (f->flags & AIC_FRAME_BLOOM) && bloom_opt.bloom_intensity > 0.0f;
+    if (bloom_opt.bloom_intensity != 0.0f && !bloom) flaws |= AIC_FLAW_NO_BLOOM;  // renderer.rs:293-297
     F.width = f->width;
     F.height = f->height;
     F.n_sub = k;
     // the encoder and the sampling pattern follow the WORLD camera's options (renderer.rs:283-291, 426)
     F.pixel_centers = (f->flags & AIC_FRAME_PIXEL_CENTERS) && !patches ? 1 : 0;
-    F.out_mode = (f->flags & AIC_FRAME_OUT_LINEAR) ? 1 : ((f->flags & AIC_FRAME_OUT_COLORBUF) ? 2 : 0);
+    F.out_mode = (f->flags & AIC_FRAME_OUT_LINEAR) ? 1 : ((f->flags & AIC_FRAME_OUT_COLORBUF) || bloom ? 2 : 0);  // (a bloomed frame: its ColorBuf, into the slot's scratch)
     F.patches = patches;
     F.n_patches = n_patches;
     F.ortho = ortho;
@@ -1150,6 +1159,11 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
         S.has_backdrop = !(frames[j].backdrop[0] == 0.f && frames[j].backdrop[1] == 0.f && frames[j].backdrop[2] == 0.f && frames[j].backdrop[3] == 0.f);
         S.exposure = ortho_n ? 1.0f : frames[j].world.exposure + 0.0f;  // (PositiveSign: checked above; -0.0 becomes +0.0)
         S.out = out_devices[j];
+        if (bloom) {
+            if ((e = sb.bloom_cb.ensure(npix)) != hipSuccess || (e = sb.bloom_mips.ensure(bloom_geometry(f->width, f->height).texels)) != hipSuccess)
+                return hip_fail(c, "alloc bloom scratch", e);
+            S.out = reinterpret_cast<uint32_t *>(sb.bloom_cb.p);
+        }
         if ((e = sb.counters.ensure(1)) != hipSuccess) return hip_fail(c, "alloc frame counters", e);
         S.counters = sb.counters.p;
         if (!sb.host_counters) {  // (on a sub-frame's first frame: most contexts only ever use slot 0, and a context is cheap to make and drop)
@@ -1269,6 +1283,23 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     fs.tile_queues = F.n_queues;
     launch_trace_image(F, diag, fs.stream);
     HIP_TRY(c, hipGetLastError());
+    if (bloom) {
+        // each frame's ColorBuf through the chain and the composite into the caller's buffer; ev1 (kernel_ms, aic_stream_wait_frame) is behind it
+        const BloomGeom geom = bloom_geometry(f->width, f->height);
+        for (uint32_t j = 0; j < k; j++) {
+            BloomParams bp;
+            bp.colorbuf = fs.sub[j].bloom_cb.p;
+            bp.mips = fs.sub[j].bloom_mips.p;
+            bp.out = out_devices[j];
+            bp.exposure = F.sub[j].exposure;
+            bp.intensity = bloom_opt.bloom_intensity;
+            bp.tone_mapping = F.tone_mapping;
+            bp.maximum_intensity = F.maximum_intensity;
+            bp.srgb_thr = c->srgb_thr.p;
+            launch_bloom(geom, bp, fs.stream);
+        }
+        HIP_TRY(c, hipGetLastError());
+    }
     HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
     // behind the trace: the frame's sums are in pinned host memory -- written by the last wave of the trace itself, or (profile builds: the whole
     // counter block) copied there; ev2 is what a wait waits for ...
@@ -1526,6 +1557,7 @@ int aic_trace_patches(aic_ctx *c, const aic_frame_desc *f, uint32_t n, const dou
     if (!n) return AIC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_trace_patches: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (f->flags & AIC_FRAME_BLOOM) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_patches: AIC_FRAME_BLOOM needs a whole frame");
     // the batch is laid out as an image of up to 2048 columns; pixel i of that image traces rects[i]
     aic_frame_desc g = *f;
     g.width = n < 2048u ? n : 2048u;
@@ -1753,6 +1785,38 @@ int aic_probe_expf(aic_ctx *c, const float *x, uint32_t n, float *out) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return AIC_OK;
+}
+
+int aic_probe_bloom(aic_ctx *c, uint32_t width, uint32_t height, const float *colorbuf, float exposure, const aic_options *options, uint8_t *out_rgba8,
+                    uint16_t *out_mip0, uint32_t mip0_size[2]) {
+    if (!c || !colorbuf || !options || !out_rgba8 || !width || !height) return fail(c, AIC_ERR_INVALID, "aic_probe_bloom: bad argument");
+    if (width > 65535u || height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_probe_bloom: frame dimensions above 65535 are not supported");
+    if (!(exposure >= 0.f) || !(options->bloom_intensity >= 0.f)) return fail(c, AIC_ERR_INVALID, "aic_probe_bloom: exposure or bloom_intensity is negative or NaN");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_probe_bloom: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    const BloomGeom geom = bloom_geometry(width, height);
+    const size_t npix = (size_t)width * height;
+    aic_ctx::SubSlot &sb = c->slots[0].sub[0];
+    hipError_t e;
+    if ((e = sb.bloom_cb.ensure(npix)) != hipSuccess || (e = sb.bloom_mips.ensure(geom.texels)) != hipSuccess || (e = c->out.ensure(npix)) != hipSuccess)
+        return hip_fail(c, "alloc bloom scratch", e);
+    HIP_TRY(c, hipMemcpyAsync(sb.bloom_cb.p, colorbuf, npix * 16, hipMemcpyHostToDevice, c->stream));
+    BloomParams bp;
+    bp.colorbuf = sb.bloom_cb.p;
+    bp.mips = sb.bloom_mips.p;
+    bp.out = c->out.p;
+    bp.exposure = exposure + 0.0f;
+    bp.intensity = options->bloom_intensity;
+    bp.tone_mapping = options->tone_mapping;
+    bp.maximum_intensity = options->maximum_intensity;
+    bp.srgb_thr = c->srgb_thr.p;
+    launch_bloom(geom, bp, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->out.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_mip0) HIP_TRY(c, hipMemcpyAsync(out_mip0, sb.bloom_mips.p, (size_t)geom.mw[0] * geom.mh[0] * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (mip0_size) { mip0_size[0] = geom.mw[0]; mip0_size[1] = geom.mh[0]; }
     return AIC_OK;
 }
 

@@ -1,0 +1,62 @@
+// aic_bloom.h -- the bloom post-process (aic_bloom.hip) as the host ABI code sees it: the chain's geometry and the launch.
+//
+// The reference's GPU renderer blooms every frame whose GraphicsOptions ask for it, raytraced frames included
+// (all-is-cubes-gpu/src/raytrace_to_texture.rs:644-661 hands the raytracer's ColorBuf to the post-process): a "dual filter" mip chain
+// (bloom.rs:41-60, mip_ping.rs:301-420, shaders/resampling.wgsl) mixed into the scene before tone mapping (shaders/postprocess.wgsl:140-158).
+// What is restated, and the three decisions taken where the reference leaves room, are in DESIGN.md "Bloom".
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace aic {
+
+constexpr uint32_t kBloomMaxLevels = 6;        // bloom.rs:57
+constexpr uint32_t kBloomRepetitions = 3;      // bloom.rs:58
+
+// Sizes of one frame's chain (mip_ping.rs:460-481 size_and_mip_levels_for_texture, on the half-size request of bloom.rs:50-53).
+struct BloomGeom {
+    uint32_t width = 0, height = 0;  // the frame: the scene texture S
+    uint32_t levels = 0;             // L
+    uint32_t mw[kBloomMaxLevels] = {0}, mh[kBloomMaxLevels] = {0};  // mip k: T0 >> k
+    uint32_t off[kBloomMaxLevels] = {0};                            // first texel of mip k in the chain buffer
+    uint32_t texels = 0;             // the whole chain
+};
+
+inline uint32_t bloom_ilog2(uint32_t v) { uint32_t r = 0; while (v >>= 1) r++; return r; }
+
+inline BloomGeom bloom_geometry(uint32_t width, uint32_t height) {
+    BloomGeom g;
+    g.width = width;
+    g.height = height;
+    const uint32_t rx = (width + 1u) / 2u, ry = (height + 1u) / 2u;  // div_ceil(2)
+    const uint32_t m = rx < ry ? rx : ry;
+    g.levels = m ? bloom_ilog2(m) + 1u : 1u;
+    if (g.levels > kBloomMaxLevels) g.levels = kBloomMaxLevels;
+    const uint32_t d = 1u << g.levels;
+    const uint32_t t0x = (rx + d - 1u) / d * d, t0y = (ry + d - 1u) / d * d;  // next_multiple_of(2^L)
+    for (uint32_t k = 0; k < g.levels; k++) {
+        g.mw[k] = t0x >> k;
+        g.mh[k] = t0y >> k;
+        g.off[k] = g.texels;
+        g.texels += g.mw[k] * g.mh[k];
+    }
+    return g;
+}
+
+struct BloomParams {
+    const float4 *colorbuf;  // [height][width] ColorBuf l0, l1, l2, t: the trace's AIC_FRAME_OUT_COLORBUF output
+    uint2 *mips;             // [geom.texels] f16 x 4 per texel
+    uint32_t *out;           // [height][width] RGBA8
+    float exposure;          // the world camera's
+    float intensity;         // GraphicsOptions::bloom_intensity
+    int32_t tone_mapping;
+    float maximum_intensity;
+    const float *srgb_thr;   // the context's 256 sRGB8 thresholds (as DevFrame::srgb_thr)
+};
+
+// Queues the whole post-process on `stream`: the chain (downsample 0 from the ColorBuf, then the stages of mip_ping.rs:301-420) and the composite into
+// p.out. Launches: one per stage, 6 L - 5 of them (31 at L = 6: a 1080p or 4K frame), then the composite.
+void launch_bloom(const BloomGeom &g, const BloomParams &p, hipStream_t stream);
+
+}  // namespace aic

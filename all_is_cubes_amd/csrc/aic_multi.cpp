@@ -215,6 +215,7 @@ int aic_multi_light_cubes_changed(aic_multi *m, int layer, uint32_t n, const int
 // (record.rs:97-113) gets from a single context's aic_render_submit / aic_render_wait.
 int aic_multi_render_submit(aic_multi *m, const aic_frame_desc *f, void *out_rgba8, int out_is_device, uint32_t slot) {
     if (!m || !f || !out_rgba8 || slot >= AIC_MULTI_MAX_IN_FLIGHT) return mfail(m, AIC_ERR_INVALID, "aic_multi_render_submit: bad argument");
+    if (f->flags & AIC_FRAME_BLOOM) return mfail(m, AIC_ERR_UNSUPPORTED, "aic_multi_render_submit: AIC_FRAME_BLOOM is for single-device contexts (device 0 would first need every strip's ColorBuf)");
     if (f->flags & (AIC_FRAME_AUX | AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF))
         return mfail(m, AIC_ERR_INVALID, "aic_multi_render: RGBA8 frames only (use a single context for aux records / float output)");
     if (f->partition.n_parts > 1) return mfail(m, AIC_ERR_INVALID, "aic_multi_render partitions the frame itself");

@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "aic_device.h"
+#include "aic_encode.h"
 #include "aic_lightmath.h"
 
 namespace aic {
@@ -382,16 +383,11 @@ AIC_DEV void intersection_point(const Lvl s, double ox, double oy, double oz, do
 // ---------------------------------------------------------------------------------------
 // colour helpers (f32, reference operation order)
 
-AIC_DEV float ps_clamped(float v) { return v > 0.f ? v : 0.f; }          // restricted_number.rs:240-248
 AIC_DEV float zo_clamped(float v) {                                        // restricted_number.rs:315-326
     if (v > 0.f && v <= 1.f) return v;
     if (v <= 0.f) return 0.f;
     return 1.f;
 }
-// PositiveSign::mul: 0 * inf => 0. Both factors are PositiveSign values (not NaN, sign bit clear: what the reference's type holds and aic_upload_* / the
-// kernel's own clamps guarantee), so the product is >= +0 or the NaN of 0 * inf, and max(product, 0) -- one instruction: it returns the operand that
-// is a number -- is the reference's "NaN becomes zero" (a compare and a select until round 6; fifteen of them in a SHADE event).
-AIC_DEV float ps_mul(float a, float b) { return fmaxf(a * b, 0.0f); }
 
 // f32::powf as the reference's libm computes it on x86-64 Linux. Rust's `f32::powf` is the C library's
 // powf; glibc's (sysdeps/ieee754/flt-32/e_powf.c, from ARM's optimized-routines; not under
@@ -502,9 +498,6 @@ AIC_DEV float expf_table(float x, const double *s_pow) {
     return (float)y;
 }
 
-struct ColorBuf {  // raytracer_components.rs:20-39
-    float l0, l1, l2, t;
-};
 AIC_DEV void cb_add(ColorBuf &b, float s0, float s1, float s2, float st) {  // :87-92
     b.l0 += s0 * b.t;
     b.l1 += s1 * b.t;
@@ -512,33 +505,9 @@ AIC_DEV void cb_add(ColorBuf &b, float s0, float s1, float s2, float st) {  // :
     b.t *= st;
 }
 AIC_DEV bool cb_opaque(const ColorBuf &b) { return b.t < 1.0f / 256.0f; }  // :105-109
-AIC_DEV float luminance(float r, float g, float b) { return g * 0.7152f + (r * 0.2126f + b * 0.0722f); }
-
-// Rgba::from(ColorBuf) (raytracer_components.rs:122-147)
-AIC_DEV void cb_to_rgba(const ColorBuf &b, float out[4]) {
-    if (b.t >= 1.0f) {
-        out[0] = out[1] = out[2] = out[3] = 0.f;
-        return;
-    }
-    float alpha = 1.0f - b.t;
-    float c0 = b.l0, c1 = b.l1, c2 = b.l2;
-    if (__ballot(alpha != 1.0f) != 0ull) {  // x / 1.0f == x: fully opaque pixels (the usual case) need no division
-        c0 = b.l0 / alpha; c1 = b.l1 / alpha; c2 = b.l2 / alpha;
-    }
-    bool ok = (c0 >= 0.f) & (c1 >= 0.f) & (c2 >= 0.f);  // false for negative or NaN
-    out[0] = ok ? (c0 > 0.f ? c0 : 0.f) : 1.0f;
-    out[1] = ok ? (c1 > 0.f ? c1 : 0.f) : 0.0f;
-    out[2] = ok ? (c2 > 0.f ? c2 : 0.f) : 0.0f;
-    out[3] = (alpha > 0.f && alpha <= 1.f) ? alpha : (alpha == 0.f ? 0.f : 1.0f);
-}
 
 
-AIC_DEV uint32_t round_sat_u8(float x) {  // `(x).round() as u8`
-    float r = roundf(x);
-    if (!(r > 0.f)) return 0u;  // NaN, negatives, zero
-    if (r >= 255.f) return 255u;
-    return (uint32_t)r;
-}
+
 
 // ---------------------------------------------------------------------------------------
 // light (space/light/data.rs, space/sky.rs, sr.rs:241-359)
@@ -900,51 +869,6 @@ constexpr float NO_WORLD_TO_SHOW = 0.5028865f;  // palette.rs:76 #BCBCBC decoded
 AIC_DEV double fb_x_edge(uint32_t w, uint32_t x) { return ((double)x) / (double)w * 2.0 - 1.0; }
 AIC_DEV double fb_y_edge(uint32_t h, uint32_t y) { return -(((double)y) / (double)h * 2.0 - 1.0); }
 
-// Rgba::to_srgb8 colour channels (color.rs:1038-1054) without powf: `thr[k]` (k = 1..255) is the smallest f32 whose reference encoding is >= k (built on
-// the host with the reference formula), so the encoding of c is the number of thresholds <= c. A fast estimate k seeds the count, the thresholds make
-// it exact. The kernel holds them as a WINDOW table `w` of kSrgbWindowWords floats -- w[j] = thr[j - 1], with -inf below thr[1] and NaN above
-// thr[255] -- so that the four thresholds around an estimate, thr[k - 1 .. k + 2], are w[k .. k + 3] for every k in 0..255: c >= -inf always holds,
-// c >= NaN never. The three channels' eight reads are issued together and compared without a branch; the count of thresholds <= c among the four
-// settles the encoding unless it is 0 or 4 (the estimate was off by two or more: v_log_f32 / v_exp_f32 are good to about an ulp, so never seen), and
-// then the thresholds are searched as before round 6 (two dependent LDS reads per step of two loops per channel, for every pixel).
-constexpr uint32_t kSrgbWindowWords = 260u;
-AIC_DEV void srgb_window_to_lds(float *w, const float *thr, uint32_t tid, uint32_t nthreads) {
-    for (uint32_t i = tid; i < kSrgbWindowWords; i += nthreads)
-        w[i] = i < 2u ? __uint_as_float(0xff800000u) : (i <= 256u ? thr[i - 1u] : __uint_as_float(0x7fc00000u));
-}
-AIC_DEV int srgb8_estimate(float c) {  // 0..255 (c > 0)
-    const float cc = fminf(c, 1.0f);
-    const float e = cc <= 0.0031308f ? cc * 12.92f : 1.055f * __builtin_amdgcn_exp2f(0.41666666f * __builtin_amdgcn_logf(cc)) - 0.055f;
-    const int k = (int)(e * 255.f + 0.5f);
-    return k < 0 ? 0 : (k > 255 ? 255 : k);
-}
-AIC_DEV uint32_t srgb8_search(float c, int k, const float *__restrict__ w) {  // c > 0; thr[j] = w[j + 1]
-    while (k < 255 && c >= w[k + 2]) k++;
-    while (k > 0 && c < w[k + 1]) k--;
-    return (uint32_t)k;
-}
-AIC_DEV void srgb8_rgb(float r, float g, float b, const float *__restrict__ w, uint32_t &R, uint32_t &G, uint32_t &B) {
-    // 0, negatives (cannot occur) and NaN encode to 0
-    const bool pr = r > 0.f, pg = g > 0.f, pb = b > 0.f;
-    const int kr = pr ? srgb8_estimate(r) : 0, kg = pg ? srgb8_estimate(g) : 0, kb = pb ? srgb8_estimate(b) : 0;
-    const float r0 = w[kr], r1 = w[kr + 1], r2 = w[kr + 2], r3 = w[kr + 3];
-    const float g0 = w[kg], g1 = w[kg + 1], g2 = w[kg + 2], g3 = w[kg + 3];
-    const float b0 = w[kb], b1 = w[kb + 1], b2 = w[kb + 2], b3 = w[kb + 3];
-    const int nr = (int)(r >= r0) + (int)(r >= r1) + (int)(r >= r2) + (int)(r >= r3);
-    const int ng = (int)(g >= g0) + (int)(g >= g1) + (int)(g >= g2) + (int)(g >= g3);
-    const int nb = (int)(b >= b0) + (int)(b >= b1) + (int)(b >= b2) + (int)(b >= b3);
-    R = pr ? (uint32_t)(kr - 2 + nr) : 0u;
-    G = pg ? (uint32_t)(kg - 2 + ng) : 0u;
-    B = pb ? (uint32_t)(kb - 2 + nb) : 0u;
-    // (n - 1) > 2 unsigned <=> n is 0 or 4
-    const bool open_r = pr & ((uint32_t)(nr - 1) > 2u), open_g = pg & ((uint32_t)(ng - 1) > 2u), open_b = pb & ((uint32_t)(nb - 1) > 2u);
-    if (__builtin_amdgcn_ballot_w64(open_r | open_g | open_b) != 0ull) {
-        AIC_RARE_PATH();
-        if (open_r) R = srgb8_search(r, kr, w);
-        if (open_g) G = srgb8_search(g, kg, w);
-        if (open_b) B = srgb8_search(b, kb, w);
-    }
-}
 
 // lane event word (ev): what the lane needs next. Values below 4 mean "stepping" (the wave scheduler's test), with
 //   1  EV_FRESH   the first cube of a level was emitted by the event that set the level up: look it up without stepping

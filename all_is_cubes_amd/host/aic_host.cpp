@@ -596,6 +596,7 @@ static ImageInfo to_info(const aic_frame_info &fi, uint32_t w, uint32_t h) {
 
 Rendering HipRtRenderer::draw_rgba(const std::string &info_text) {  // renderer.rs:282-308
     aic_frame_desc f = make_frame();
+    if (bloom_) f.flags |= AIC_FRAME_BLOOM;  // (the library reports NO_BLOOM below unless it bloomed the frame)
     Rendering r;
     r.width = f.width;
     r.height = f.height;

@@ -306,6 +306,10 @@ class HipRtRenderer : public HeadlessRenderer {
     void update(const Cursor *cursor) override { (void)update_scene(cursor); }
     Rendering draw(const std::string &info_text) override { return draw_rgba(info_text); }
     Rendering draw_rgba(const std::string &info_text);
+    // Opt-in, off by default: draw_rgba blooms its frames as the reference's GPU renderer does (AIC_FRAME_BLOOM) whenever the world options'
+    // bloom_intensity is above zero, and such a Rendering does not report Flaws::NO_BLOOM. The info text is drawn over the bloomed frame.
+    void set_bloom(bool on) { bloom_ = on; }
+    bool bloom() const { return bloom_; }
     // Replaying a recorded frame (all_is_cubes_amd/replay.py, bench.py --workload replay:<file>): the world camera's
     // inverse_projection_view and exposure exactly as the recording has them, instead of the values derived from the
     // StandardCameras' view transform (which would be equal only up to rounding). nullptr: back to the cameras.
@@ -372,6 +376,7 @@ class HipRtRenderer : public HeadlessRenderer {
     double cam_override_inv_[16] = {0};
     float cam_override_exposure_ = 1.0f;
     bool had_cursor_ = false;
+    bool bloom_ = false;  // set_bloom
     // snapshot taken by update(): draw() must not touch the scene objects (headless.rs:33-39)
     Camera world_camera_, ui_camera_;
     float backdrop_[4] = {0, 0, 0, 0};

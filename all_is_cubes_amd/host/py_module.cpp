@@ -226,6 +226,8 @@ PYBIND11_MODULE(_host, m) {
             r.set_world_camera_override(m.data(), exposure);
         }, py::arg("inverse_projection_view"), py::arg("exposure") = 1.0f)
         .def("draw_rgba", [](HipRtRenderer &r, const std::string &t) { py::gil_scoped_release rel; return r.draw_rgba(t); }, py::arg("info_text") = "")
+        .def("set_bloom", &HipRtRenderer::set_bloom, py::arg("on"))
+        .def_property_readonly("bloom", &HipRtRenderer::bloom)
         .def("draw_rows_to_device", [](HipRtRenderer &r, uintptr_t ptr, uint32_t strip_rows, uint32_t n_parts, uint32_t part, bool counters, bool no_feedback) {
             py::gil_scoped_release rel;
             return r.draw_rows_to_device(reinterpret_cast<void *>(ptr), strip_rows, n_parts, part, counters, no_feedback);

@@ -97,7 +97,7 @@ typedef struct aic_options {
     int32_t debug_pixel_cost;
     int32_t tone_mapping;     /* ToneMappingOperator: 0 Clamp, 1 Reinhard */
     float maximum_intensity;  /* may be +inf */
-    float bloom_intensity;    /* only reported back as AIC_FLAW_NO_BLOOM */
+    float bloom_intensity;    /* reported back as AIC_FLAW_NO_BLOOM, unless a frame asks for AIC_FRAME_BLOOM */
     double view_distance;     /* already `repair()`ed: clamped to 1..10000 (graphics_options.rs:194-198) */
 } aic_options;
 
@@ -153,6 +153,18 @@ typedef struct aic_frame_desc {
 #define AIC_FRAME_NO_FEEDBACK 32u  /* neither use nor record the tile-cost feedback (the order in which this context hands out
                                     * work tiles, learnt from its previous frame of the same shape and camera): a "cold" single
                                     * frame, as the first frame of any sequence is */
+/* Bloom (ABI 3, backward compatible): the reference's GPU renderer blooms every frame, raytraced ones included (all-is-cubes-gpu
+ * raytrace_to_texture.rs:644-661, bloom.rs:41-60, mip_ping.rs:301-420); the raytracer itself reports AIC_FLAW_NO_BLOOM (renderer.rs:293-297).
+ * With this flag, and world options with bloom_intensity > 0, the frame's ColorBuf goes into context-owned scratch (per slot, allocated on
+ * first use: 16 bytes per pixel plus the mip chain, about 5 MB at 1080p), through the dual-filter chain (3 repetitions of up to 6 f16 levels)
+ * and is mixed into the scene before the tone map; the caller's buffer receives that RGBA8 and the frame does not report AIC_FLAW_NO_BLOOM.
+ * Mix in straight alpha: x = ps_mul(c, exposure) (1 - i) + (B / a) i, c and a = Rgba::from(ColorBuf), then the usual tone map and sRGB8
+ * encode; a pixel with a = 0 is unchanged (DESIGN.md "Bloom" has the chain and why). Honoured by aic_render, aic_render_submit / _wait and
+ * aic_render_submit_batch / _wait_batch; aic_frame_info.kernel_ms then covers the trace AND the bloom, and aic_render_wait /
+ * aic_stream_wait_frame order behind the composite. At bloom_intensity 0 the flag changes nothing.
+ * AIC_ERR_INVALID with AIC_FRAME_OUT_LINEAR / AIC_FRAME_OUT_COLORBUF; AIC_ERR_UNSUPPORTED with a partition of n_parts > 1 (bloom needs the
+ * whole frame), in aic_trace_patches and in every aic_multi_* render. The context stays usable after either. */
+#define AIC_FRAME_BLOOM 64u
 #define AIC_FRAME_PIXEL_CENTERS 4u /* one ray through each pixel centre, Viewport::normalize_fb_x/_y (viewport.rs:89-99),
                                     * as the text renderer casts them (sr.rs:400-472); default: the image path's patch
                                     * centres / antialiasing points (renderer.rs:424-451) */
@@ -164,7 +176,7 @@ typedef struct aic_frame_info {
     uint64_t n_inner;      /* in-bounds voxel lookups */
     uint64_t n_hits;       /* surfaces converted to light (Surface::to_light returned Some) */
     uint64_t n_light;      /* light texel fetches */
-    float kernel_ms;       /* HIP-event time of the trace kernel on the context's stream */
+    float kernel_ms;       /* HIP-event time of the trace kernel on the context's stream (with AIC_FRAME_BLOOM: the trace and the bloom) */
     float total_ms;        /* launch + read-back wall time of the call */
     uint32_t rows_rendered;
     uint32_t flaws;        /* AIC_FLAW_* */
@@ -370,6 +382,12 @@ int aic_probe_raycast(aic_ctx *ctx, const double origin[3], const double directi
 int aic_probe_powf(aic_ctx *ctx, const float *x, const float *y, uint32_t n, float *out);
 /* the device's f32::exp as distance_fog uses it (sr.rs:745-768): out[i] = e^x[i]; AIC_ERR_INVALID unless every |x[i]| < 88 */
 int aic_probe_expf(aic_ctx *ctx, const float *x, uint32_t n, float *out);
+/* The bloom post-process of AIC_FRAME_BLOOM on host memory: colorbuf = [height][width][4] ColorBuf l0, l1, l2, t (what AIC_FRAME_OUT_COLORBUF
+ * writes) -> out_rgba8 = [height][width][4], with options' bloom_intensity, tone_mapping and maximum_intensity and the world camera's exposure.
+ * Runs the chain and the composite even at intensity 0. out_mip0 (may be NULL) = the chain's result, mip 0, as f16 bits [T0y][T0x][4];
+ * mip0_size (may be NULL) = {T0x, T0y}: (ceil(width / 2), ceil(height / 2)) rounded up to a multiple of 2^levels. */
+int aic_probe_bloom(aic_ctx *ctx, uint32_t width, uint32_t height, const float *colorbuf, float exposure, const aic_options *options,
+                    uint8_t *out_rgba8, uint16_t *out_mip0, uint32_t mip0_size[2]);
 /* the device's PackedLight decode table (light/data.rs:301-354) */
 int aic_probe_light_lut(aic_ctx *ctx, float out[256]);
 

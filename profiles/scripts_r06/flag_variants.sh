@@ -8,7 +8,7 @@ mkdir -p variants/flags
 build() {
   local name=$1; shift
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Rpass-analysis=kernel-resource-usage "$@" -c $C/aic_trace.hip -o variants/flags/trace_$name.o > variants/flags/$name.log 2>&1 \
-    && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o variants/libaic_hip_$name.so variants/flags/trace_$name.o $C/aic_light.o $C/aic_abi.o $C/aic_multi.o \
+    && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o variants/libaic_hip_$name.so variants/flags/trace_$name.o $C/aic_light.o $C/aic_abi.o $C/aic_multi.o $(ls $C/aic_bloom.o 2>/dev/null) \
     && echo "built $name ($*)" || echo "FAILED $name: $(tail -2 variants/flags/$name.log)"
   rm -f variants/flags/trace_$name.o
 }

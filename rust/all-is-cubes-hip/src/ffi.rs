@@ -23,6 +23,7 @@ pub const AIC_FRAME_PIXEL_CENTERS: u32 = 4;
 pub const AIC_FRAME_OUT_LINEAR: u32 = 8;
 pub const AIC_FRAME_OUT_COLORBUF: u32 = 16;
 pub const AIC_FRAME_NO_FEEDBACK: u32 = 32;
+pub const AIC_FRAME_BLOOM: u32 = 64;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
 pub const AIC_MULTI_MAX_IN_FLIGHT: u32 = 8;
 pub const AIC_TUNE_QUEUES_SHIFT: u32 = 0;
@@ -237,6 +238,7 @@ unsafe extern "C" {
     pub fn aic_probe_raycast(ctx: *mut aic_ctx, origin: *const f64, direction: *const f64, use_bounds: c_int, lo: *const i32, hi: *const i32, include_exit: c_int, max_steps: u32, out: *mut aic_rc_step, n_out: *mut u32, ended: *mut c_int) -> c_int;
     pub fn aic_probe_powf(ctx: *mut aic_ctx, x: *const f32, y: *const f32, n: u32, out: *mut f32) -> c_int;
     pub fn aic_probe_expf(ctx: *mut aic_ctx, x: *const f32, n: u32, out: *mut f32) -> c_int;
+    pub fn aic_probe_bloom(ctx: *mut aic_ctx, width: u32, height: u32, colorbuf: *const f32, exposure: f32, options: *const aic_options, out_rgba8: *mut u8, out_mip0: *mut u16, mip0_size: *mut u32) -> c_int;
     pub fn aic_probe_light_lut(ctx: *mut aic_ctx, out: *mut f32) -> c_int;
     // light propagation on the device (Space::evaluate_light / fast_evaluate_light)
     pub fn aic_evaluate_light(ctx: *mut aic_ctx, layer: c_int, params: *const aic_light_params, info: *mut aic_light_info) -> c_int;

@@ -259,6 +259,8 @@ pub struct HipRtRenderer {
     had_cursor: bool,
     /// `Some(maximum_distance)`: the world layer's light is computed on the device (see `set_device_light`)
     device_light: Option<u8>,
+    /// frames are bloomed on the device (`AIC_FRAME_BLOOM`, see `set_bloom`)
+    bloom: bool,
 }
 
 // SAFETY: the contexts are only used through `&mut self`; libaic_hip keeps no thread affinity besides hipSetDevice,
@@ -343,7 +345,20 @@ impl HipRtRenderer {
                     .ok_or_else(|| format!("aic_create_multi failed with status {status}"))?,
             ),
         };
-        Ok(Self { device, cameras, size_policy, layers: Layers::default(), had_cursor: false, device_light: None })
+        Ok(Self { device, cameras, size_policy, layers: Layers::default(), had_cursor: false, device_light: None, bloom: false })
+    }
+
+    /// Blooms the frames drawn from now on as the reference's GPU renderer does (`AIC_FRAME_BLOOM`; all-is-cubes-gpu raytrace_to_texture.rs:644-661)
+    /// whenever the world options' `bloom_intensity` is above zero; such a `Rendering` does not report `Flaws::NO_BLOOM`. Off by default.
+    /// A multi-device renderer ignores it and keeps reporting `NO_BLOOM`.
+    pub fn set_bloom(&mut self, on: bool) {
+        self.bloom = on;
+    }
+
+    /// Whether frames are drawn with `AIC_FRAME_BLOOM`: [`Self::set_bloom`] on a single-device renderer (`aic_multi_render` has no bloom: device 0
+    /// would first need every device's strips as ColorBufs).
+    fn bloom_applies(&self) -> bool {
+        self.bloom && matches!(self.device, Device::One(_))
     }
 
     /// Hands the world space's light over to the device: from now on `update` forwards block changes
@@ -453,7 +468,7 @@ impl HipRtRenderer {
                 [backdrop.red().into_inner(), backdrop.green().into_inner(), backdrop.blue().into_inner(), backdrop.alpha().into_inner()]
             },
             partition: ffi::aic_partition::default(),
-            flags: 0,
+            flags: if self.bloom_applies() { ffi::AIC_FRAME_BLOOM } else { 0 },
             tuning: 0, // the library's choices (tile queues, kernel variant); `HipInfo` reports what ran
         };
         (viewport, frame)
@@ -489,8 +504,8 @@ impl HipRtRenderer {
         if info.flaws & ffi::AIC_FLAW_UNSUPPORTED != 0 {
             flaws |= Flaws::UNSUPPORTED;
         }
-        if options.bloom_intensity != ZeroOne::ZERO {
-            flaws |= Flaws::NO_BLOOM; // renderer.rs:293-297
+        if options.bloom_intensity != ZeroOne::ZERO && !self.bloom_applies() {
+            flaws |= Flaws::NO_BLOOM; // renderer.rs:293-297 (a bloomed frame has what the reference's GPU renderer adds)
         }
         if self.had_cursor {
             flaws |= Flaws::NO_CURSOR; // renderer.rs:298-300

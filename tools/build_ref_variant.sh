@@ -12,7 +12,12 @@ F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC"
 /opt/rocm/bin/hipcc $F -x hip -c $C/aic_abi.cpp -o $D/abi.o &
 /opt/rocm/bin/hipcc $F -c $C/aic_light.hip -o $D/light.o &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -x hip -c $C/aic_multi.cpp -o $D/multi.o &
+OBJS="$D/trace.o $D/light.o $D/abi.o $D/multi.o"
+if [ -f $C/aic_bloom.hip ]; then  # (revisions from the bloom post-process on)
+  /opt/rocm/bin/hipcc $F -c $C/aic_bloom.hip -o $D/bloom.o &
+  OBJS="$OBJS $D/bloom.o"
+fi
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o variants/libaic_hip_$NAME.so $D/trace.o $D/light.o $D/abi.o $D/multi.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -Wl,--no-undefined -o variants/libaic_hip_$NAME.so $OBJS
 rm -f $D/*.o
 echo "built variants/libaic_hip_$NAME.so from $REV"
