@@ -1,5 +1,5 @@
 // aic_light.h -- device-side data layout of the light updater, shared by the host code
-// (aic_light_host.inc) and the gather kernel (aic_light.hip).
+// (aic_light_host.cpp) and the gather kernel (aic_light.hip).
 //
 // The reference's light updater (all-is-cubes/src/space/light/updater.rs) pops cubes off a priority queue,
 // computes each cube's new light by walking a precomputed tree of ray bundles ("chart") through the space,
@@ -94,6 +94,10 @@ struct LightJob {
     uint32_t n_front;          // 1 + the number of positions whose parent has more than one child
     float *valpha;             // [waves][n_tree]: the alpha a visited bundle is entered with
 };
+
+// The LDS words of the wave-per-cube kernel's bitmaps (4 + 2 + 1 bits per tree position, each bitmap in whole words): the
+// launch is sized by it (aic_light.hip), and so is the number of waves a CU can hold (aic_light_host.cpp).
+inline uint32_t light_wave_bitmap_words(uint32_t n_tree) { return ((4u * n_tree + 31u) / 32u) + ((2u * n_tree + 31u) / 32u) + ((n_tree + 31u) / 32u); }
 
 void launch_compute_light(const LightJob &job, hipStream_t stream);
 void launch_compute_light_waves(const LightJob &job, uint32_t n_blocks, uint32_t threads_per_cube, hipStream_t stream);

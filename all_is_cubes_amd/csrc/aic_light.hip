@@ -1221,10 +1221,9 @@ void launch_compute_light(const LightJob &job, hipStream_t stream) {
 
 namespace {
 constexpr uint32_t kLightLdsQueueBudget = 96u << 10;  // dynamic LDS a small-batch block may take for bitmaps + queue (one block per CU; 17.5 KB are static)
-uint32_t light_wave_bitmap_words(const LightJob &job) { return ((4u * job.n_tree + 31u) / 32u) + ((2u * job.n_tree + 31u) / 32u) + ((job.n_tree + 31u) / 32u); }
-uint32_t light_wave_ldsq_bytes(const LightJob &job) { return ((light_wave_bitmap_words(job) + 3u) & ~3u) * 4u + job.n_front * 16u; }
+uint32_t light_wave_ldsq_bytes(const LightJob &job) { return ((light_wave_bitmap_words(job.n_tree) + 3u) & ~3u) * 4u + job.n_front * 16u; }
 uint32_t light_wave_lds(const LightJob &job) {
-    const uint32_t lds = light_wave_bitmap_words(job) * 4u;
+    const uint32_t lds = light_wave_bitmap_words(job.n_tree) * 4u;
     // more dynamic LDS than the default limit needs an opt-in, per device
     static uint32_t lds_allowed[64] = {0};
     int dev = 0;

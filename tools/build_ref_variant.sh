@@ -13,6 +13,10 @@ F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC"
 /opt/rocm/bin/hipcc $F -c $C/aic_light.hip -o $D/light.o &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -x hip -c $C/aic_multi.cpp -o $D/multi.o &
 OBJS="$D/trace.o $D/light.o $D/abi.o $D/multi.o"
+if [ -f $C/aic_light_host.cpp ]; then  # (revisions from the light host code's own translation unit on; before, aic_abi.cpp included it)
+  /opt/rocm/bin/hipcc $F -x hip -c $C/aic_light_host.cpp -o $D/lighthost.o &
+  OBJS="$OBJS $D/lighthost.o"
+fi
 if [ -f $C/aic_bloom.hip ]; then  # (revisions from the bloom post-process on)
   /opt/rocm/bin/hipcc $F -c $C/aic_bloom.hip -o $D/bloom.o &
   OBJS="$OBJS $D/bloom.o"
