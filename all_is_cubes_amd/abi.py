@@ -22,6 +22,8 @@ MAX_IN_FLIGHT = 32  # AIC_MAX_IN_FLIGHT
 FLAW_UNSUPPORTED, FLAW_NO_BLOOM = 1, 2
 FRAME_COUNTERS, FRAME_AUX, FRAME_PIXEL_CENTERS, FRAME_OUT_LINEAR, FRAME_OUT_COLORBUF, FRAME_NO_FEEDBACK = 1, 2, 4, 8, 16, 32
 FRAME_BLOOM = 64  # AIC_FRAME_BLOOM: bloom the frame when the world options' bloom_intensity > 0 (RGBA8 output, whole frames)
+RAYS_NO_SKY, RAYS_DEVICE = 128, 256  # aic_trace_rays only: include_sky = false; rays / out / aux are device pointers
+MAX_RAYS = 2048 * 65535  # rays in one aic_trace_rays call
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
@@ -53,7 +55,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
@@ -183,6 +185,7 @@ def load() -> C.CDLL:
         lib.aic_render_submit_batch.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(FrameDesc), C.POINTER(C.c_void_p), C.c_uint32]
         lib.aic_render_wait_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FrameInfo)]
         lib.aic_trace_patches.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
+        lib.aic_trace_rays.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_read_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -474,6 +477,27 @@ class Context:
         info = FrameInfo()
         self._check(self._lib.aic_trace_patches(self._h, C.byref(frame), len(r), _ptr(r), _ptr(out), _ptr(aux), C.byref(info)))
         return {"rgba8": out, "aux": aux, "info": info}
+
+    def trace_rays(self, layer: int, rays, include_sky: bool = True, flags: int = 0, exposure: float = 1.0, want_aux: bool = False):
+        """SpaceRaytracer::trace_ray for a batch of world-space rays [n,6] = (origin xyz, direction xyz) against the layer's space (aic_trace_rays).
+        `flags`: FRAME_OUT_COLORBUF / FRAME_OUT_LINEAR (float [n,4]; neither: RGBA8 [n,4]), FRAME_COUNTERS. Returns dict(rgba8, aux or None, info)."""
+        r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        flags = (int(flags) & ~RAYS_DEVICE) | (0 if include_sky else RAYS_NO_SKY)
+        out = np.zeros((len(r), 4), np.float32 if flags & (FRAME_OUT_LINEAR | FRAME_OUT_COLORBUF) else np.uint8)
+        aux = np.zeros(len(r), PIXEL_AUX_DTYPE) if want_aux else None
+        info = FrameInfo()
+        self._check(self._lib.aic_trace_rays(self._h, int(layer), len(r), _ptr(r), flags, float(exposure), _ptr(out), _ptr(aux), C.byref(info)))
+        return {"rgba8": out, "aux": aux, "info": info}
+
+    def trace_rays_device(self, layer: int, n: int, rays_ptr: int, out_ptr: int, aux_ptr: int = 0, include_sky: bool = True, flags: int = 0,
+                          exposure: float = 1.0) -> FrameInfo:
+        """The same with the rays ([n,6] f64), the results and (aux_ptr != 0) the [n] first-hit records in HBM on the context's device, e.g. torch tensors'
+        data_ptr(): no staging copy, no read-back (AIC_RAYS_DEVICE). Returns once the batch is done."""
+        flags = int(flags) | RAYS_DEVICE | (0 if include_sky else RAYS_NO_SKY)
+        info = FrameInfo()
+        self._check(self._lib.aic_trace_rays(self._h, int(layer), int(n), C.c_void_p(rays_ptr), flags, float(exposure), C.c_void_p(out_ptr),
+                                             C.c_void_p(aux_ptr or None), C.byref(info)))
+        return info
 
     def render_submit(self, frame: FrameDesc, device_ptr: int, slot: int) -> None:
         """Queues a frame on `slot` (0..MAX_IN_FLIGHT-1); returns without waiting (aic_render_submit)."""

@@ -818,8 +818,18 @@ bool cameras_close(const double a[16], const double b[16]) {
 // Queues the frames of one launch on a slot's stream: counters reset, optional UI pre-pass, the trace. No waiting. k = 1: a plain frame. k = 2, 4, 8
 // (aic_render_submit_batch): frames of the same shape, partition and flags under the scene and options as they stand, each with its own cameras, backdrop,
 // output buffer, counters and cost record -- traced side by side by ONE launch per pass (DevSub), every persistent workgroup bound to one of them.
+// A ray batch (aic_trace_rays): n world-space rays on the device replace the camera; the space traced is the launch's world layer (the caller swaps it in, as
+// aic_render_orthographic does), labelled `layer` in first-hit records, which go to `aux_target` when the caller's own device buffer receives them.
+struct RayBatch {
+    const double *rays;
+    uint32_t n;
+    bool no_sky;
+    uint32_t layer;
+    DevAux *aux_target;
+};
 int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t *const *out_devices, uint32_t slot, bool allow_aux, const double *patches = nullptr,
-                  uint32_t n_patches = 0, const DevOrthoView *ortho = nullptr, int32_t ortho_n = 0) {
+                  uint32_t n_patches = 0, const DevOrthoView *ortho = nullptr, int32_t ortho_n = 0, const RayBatch *rb = nullptr) {
+    if (rb) n_patches = rb->n;
     aic_ctx::FrameSlot &fs = c->slots[slot];
     const aic_frame_desc *f = &frames[0];
     fs.t_begin = std::chrono::steady_clock::now();
@@ -834,13 +844,13 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     if (f->flags & AIC_FRAME_BLOOM) {  // (checked before anything is queued: the context stays as it was)
         if (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) return fail(c, AIC_ERR_INVALID, "aic_render: AIC_FRAME_BLOOM is for RGBA8 output only");
         if (part.n_parts > 1u) return fail(c, AIC_ERR_UNSUPPORTED, "aic_render: AIC_FRAME_BLOOM needs the whole frame (partition.n_parts = 1)");
-        if (patches || ortho_n) return fail(c, AIC_ERR_UNSUPPORTED, "AIC_FRAME_BLOOM: not for patches or orthographic views");
+        if (patches || ortho_n || rb) return fail(c, AIC_ERR_UNSUPPORTED, "AIC_FRAME_BLOOM: not for patches, rays or orthographic views");
     }
     const uint32_t local_rows = aic_partition_rows(f->height, &part);
     const size_t npix = (size_t)f->width * local_rows;
     for (uint32_t j = 0; j < k; j++)
         if (npix && !out_devices[j]) return fail(c, AIC_ERR_INVALID, "aic_render: output buffer is null");
-    if (!patches)
+    if (!patches && !rb)
         for (uint32_t j = 0; j < k; j++) dump_record(c, DUMP_FRAME, slot, {{&frames[j], sizeof(frames[j])}});
     if (f->width > 65535u || local_rows > 65535u) return fail(c, AIC_ERR_INVALID, "aic_render: frame dimensions above 65535 are not supported");
     for (uint32_t j = 0; j < k; j++)  // Camera::exposure() is a PositiveSign<f32> (camera_struct.rs:365-367)
@@ -866,6 +876,9 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     F.n_patches = n_patches;
     F.ortho = ortho;
     F.ortho_n = ortho_n;
+    F.rays = rb ? rb->rays : nullptr;
+    F.bare_trace = (ortho_n || rb) ? 1 : 0;
+    if (rb) hl[1].present = 0;  // trace_ray knows one space: no UI layering (and, below, one ray per result whatever `antialiasing` says)
     if (ortho_n) {
         // render_orthographic traces with GraphicsOptions::UNALTERED_COLORS and no UI layer (ortho.rs:44, 103-131)
         hl[1].present = 0;
@@ -875,7 +888,7 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
         hl[0].exposure = 1.0f;
         flaws = 0;
     }
-    F.antialias = (hl[0].opt.antialiasing == 2 && !F.pixel_centers) ? 1 : 0;
+    F.antialias = (hl[0].opt.antialiasing == 2 && !F.pixel_centers && !rb) ? 1 : 0;
     F.maximum_intensity = hl[0].opt.maximum_intensity;
     F.tone_mapping = hl[0].opt.tone_mapping;
     F.strip_rows = part.strip_rows;
@@ -929,8 +942,12 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     if (!npix) return AIC_OK;
     hipError_t e;
     if (want_aux) {
-        if ((e = c->aux.ensure(npix)) != hipSuccess) return hip_fail(c, "alloc aux", e);
-        F.aux = c->aux.p;
+        if (rb && rb->aux_target) {
+            F.aux = rb->aux_target;
+        } else {
+            if ((e = c->aux.ensure(npix)) != hipSuccess) return hip_fail(c, "alloc aux", e);
+            F.aux = c->aux.p;
+        }
     }
     const bool ui = hl[1].present != 0;
     const uint32_t n_tiles = F.macros_x * F.macros_y;  // the feedback works on macro tiles
@@ -941,7 +958,7 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     const int super_env = (int)((f->tuning >> AIC_TUNE_SUPER_SHIFT) & 31u) - 1;
     uint32_t n_queues = queues_env > 0 ? (uint32_t)queues_env : (uint32_t)c->n_cus / 32u;
     if (n_queues > kMaxTileQueues) n_queues = kMaxTileQueues;
-    if (n_queues < 2u || patches || ortho_n || !n_tiles) n_queues = 0u;
+    if (n_queues < 2u || patches || rb || ortho_n || !n_tiles) n_queues = 0u;
     const uint32_t macro_log2 = F.macro >= 16 ? 4u : (F.macro >= 8 ? 3u : (F.macro >= 4 ? 2u : (F.macro >= 2 ? 1u : 0u)));
     const uint32_t tile_log2 = F.tile >= 16 ? 4u : 3u;
     // default super-block edge: the largest power of two within an eighth of the (local) image height -- 128 pixels at 1080p, 256 at 4K, ~135 blocks
@@ -952,7 +969,7 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     const uint32_t sb_shift = super_env >= 0 ? (uint32_t)std::min(super_env, 12) : (sb_px_log2 > macro_log2 + tile_log2 ? sb_px_log2 - macro_log2 - tile_log2 : 0u);
     // tile order for a frame from the cost the sub-frame's previous frame recorded, if that frame
     // had the same shape (else index order); the record was turned into an order, and cleared, behind that frame
-    const bool use_feedback = c->sw.feedback && n_tiles && !patches && !ortho_n && !(f->flags & AIC_FRAME_NO_FEEDBACK);
+    const bool use_feedback = c->sw.feedback && n_tiles && !patches && !rb && !ortho_n && !(f->flags & AIC_FRAME_NO_FEEDBACK);
     const uint32_t sig[4] = {f->width, local_rows, (part.n_parts << 16) | part.part, (part.strip_rows << 8) | (F.macro << 4) | (F.tile >> 3)};
     uint32_t order_key[6] = {sig[0], sig[1], sig[2], sig[3], n_queues, sb_shift};
     const bool ordered = use_feedback || n_queues;  // the frames take their tiles through an order (else: the plain counter, index order)
@@ -1026,7 +1043,7 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
             S.acc_buf = sb.acc.p;
         }
     }
-    if (!patches && !ortho_n) {
+    if (!patches && !rb && !ortho_n) {
         // Viewport's pixel edges (viewport.rs:104-113), once per frame shape: x / width * 2 - 1 and -(y / height * 2 - 1) in the reference's own f64
         // operations (this file is built with -ffp-contract=off, like the kernels), so that the kernel reads them instead of dividing per ray
         if (fs.edges_w != f->width || fs.edges_h != f->height || !fs.edges.p) {
@@ -1070,6 +1087,7 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
     if (ui) {
         F.pass = 1;
+        F.hit_layer = 1u;
         F.use_init = 0;
         F.layer = hl[1];
         F.layer_transparency = hl[1].opt.transparency;
@@ -1091,7 +1109,8 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
         for (uint32_t j = 0; j < k; j++) HIP_TRY(c, hipMemsetAsync(&fs.sub[j].counters.p->tile_next, 0, sizeof(uint32_t), fs.stream));
         F.use_init = 1;
     }
-    F.pass = 0;
+    F.pass = (rb && rb->no_sky) ? 2 : 0;
+    F.hit_layer = rb ? rb->layer : 0u;
     for (uint32_t j = 0; j < k; j++) {
         std::memcpy(F.sub[j].inv, ortho_n ? hl[0].inv : frames[j].world.inverse_projection_view, sizeof(F.sub[j].inv));
 #ifndef AIC_PROFILE
@@ -1166,7 +1185,7 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
         for (uint32_t j = 0; j < k; j++) cleared = (hipMemsetAsync(fs.sub[j].counters.p, 0, sizeof(DevCounters), fs.stream) == hipSuccess) && cleared;
     }
     for (uint32_t j = 0; j < k; j++) fs.sub[j].counters_clean = cleared;
-    if (want_aux) c->aux_records = npix;
+    if (want_aux && !(rb && rb->aux_target)) c->aux_records = npix;
     return AIC_OK;
 }
 int submit_frame(aic_ctx *c, const aic_frame_desc *f, uint32_t *out_device, uint32_t slot, bool allow_aux, const double *patches = nullptr,
@@ -1402,6 +1421,58 @@ int aic_trace_patches(aic_ctx *c, const aic_frame_desc *f, uint32_t n, const dou
     if (aux) {
         HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
     }
+    if (info) info->rows_rendered = n;
+    return AIC_OK;
+}
+
+int aic_trace_rays(aic_ctx *c, int layer, uint32_t n, const double *rays, uint32_t flags, float exposure, void *out, aic_pixel_aux *aux,
+                   aic_frame_info *info) {
+    if (!c || !valid_layer(layer) || (n && (!rays || !out))) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (flags & AIC_FRAME_BLOOM) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_rays: AIC_FRAME_BLOOM needs a whole frame");
+    if ((flags & AIC_FRAME_OUT_LINEAR) && (flags & AIC_FRAME_OUT_COLORBUF)) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: AIC_FRAME_OUT_LINEAR and AIC_FRAME_OUT_COLORBUF exclude each other");
+    if (!(exposure >= 0.f)) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: exposure is negative or NaN");
+    if (!n) return AIC_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (!c->layers[layer].present) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: no space uploaded for this layer");
+    const bool on_device = (flags & AIC_RAYS_DEVICE) != 0;
+    const size_t px_words = (flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) ? 4 : 1;
+    // (the kernel fetches a ray with 16-byte loads and stores a float result as one: an allocation's start, or any whole number of rays / results into it)
+    if (on_device && (((uintptr_t)rays & 15u) || ((uintptr_t)out & (px_words * 4u - 1u)) || ((uintptr_t)aux & 7u)))
+        return fail(c, AIC_ERR_INVALID, "aic_trace_rays: AIC_RAYS_DEVICE wants rays at a 16-byte boundary, out and aux at their element's");
+    // the batch is laid out as an image of up to 2048 columns, like a patch batch; pixel i of that image traces rays[i]
+    aic_frame_desc g;
+    std::memset(&g, 0, sizeof(g));
+    g.width = n < 2048u ? n : 2048u;
+    g.height = (n + g.width - 1u) / g.width;
+    if (g.height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: more than 2048 x 65535 rays in one call");
+    g.partition = aic_partition{0, 1, 0, 0};
+    g.flags = (flags & (AIC_FRAME_COUNTERS | AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) | (aux ? AIC_FRAME_AUX : 0u);
+    g.tuning = flags & (3u << AIC_TUNE_VARIANT_SHIFT);  // (the variant bits sit above every flag: measurement and tests ask for a production variant here)
+    g.world.exposure = exposure;
+    g.ui.exposure = 1.0f;
+    hipError_t e;
+    RayBatch rb{rays, n, (flags & AIC_RAYS_NO_SKY) != 0, (uint32_t)layer, on_device ? reinterpret_cast<DevAux *>(aux) : nullptr};
+    uint32_t *target = (uint32_t *)out;
+    hipStream_t stream = c->slots[0].stream;
+    if (!on_device) {
+        if ((e = c->out.ensure((size_t)n * px_words)) != hipSuccess) return hip_fail(c, "alloc output", e);
+        if ((e = c->staging.ensure((size_t)n * 48)) != hipSuccess) return hip_fail(c, "alloc staging", e);
+        HIP_TRY(c, hipMemcpyAsync(c->staging.p, rays, (size_t)n * 48, hipMemcpyHostToDevice, stream));
+        rb.rays = (const double *)c->staging.p;
+        target = c->out.p;
+    }
+    // the rays are traced as the WORLD layer of the launch, whatever layer holds the space (aic_render_orthographic does the same)
+    const bool swap_layers = layer != AIC_LAYER_WORLD;
+    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
+    int rc = submit_frames(c, 1, &g, &target, 0, true, nullptr, 0, nullptr, 0, &rb);
+    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
+    if (rc != AIC_OK) return rc;
+    if (!on_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, (size_t)n * px_words * 4, hipMemcpyDeviceToHost, stream));
+    rc = wait_frame(c, 0, info, !on_device);
+    if (rc != AIC_OK) return rc;
+    if (aux && !on_device) HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
     if (info) info->rows_rendered = n;
     return AIC_OK;
 }

@@ -165,14 +165,17 @@ struct DevFrame {
     uint32_t macros_x, macros_y;  // macro-tile grid; tile_order / tile_cost are indexed by macro tile
     uint32_t n_cus;          // compute units of the device (sizes the persistent grid)
     uint32_t tiles_per_wave; // host-side: tiles a wave should get on average when the frame is smaller than the chip (1 = latency, 4 = streamed frames)
-    int32_t pass;            // 0: final pass (world layer + encode); 1: UI pre-pass
+    int32_t pass;            // 0: final pass (world layer + encode); 1: UI pre-pass; 2: final pass traced with include_sky = false (aic_trace_rays, AIC_RAYS_NO_SKY)
+    uint32_t hit_layer;      // the layer a first-hit record of this launch names (DevAux::layer): 1 in the UI pre-pass, 0 in the final pass, the layer traced in a ray batch
     int32_t use_init;        // final pass: start each sample from acc_buf (written by the UI pre-pass)
     int32_t pixel_centers;   // AIC_FRAME_PIXEL_CENTERS
     int32_t out_mode;        // 0 sRGB RGBA8 (4 B/pixel); 1 linear Rgba f32x4; 2 ColorBuf f32x4 (16 B/pixel)
     const DevOrthoView *ortho;  // aic_render_orthographic: the views (device memory), else null
     int32_t ortho_n;
     const double *patches;   // aic_trace_patches: [n_patches][4] NDC rectangles replacing the pixel grid (pixel i = row-major index)
-    uint32_t n_patches;
+    uint32_t n_patches;      // ... or the rays of a ray batch; 0: a whole image. Pixels of the batch's last row from here on do not exist
+    int32_t bare_trace;      // the launch is trace_ray and nothing of the image path's layer tail (no NO_WORLD_TO_SHOW paint): orthographic views, ray batches
+    const double *rays;      // aic_trace_rays: [n_patches][6] world-space rays, origin xyz then direction xyz, replacing the camera (pixel i = row-major index), else null
     DevAux *aux;             // [local_rows][width] or null (the recording variants; single frames only)
     // XCD-local tile queues (0: one queue for the whole chip, counters->tile_next). tile_order is then n_queues segments, segment q =
     // positions queue_start[q] .. queue_start[q+1] of it (queue_start: device array of n_queues + 1), each costliest first. A macro

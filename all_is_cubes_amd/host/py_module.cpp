@@ -220,6 +220,23 @@ PYBIND11_MODULE(_host, m) {
         .def("update", [](HipRtRenderer &r, py::object cursor) { Cursor c; return r.update_scene(cursor.is_none() ? nullptr : &c); }, py::arg("cursor") = py::none())
         .def("draw", [](HipRtRenderer &r, const std::string &t) { py::gil_scoped_release rel; return r.draw(t); }, py::arg("info_text") = "")
         .def("draw_text", [](HipRtRenderer &r, const std::string &le) { py::gil_scoped_release rel; return r.draw_text(le); }, py::arg("line_ending") = "\n")
+        .def("trace_rays", [](HipRtRenderer &r, int layer, py::array_t<double, py::array::c_style | py::array::forcecast> rays, bool include_sky) {
+            // rays [n, 6] = origin xyz, direction xyz -> dict(colorbuf [n, 4] f32, hits [n, sizeof(aic_pixel_aux)] u8 -- view it as abi.PIXEL_AUX_DTYPE --, info)
+            if (rays.size() % 6 != 0) throw std::invalid_argument("rays: [n, 6] doubles");
+            std::vector<Ray> v((size_t)rays.size() / 6);
+            if (!v.empty()) std::memcpy(&v[0], rays.data(), v.size() * sizeof(Ray));
+            HipRtRenderer::RayResults res;
+            { py::gil_scoped_release rel; res = r.trace_rays(layer, v, include_sky); }
+            py::array_t<float> colors({(py::ssize_t)v.size(), (py::ssize_t)4});
+            py::array_t<uint8_t> hits({(py::ssize_t)v.size(), (py::ssize_t)sizeof(aic_pixel_aux)});
+            if (!v.empty()) {
+                std::memcpy(colors.mutable_data(), res.colors.data(), v.size() * 16);
+                std::memcpy(hits.mutable_data(), res.hits.data(), v.size() * sizeof(aic_pixel_aux));
+            }
+            py::dict d;
+            d["colorbuf"] = colors; d["hits"] = hits; d["info"] = res.info;
+            return d;
+        }, py::arg("layer"), py::arg("rays"), py::arg("include_sky") = true)
         .def("set_world_camera_override", [](HipRtRenderer &r, py::object inv, float exposure) {
             if (inv.is_none()) { r.set_world_camera_override(nullptr, 1.0f); return; }
             const auto m = inv.cast<std::array<double, 16>>();

@@ -181,7 +181,7 @@ typedef struct aic_frame_info {
     uint32_t rows_rendered;
     uint32_t flaws;        /* AIC_FLAW_* */
     uint32_t variant;      /* AIC_VARIANT_*: the trace kernel variant that traced the frame's world pass (ABI 3) */
-    uint32_t tile_queues;  /* tile queues the frame's work tiles were dealt to (0: the single counter -- patch batches, orthographic views) */
+    uint32_t tile_queues;  /* tile queues the frame's work tiles were dealt to (0: the single counter -- patch and ray batches, orthographic views) */
 } aic_frame_info;
 
 /* Optional per-pixel record (N4 "other accumulators": first-hit id and depth): the first
@@ -288,6 +288,23 @@ int aic_render_wait_batch(aic_ctx *ctx, uint32_t slot, uint32_t n_frames, aic_fr
  * Only the cameras, backdrop and flags of `frame` are used. */
 int aic_trace_patches(aic_ctx *ctx, const aic_frame_desc *frame, uint32_t n, const double *rects, void *out_rgba8,
                       aic_pixel_aux *aux, aic_frame_info *info);
+/* replaces: SpaceRaytracer::trace_ray(ray, accumulator, include_sky) (sr.rs:113-120) for a batch of world-space rays against ONE layer's space:
+ * no camera, no pixel grid -- picking rays that are not pixels, panoramic / fisheye / cube-map projections made by the host, light probes, line-of-sight
+ * batches. rays = [n][6] {origin x, y, z, direction x, y, z}; each is traced as trace_ray_impl(ray, ColorBuf, include_sky, allow_ray_bounce = true) under
+ * the layer's options and nothing of the image path: one ray per result whatever `antialiasing` says, no UI / world layering, no backdrop, no
+ * "no world to show" paint. A direction is taken as given, not normalised (t runs in units of it); zero, NaN and infinite components are legal and
+ * trace what the reference traces for them (no steps, the sky). LightingOption::Bounce seeds its generator from the direction's bits (sr.rs:165-178).
+ * flags: AIC_FRAME_OUT_COLORBUF (out = [n] float[4], what trace_ray leaves in its accumulator) | AIC_FRAME_OUT_LINEAR (out = [n] float[4],
+ * Rgba::from(ColorBuf)) | neither (out = [n] sRGB RGBA8 under the layer's tone mapping and `exposure`) | AIC_FRAME_COUNTERS | AIC_RAYS_NO_SKY |
+ * AIC_RAYS_DEVICE; other AIC_FRAME_* bits are ignored. Bits 9-10 (AIC_TUNE_VARIANT_SHIFT) ask for a production variant of the trace kernel as
+ * aic_frame_desc.tuning does (measurement and tests; 0: by the batch's size; any value gives the same results). aux (may be NULL) = [n] first-hit records, `layer` = the layer traced; info as for
+ * aic_trace_patches (rows_rendered = n). The call returns when the batch is done. AIC_ERR_INVALID: a frame still occupies slot 0, a layer without a
+ * space, more than 2048 x 65535 rays, a NaN or negative exposure, both float flags; AIC_ERR_UNSUPPORTED: AIC_FRAME_BLOOM. n = 0 is AIC_OK. */
+#define AIC_RAYS_NO_SKY 128u /* include_sky = false: a ray that hits nothing ends transparent, and fog takes no sky light (sr.rs:145-161, 228-237) */
+#define AIC_RAYS_DEVICE 256u /* rays, out and aux are device pointers on the context's device (no staging copy, no read-back); rays at a 16-byte
+                              * boundary -- an allocation's start, or any whole number of rays into one */
+int aic_trace_rays(aic_ctx *ctx, int layer, uint32_t n, const double *rays, uint32_t flags, float exposure, void *out, aic_pixel_aux *aux,
+                   aic_frame_info *info);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

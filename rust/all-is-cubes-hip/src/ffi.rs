@@ -24,6 +24,8 @@ pub const AIC_FRAME_OUT_LINEAR: u32 = 8;
 pub const AIC_FRAME_OUT_COLORBUF: u32 = 16;
 pub const AIC_FRAME_NO_FEEDBACK: u32 = 32;
 pub const AIC_FRAME_BLOOM: u32 = 64;
+pub const AIC_RAYS_NO_SKY: u32 = 128;
+pub const AIC_RAYS_DEVICE: u32 = 256;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
 pub const AIC_MULTI_MAX_IN_FLIGHT: u32 = 8;
 pub const AIC_TUNE_QUEUES_SHIFT: u32 = 0;
@@ -214,6 +216,7 @@ unsafe extern "C" {
     pub fn aic_assemble_strips(ctx: *mut aic_ctx, gathered_device: *const c_void, out_device: *mut c_void, width: u32, height: u32, strip_rows: u32, n_parts: u32) -> c_int;
     pub fn aic_assemble_strips_async(ctx: *mut aic_ctx, gathered_device: *const c_void, out_device: *mut c_void, width: u32, height: u32, strip_rows: u32, n_parts: u32) -> c_int;
     pub fn aic_assemble_strips_on(ctx: *mut aic_ctx, gathered_device: *const c_void, out_device: *mut c_void, width: u32, height: u32, strip_rows: u32, n_parts: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn aic_trace_rays(ctx: *mut aic_ctx, layer: c_int, n: u32, rays: *const f64, flags: u32, exposure: f32, out: *mut c_void, aux: *mut aic_pixel_aux, info: *mut aic_frame_info) -> c_int;
     pub fn aic_read_aux(ctx: *mut aic_ctx, out: *mut aic_pixel_aux, n_records: u64) -> c_int;
     pub fn aic_synchronize(ctx: *mut aic_ctx) -> c_int;
     pub fn aic_stream(ctx: *mut aic_ctx) -> *mut c_void;

@@ -560,6 +560,31 @@ impl HipRtRenderer {
         &self.cameras
     }
 
+    /// `SpaceRaytracer::trace_ray(ray, accumulator, include_sky)` (sr.rs:113-120) for a batch of world-space rays against the
+    /// space of `layer` (`ffi::AIC_LAYER_WORLD` / `ffi::AIC_LAYER_UI`) as last uploaded by `update`: no camera, no layering, one
+    /// ray per result. `rays[i]` = origin x, y, z, direction x, y, z; a direction is taken as given, not normalised. Returns,
+    /// per ray, the `ColorBuf` `trace_ray` leaves in its accumulator (light r, g, b and transmittance) and the first-hit
+    /// record (`hit == 0`: none; `t_distance` in units of the direction).
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer (ray batches are not sharded), a layer without a space, or more than 2048 x 65535 rays.
+    pub fn trace_rays(&mut self, layer: core::ffi::c_int, rays: &[[f64; 6]], include_sky: bool) -> Result<(Vec<[f32; 4]>, Vec<ffi::aic_pixel_aux>), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("trace_rays needs a single-device renderer") };
+        let n = u32::try_from(rays.len()).expect("more than u32::MAX rays");
+        let mut colors = vec![[0.0f32; 4]; rays.len()];
+        let mut hits = vec![ffi::aic_pixel_aux::default(); rays.len()];
+        let mut info = ffi::aic_frame_info::default();
+        let flags = ffi::AIC_FRAME_OUT_COLORBUF | if include_sky { 0 } else { ffi::AIC_RAYS_NO_SKY };
+        // SAFETY: the context is live; the three buffers hold `n` elements each and outlive the call, which returns when the batch is done
+        self.device.check(unsafe {
+            ffi::aic_trace_rays(ctx.as_ptr(), layer, n, rays.as_ptr().cast(), flags, 1.0, colors.as_mut_ptr().cast(), hits.as_mut_ptr(), &mut info)
+        })?;
+        Ok((colors, hits))
+    }
+
     fn light_params(maximum_distance: u8, fast: bool, epsilon: u8, n_queue: i32, max_updates: u64) -> ffi::aic_light_params {
         ffi::aic_light_params {
             maximum_distance: i32::from(maximum_distance),
