@@ -171,8 +171,11 @@ AIC_DEV bool cube_containing_flat(double x, double y, double z, int out[3]) {  /
     asm("v_cvt_i32_f64 %0, %1" : "=v"(out[2]) : "v"(fz));
     return ok != 0;
 }
+// `skip_ff_inside` (NEWRAY, AIC_NEWRAY_SKIP_FF): when every active lane's origin lies inside the bounds -- lo <= o <= hi on all three axes, as doubles; a NaN
+// fails -- the fast-forward and the cube of the fast-forwarded origin are skipped behind one wave-uniform branch. For such a lane every moving axis's signed
+// quotient is <= 0, so max_t is zero, `go` is false, t_start = +0 and `ff` is the origin, whose cube is at hand: the same bits by construction.
 AIC_DEV LvlLim lvl_init(double ox, double oy, double oz, const RayDir rd, bool bounded, int lox, int loy,
-                        int loz, int hix, int hiy, int hiz, bool include_exit, double half_over_len) {
+                        int loz, int hix, int hiy, int hiz, bool include_exit, double half_over_len, bool skip_ff_inside = false) {
     LvlLim out;
     Lvl &s = out.s;
     Lim &lim = out.lim;
@@ -196,7 +199,16 @@ AIC_DEV LvlLim lvl_init(double ox, double oy, double oz, const RayDir rd, bool b
     // One copy of the t_max arithmetic serves both (round 6; it was written twice, each copy behind its own per-lane branch).
     double t_start = 0.0;
     double ffx = ox, ffy = oy, ffz = oz;
-    if (bounded) {
+    int cube[3] = {cube_o[0], cube_o[1], cube_o[2]};
+    bool need_ff = bounded;
+    if (bounded && skip_ff_inside) {
+        const bool inside = ((double)lox <= ox) & (ox <= (double)hix) & ((double)loy <= oy) & (oy <= (double)hiy) & ((double)loz <= oz) & (oz <= (double)hiz);
+        need_ff = __builtin_amdgcn_ballot_w64(!inside) != 0ull;
+    }
+    if (need_ff) {
+        // (the empty asm is here only to keep this a branch -- the arithmetic below is otherwise speculated and selected -- not because the path is
+        //  rare: a camera outside the space takes it at every NEWRAY)
+        if (skip_ff_inside) AIC_RARE_PATH();
         const double pox = (double)((rd.sx < 0) ? hix : lox);
         const double poy = (double)((rd.sy < 0) ? hiy : loy);
         const double poz = (double)((rd.sz < 0) ? hiz : loz);
@@ -223,9 +235,9 @@ AIC_DEV LvlLim lvl_init(double ox, double oy, double oz, const RayDir rd, bool b
         t_start = go ? ts : 0.0;
         ffx = go ? ox + rd.dx * ts : ox; ffy = go ? oy + rd.dy * ts : oy; ffz = go ? oz + rd.dz * ts : oz;
     }
-    // the cube of the (fast-forwarded) origin; a fast-forwarded origin without one makes the level State::EMPTY
-    int cube[3];
-    valid &= (int)cube_containing_flat(ffx, ffy, ffz, cube);
+    // the cube of the fast-forwarded origin; a fast-forwarded origin without one makes the level State::EMPTY (without a fast-forward it is the
+    // origin's own cube, which `valid` has already judged)
+    if (need_ff) valid &= (int)cube_containing_flat(ffx, ffy, ffz, cube);
     {
         // scale_to_integer_step on each axis (raycast.rs:797-819). The dividends are in [2^-53, 1] or +0: with a direction in the window (RayDir::fast)
         // div_known_recip's precondition holds
@@ -905,6 +917,36 @@ constexpr uint32_t ST_IN_BLOCK = 1u << 9, ST_HAS_LAST = 1u << 10, ST_OPAQUE = 1u
 #ifndef AIC_FAST_STEPS
 #define AIC_FAST_STEPS 16  // bookkeeping-free steps a lane may take ahead of each full pass (0: none; 8 until round 4) ...
 #endif
+#ifndef AIC_FIRST_LOOKUP
+#define AIC_FIRST_LOOKUP 1  // ENTER and NEWRAY look up the first cube / voxel of the level they set up; an invisible one is counted there and the lane
+                            // leaves the event stepping instead of FRESH (!DIAG && !BIG only, with or without the lane exchange: the recording ones count lookups per level,
+                            // BIG needs the class table)
+#endif
+#ifndef AIC_NEWRAY_SKIP_FF
+#define AIC_NEWRAY_SKIP_FF 0  // 1: NEWRAY skips lvl_init's fast-forward when every lane's origin lies inside the space (a camera inside the hall). Off:
+                              // its counter pass (SQ_INSTS_VALU with and without it) has not been made; DESIGN.md 4.2 has the listing's static count
+#endif
+// Waits for a lookup issued into a register (`raw`, in the stepping trip) by an earlier asm statement. The loaded register goes in as a plain INPUT and the code comes
+// out in a fresh register, copied AFTER the wait: every later use depends on this statement. (Until round 4 this was
+// `asm("s_waitcnt vmcnt(0)" : "+v"(raw))`: a tied operand, for which the compiler may place a register copy in front of the
+// statement -- i.e. read the destination of a load still in flight. Register allocation happened never to need one; the first
+// change that gave `raw` another live range -- the speculative lookups -- made it appear, in front of the full pass's wait.)
+#define AIC_WAIT_LOOKUP(reg_) { const uint32_t in_flight_ = reg_; asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %1" : "=&v"(reg_) : "v"(in_flight_)); }
+#define AIC_WAIT_RAW() AIC_WAIT_LOOKUP(raw)
+// The first lookup of a level, issued by the event that set it up as soon as `boff` exists: under the eligible lanes (a wave mask), so that the event's
+// remaining assignments run under its latency. AIC_WAIT_LOOKUP(reg_) ends it.
+#define AIC_ISSUE_FIRST_LOOKUP(elig_, reg_)                                                                                                            \
+    {                                                                                                                                              \
+        const unsigned long long m_first_ = __builtin_amdgcn_ballot_w64(elig_);                                                                    \
+        unsigned long long sv_first_;                                                                                                              \
+        asm volatile("s_mov_b64 %[sv], exec\n\t"                                                                                                   \
+                     "s_mov_b64 exec, %[m]\n\t"                                                                                                    \
+                     "global_load_ushort %[raw], %[bo], %[pool]\n\t"                                                                               \
+                     "s_mov_b64 exec, %[sv]\n\t"                                                                                                   \
+                     : [raw] "+v"(reg_), [sv] "=&s"(sv_first_)                                                                                     \
+                     : [bo] "v"(boff), [pool] "s"(pool_bits), [m] "s"(m_first_)                                                                    \
+                     : "memory");                                                                                                                  \
+    }
 // ---- Lane exchange between the waves of a workgroup ("regime-sorted waves"; DESIGN.md 4.2, tools/wave_sim) ----
 // A wave runs ONE kind of work per scheduler round (a stepping trip, or one kind of event) and the lanes of the other kinds idle: every phase
 // ran at 25-39 of 64 lanes (profiles/r04_phase_cycles.txt) on a kernel bound by instruction issue. The production variants therefore share a POOL
@@ -2068,18 +2110,31 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                 const RayDir rd = make_rd(edx, edy, edz);
                 const LvlLim ll = lvl_init(sx_, sy_, sz_, rd, true, ilx, ily, ilz, ilx + isx, ily + isy, ilz + isz, true, 0.5 / c64[C_TABS][col]);  // (0.5 / direction.length(), raycast.rs:669: the quotient NEWRAY's fast-forward used)
                 const FirstCube f = lvl_first_masks(ll.s, rd, ilx, ily, ilz, ilx + isx, ily + isy, ilz + isz);
-                tx = f.tx; ty = f.ty; tz = f.tz; last_t = f.last_t;
                 const int vcx = f.cx - ilx, vcy = f.cy - ily, vcz = f.cz - ilz;
+                boff = 2u * (vox_off + (uint32_t)(((uint32_t)vcx * (uint32_t)isy + (uint32_t)vcy) * (uint32_t)isz + (uint32_t)vcz));
+                // The first voxel's lookup, taken here where the stepping trip would count it and do nothing else: the level goes on, no span is pending
+                // (DepthIter), the ray is not opaque and the step stays under the 1000-step cap (count_step_should_stop, sr.rs:625-656).
+                constexpr bool first_lookup = AIC_FIRST_LOOKUP && !DIAG && !BIG;
+                const bool first_elig = first_lookup && f.got && f.inbounds && !(st & (ST_HAS_LAST | ST_OPAQUE)) && count <= 999u;
+                uint32_t first_raw = 0u;  // (a register of its own: `raw` keeps the live range it has without this lookup)
+                if constexpr (first_lookup) { AIC_ISSUE_FIRST_LOOKUP(first_elig, first_raw); }
+                tx = f.tx; ty = f.ty; tz = f.tz; last_t = f.last_t;
                 rx = posx ? (uint32_t)(isx - 1 - vcx) : (uint32_t)vcx;
                 ry = posy ? (uint32_t)(isy - 1 - vcy) : (uint32_t)vcy;
                 rz = posz ? (uint32_t)(isz - 1 - vcz) : (uint32_t)vcz;
-                boff = 2u * (vox_off + (uint32_t)(((uint32_t)vcx * (uint32_t)isy + (uint32_t)vcy) * (uint32_t)isz + (uint32_t)vcz));
                 ssx = posx ? 2 * isy * isz : -2 * isy * isz; ssy = posy ? 2 * isz : -2 * isz; ssz = posz ? 2 : -2;
                 thr = n_invisible;
-                // a produced first voxel still needs its lookup (FRESH); a level that produced nothing, or ended with it, is DEAD
                 lax = f.lax;
                 st |= ST_IN_BLOCK;
-                ev = (f.got ? EV_FRESH : 0u) | (f.inbounds ? 0u : EV_DEAD);
+                // a produced first voxel still needs its lookup (FRESH) unless the lookup made here found an invisible one: that is an Invisible TraceStep,
+                // counted, and the lane leaves stepping; a level that produced nothing, or ended with it, is DEAD
+                bool first_invisible = false;
+                if constexpr (first_lookup) {
+                    AIC_WAIT_LOOKUP(first_raw);
+                    first_invisible = first_elig && first_raw < thr;
+                    count += first_invisible ? 1u : 0u;
+                }
+                ev = ((f.got && !first_invisible) ? EV_FRESH : 0u) | (f.inbounds ? 0u : EV_DEAD);
             }
             AIC_SECTION(enter_end);
             } else {
@@ -2350,14 +2405,20 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     const int ohx = olx + osx_i, ohy = oly + osy_i, ohz = olz + osz_i;
                     // the sanitised direction equals the original unless it was zeroed, in which case no fast-forward happens
                     const double half_over_len = 0.5 / t_abs;
-                    const LvlLim ll = lvl_init(ox, oy, oz, rd, true, olx, oly, olz, ohx, ohy, ohz, true, half_over_len);
+                    const LvlLim ll = lvl_init(ox, oy, oz, rd, true, olx, oly, olz, ohx, ohy, ohz, true, half_over_len, AIC_NEWRAY_SKIP_FF != 0);
                     const FirstCube fs = lvl_first_masks(ll.s, rd, olx, oly, olz, ohx, ohy, ohz);
-                    tx = fs.tx; ty = fs.ty; tz = fs.tz; last_t = fs.last_t;
                     const int ccx = fs.cx - olx, ccy = fs.cy - oly, ccz = fs.cz - olz;
+                    boff = 2u * (uint32_t)(((uint32_t)ccx * (uint32_t)osy_i + (uint32_t)ccy) * (uint32_t)osz_i + (uint32_t)ccz);
+                    // the first cube's lookup, as in ENTER: a new ray has no span pending and its count is zero; one that starts opaque (the backdrop, the UI
+                    // pass's pixel) stays FRESH and ends in the stepping trip with its one step
+                    constexpr bool first_lookup = AIC_FIRST_LOOKUP && !DIAG && !BIG;
+                    const bool first_elig = first_lookup && fs.got && fs.inbounds && !cb_opaque(acc);
+                    uint32_t first_raw = 0u;  // (a register of its own: `raw` keeps the live range it has without this lookup)
+                    if constexpr (first_lookup) { AIC_ISSUE_FIRST_LOOKUP(first_elig, first_raw); }
+                    tx = fs.tx; ty = fs.ty; tz = fs.tz; last_t = fs.last_t;
                     rx = qx ? (uint32_t)(osx_i - 1 - ccx) : (uint32_t)ccx;
                     ry = qy ? (uint32_t)(osy_i - 1 - ccy) : (uint32_t)ccy;
                     rz = qz ? (uint32_t)(osz_i - 1 - ccz) : (uint32_t)ccz;
-                    boff = 2u * (uint32_t)(((uint32_t)ccx * (uint32_t)osy_i + (uint32_t)ccy) * (uint32_t)osz_i + (uint32_t)ccz);
                     ssx = qx ? ostx : -ostx; ssy = qy ? osty : -osty; ssz = qz ? 2 : -2;
                     thr = outer_thr;
                     lax = fs.lax;
@@ -2366,7 +2427,13 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     s_ray_t0[col] = (uint32_t)__builtin_readcyclecounter();
 #endif
                     if (cb_opaque(acc)) st |= ST_OPAQUE;
-                    ev = (fs.got ? EV_FRESH : 0u) | (fs.inbounds ? 0u : EV_DEAD);
+                    bool first_invisible = false;
+                    if constexpr (first_lookup) {
+                        AIC_WAIT_LOOKUP(first_raw);
+                        first_invisible = first_elig && first_raw < thr;
+                        count += first_invisible ? 1u : 0u;
+                    }
+                    ev = ((fs.got && !first_invisible) ? EV_FRESH : 0u) | (fs.inbounds ? 0u : EV_DEAD);
                 } else {
                     ev = EV_FINISH;
                 }
@@ -2413,12 +2480,6 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
         if (__builtin_amdgcn_readfirstlane((int)dry)) { tail_trips++; tail_lanes += (uint32_t)__popcll(m_act); AIC_PROF(29, 1); }
 #endif
 #define AIC_LANE(m) __builtin_amdgcn_inverse_ballot_w64(m)
-// Waits for a lookup issued into `raw` by an earlier asm statement. The loaded register goes in as a plain INPUT and the code comes
-// out in a fresh register, copied AFTER the wait: every later use depends on this statement. (Until round 4 this was
-// `asm("s_waitcnt vmcnt(0)" : "+v"(raw))`: a tied operand, for which the compiler may place a register copy in front of the
-// statement -- i.e. read the destination of a load still in flight. Register allocation happened never to need one; the first
-// change that gave `raw` another live range -- the speculative lookups -- made it appear, in front of the full pass's wait.)
-#define AIC_WAIT_RAW() { const uint32_t raw_in_flight_ = raw; asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %1" : "=&v"(raw) : "v"(raw_in_flight_)); }
 #pragma unroll 1
         for (int rep = 0; rep < AIC_STEP_REPS && m_act != 0ull; rep++) {
             AIC_PROF(10, 1);

@@ -180,6 +180,10 @@ extern "C" int simulate(const char *tok, const long *off, const Params *Pp, Out 
     }
     // (SIM_COST=<file of n_macro int32>: another cost record -- e.g. an estimate made before the frame -- in place of the true one; a policy experiment)
     if (const char *cf = getenv("SIM_COST")) { if (FILE *f = fopen(cf, "rb")) { size_t got = fread(cost.data(), 4, (size_t)n_macro, f); fclose(f); if (got != (size_t)n_macro) return 7; } }
+    // (SIM_FIRST_LOOKUP=1: the event that sets a level up takes the level's first lookup itself when it finds nothing -- ENTER and RAY consume a leading 'l'
+    //  token of the lane they serve, as the kernel's AIC_FIRST_LOOKUP does; the lane leaves the event as an ordinary stepping lane)
+    const char *fl_env = getenv("SIM_FIRST_LOOKUP");
+    const bool first_lookup = fl_env && atoi(fl_env) != 0;
     // queues: super-blocks of 128 px (8 macro tiles), (bx + 3 by) mod 8
     const int NQ = 8;
     int sb_px = 1; while (sb_px * 2 <= H / 8) sb_px *= 2;
@@ -394,7 +398,7 @@ extern "C" int simulate(const char *tok, const long *off, const Params *Pp, Out 
             }
             inst += P.c_shade; O->inst_kind[K_SHADE] += P.c_shade;
         } else if (run == K_ENTER) {
-            for (auto &l : w.l) if (l.kind == K_ENTER) { served++; l.pos++; l.kind = K_STEP; }
+            for (auto &l : w.l) if (l.kind == K_ENTER) { served++; l.pos++; l.kind = K_STEP; if (first_lookup && tk(l) == 'l') l.pos++; }
             inst += P.c_enter; O->inst_kind[K_ENTER] += P.c_enter;
         } else if (run == K_RAY) {
             bool refilled = false;
@@ -415,6 +419,7 @@ extern "C" int simulate(const char *tok, const long *off, const Params *Pp, Out 
                 l.ray = y * W + x; l.pos = 0;
                 l.kind = raylen(l.ray) == 0 ? K_RAY : K_STEP;
                 if (raylen(l.ray) == 0) l.ray = -1;  // missed the space: finishes at the next RAY phase (counted as a refill only)
+                else if (first_lookup && tk(l) == 'l') l.pos++;
             }
             (void)refilled;
             inst += P.c_finish + P.c_refill + P.c_newray; O->inst_kind[K_RAY] += P.c_finish + P.c_refill + P.c_newray;
