@@ -22,6 +22,7 @@ MAX_IN_FLIGHT = 32  # AIC_MAX_IN_FLIGHT
 FLAW_UNSUPPORTED, FLAW_NO_BLOOM = 1, 2
 FRAME_COUNTERS, FRAME_AUX, FRAME_PIXEL_CENTERS, FRAME_OUT_LINEAR, FRAME_OUT_COLORBUF, FRAME_NO_FEEDBACK = 1, 2, 4, 8, 16, 32
 FRAME_BLOOM = 64  # AIC_FRAME_BLOOM: bloom the frame when the world options' bloom_intensity > 0 (RGBA8 output, whole frames)
+FRAME_OUT_SPLIT = 512  # AIC_FRAME_OUT_SPLIT: an f16x4 colour plane and an f32 depth plane (12 bytes per pixel), raytrace_to_texture's two texels
 RAYS_NO_SKY, RAYS_DEVICE = 128, 256  # aic_trace_rays only: include_sky = false; rays / out / aux are device pointers
 MAX_RAYS = 2048 * 65535  # rays in one aic_trace_rays call
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
@@ -39,6 +40,16 @@ def bloom_geometry(width: int, height: int):
     return levels, ((rx + d - 1) // d * d, (ry + d - 1) // d * d)
 
 
+def split_planes(buf, rows: int, width: int):
+    """The two planes of an AIC_FRAME_OUT_SPLIT buffer of rows x width pixels (12 bytes each; `buf`: anything numpy can view as bytes, e.g. what a
+    submitted frame left in device memory, copied to the host): {"color_f16": [rows, width, 4] float16, "depth": [rows, width] float32}."""
+    raw = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
+    n = int(rows) * int(width)
+    if raw.size < n * 12:
+        raise ValueError(f"a Split frame of {rows} x {width} pixels is {n * 12} bytes, the buffer has {raw.size}")
+    return {"color_f16": raw[:n * 8].view(np.float16).reshape(rows, width, 4), "depth": raw[n * 8:n * 12].view(np.float32).reshape(rows, width)}
+
+
 def tuning(queues=None, super_shift=None, variant=None) -> int:
     """aic_frame_desc.tuning: the number of tile queues (1..8), the super-block edge in macro tiles (log2) and the production variant of the
     trace kernel (VARIANT_*); None leaves the library's choice. Any value gives the same image."""
@@ -54,13 +65,13 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 # every symbol include/aic_hip.h declares
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
-    "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options",
+    "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
     "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
     "aic_create_multi", "aic_destroy_multi", "aic_multi_device_count", "aic_multi_context", "aic_multi_last_error", "aic_multi_upload_space",
-    "aic_multi_clear_space", "aic_multi_update_cubes", "aic_multi_update_light_volume", "aic_multi_evaluate_light", "aic_multi_light_cubes_changed", "aic_multi_replace_blocks", "aic_multi_set_options",
+    "aic_multi_clear_space", "aic_multi_update_cubes", "aic_multi_update_light_volume", "aic_multi_evaluate_light", "aic_multi_light_cubes_changed", "aic_multi_replace_blocks", "aic_multi_set_options", "aic_multi_set_depth_transform",
     "aic_multi_render", "aic_multi_render_submit", "aic_multi_render_wait",
 ]
 
@@ -179,6 +190,7 @@ def load() -> C.CDLL:
         lib.aic_replace_block.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(BlockDesc), C.c_void_p, C.c_void_p]
         lib.aic_replace_blocks.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.aic_set_options.argtypes = [C.c_void_p, C.c_int, C.POINTER(Options)]
+        lib.aic_set_depth_transform.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.aic_render.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_void_p, C.c_int, C.POINTER(FrameInfo)]
         lib.aic_render_submit.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_void_p, C.c_uint32]
         lib.aic_render_wait.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(FrameInfo)]
@@ -417,6 +429,10 @@ class Context:
     def set_options(self, layer: int, options: Options) -> None:
         self._check(self._lib.aic_set_options(self._h, layer, C.byref(options)))
 
+    def set_depth_transform(self, zw) -> None:
+        """aic_set_depth_transform: zw = (m33, m43, m34, m44) of the depth transform FRAME_OUT_SPLIT frames apply; (1, 0, 0, 1) = linear depth."""
+        self._check(self._lib.aic_set_depth_transform(self._h, (C.c_double * 4)(*[float(v) for v in zw])))
+
     # -- drawing ---------------------------------------------------------------------------
     @staticmethod
     def make_frame(width, height, world_inv=None, ui_inv=None, exposure=1.0, ui_exposure=1.0, backdrop=(0, 0, 0, 0),
@@ -441,7 +457,8 @@ class Context:
         return int(self._lib.aic_partition_rows(height, C.byref(p)))
 
     def render(self, frame: FrameDesc, want_aux: bool = False, counters: bool = False):
-        """Returns dict(rgba8 [rows,w,4], info FrameInfo, aux or None). `frame` is left as it was given (until round 6 want_aux / counters
+        """Returns dict(rgba8 [rows,w,4], info FrameInfo, aux or None); for a FRAME_OUT_SPLIT frame dict(color_f16 [rows,w,4] float16, depth [rows,w]
+        float32, info, aux or None). `frame` is left as it was given (until round 6 want_aux / counters
         stayed set in it, and a later plain render of the same object quietly ran the recording variant again)."""
         keep_flags = frame.flags
         if want_aux:
@@ -450,7 +467,8 @@ class Context:
             frame.flags |= FRAME_COUNTERS
         rows = int(self._lib.aic_partition_rows(frame.height, C.byref(frame.partition)))
         floats = bool(frame.flags & (FRAME_OUT_LINEAR | FRAME_OUT_COLORBUF))  # 16-byte float pixels instead of RGBA8
-        out = np.zeros((rows, frame.width, 4), np.float32 if floats else np.uint8)
+        split = bool(frame.flags & FRAME_OUT_SPLIT) and not floats
+        out = np.zeros(rows * frame.width * 3, np.uint32) if split else np.zeros((rows, frame.width, 4), np.float32 if floats else np.uint8)
         info = FrameInfo()
         try:
             self._check(self._lib.aic_render(self._h, C.byref(frame), _ptr(out), 0, C.byref(info)))
@@ -461,6 +479,8 @@ class Context:
             aux = np.zeros((rows, frame.width), PIXEL_AUX_DTYPE)
             if aux.size:
                 self._check(self._lib.aic_read_aux(self._h, _ptr(aux), aux.size))
+        if split:
+            return {**split_planes(out, rows, frame.width), "info": info, "aux": aux}
         return {"rgba8": out, "info": info, "aux": aux}
 
     def render_to_device(self, frame: FrameDesc, device_ptr: int) -> FrameInfo:
@@ -500,7 +520,8 @@ class Context:
         return info
 
     def render_submit(self, frame: FrameDesc, device_ptr: int, slot: int) -> None:
-        """Queues a frame on `slot` (0..MAX_IN_FLIGHT-1); returns without waiting (aic_render_submit)."""
+        """Queues a frame on `slot` (0..MAX_IN_FLIGHT-1); returns without waiting (aic_render_submit). A FRAME_OUT_SPLIT frame leaves 12 bytes per
+        pixel at `device_ptr`: `split_planes` views a host copy of them as the two planes."""
         self._check(self._lib.aic_render_submit(self._h, C.byref(frame), C.c_void_p(device_ptr), int(slot)))
 
     def render_submit_batch(self, frames, device_ptrs, slot: int) -> None:
@@ -676,6 +697,7 @@ class MultiContext:
         lib.aic_multi_upload_space.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.aic_multi_clear_space.argtypes = [C.c_void_p, C.c_int]
         lib.aic_multi_set_options.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.aic_multi_set_depth_transform.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.aic_multi_update_light_volume.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.aic_multi_evaluate_light.argtypes = [C.c_void_p, C.c_int, C.POINTER(LightParams), C.POINTER(LightInfo)]
         lib.aic_multi_light_cubes_changed.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
@@ -717,6 +739,9 @@ class MultiContext:
 
     def set_options(self, layer: int, options: Options) -> None:
         self._check(self._lib.aic_multi_set_options(self._h, layer, C.byref(options)))
+
+    def set_depth_transform(self, zw) -> None:
+        self._check(self._lib.aic_multi_set_depth_transform(self._h, (C.c_double * 4)(*[float(v) for v in zw])))
 
     def update_light_volume(self, layer: int, light) -> None:
         lt = np.ascontiguousarray(light, np.uint8)

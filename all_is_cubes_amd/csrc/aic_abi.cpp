@@ -775,6 +775,16 @@ int aic_set_options(aic_ctx *c, int layer, const aic_options *o) {
     return AIC_OK;
 }
 
+int aic_set_depth_transform(aic_ctx *c, const double zw[4]) {
+    if (!c || !zw) return fail(c, AIC_ERR_INVALID, "aic_set_depth_transform: bad argument");
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(zw[i])) return fail(c, AIC_ERR_INVALID, "aic_set_depth_transform: a component is not finite");
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int rc = quiesce(c); if (rc != AIC_OK) return rc; }
+    std::memcpy(c->depth_zw, zw, sizeof(c->depth_zw));
+    return AIC_OK;
+}
+
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *p) {
     if (!p || p->n_parts <= 1 || p->strip_rows == 0) return height;
     if (p->part >= p->n_parts) return 0;
@@ -846,10 +856,16 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
         if (part.n_parts > 1u) return fail(c, AIC_ERR_UNSUPPORTED, "aic_render: AIC_FRAME_BLOOM needs the whole frame (partition.n_parts = 1)");
         if (patches || ortho_n || rb) return fail(c, AIC_ERR_UNSUPPORTED, "AIC_FRAME_BLOOM: not for patches, rays or orthographic views");
     }
+    // AIC_FRAME_OUT_SPLIT (whole frames only: patch and ray batches mask the flags they pass on, orthographic views pass none)
+    const bool split = (f->flags & AIC_FRAME_OUT_SPLIT) != 0;
+    if (split && (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF | AIC_FRAME_BLOOM)))
+        return fail(c, AIC_ERR_INVALID, "aic_render: AIC_FRAME_OUT_SPLIT excludes AIC_FRAME_OUT_LINEAR, AIC_FRAME_OUT_COLORBUF and AIC_FRAME_BLOOM");
     const uint32_t local_rows = aic_partition_rows(f->height, &part);
     const size_t npix = (size_t)f->width * local_rows;
-    for (uint32_t j = 0; j < k; j++)
+    for (uint32_t j = 0; j < k; j++) {
         if (npix && !out_devices[j]) return fail(c, AIC_ERR_INVALID, "aic_render: output buffer is null");
+        if (split && ((uintptr_t)out_devices[j] & 7u)) return fail(c, AIC_ERR_INVALID, "aic_render: an AIC_FRAME_OUT_SPLIT buffer starts at an 8-byte boundary");
+    }
     if (!patches && !rb)
         for (uint32_t j = 0; j < k; j++) dump_record(c, DUMP_FRAME, slot, {{&frames[j], sizeof(frames[j])}});
     if (f->width > 65535u || local_rows > 65535u) return fail(c, AIC_ERR_INVALID, "aic_render: frame dimensions above 65535 are not supported");
@@ -871,7 +887,8 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     F.n_sub = k;
     // the encoder and the sampling pattern follow the WORLD camera's options (renderer.rs:283-291, 426)
     F.pixel_centers = (f->flags & AIC_FRAME_PIXEL_CENTERS) && !patches ? 1 : 0;
-    F.out_mode = (f->flags & AIC_FRAME_OUT_LINEAR) ? 1 : ((f->flags & AIC_FRAME_OUT_COLORBUF) || bloom ? 2 : 0);  // (a bloomed frame: its ColorBuf, into the slot's scratch)
+    F.out_mode = split ? 3 : ((f->flags & AIC_FRAME_OUT_LINEAR) ? 1 : ((f->flags & AIC_FRAME_OUT_COLORBUF) || bloom ? 2 : 0));  // (a bloomed frame: its ColorBuf, into the slot's scratch)
+    std::memcpy(F.depth_zw, c->depth_zw, sizeof(F.depth_zw));
     F.patches = patches;
     F.n_patches = n_patches;
     F.ortho = ortho;
@@ -930,7 +947,7 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     F.srgb_thr = c->srgb_thr.p;
 
     const bool want_aux = allow_aux && (f->flags & AIC_FRAME_AUX) != 0;
-    const bool diag = want_aux || (f->flags & AIC_FRAME_COUNTERS) != 0;
+    const bool diag = want_aux || split || (f->flags & AIC_FRAME_COUNTERS) != 0;  // (the Split's depth and layer live in the recording variants only)
     fs.diag = diag;
     fs.flaws = flaws;
     fs.light_used[0] = hl[0].light;
@@ -1041,7 +1058,12 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
             const size_t samples = F.antialias ? 4 : 1;
             if ((e = sb.acc.ensure(samples * npix)) != hipSuccess) return hip_fail(c, "alloc accumulators", e);
             S.acc_buf = sb.acc.p;
+            if (split) {  // every sample's DepthBuf, handed from the UI pre-pass to the world pass
+                if ((e = sb.split_depth.ensure(samples * npix)) != hipSuccess) return hip_fail(c, "alloc sample depths", e);
+                F.split_depth[j] = sb.split_depth.p;
+            }
         }
+        F.split_ui_exposure[j] = frames[j].ui.exposure + 0.0f;
     }
     if (!patches && !rb && !ortho_n) {
         // Viewport's pixel edges (viewport.rs:104-113), once per frame shape: x / width * 2 - 1 and -(y / height * 2 - 1) in the reference's own f64
@@ -1257,7 +1279,7 @@ int aic_render(aic_ctx *c, const aic_frame_desc *f, void *out_rgba8, int out_is_
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_render: a submitted frame still occupies slot 0 (aic_render_wait it first)");
     uint32_t *target = (uint32_t *)out_rgba8;
-    const size_t px_words = (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) ? 4 : 1;  // 16 or 4 bytes per pixel
+    const size_t px_words = (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) ? 4 : ((f->flags & AIC_FRAME_OUT_SPLIT) ? 3 : 1);  // 16, 12 or 4 bytes per pixel
     if (!out_is_device && out_rgba8) {
         aic_partition part = f->partition;
         if (part.n_parts <= 1 || part.strip_rows == 0) { part.n_parts = 1; part.part = 0; part.strip_rows = f->height ? f->height : 1; }
@@ -1400,6 +1422,7 @@ int aic_trace_patches(aic_ctx *c, const aic_frame_desc *f, uint32_t n, const dou
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_trace_patches: a submitted frame still occupies slot 0 (aic_render_wait it first)");
     if (f->flags & AIC_FRAME_BLOOM) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_patches: AIC_FRAME_BLOOM needs a whole frame");
+    if (f->flags & AIC_FRAME_OUT_SPLIT) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_patches: AIC_FRAME_OUT_SPLIT is for whole frames");
     // the batch is laid out as an image of up to 2048 columns; pixel i of that image traces rects[i]
     aic_frame_desc g = *f;
     g.width = n < 2048u ? n : 2048u;

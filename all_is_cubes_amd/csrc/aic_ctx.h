@@ -118,6 +118,7 @@ struct aic_ctx {
     DevBuf<unsigned char> staging;  // scratch for scatter updates / probes
     DevBuf<DevOrthoView> ortho_views;  // aic_render_orthographic
     uint64_t aux_records = 0;
+    double depth_zw[4] = {1.0, 0.0, 0.0, 1.0};  // aic_set_depth_transform: the Split frames' depth transform
     bool streaming_submit = false;  // set around aic_render_submit: frames meant to overlap are sized for throughput, synchronous ones for latency
     // frames in flight: slot 0 runs on `stream` (and serves the synchronous aic_render), slot 1 on a
     // second stream so that a submitted frame's trace can start while the previous one drains
@@ -134,6 +135,7 @@ struct aic_ctx {
         bool record_ready = false;         // tile_order / queue_start hold the cost order of the frame described by cost_sig / cost_cam / order_key
         uint32_t order_key[6] = {0, 0, 0, 0, 0, 0};  // cost_sig + number of queues + super-block shift
         DevBuf<float4> acc;  // UI pre-pass accumulators
+        DevBuf<double> split_depth;  // ... and every sample's DepthBuf (AIC_FRAME_OUT_SPLIT frames over a UI space)
         // cost feedback: the longest ray of every tile of the sub-frame's last frame, and the tile order made from it
         DevBuf<uint32_t> tile_cost, tile_order, queue_start;
         // AIC_FRAME_BLOOM (on the sub-frame's first bloomed frame): the trace's ColorBuf, then the bloom chain's mips (aic_bloom.h)
@@ -142,7 +144,7 @@ struct aic_ctx {
         uint32_t cost_sig[4] = {0, 0, 0, 0};  // width, local rows, partition of the frame tile_cost describes
         double cost_cam[16] = {0};            // ... and its world camera
         void release() {
-            counters.release(); acc.release(); tile_cost.release(); tile_order.release(); queue_start.release(); bloom_cb.release(); bloom_mips.release();
+            counters.release(); acc.release(); split_depth.release(); tile_cost.release(); tile_order.release(); queue_start.release(); bloom_cb.release(); bloom_mips.release();
             if (host_counters) (void)hipHostFree(host_counters);
             host_counters = nullptr;
             counters_clean = record_ready = false; cost_clean_n = 0;

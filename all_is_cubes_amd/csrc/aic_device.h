@@ -169,7 +169,7 @@ struct DevFrame {
     uint32_t hit_layer;      // the layer a first-hit record of this launch names (DevAux::layer): 1 in the UI pre-pass, 0 in the final pass, the layer traced in a ray batch
     int32_t use_init;        // final pass: start each sample from acc_buf (written by the UI pre-pass)
     int32_t pixel_centers;   // AIC_FRAME_PIXEL_CENTERS
-    int32_t out_mode;        // 0 sRGB RGBA8 (4 B/pixel); 1 linear Rgba f32x4; 2 ColorBuf f32x4 (16 B/pixel)
+    int32_t out_mode;        // 0 sRGB RGBA8 (4 B/pixel); 1 linear Rgba f32x4; 2 ColorBuf f32x4 (16 B/pixel); 3 Split: an f16x4 plane and an f32 depth plane (12 B/pixel)
     const DevOrthoView *ortho;  // aic_render_orthographic: the views (device memory), else null
     int32_t ortho_n;
     const double *patches;   // aic_trace_patches: [n_patches][4] NDC rectangles replacing the pixel grid (pixel i = row-major index)
@@ -201,6 +201,11 @@ struct DevFrame {
     uint32_t ray_mode;
     uint32_t exchange;       // host-side: launch the exchanging variant (aic_trace.hip "lane exchange") -- a frame with several tiles per persistent wave; a frame of
                              // about one tile per wave (a rank's share at N >= 4, small images) runs the variant without the pool, which it would only pay for
+    // AIC_FRAME_OUT_SPLIT (out_mode 3; the recording variants only -- appended, so that no field the production variants read moves): sub[j].out holds
+    // [local_rows][width] of four f16, then [local_rows][width] of f32 (raytrace_to_texture.rs:646-674)
+    double depth_zw[4];                // {m33, m43, m34, m44} of the depth transform (aic_set_depth_transform)
+    double *split_depth[kMaxSub];      // per frame: [samples][local_rows][width] DepthBuf of every sample after the UI pre-pass (written by it, read by the world pass), or null
+    float split_ui_exposure[kMaxSub];  // per frame: the UI Camera::exposure() (the world's is DevSub::exposure)
 };
 
 // order_tiles_kernel's jobs: one workgroup each -- the cost record to read (null: index order), the order and the queues' starts to write, and words to clear

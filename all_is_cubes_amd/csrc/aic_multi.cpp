@@ -167,6 +167,7 @@ int aic_multi_replace_blocks(aic_multi *m, int layer, uint32_t n, const uint32_t
     AIC_MULTI_FORWARD(aic_replace_blocks(m->ctx[i], layer, n, indices, descs, voxels, palettes))
 }
 int aic_multi_set_options(aic_multi *m, int layer, const aic_options *o) { AIC_MULTI_FORWARD(aic_set_options(m->ctx[i], layer, o)) }
+int aic_multi_set_depth_transform(aic_multi *m, const double zw[4]) { AIC_MULTI_FORWARD(aic_set_depth_transform(m->ctx[i], zw)) }
 
 // The light updater is a sequential relaxation (it does not shard): it runs on the first device, and the resulting volume
 // is handed to the others, so that every device traces the same light.
@@ -216,6 +217,7 @@ int aic_multi_light_cubes_changed(aic_multi *m, int layer, uint32_t n, const int
 int aic_multi_render_submit(aic_multi *m, const aic_frame_desc *f, void *out_rgba8, int out_is_device, uint32_t slot) {
     if (!m || !f || !out_rgba8 || slot >= AIC_MULTI_MAX_IN_FLIGHT) return mfail(m, AIC_ERR_INVALID, "aic_multi_render_submit: bad argument");
     if (f->flags & AIC_FRAME_BLOOM) return mfail(m, AIC_ERR_UNSUPPORTED, "aic_multi_render_submit: AIC_FRAME_BLOOM is for single-device contexts (device 0 would first need every strip's ColorBuf)");
+    if (f->flags & AIC_FRAME_OUT_SPLIT) return mfail(m, AIC_ERR_UNSUPPORTED, "aic_multi_render_submit: AIC_FRAME_OUT_SPLIT is for single-device contexts (the strips are gathered as RGBA8)");
     if (f->flags & (AIC_FRAME_AUX | AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF))
         return mfail(m, AIC_ERR_INVALID, "aic_multi_render: RGBA8 frames only (use a single context for aux records / float output)");
     if (f->partition.n_parts > 1) return mfail(m, AIC_ERR_INVALID, "aic_multi_render partitions the frame itself");

@@ -1201,6 +1201,15 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
         for (int a = 0; a < 3; a++) dg.cube[a] = dg.voxel[a] = 0;
     }
     uint32_t tot_outer = 0, tot_inner = 0, tot_hits = 0, tot_light = 0;
+    // DIAG: the Split accumulator's depth and layer (raytrace_to_texture.rs:922-977) beside `dg` -- DepthBuf of the sample being traced and of the pixel so far
+    // (the minimum t_distance, accum.rs:266-297), and the layers: bits 0-1 the sample's, bits 2-3 the pixel's (0 none, SPLIT_WORLD, SPLIT_UI)
+    constexpr uint32_t SPLIT_WORLD = 1u, SPLIT_UI = 2u;
+    double sp_smp = __longlong_as_double(0x7ff0000000000000LL), sp_px = sp_smp;
+    uint32_t sp_lay = 0u;
+    // a hit of `layer_code`'s layer reached the accumulator: Split::add's layer rule (ColorBuf::opacity_category is Invisible iff the transmittance is 1)
+    auto split_layer_after_add = [&](uint32_t layer_code) {
+        if (!(sp_lay & 3u) && acc.t != 1.0f) sp_lay |= layer_code;
+    };
 
     uint32_t ev = EV_NEWRAY | EV_TAKE;  // every lane starts by taking a pixel
 #ifdef AIC_PROFILE
@@ -2069,6 +2078,8 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     if (DIAG) {
                         dg.n_hits++;
                         dg.n_light += sd.nlight;
+                        sp_smp = fmin(sp_smp, t_enter);
+                        split_layer_after_add(F.hit_layer ? SPLIT_UI : SPLIT_WORLD);
                         if (!dg.hit) {
                             dg.hit = 1;
                             dg.layer = F.hit_layer;
@@ -2172,7 +2183,11 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     { const uint32_t dur_ = (uint32_t)__builtin_readcyclecounter() - s_ray_t0[col];
                       if (dur_ > ray_dur_max) { ray_dur_max = dur_; ray_dur_steps = count; } }
 #endif
-                    if (DIAG) px_steps += count + (LMODE == 3 ? sec_steps : 0u);
+                    if (DIAG) {
+                        px_steps += count + (LMODE == 3 ? sec_steps : 0u);
+                        // the Sky hit (t_distance +inf: no smaller depth) and the DebugOverrideRg hit are made with the options of the layer traced
+                        split_layer_after_add(F.hit_layer ? SPLIT_UI : SPLIT_WORLD);
+                    }
                 }
                 const uint32_t x = pxy & 0xffffu, lrow = pxy >> 16;
                 float aa_sum[4] = {0.f, 0.f, 0.f, 0.f};
@@ -2186,6 +2201,10 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                 const size_t pix = (size_t)lrow * F.width + x;
                 if (ui_pass) {
                     S.acc_buf[(size_t)sample * npix + pix] = make_float4(acc.l0, acc.l1, acc.l2, acc.t);
+                    if (DIAG) {  // (the sample's layer needs no carrying: after a UI trace it is the UI's iff the ColorBuf is visible)
+                        double *const sd_ = F.split_depth[F.n_sub > 1u ? (blockIdx.x & (F.n_sub - 1u)) : 0u];
+                        if (sd_) sd_[(size_t)sample * npix + pix] = sp_smp;
+                    }
                 } else {
                     if (!F.bare_trace && !cb_opaque(acc)) {  // renderer.rs:474-477: P::paint(NO_WORLD_TO_SHOW) replaces the accumulator
                         // (render_orthographic has no such layer tail: ortho.rs:103-131; nor has SpaceRaytracer::trace_ray, aic_trace_rays)
@@ -2193,6 +2212,14 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                         acc.l1 = acc.l0;
                         acc.l2 = acc.l0;
                         acc.t = 1.0f * (1.0f - 1.0f);
+                        if (DIAG) {  // P::paint: a default Split and one Paint hit, made with the world's options and no t_distance
+                            sp_smp = __longlong_as_double(0x7ff0000000000000LL);
+                            sp_lay = (sp_lay & ~3u) | SPLIT_WORLD;
+                        }
+                    }
+                    if (DIAG) {  // Split::mean: the smallest depth, the first sample's layer that has one
+                        sp_px = fmin(sp_px, sp_smp);
+                        if (!(sp_lay & 12u)) sp_lay |= (sp_lay & 3u) << 2;
                     }
                     if (n_samples == 4) {
                         cold_sums_load(aa_sum);
@@ -2214,7 +2241,26 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                         // encoder: Camera::post_process_color(Rgba::from(buf)).to_srgb8()
                         float c[4];
                         cb_to_rgba(pixel, c);
-                        if (F.out_mode != 0) {  // float outputs: the linear Rgba, or the ColorBuf as it is
+                        if (DIAG && F.out_mode == 3) {
+                            // Split: the two texels raytrace_to_texture stores (raytrace_to_texture.rs:646-674) -- one 8-byte and one 4-byte store
+                            const uint32_t sub_ = F.n_sub > 1u ? (blockIdx.x & (F.n_sub - 1u)) : 0u;
+                            const uint32_t pl = (sp_lay >> 2) & 3u;
+                            const float e = pl == SPLIT_UI ? F.split_ui_exposure[sub_] : (pl == SPLIT_WORLD ? S.exposure : 1.0f);
+                            float a = 1.0f - pixel.t;  // into_premultiplied_rgba: (1 - t).clamp(0, 1)
+                            a = a < 0.0f ? 0.0f : a;
+                            a = a > 1.0f ? 1.0f : a;
+                            auto f16_bits = [](float v) -> uint32_t { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)v); };  // half::f16::from_f32: to nearest even, overflow to infinity
+                            reinterpret_cast<uint2 *>(S.out)[pix] =
+                                make_uint2(f16_bits(pixel.l0 * e) | (f16_bits(pixel.l1 * e) << 16), f16_bits(pixel.l2 * e) | (f16_bits(a) << 16));
+                            double d = sp_px;  // depth_buf.depth().clamp(0.0, 1.0)
+                            d = d < 0.0 ? 0.0 : d;
+                            d = d > 1.0 ? 1.0 : d;
+                            // depth_transform.transform_point3d_homogeneous(point3(0., 0., d)), euclid's operation order
+                            const double z_ = ((0.0 * 0.0 + 0.0 * 0.0) + d * F.depth_zw[0]) + F.depth_zw[1];
+                            const double w_ = ((0.0 * 0.0 + 0.0 * 0.0) + d * F.depth_zw[2]) + F.depth_zw[3];
+                            const float layer_factor = pl == SPLIT_WORLD ? 1.0f : -1.0f;  // layer.unwrap_or(InLayer::Ui) as i8
+                            reinterpret_cast<float *>(reinterpret_cast<char *>(S.out) + npix * 8u)[pix] = (float)(z_ / w_) * layer_factor;
+                        } else if (F.out_mode != 0) {  // float outputs: the linear Rgba, or the ColorBuf as it is
                             reinterpret_cast<float4 *>(S.out)[pix] =
                                 F.out_mode == 1 ? make_float4(c[0], c[1], c[2], c[3]) : make_float4(pixel.l0, pixel.l1, pixel.l2, pixel.t);
                         } else {
@@ -2367,11 +2413,22 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                             dg.layer = a.layer;
                             px_steps_prev = a.cubes_traced;
                         }
+                        sp_px = __longlong_as_double(0x7ff0000000000000LL);
+                        sp_lay = 0u;
                     }
+                }
+                if (DIAG) {
+                    sp_smp = __longlong_as_double(0x7ff0000000000000LL);
+                    sp_lay &= ~3u;
                 }
                 if (F.use_init) {
                     const float4 v = S.acc_buf[(size_t)sample * npix + pix];
                     acc.l0 = v.x; acc.l1 = v.y; acc.l2 = v.z; acc.t = v.w;
+                    if (DIAG) {  // the sample's Split as the UI trace left it
+                        const double *const sd_ = F.split_depth[F.n_sub > 1u ? (blockIdx.x & (F.n_sub - 1u)) : 0u];
+                        if (sd_) sp_smp = sd_[(size_t)sample * npix + pix];
+                        split_layer_after_add(SPLIT_UI);
+                    }
                 } else {
                     acc.l0 = acc.l1 = acc.l2 = 0.f;
                     acc.t = KF(1.0f);  // made here: as a literal it is hoisted into a register that lives across the whole loop
@@ -2380,6 +2437,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                 if (!ui_pass && S.has_backdrop) {  // Exception::Backdrop hit: ColorBuf::from(Rgba)
                     const float a = opaque_s(S.backdrop[3]);
                     cb_add(acc, S.backdrop[0] * a, S.backdrop[1] * a, S.backdrop[2] * a, 1.0f - a);
+                    if (DIAG) split_layer_after_add(SPLIT_UI);  // (made with the UI's options, renderer.rs:242-250; no t_distance)
                 }
                 count = 0;
                 st = (uint32_t)sample << 14;
@@ -2708,6 +2766,8 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     if (DIAG && apply && pend_visible) {
                         dg.n_hits++;
                         dg.n_light += pend_d.nlight;
+                        sp_smp = fmin(sp_smp, pend_t);
+                        split_layer_after_add(hit_layer_s ? SPLIT_UI : SPLIT_WORLD);
                         if (!dg.hit) {
                             dg.hit = 1;
                             dg.layer = hit_layer_s;

@@ -240,6 +240,12 @@ void Camera::compute_matrices() {  // camera_struct.rs:387-416
     if (!world_to_eye_.then(projection_).inverse(&inverse_projection_view_))
         throw std::runtime_error("projection and view matrix was not invertible");
 }
+std::array<double, 4> Camera::depth_transform_zw() const {  // raytrace_to_texture.rs:613-618
+    const double depth_scale = -(view_distance() - near_plane_distance());
+    const double depth_bias = -near_plane_distance();
+    const Mat4 &p = projection_;
+    return {depth_scale * MM(p, 3, 3), depth_bias * MM(p, 3, 3) + MM(p, 4, 3), depth_scale * MM(p, 3, 4), depth_bias * MM(p, 3, 4) + MM(p, 4, 4)};
+}
 Vec3 Camera::project_ndc3_into_world(const Vec3 &ndc) const {
     Vec3 out;
     if (!inverse_projection_view_.transform_point3d(ndc, &out)) {
@@ -618,6 +624,31 @@ Rendering HipRtRenderer::draw_rgba(const std::string &info_text) {  // renderer.
         encode_paint(world_camera_, paint_exposure, k1, white);
         draw_info_text(r.data.data(), f.width, f.height, black, white, info_text);
     }
+    return r;
+}
+
+SplitRendering HipRtRenderer::draw_split() {
+    aic_frame_desc f = make_frame();
+    f.flags |= AIC_FRAME_OUT_SPLIT;
+    const std::array<double, 4> zw = world_camera_.depth_transform_zw();
+    check(aic_set_depth_transform(ctx_, zw.data()), "aic_set_depth_transform");
+    SplitRendering r;
+    r.width = f.width;
+    r.height = f.height;
+    const size_t npix = (size_t)f.width * f.height;
+    std::vector<uint32_t> planes(npix * 3, 0u);  // 8 bytes of colour per pixel, then 4 of depth
+    aic_frame_info fi;
+    check(aic_render(ctx_, &f, planes.data(), 0, &fi), "aic_render");
+    r.color.resize(npix * 4);
+    r.depth.resize(npix);
+    if (npix) {
+        std::memcpy(r.color.data(), planes.data(), npix * 8);
+        std::memcpy(r.depth.data(), planes.data() + npix * 2, npix * 4);
+    }
+    r.info = to_info(fi, f.width, f.height);
+    if (fi.flaws & AIC_FLAW_UNSUPPORTED) r.flaws |= Flaws::UNSUPPORTED;
+    if (fi.flaws & AIC_FLAW_NO_BLOOM) r.flaws |= Flaws::NO_BLOOM;
+    if (had_cursor_) r.flaws |= Flaws::NO_CURSOR;
     return r;
 }
 

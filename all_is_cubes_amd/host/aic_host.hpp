@@ -135,6 +135,10 @@ class Camera {
     double view_distance() const { return options_.view_distance; }
     double near_plane_distance() const { return 1.0 / 32.0; }
     Mat4 projection_matrix() const { return projection_; }
+    // {m33, m43, m34, m44} of raytrace_to_texture's depth_transform (raytrace_to_texture.rs:613-618): the projection, pre-translated by -near along z
+    // and pre-scaled by -(far - near), which maps a ray's t (0 at the near plane, 1 at the view distance) to the projected depth -- what
+    // aic_set_depth_transform takes
+    std::array<double, 4> depth_transform_zw() const;
     Mat4 view_matrix() const { return world_to_eye_; }
     Mat4 inverse_projection_view() const { return inverse_projection_view_; }
     Vec3 view_position() const { return view_position_; }
@@ -253,6 +257,13 @@ struct ImageInfo {  // renderer.rs:617-647 + RaytraceInfo sr.rs:520-522
     uint32_t width = 0, height = 0, rows_rendered = 0;
     std::string status_text() const;
 };
+struct SplitRendering {  // raytrace_to_texture's two render targets (raytrace_to_texture.rs:594-675), as AIC_FRAME_OUT_SPLIT writes them
+    uint32_t width = 0, height = 0;
+    std::vector<uint16_t> color;  // [h][w][4] IEEE f16 bits: premultiplied light times the pixel's layer's exposure, alpha
+    std::vector<float> depth;     // [h][w] projected depth of the nearest surface; sign bit set on UI pixels
+    uint16_t flaws = 0;
+    ImageInfo info;
+};
 struct Rendering {  // headless.rs:52-67
     uint32_t width = 0, height = 0;
     std::vector<uint8_t> data;  // [h][w][4] sRGB RGBA8
@@ -306,6 +317,9 @@ class HipRtRenderer : public HeadlessRenderer {
     void update(const Cursor *cursor) override { (void)update_scene(cursor); }
     Rendering draw(const std::string &info_text) override { return draw_rgba(info_text); }
     Rendering draw_rgba(const std::string &info_text);
+    // The frame as all-is-cubes-gpu's raytrace_to_texture wants it: sets the depth transform from the world camera (Camera::depth_transform_zw) and
+    // renders with AIC_FRAME_OUT_SPLIT. No info text, no bloom (that renderer blooms its own frames).
+    SplitRendering draw_split();
     // Opt-in, off by default: draw_rgba blooms its frames as the reference's GPU renderer does (AIC_FRAME_BLOOM) whenever the world options'
     // bloom_intensity is above zero, and such a Rendering does not report Flaws::NO_BLOOM. The info text is drawn over the bloomed frame.
     void set_bloom(bool on) { bloom_ = on; }

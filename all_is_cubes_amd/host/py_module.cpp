@@ -96,6 +96,7 @@ PYBIND11_MODULE(_host, m) {
         .def("set_measured_exposure", &Camera::set_measured_exposure).def("exposure", &Camera::exposure)
         .def("fov_y", &Camera::fov_y).def("view_distance", &Camera::view_distance).def("near_plane_distance", &Camera::near_plane_distance)
         .def("projection_matrix", [](const Camera &c) { return mat(c.projection_matrix()); })
+        .def("depth_transform_zw", &Camera::depth_transform_zw)
         .def("view_matrix", [](const Camera &c) { return mat(c.view_matrix()); })
         .def("inverse_projection_view", [](const Camera &c) { return mat(c.inverse_projection_view()); })
         .def("view_position", [](const Camera &c) { return a3(c.view_position()); })
@@ -205,6 +206,20 @@ PYBIND11_MODULE(_host, m) {
             return a;
         });
 
+    py::class_<SplitRendering>(m, "SplitRendering")
+        .def_readonly("width", &SplitRendering::width).def_readonly("height", &SplitRendering::height).def_readonly("flaws", &SplitRendering::flaws)
+        .def_readonly("info", &SplitRendering::info)
+        .def_property_readonly("color_f16_bits", [](const SplitRendering &r) {  // [h, w, 4] uint16: view it as numpy float16
+            py::array_t<uint16_t> a({(py::ssize_t)r.height, (py::ssize_t)r.width, (py::ssize_t)4});
+            if (!r.color.empty()) std::memcpy(a.mutable_data(), r.color.data(), r.color.size() * 2);
+            return a;
+        })
+        .def_property_readonly("depth", [](const SplitRendering &r) {
+            py::array_t<float> a({(py::ssize_t)r.height, (py::ssize_t)r.width});
+            if (!r.depth.empty()) std::memcpy(a.mutable_data(), r.depth.data(), r.depth.size() * 4);
+            return a;
+        });
+
     auto flaws = m.def_submodule("Flaws");
     flaws.attr("OTHER") = Flaws::OTHER; flaws.attr("UNSUPPORTED") = Flaws::UNSUPPORTED; flaws.attr("NO_BLOOM") = Flaws::NO_BLOOM;
     flaws.attr("NO_CURSOR") = Flaws::NO_CURSOR; flaws.attr("OUT_OF_MEMORY") = Flaws::OUT_OF_MEMORY;
@@ -243,6 +258,7 @@ PYBIND11_MODULE(_host, m) {
             r.set_world_camera_override(m.data(), exposure);
         }, py::arg("inverse_projection_view"), py::arg("exposure") = 1.0f)
         .def("draw_rgba", [](HipRtRenderer &r, const std::string &t) { py::gil_scoped_release rel; return r.draw_rgba(t); }, py::arg("info_text") = "")
+        .def("draw_split", [](HipRtRenderer &r) { py::gil_scoped_release rel; return r.draw_split(); })
         .def("set_bloom", &HipRtRenderer::set_bloom, py::arg("on"))
         .def_property_readonly("bloom", &HipRtRenderer::bloom)
         .def("draw_rows_to_device", [](HipRtRenderer &r, uintptr_t ptr, uint32_t strip_rows, uint32_t n_parts, uint32_t part, bool counters, bool no_feedback) {

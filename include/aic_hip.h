@@ -165,6 +165,24 @@ typedef struct aic_frame_desc {
  * AIC_ERR_INVALID with AIC_FRAME_OUT_LINEAR / AIC_FRAME_OUT_COLORBUF; AIC_ERR_UNSUPPORTED with a partition of n_parts > 1 (bloom needs the
  * whole frame), in aic_trace_patches and in every aic_multi_* render. The context stays usable after either. */
 #define AIC_FRAME_BLOOM 64u
+/* Split (ABI 3, backward compatible): the two texels all-is-cubes-gpu's raytrace_to_texture stores per pixel from its `Split { color, depth, layer }`
+ * accumulator (raytrace_to_texture.rs:594-675, 922-977). The output buffer (8-byte aligned) holds two planes, one after the other, 12 bytes per pixel:
+ *   colour [rows][width] of four IEEE f16: (l0 e, l1 e, l2 e, a), (l0, l1, l2, a) = ColorBuf::into_premultiplied_rgba of the pixel's (mean) ColorBuf
+ *          -- the one AIC_FRAME_OUT_COLORBUF writes, a = clamp(1 - t, 0, 1) --, e = the exposure of the pixel's layer (frame->ui.exposure, frame->world.exposure,
+ *          1.0 for no layer), plain f32 products converted as half::f16::from_f32 does (to nearest even, overflow to infinity);
+ *   depth  [rows][width] of f32, at byte offset rows * width * 8: the projected depth of the nearest surface, negative (sign bit set: -0.0 at depth 0) for
+ *          a UI pixel or a pixel of no layer.
+ * rows = the rows the partition selects, compacted as for RGBA8. A sample's layer is that of the first hit after which its ColorBuf is no longer
+ * invisible (exception hits carry the layer whose options they are made with: the sky the layer traced, the backdrop the UI's, the NO_WORLD_TO_SHOW paint
+ * the world's), the pixel's the first sample's that has one. A sample's depth is the minimum t_distance over its hits that carry one (the UI trace, then the
+ * world trace, each in its own camera's ray units; +inf for the sky and after a paint), the pixel's the minimum over its samples (DepthBuf::mean,
+ * accum.rs:284-297). Then, in f64, d = clamp(depth, 0, 1), z = d zw[0] + zw[1], w = d zw[2] + zw[3] (euclid's transform_point3d_homogeneous of (0, 0, d))
+ * and the value is (float)(z / w), times -1.0f for a UI pixel or none; zw: aic_set_depth_transform.
+ * Honoured by aic_render (host or device target; with AIC_FRAME_AUX too), aic_render_submit / _wait and aic_render_submit_batch / _wait_batch, with any
+ * partition; the frame is traced by the recording variant (AIC_VARIANT_RECORDING), whatever `tuning` asks for. AIC_ERR_INVALID with AIC_FRAME_OUT_LINEAR,
+ * AIC_FRAME_OUT_COLORBUF or AIC_FRAME_BLOOM; AIC_ERR_UNSUPPORTED in aic_trace_patches and every aic_multi_* render; aic_trace_rays has no such output (bit 9 of
+ * its flags asks for a kernel variant). The context stays usable after a rejection. */
+#define AIC_FRAME_OUT_SPLIT 512u
 #define AIC_FRAME_PIXEL_CENTERS 4u /* one ray through each pixel centre, Viewport::normalize_fb_x/_y (viewport.rs:89-99),
                                     * as the text renderer casts them (sr.rs:400-472); default: the image path's patch
                                     * centres / antialiasing points (renderer.rs:424-451) */
@@ -240,6 +258,10 @@ int aic_replace_blocks(aic_ctx *ctx, int layer, uint32_t n, const uint32_t *indi
 int aic_compact(aic_ctx *ctx, int layer);
 /* replaces: the graphics_options DynSource (updating.rs:24,68-73). */
 int aic_set_options(aic_ctx *ctx, int layer, const aic_options *options);
+/* The depth transform of AIC_FRAME_OUT_SPLIT frames: zw = {m33, m43, m34, m44} of the caller's depth_transform (raytrace_to_texture.rs:613-618: the
+ * camera's projection, pre-translated by -near along z and pre-scaled by -(far - near)), euclid names. Default {1, 0, 0, 1}: the plane is the linear depth.
+ * Waits for the frames in flight; the frames submitted from then on use it. AIC_ERR_INVALID for a component that is not finite. */
+int aic_set_depth_transform(aic_ctx *ctx, const double zw[4]);
 
 /* --- drawing: RtRenderer::draw_rgba / HeadlessRenderer::draw --------------------------- */
 /* replaces: RtRenderer::draw_rgba -> trace_scene_to_image_impl (renderer.rs:282-308, 516-556):
@@ -371,6 +393,7 @@ int aic_multi_update_light_volume(aic_multi *m, int layer, const uint8_t *light)
 int aic_multi_replace_blocks(aic_multi *m, int layer, uint32_t n, const uint32_t *indices, const aic_block_desc *descs,
                              const uint16_t *const *voxels, const float *const *palettes);
 int aic_multi_set_options(aic_multi *m, int layer, const aic_options *options);
+int aic_multi_set_depth_transform(aic_multi *m, const double zw[4]);
 /* out_rgba8: [height][width] RGBA8; out_is_device != 0: a device pointer on device_ids[0] */
 int aic_multi_render(aic_multi *m, const aic_frame_desc *frame, void *out_rgba8, int out_is_device, aic_frame_info *info);
 /* The streaming pair of the multi-device context (ABI 3), as aic_render_submit / aic_render_wait are of one context's: submit queues the frame on

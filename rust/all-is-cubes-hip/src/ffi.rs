@@ -24,6 +24,7 @@ pub const AIC_FRAME_OUT_LINEAR: u32 = 8;
 pub const AIC_FRAME_OUT_COLORBUF: u32 = 16;
 pub const AIC_FRAME_NO_FEEDBACK: u32 = 32;
 pub const AIC_FRAME_BLOOM: u32 = 64;
+pub const AIC_FRAME_OUT_SPLIT: u32 = 512;
 pub const AIC_RAYS_NO_SKY: u32 = 128;
 pub const AIC_RAYS_DEVICE: u32 = 256;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
@@ -206,6 +207,7 @@ unsafe extern "C" {
     pub fn aic_replace_blocks(ctx: *mut aic_ctx, layer: c_int, n: u32, indices: *const u32, descs: *const aic_block_desc, voxels: *const *const u16, palettes: *const *const f32) -> c_int;
     pub fn aic_compact(ctx: *mut aic_ctx, layer: c_int) -> c_int;
     pub fn aic_set_options(ctx: *mut aic_ctx, layer: c_int, options: *const aic_options) -> c_int;
+    pub fn aic_set_depth_transform(ctx: *mut aic_ctx, zw: *const f64) -> c_int;
     pub fn aic_render(ctx: *mut aic_ctx, frame: *const aic_frame_desc, out_rgba8: *mut c_void, out_is_device: c_int, info: *mut aic_frame_info) -> c_int;
     pub fn aic_render_submit(ctx: *mut aic_ctx, frame: *const aic_frame_desc, out_device: *mut c_void, slot: u32) -> c_int;
     pub fn aic_render_wait(ctx: *mut aic_ctx, slot: u32, info: *mut aic_frame_info) -> c_int;
@@ -235,6 +237,7 @@ unsafe extern "C" {
     pub fn aic_multi_update_light_volume(m: *mut aic_multi, layer: c_int, light: *const u8) -> c_int;
     pub fn aic_multi_replace_blocks(m: *mut aic_multi, layer: c_int, n: u32, indices: *const u32, descs: *const aic_block_desc, voxels: *const *const u16, palettes: *const *const f32) -> c_int;
     pub fn aic_multi_set_options(m: *mut aic_multi, layer: c_int, options: *const aic_options) -> c_int;
+    pub fn aic_multi_set_depth_transform(m: *mut aic_multi, zw: *const f64) -> c_int;
     pub fn aic_multi_render(m: *mut aic_multi, frame: *const aic_frame_desc, out_rgba8: *mut c_void, out_is_device: c_int, info: *mut aic_frame_info) -> c_int;
     pub fn aic_multi_render_submit(m: *mut aic_multi, frame: *const aic_frame_desc, out_rgba8: *mut c_void, out_is_device: c_int, slot: u32) -> c_int;
     pub fn aic_multi_render_wait(m: *mut aic_multi, slot: u32, info: *mut aic_frame_info) -> c_int;

@@ -487,6 +487,41 @@ impl HipRtRenderer {
         self.wrap_rendering(viewport, data, info, info_text)
     }
 
+    /// The frame as all-is-cubes-gpu's `raytrace_to_texture` stores it (raytrace_to_texture.rs:594-675): per pixel the `[f16; 4]` premultiplied colour
+    /// times the exposure of the pixel's layer (as `f16` bits) and the `f32` projected depth of the nearest surface, negative on UI pixels -- the two
+    /// texels of its `Split { color, depth, layer }` accumulator, written by the device (`AIC_FRAME_OUT_SPLIT`). The depth transform is that renderer's
+    /// own (lines 613-618), taken from the world camera. No info text and no bloom: that renderer post-processes the colour target itself.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer (its strips are gathered as RGBA8).
+    pub fn draw_split(&mut self) -> Result<(Vec<[u16; 4]>, Vec<f32>), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("draw_split needs a single-device renderer") };
+        let (viewport, mut frame) = self.frame_desc();
+        frame.flags = ffi::AIC_FRAME_OUT_SPLIT;
+        let camera = &self.cameras.cameras().world;
+        let depth_scale = -(camera.view_distance().into_inner() - camera.near_plane_distance().into_inner());
+        let depth_bias = -camera.near_plane_distance().into_inner();
+        let p = camera.projection_matrix();
+        let zw = [depth_scale * p.m33, depth_bias * p.m33 + p.m43, depth_scale * p.m34, depth_bias * p.m34 + p.m44];
+        // SAFETY: the context is live; `zw` holds the four coefficients the call copies
+        self.device.check(unsafe { ffi::aic_set_depth_transform(ctx.as_ptr(), zw.as_ptr()) })?;
+        let size = viewport.framebuffer_size;
+        let n = (size.width as usize) * (size.height as usize);
+        // one allocation of u64 words (the colour plane wants 8-byte texels): n of colour, then n / 2 rounded up of depth
+        let mut planes = vec![0u64; n + n.div_ceil(2)];
+        let mut info = ffi::aic_frame_info::default();
+        if n != 0 {
+            // SAFETY: the context is live; `planes` holds the 12 bytes per pixel the call writes and outlives it
+            self.device.check(unsafe { ffi::aic_render(ctx.as_ptr(), &frame, planes.as_mut_ptr().cast(), 0, &mut info) })?;
+        }
+        let color = planes[..n].iter().map(|t| [*t as u16, (*t >> 16) as u16, (*t >> 32) as u16, (*t >> 48) as u16]).collect();
+        let depth = (0..n).map(|i| f32::from_bits((planes[n + i / 2] >> (32 * (i % 2))) as u32)).collect();
+        Ok((color, depth))
+    }
+
     /// The finished pixels as the trait's `Rendering`: info text, flaws, info.
     fn wrap_rendering(&self, viewport: Viewport, mut data: Vec<[u8; 4]>, info: ffi::aic_frame_info, info_text: &str) -> Result<Rendering, RenderError> {
         let size = viewport.framebuffer_size;
