@@ -1,8 +1,9 @@
 // aic_ctx.h -- what the translation units of the C ABI's host side share: the context behind the opaque `aic_ctx` of
-// include/aic_hip.h, its layers and device buffers, and the error helpers. Internal: included by aic_abi.cpp and
-// aic_light_host.cpp only (both are written inside `using namespace aic`, and so is this header). Whatever one of the two
+// include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
+// (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace) and
+// aic_light_host.cpp only (all three are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
-// launchers both call.
+// launchers they call.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -217,6 +219,11 @@ int hip_fail(aic_ctx *c, const char *what, hipError_t e);
 inline bool valid_layer(int l) { return l == AIC_LAYER_WORLD || l == AIC_LAYER_UI; }
 
 // aic_abi.cpp
+aic_options default_options();
+// the call recorder (AIC_DUMP): appends one record {tag, layer, bytes, payload} to the context's dump file, if it has one
+enum DumpTag : uint32_t { DUMP_UPLOAD = 1, DUMP_CLEAR = 2, DUMP_CUBES = 3, DUMP_LIGHT = 4, DUMP_BLOCK = 5, DUMP_OPTIONS = 6, DUMP_FRAME = 7 };
+struct DumpPart { const void *p; size_t n; };
+void dump_record(aic_ctx *c, uint32_t tag, uint32_t layer, std::initializer_list<DumpPart> parts);
 int take_light_spare(aic_ctx *c, Layer &l, int layer, size_t n, int *index);
 int quiesce(aic_ctx *c);
 // aic_light_host.cpp

@@ -333,7 +333,7 @@ def test_xcd_local_tile_queues_trace_every_pixel_once(ctx, synth_space):
 
 def test_frames_of_changing_shape_on_one_slot(ctx, synth_space):
     """A slot prepares its next frame behind the one that is done (counters and cost record cleared, the record turned into a tile order:
-    csrc/aic_abi.cpp submit_frame), keyed by the frame's shape and view. Frames of different sizes, views and feedback settings taken in turn on the
+    csrc/aic_frame.cpp prepare_next_frame), keyed by the frame's shape and view. Frames of different sizes, views and feedback settings taken in turn on the
     same slot must each be what a fresh context gives, sums included -- nothing of a neighbour's record, order or counters may leak."""
     opt = oracle.make_options(fog=1, transparency=1, lighting=2)
     ctx.upload_space(abi.LAYER_WORLD, synth_space)
@@ -815,7 +815,7 @@ def test_two_frames_in_flight_equal_synchronous_frames(ctx):
 @pytest.mark.parametrize("in_flight_n", [3, 4, 8])
 def test_streamed_full_size_frames_on_a_part_of_the_chip_equal_synchronous_frames(ctx, in_flight_n):
     """A streamed frame with several tiles per resident wave that is submitted while others are in flight is launched on a part of the resident
-    grid (aic_abi.cpp submit_frames: a third with three others queued, a quarter from four on). Same frames, byte for byte, same step totals --
+    grid (aic_frame.cpp part_grid_tiles_per_wave: a third with three others queued, a quarter from four on). Same frames, byte for byte, same step totals --
     whatever the grid: ten 1920x1080 frames of the C2 scene, a different camera each."""
     import torch
 

@@ -17,6 +17,10 @@ if [ -f $C/aic_light_host.cpp ]; then  # (revisions from the light host code's o
   /opt/rocm/bin/hipcc $F -x hip -c $C/aic_light_host.cpp -o $D/lighthost.o &
   OBJS="$OBJS $D/lighthost.o"
 fi
+if [ -f $C/aic_frame.cpp ]; then  # (revisions from the frame path's own translation unit on; before, it was part of aic_abi.cpp)
+  /opt/rocm/bin/hipcc $F -x hip -c $C/aic_frame.cpp -o $D/frame.o &
+  OBJS="$OBJS $D/frame.o"
+fi
 if [ -f $C/aic_bloom.hip ]; then  # (revisions from the bloom post-process on)
   /opt/rocm/bin/hipcc $F -c $C/aic_bloom.hip -o $D/bloom.o &
   OBJS="$OBJS $D/bloom.o"

@@ -15,14 +15,18 @@ if [ -n "$AIC_PATCH" ]; then
 fi
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
-  ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_trace.hip -o variants/trace_$name.o &&
+  ( OBJS="variants/trace_$name.o variants/light_$name.o variants/abi_$name.o variants/lighthost_$name.o variants/multi_$name.o variants/bloom_$name.o"
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_trace.hip -o variants/trace_$name.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -x hip -c $C/aic_abi.cpp -o variants/abi_$name.o &&
+    if [ -f $C/aic_frame.cpp ]; then  # (the frame path's own translation unit; an AIC_PATCH tree of an older revision has it inside aic_abi.cpp)
+      OBJS="$OBJS variants/frame_$name.o"
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -x hip -c $C/aic_frame.cpp -o variants/frame_$name.o
+    fi &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -x hip -c $C/aic_light_host.cpp -o variants/lighthost_$name.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_light.hip -o variants/light_$name.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $flags -x hip -c $C/aic_multi.cpp -o variants/multi_$name.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_bloom.hip -o variants/bloom_$name.o &&
     # (--no-undefined: an object missing from this list fails here, not when the library is loaded)
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -Wl,--no-undefined -o variants/libaic_hip_$name.so variants/trace_$name.o variants/light_$name.o variants/abi_$name.o variants/lighthost_$name.o \
-      variants/multi_$name.o variants/bloom_$name.o && rm variants/*_$name.o && echo "built $name" ) &
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -Wl,--no-undefined -o variants/libaic_hip_$name.so $OBJS && rm variants/*_$name.o && echo "built $name" ) &
 done
 wait

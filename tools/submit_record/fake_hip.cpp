@@ -1,0 +1,238 @@
+// fake_hip.cpp -- a recording stand-in for the HIP runtime calls and kernel launchers the host side of the C ABI (aic_abi.cpp, aic_frame.cpp) uses.
+// Nothing of the real runtime is loaded: device memory is host memory, streams and events are ordinals, a launch is a line of text. Every call is logged
+// with its sizes; streams and events by creation ordinal, every device pointer as allocation ordinal + offset, so that two builds of the host code driven
+// through the same scenarios (driver.cpp) give byte-identical records exactly when they make the same calls in the same order.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+
+#include "aic_bloom.h"
+#include "aic_device.h"
+#include "record.h"
+
+namespace {
+
+struct Alloc { size_t size; int ordinal; };
+std::map<const char *, Alloc> g_allocs;  // by base address
+std::map<const void *, int> g_handles;   // streams and events
+std::map<std::string, int> g_calls, g_fail_at;
+int g_next_alloc = 0, g_next_stream = 0, g_next_event = 0;
+bool g_bail = false;
+
+std::string handle(const void *h, char kind) {
+    if (!h) return std::string(1, kind) + "-";
+    auto it = g_handles.find(h);
+    return std::string(1, kind) + (it == g_handles.end() ? "?" : std::to_string(it->second));
+}
+#define P(x) rec_ptr(x).c_str()
+#define S(x) handle(x, 'S').c_str()
+#define E(x) handle(x, 'E').c_str()
+
+// counts the call; true when it is the one fake_fail asked to fail
+bool failing(const char *fn) {
+    const int n = g_calls[fn]++;
+    auto it = g_fail_at.find(fn);
+    if (it == g_fail_at.end() || it->second != n) return false;
+    g_fail_at.erase(it);
+    rec("%s FAILS", fn);
+    return true;
+}
+#define FAKE(fn, ...)                                      \
+    do {                                                   \
+        rec(__VA_ARGS__);                                  \
+        if (failing(fn)) return std::strcmp(fn, "hipMalloc") ? hipErrorInvalidValue : hipErrorOutOfMemory; \
+    } while (0)
+
+void rec_words(const char *name, const void *p, size_t n_words) {  // floats and ints alike, as 32-bit words
+    std::string s = name;
+    for (size_t i = 0; i < n_words; i++) { char b[16]; std::snprintf(b, sizeof(b), " %08x", ((const uint32_t *)p)[i]); s += b; }
+    rec("%s", s.c_str());
+}
+
+void rec_layer(const aic::DevLayer &l) {
+    rec("  layer pool %s cls %s light %s blocks %s palette %s n_blocks %u present %d air %d sky_kind %d cls_in_code %u", P(l.pool), P(l.cls), P(l.light), P(l.blocks),
+        P(l.palette), l.n_blocks, l.present, l.air_index, l.sky_kind, l.cls_in_code);
+    rec_words("  layer lo size", l.lo, 6);
+    rec_words("  layer sky", l.sky, 24);
+    rec_words("  layer block_sky", l.block_sky, 7);
+    rec("  layer opt fog %d transparency %d threshold %a lighting %d antialiasing %d debug_pixel_cost %d tone_mapping %d maximum_intensity %a bounce_samples %d pad %d view_distance %a exposure %a",
+        l.opt.fog, l.opt.transparency, l.opt.threshold, l.opt.lighting, l.opt.antialiasing, l.opt.debug_pixel_cost, l.opt.tone_mapping, l.opt.maximum_intensity,
+        l.opt.bounce_samples, l.opt.pad_, l.opt.view_distance, l.exposure);
+    rec_words("  layer inv", l.inv, 32);
+}
+
+void rec_frame(const aic::DevFrame &F) {
+    rec_layer(F.layer);
+    rec("  transparency %d lighting %d size %ux%u antialias %d maximum_intensity %a tone_mapping %d strip_rows %u n_parts %u part %u local_rows %u", F.layer_transparency,
+        F.layer_lighting, F.width, F.height, F.antialias, F.maximum_intensity, F.tone_mapping, F.strip_rows, F.n_parts, F.part, F.local_rows);
+    rec("  tiles %ux%u tile %u macro %u macros %ux%u n_cus %u tiles_per_wave %u pass %d hit_layer %u use_init %d pixel_centers %d out_mode %d", F.tiles_x, F.tiles_y, F.tile,
+        F.macro, F.macros_x, F.macros_y, F.n_cus, F.tiles_per_wave, F.pass, F.hit_layer, F.use_init, F.pixel_centers, F.out_mode);
+    rec("  ortho %s ortho_n %d patches %s n_patches %u bare_trace %d rays %s aux %s n_queues %u n_sub %u", P(F.ortho), F.ortho_n, P(F.patches), F.n_patches, F.bare_trace, P(F.rays),
+        P(F.aux), F.n_queues, F.n_sub);
+    rec("  light_lut %s srgb_thr %s edge_x %s edge_y %s ray_cold %s ray_cold_groups %u ray_mode %u exchange %u", P(F.light_lut), P(F.srgb_thr), P(F.edge_x), P(F.edge_y),
+        P(F.ray_cold), F.ray_cold_groups, F.ray_mode, F.exchange);
+    rec_words("  depth_zw", F.depth_zw, 8);
+    static const aic::DevSub none = {};
+    for (uint32_t j = 0; j < aic::kMaxSub; j++) {
+        const aic::DevSub &s = F.sub[j];
+        if (j >= F.n_sub && !std::memcmp(&s, &none, sizeof(s)) && !F.split_depth[j] && F.split_ui_exposure[j] == 0.f) continue;  // (an unused sub-frame left at zero)
+        rec("  sub %u exposure %a has_backdrop %d out %s acc %s counters %s host_counters %s tile_order %s tile_cost %s queue_start %s split_depth %s ui_exposure %a", j, s.exposure,
+            s.has_backdrop, P(s.out), P(s.acc_buf), P(s.counters), P(s.host_counters), P(s.tile_order), P(s.tile_cost), P(s.queue_start), P(F.split_depth[j]), F.split_ui_exposure[j]);
+        rec_words("  sub inv", s.inv, 32);
+        rec_words("  sub backdrop", s.backdrop, 4);
+    }
+}
+
+}  // namespace
+
+void rec(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vprintf(fmt, ap);
+    va_end(ap);
+    std::putchar('\n');
+}
+std::string rec_ptr(const void *p) {
+    if (!p) return "null";
+    auto it = g_allocs.upper_bound((const char *)p);
+    if (it != g_allocs.begin()) {
+        --it;
+        const size_t off = (size_t)((const char *)p - it->first);
+        if (off < it->second.size) return "A" + std::to_string(it->second.ordinal) + "+" + std::to_string(off);
+    }
+    return "host";
+}
+void fake_reset() {
+    if (!g_allocs.empty() || !g_handles.empty()) rec("LEAK %zu allocations, %zu streams and events", g_allocs.size(), g_handles.size());
+    g_next_alloc = g_next_stream = g_next_event = 0;
+    g_calls.clear();
+    g_fail_at.clear();
+    g_bail = false;
+}
+void fake_fail(const char *fn, int nth) { g_fail_at[fn] = g_calls[fn] + nth; }
+int fake_calls(const char *fn) { return g_calls[fn]; }
+void fake_bail(bool on) { g_bail = on; }
+
+// ---- the runtime
+extern "C" {
+
+hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
+hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
+hipError_t hipSetDevice(int) { return hipSuccess; }  // (every entry point begins with it: not logged)
+hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) {
+    std::memset(p, 0, sizeof(*p));
+    p->multiProcessorCount = 256;
+    std::snprintf(p->name, sizeof(p->name), "fake");
+    std::snprintf(p->gcnArchName, sizeof(p->gcnArchName), "gfx950");
+    return hipSuccess;
+}
+hipError_t hipGetLastError(void) { return hipSuccess; }
+const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "invalid value"; }
+
+hipError_t hipMalloc(void **p, size_t bytes) {
+    FAKE("hipMalloc", "hipMalloc %zu -> A%d", bytes, g_next_alloc);
+    *p = std::calloc(1, bytes);
+    g_allocs[(const char *)*p] = Alloc{bytes, g_next_alloc++};
+    return hipSuccess;
+}
+hipError_t hipFree(void *p) {
+    rec("hipFree %s", P(p));
+    g_allocs.erase((const char *)p);
+    std::free(p);
+    return hipSuccess;
+}
+hipError_t hipHostMalloc(void **p, size_t bytes, unsigned int flags) {
+    FAKE("hipHostMalloc", "hipHostMalloc %zu flags %u", bytes, flags);
+    *p = std::calloc(1, bytes);
+    return hipSuccess;
+}
+hipError_t hipHostFree(void *p) { rec("hipHostFree"); std::free(p); return hipSuccess; }
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    FAKE("hipMemcpyAsync", "hipMemcpyAsync %s <- %s bytes %zu kind %d %s", P(dst), P(src), bytes, (int)kind, S(s));
+    std::memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+hipError_t hipMemcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+    FAKE("hipMemcpy", "hipMemcpy %s <- %s bytes %zu kind %d", P(dst), P(src), bytes, (int)kind);
+    std::memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+hipError_t hipMemsetAsync(void *dst, int value, size_t bytes, hipStream_t s) {
+    FAKE("hipMemsetAsync", "hipMemsetAsync %s value %d bytes %zu %s", P(dst), value, bytes, S(s));
+    std::memset(dst, value, bytes);
+    return hipSuccess;
+}
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned int flags) {
+    FAKE("hipStreamCreateWithFlags", "hipStreamCreateWithFlags %u -> S%d", flags, g_next_stream);
+    *s = (hipStream_t) new char;
+    g_handles[*s] = g_next_stream++;
+    return hipSuccess;
+}
+hipError_t hipStreamDestroy(hipStream_t s) { rec("hipStreamDestroy %s", S(s)); g_handles.erase(s); delete (char *)s; return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s) { FAKE("hipStreamSynchronize", "hipStreamSynchronize %s", S(s)); return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned int flags) { FAKE("hipStreamWaitEvent", "hipStreamWaitEvent %s %s %u", S(s), E(e), flags); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned int flags) {
+    FAKE("hipEventCreate", "hipEventCreate flags %u -> E%d", flags, g_next_event);
+    *e = (hipEvent_t) new char;
+    g_handles[*e] = g_next_event++;
+    return hipSuccess;
+}
+hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
+hipError_t hipEventDestroy(hipEvent_t e) { rec("hipEventDestroy %s", E(e)); g_handles.erase(e); delete (char *)e; return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { FAKE("hipEventRecord", "hipEventRecord %s %s", E(e), S(s)); return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { FAKE("hipEventSynchronize", "hipEventSynchronize %s", E(e)); return hipSuccess; }
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { FAKE("hipEventElapsedTime", "hipEventElapsedTime %s %s", E(a), E(b)); *ms = 1.0f; return hipSuccess; }
+
+}  // extern "C"
+
+// ---- the kernel launchers and the light updater's hooks
+struct aic_ctx;
+namespace aic {
+
+struct LightState;
+void light_state_free(LightState *) {}
+void light_state_cubes_updated(LightState *, uint64_t, uint64_t, uint32_t, const int32_t *, const uint16_t *, const uint8_t *) {}
+int light_job_finish(aic_ctx *) { return 0; }
+
+size_t trace_ray_cold_bytes(uint32_t n_cus, uint32_t *groups) {  // (a pure question, not a launch: not logged. The numbers are arbitrary, not the library's: any non-zero size serves)
+    *groups = n_cus * 4u;
+    return (size_t)*groups * 320u * 16u;
+}
+void launch_trace_image(const DevFrame &F, bool diag, hipStream_t stream) {
+    rec("launch_trace_image diag %d %s", (int)diag, S(stream));
+    rec_frame(F);
+    if (g_bail && F.sub[0].host_counters) F.sub[0].host_counters[5] = 1;  // DevCounters::bailed
+}
+void launch_order_tiles(const uint32_t *cost, uint32_t *order, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, uint32_t *queue_start, hipStream_t stream,
+                        bool clear_cost, uint32_t *clear_words, uint32_t n_clear_words) {
+    rec("launch_order_tiles cost %s order %s n_tiles %u macros_x %u sb_shift %u n_queues %u queue_start %s %s clear_cost %d clear_words %s %u", P(cost), P(order), n_tiles, macros_x,
+        sb_shift, n_queues, P(queue_start), S(stream), (int)clear_cost, P(clear_words), n_clear_words);
+}
+void launch_order_tiles_jobs(const OrderJobs &jobs, uint32_t n_jobs, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, hipStream_t stream, bool clear_cost,
+                             uint32_t n_clear_words) {
+    rec("launch_order_tiles_jobs n_jobs %u n_tiles %u macros_x %u sb_shift %u n_queues %u %s clear_cost %d n_clear_words %u", n_jobs, n_tiles, macros_x, sb_shift, n_queues, S(stream),
+        (int)clear_cost, n_clear_words);
+    for (uint32_t j = 0; j < kMaxSub; j++)
+        if (j < n_jobs || jobs.cost[j] || jobs.order[j] || jobs.queue_start[j] || jobs.clear_words[j])
+            rec("  job %u cost %s order %s queue_start %s clear_words %s", j, P(jobs.cost[j]), P(jobs.order[j]), P(jobs.queue_start[j]), P(jobs.clear_words[j]));
+}
+void launch_bloom(const BloomGeom &g, const BloomParams &p, hipStream_t stream) {
+    rec("launch_bloom %ux%u levels %u texels %u colorbuf %s mips %s out %s exposure %a intensity %a tone_mapping %d maximum_intensity %a srgb_thr %s %s", g.width, g.height, g.levels,
+        g.texels, P(p.colorbuf), P(p.mips), P(p.out), p.exposure, p.intensity, p.tone_mapping, p.maximum_intensity, P(p.srgb_thr), S(stream));
+}
+void launch_tag_cubes(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged, hipStream_t stream) {
+    rec("launch_tag_cubes %s n %zu cls %s %d %d %s", P(grid), n, P(cls), from_tagged, to_tagged, S(stream));
+}
+// (what the scenarios never reach: scene updates, strip assembly, the probes)
+void launch_scatter_cubes(uint16_t *, uint32_t *, const int32_t *, const uint16_t *, const uint32_t *, uint32_t, const int[3], const int[3], const uint32_t *, hipStream_t) { rec("launch_scatter_cubes"); }
+void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
+void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
+void launch_assemble_strips(const uint32_t *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t) { rec("launch_assemble_strips"); }
+void launch_probe_raycast(const double *, int, const int *, int, uint32_t, double *, uint32_t *, int *, hipStream_t) { rec("launch_probe_raycast"); }
+
+}  // namespace aic
