@@ -3,7 +3,7 @@
 // Owns the device-resident snapshot of up to two Spaces (world + UI), i.e. what the
 // reference keeps in `RtRenderer.rts: Layers<Option<UpdatingSpaceRaytracer>>`
 // (all-is-cubes-render/src/raytracer/renderer.rs:35-54), and launches the kernels of
-// aic_trace.hip on a private HIP stream. No CPU rendering path exists here: every entry
+// aic_trace.hip (aic_launch.h) on a private HIP stream. No CPU rendering path exists here: every entry
 // point fails with AIC_ERR_NO_DEVICE / AIC_ERR_DEVICE when HIP is unusable.
 // Here: the context, scene upload and update, options, strip assembly, synchronisation and the probes. The frame
 // path -- everything that submits or waits for a trace -- is aic_frame.cpp, the light updater aic_light_host.cpp.
@@ -27,18 +27,7 @@
 #include "aic_bloom.h"
 #include "aic_ctx.h"
 #include "aic_device.h"
-
-namespace aic {
-void launch_scatter_cubes(uint16_t *grid, uint32_t *light, const int32_t *xyz, const uint16_t *bi, const uint32_t *lt,
-                          uint32_t n, const int lo[3], const int size[3], const uint32_t *cls, hipStream_t stream);
-void launch_probe_powf(const float *x, const float *y, float *out, uint32_t n, hipStream_t stream);
-void launch_probe_expf(const float *x, float *out, uint32_t n, hipStream_t stream);
-void launch_tag_cubes(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged, hipStream_t stream);
-void launch_assemble_strips(const uint32_t *gathered, uint32_t *out, uint32_t w, uint32_t h, uint32_t strip_rows,
-                            uint32_t n_parts, uint32_t max_rows, hipStream_t stream);
-void launch_probe_raycast(const double *od, int use_bounds, const int *lohi, int include_exit, uint32_t max_steps,
-                          double *out_rec, uint32_t *n_out, int *ended, hipStream_t stream);
-}  // namespace aic
+#include "aic_launch.h"
 
 using namespace aic;
 

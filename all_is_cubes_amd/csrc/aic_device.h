@@ -140,7 +140,7 @@ struct DevSub {
     // pinned host memory for the frame's five sums (cubes_traced, n_outer, n_inner, n_hits, n_light) and the `bailed` count, written by the last wave of the world pass
     // to finish: no copy launch behind the trace (a blit kernel that, with frames streamed, waits ~0.2 ms for a CU to have room). Null: the host copies.
     unsigned long long *host_counters;
-    // cost feedback (aic_trace.hip order_tiles_kernel): tile_order[k] = k-th macro tile to hand out, longest
+    // cost feedback (aic_scene_kernels.h order_tiles_kernel): tile_order[k] = k-th macro tile to hand out, longest
     // rays of the previous frame first (null: index order); tile_cost[macro tile] receives this frame's longest ray
     const uint32_t *tile_order;
     uint32_t *tile_cost;

@@ -9,7 +9,7 @@
 #ifndef AIC_DEV
 #define AIC_DEV __device__ __forceinline__
 #endif
-// (aic_trace.hip explains it: a wave-uniform block that must stay a branch)
+// (aic_raycast.h explains it: a wave-uniform block that must stay a branch)
 #ifndef AIC_RARE_PATH
 #define AIC_RARE_PATH() asm volatile("" ::: "memory")
 #endif

@@ -19,16 +19,7 @@
 #include "aic_bloom.h"
 #include "aic_ctx.h"
 #include "aic_device.h"
-
-namespace aic {
-void launch_trace_image(const DevFrame &F, bool diag, hipStream_t stream);
-size_t trace_ray_cold_bytes(uint32_t n_cus, uint32_t *groups);
-void launch_order_tiles(const uint32_t *cost, uint32_t *order, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, uint32_t *queue_start,
-                        hipStream_t stream, bool clear_cost = false, uint32_t *clear_words = nullptr, uint32_t n_clear_words = 0);
-// the same for the frames of a batch, one workgroup each, in ONE launch (OrderJobs: aic_device.h)
-void launch_order_tiles_jobs(const OrderJobs &jobs, uint32_t n_jobs, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, hipStream_t stream,
-                             bool clear_cost, uint32_t n_clear_words);
-}  // namespace aic
+#include "aic_launch.h"
 
 using namespace aic;
 
@@ -53,7 +44,7 @@ void fill_dev_layer(const Layer &l, const aic_camera &cam, DevLayer *d) {
     d->opt.fog = o.fog;
     d->opt.transparency = o.transparency;
     d->opt.threshold = o.threshold;
-    d->opt.lighting = o.lighting;  // 5 = Bounce: traced as the reference does (surface.rs:119-166; aic_trace.hip bounce_secondary_ray)
+    d->opt.lighting = o.lighting;  // 5 = Bounce: traced as the reference does (surface.rs:119-166; aic_light_bounce.h bounce_secondary_ray)
     d->opt.bounce_samples = o.bounce_samples;
     d->opt.antialiasing = o.antialiasing;
     d->opt.debug_pixel_cost = o.debug_pixel_cost;
@@ -253,7 +244,7 @@ void plan_dispatch(const aic_ctx *c, uint32_t k, const aic_frame_desc *f, bool a
     P.want_aux = allow_aux && (f->flags & AIC_FRAME_AUX) != 0;
     P.diag = P.want_aux || P.split || (f->flags & AIC_FRAME_COUNTERS) != 0;  // (the Split's depth and layer live in the recording variants only)
     P.n_tiles = F.macros_x * F.macros_y;  // the feedback works on macro tiles
-    // XCD-local tile queues (aic_trace.hip order_tiles_kernel): one per XCD (32 CUs each on this part), a macro tile in the queue of the
+    // XCD-local tile queues (aic_scene_kernels.h order_tiles_kernel): one per XCD (32 CUs each on this part), a macro tile in the queue of the
     // 2^sb_shift-macro-tile super-block it lies in. One queue (aic_frame_desc.tuning) is the single dispenser of rounds 1-3.
     // (aic_frame_desc.tuning; environment variables read per frame until round 5)
     const int queues_env = (int)((f->tuning >> AIC_TUNE_QUEUES_SHIFT) & 15u);

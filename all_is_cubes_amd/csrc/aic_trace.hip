@@ -1,25 +1,39 @@
-// aic_trace.hip -- hand-written CDNA4 (gfx950) kernels of the voxel raytracer.
+// aic_trace.hip -- hand-written CDNA4 (gfx950) kernels of the voxel raytracer: the image kernel and its launchers. The ONE device translation
+// unit of the trace side: what it is made of lives in headers by subject, included below and compiled with it (DESIGN.md 4 has the reason --
+// compiling the small kernels on their own changes the image kernels' register allocation):
+//   aic_tunables.h       the numeric build-time tunables (AIC_*)
+//   aic_raycast.h        the Raycaster restated (lvl_init, lvl_next, lvl_first_masks, intersection_point)
+//   aic_colour.h         f32 colour arithmetic, the powf / expf tables
+//   aic_light_bounce.h   light lookup, LightingOption::Bounce's secondary rays
+//   aic_scene_kernels.h  scatter_cubes, tag_cubes, order_tiles, assemble_strips and their launchers
+//   aic_probe_kernels.h  the probe kernels and their launchers
+//   aic_launch.h         every launcher of this translation unit as the host code sees it
 //
 // Replaces, behind the C ABI of include/aic_hip.h, the reference's per-image hot loop:
 //   trace_scene_to_image_impl / RtScene::trace_patch / trace_ray_through_layers
-//       (all-is-cubes-render/src/raytracer/renderer.rs:424-478, 516-556)
+//       and the draw_rgba encoder (all-is-cubes-render/src/raytracer/renderer.rs:282-308, 424-478, 516-556)
 //   SpaceRaytracer::trace_ray_impl + TracingState (raytracer/sr.rs:135-238, 595-769)
 //   SurfaceIter / VoxelSurfaceIter / DepthIter (raytracer/surface.rs:251-491)
 //   Raycaster (all-is-cubes-base/src/raycast.rs:63-832)
 //   ColorBuf / apply_transmittance (all-is-cubes/src/raytracer_components.rs:20-258)
 //   Camera::project_ndc_into_world / post_process_color, Rgba::to_srgb8.
 //
-// Design (MI355X-first, not a translation of the reference's iterator stack):
-//  * persistent waves: the grid is what is resident at the kernel's occupancy (2 waves per SIMD);
-//    each wave pulls 8x8-pixel tiles (one wave-full) from a global counter, macro tile by macro
-//    tile, costliest macro tiles of the previous frame first, and refills idle lanes one by one.
-//  * every lane is a state machine. ONE predicated, straight-line Amanatides-Woo step serves both
-//    DDA levels (cube grid and a block's voxels share the lookup pool, the registers and the
-//    code); the expensive, divergent work -- shading a surface, entering a block, finishing /
-//    starting a ray -- is parked per lane as an event and run kind by kind when enough lanes wait.
-//  * DDA arithmetic is f64 in the reference's exact operation order (bit-exact hit
-//    cubes/voxels/faces/t); built with -ffp-contract=off. Colour arithmetic is f32 in the
-//    reference's order; powf follows the C library's algorithm, exp is evaluated in f64.
+// Design (MI355X-first, not a translation of the reference's iterator stack). The kernel is bound by instruction issue, not memory:
+//  * persistent waves: the grid is what is resident at the kernel's occupancy -- the production variants 4 waves per SIMD (128 VGPRs, no scratch,
+//    four workgroups of 256 threads per CU), the recording (DIAG) and Bounce variants 2. Each wave pulls 8x8-pixel tiles (one wave-full), macro tile
+//    by macro tile, from the tile queue of the XCD it runs on -- one queue per XCD, each ordered costliest macro tiles of the previous frame first
+//    (order_tiles_kernel); it helps the next XCD's queue when its own is empty -- and refills idle lanes one by one.
+//  * every lane is a state machine. ONE predicated, straight-line Amanatides-Woo step serves both DDA levels (cube grid and a block's voxels share
+//    the lookup pool, the registers and the code): a stepping trip is up to AIC_STEP_REPS full passes, each preceded by up to AIC_FAST_STEPS
+//    bookkeeping-free fast steps. The expensive, divergent work -- shading a surface, entering a block, finishing / starting a ray -- is parked per
+//    lane as an event and run kind by kind when enough lanes wait; ENTER and NEWRAY take the first lookup of the level they set up themselves.
+//  * hot state in registers, cold state (what only events touch) in an LDS column that belongs to the ray, not to the lane.
+//  * lane exchange (the XC variants, chosen at run time by the frame's size): the waves of a workgroup share a pool of parked rays in LDS; before a
+//    round a wave trades lanes that would idle for parked rays of the kind it is about to run, and parks such lanes while slots are free, so that
+//    the workgroup holds more rays than lanes. Nothing waits for another wave; frames are bit-identical for any pool size or policy.
+//  * DDA arithmetic is f64 in the reference's exact operation order (bit-exact hit cubes/voxels/faces/t); built with -ffp-contract=off. Colour
+//    arithmetic is f32 in the reference's order; powf and expf follow the C library's algorithms, evaluated in f64. The per-lane order of
+//    operations is the reference's, so results are bit-identical to the sequential formulation (hit cubes, t values, step counts).
 //  * no MFMA: the path is branchy integer/f64 traversal and gather loads, not a contraction.
 
 #include <hip/hip_runtime.h>
@@ -31,808 +45,26 @@
 #include "aic_device.h"
 #include "aic_encode.h"
 #include "aic_lightmath.h"
+#include "aic_launch.h"
+#include "aic_tunables.h"
+#include "aic_raycast.h"
+#include "aic_colour.h"
+#include "aic_light_bounce.h"
+#include "aic_scene_kernels.h"
+#include "aic_probe_kernels.h"
 
 namespace aic {
 
-#define AIC_DEV __device__ __forceinline__
+// ---- the image kernel's own helpers, constants and structs
 
-constexpr int FACE_WITHIN = 0;
-constexpr int I32_MIN_ = (-2147483647 - 1);
-constexpr int I32_MAX_ = 2147483647;
-
-// first_last states (raycast.rs:153-165)
-constexpr uint32_t FL_BEGINNING = 0, FL_INBOUNDS = 1, FL_ENDED = 2;
-
-// ---------------------------------------------------------------------------------------
-// f64 helpers with the reference's semantics
-
-AIC_DEV int signum_101(double x) {  // raycast.rs:782-788
-    if (x == 0.0) return 0;
-    if (x != x) return 0;
-    return (__double2hiint(x) < 0) ? -1 : 1;
-}
-
-// f64::rem_euclid(1.0): fmod(x,1) == x - trunc(x) exactly (sign of x kept, like fmod)
-AIC_DEV double rem_euclid1(double x) {
-    double r = x - trunc(x);
-    r = copysign(r, x);
-    return r < 0.0 ? r + 1.0 : r;
-}
-
-// ---- f64 divisions that cost less than the generic sequence, with the generic sequence's bits ----
-// The compiler's a / b is v_div_scale x2, v_rcp_f64 (quarter rate), four fused multiply-adds that refine the reciprocal, a multiply, two more
-// multiply-adds, v_div_fmas, v_div_fixup: 11 instructions, IEEE-correct for every input. Two cheaper forms, each used only where its precondition holds
-// for the lane (checked on the operands' exponent fields) and replaced by the generic quotient, under the lanes' exec mask, where it does not:
-//  * div_known_recip: the divisor's correctly rounded reciprocal y = RN(1 / b) is at hand (a ray's t_delta = 1 / |direction|, raycast.rs:766). Then
-//    q0 = a * y is within 1.5 ulp of a / b, q1 = q0 + (a - b q0) y is a faithful quotient, and one more residual step q2 = q1 + (a - b q1) y is a / b
-//    correctly rounded (Markstein's theorem: a faithful q, the exact residual r = a - b q, and y within half an ulp of 1 / b give RN(q + r y) = RN(a / b),
-//    absent overflow / underflow) -- five multiply-adds, no reciprocal instruction (lvl_init). tests: the probe's step tables and 400 random rays (t bit-exact).
-//  * three quotients by one divisor (the unprojection's x / w, y / w, z / w) share the reciprocal's refinement: with operands whose exponents are far from
-//    the ends of the range v_div_scale scales nothing, v_div_fmas is a plain fused multiply-add and v_div_fixup passes the quotient through, so
-//    the shared form performs the generic sequence's own operations on the same values.
-// A block behind a wave-uniform branch that must STAY a branch: arithmetic without side effects is otherwise speculated -- the compiler computes the rare
-// path for every wave and selects (seen with the generic division below: 11 instructions per quotient, executed always). An empty volatile asm
-// statement cannot be speculated.
-#define AIC_RARE_PATH() asm volatile("" ::: "memory")
-// Exponent window of an operand, on the high dword: biased exponent in [768, 1280), i.e. 2^-255 <= |v| < 2^257; and the wider [512, 1536).
-AIC_DEV bool f64_exp_in_768_1280(double v) { return (((uint32_t)__double2hiint(v) << 1) - (768u << 21)) < (512u << 21); }
-AIC_DEV bool f64_exp_in_512_1536(double v) { return (((uint32_t)__double2hiint(v) << 1) - (512u << 21)) < (1024u << 21); }
-AIC_DEV double div_known_recip(double a, double b, double y) {  // a / b for normal b > 0, y = RN(1 / b); a, b and a / b far from overflow and underflow; a is not -0
-    const double q0 = a * y;
-    const double r0 = fma(-b, q0, a);
-    const double q1 = fma(r0, y, q0);
-    const double r1 = fma(-b, q1, a);
-    return fma(r1, y, q1);
-}
-// raycast.rs:797-819, split around its division: the dividend 1 - s.rem_euclid(1) (s and ds negated together for ds < 0: |ds| is the divisor either way) ...
-AIC_DEV double scale_step_dividend(double s, double ds) { return 1.0 - rem_euclid1(ds < 0.0 ? -s : s); }
-// ... and what becomes of the quotient q = dividend / |ds|
-AIC_DEV double scale_step_result(double q, double s, double ds) {
-    return (ds == 0.0 && !(s != s)) ? __longlong_as_double(0x7ff0000000000000LL) : q;
-}
-
-// cube.rs:97-119
-AIC_DEV bool cube_containing(const double p[3], int out[3]) {
-    const double MIN_INCLUSIVE = -2147483648.0;
-    const double MAX_EXCLUSIVE = 2147483648.0;
-    bool ok = (MIN_INCLUSIVE <= p[0]) & (MIN_INCLUSIVE <= p[1]) & (MIN_INCLUSIVE <= p[2]) & (p[0] < MAX_EXCLUSIVE) &
-              (p[1] < MAX_EXCLUSIVE) & (p[2] < MAX_EXCLUSIVE);
-    if (ok) {
-        out[0] = (int)floor(p[0]);
-        out[1] = (int)floor(p[1]);
-        out[2] = (int)floor(p[2]);
-    }
-    return ok;
-}
-
-// Per-ray constants: Parameters::new (raycast.rs:749-771) minus the origin. Kept as scalars
-// (never indexed dynamically) so they live in VGPRs.
-struct RayDir {
-    double dx, dy, dz;     // direction (zeroed if any |component| is not < 1e100)
-    double tdx, tdy, tdz;  // t_delta = 1/|d|
-    int sx, sy, sz;        // step = signum_101(d)
-    bool fast;             // every component is zero or has its exponent in [768, 1280): divisions by it may use t_delta (div_by_dir)
-};
-AIC_DEV bool raydir_fast(double dx, double dy, double dz) {
-    const int fx = f64_exp_in_768_1280(dx) | (dx == 0.0), fy = f64_exp_in_768_1280(dy) | (dy == 0.0), fz = f64_exp_in_768_1280(dz) | (dz == 0.0);
-    return (fx & fy & fz) != 0;
-}
-
-AIC_DEV RayDir raydir_init(double dx, double dy, double dz) {
-    RayDir r;
-    const bool all_small = (fabs(dx) < 1e100) && (fabs(dy) < 1e100) && (fabs(dz) < 1e100);
-    r.dx = all_small ? dx : 0.0;
-    r.dy = all_small ? dy : 0.0;
-    r.dz = all_small ? dz : 0.0;
-    r.sx = signum_101(r.dx); r.sy = signum_101(r.dy); r.sz = signum_101(r.dz);
-    r.tdx = 1.0 / fabs(r.dx); r.tdy = 1.0 / fabs(r.dy); r.tdz = 1.0 / fabs(r.dz);
-    r.fast = raydir_fast(r.dx, r.dy, r.dz);
-    return r;
-}
-
-// State of one DDA level (raycast.rs:99-121 State + FirstLast), with the step deferred: the
-// reference emits `current()` and then advances; here the advance is performed at the start
-// of the following `next`, which is observationally identical and lets `c*` double as the
-// emitted cube.
-struct Lvl {
-    double tx, ty, tz;  // t_max
-    double last_t;
-    int cx, cy, cz;
-    uint32_t st;        // bits 0-1 first_last | 2-4 last_face | 5-6 pick | 7 need_step | 8 include_exit
-};
-// While INBOUNDS: the coordinate value that means "left the bounds", per axis.
-struct Lim {
-    int x, y, z;
-};
-AIC_DEV uint32_t lvl_fl(const Lvl &s) { return s.st & 3u; }
-AIC_DEV int lvl_face(const Lvl &s) { return (int)((s.st >> 2) & 7u); }
-
-AIC_DEV int pick_axis(double tx, double ty, double tz) {  // raycast.rs:584-596
-    if (tx < ty) return (tx < tz) ? 0 : 2;
-    return (ty < tz) ? 1 : 2;
-}
-
-// Raycaster::new(origin, dir) [.within(lo,hi, include_exit)]  (raycast.rs:196-230, 513-545, 632-704)
-struct LvlLim {
-    Lvl s;
-    Lim lim;
-};
-// Written without early exits (round 6): every lane computes everything and `valid` decides at the end -- a level that is State::EMPTY comes back as
-// FL_ENDED with unspecified t_max / cube (nothing reads them: Raycaster::next returns None at once). With the exits, each one cost a saved exec mask, a
-// branch and a dozen moves of default values on the path of every lane that did not take it.
-AIC_DEV bool cube_containing_flat(double x, double y, double z, int out[3]) {  // cube.rs:97-119; `out` is unspecified when there is no cube
-    const double MIN_INCLUSIVE = -2147483648.0;
-    const double MAX_EXCLUSIVE = 2147483648.0;
-    const int ok = (int)(MIN_INCLUSIVE <= x) & (int)(MIN_INCLUSIVE <= y) & (int)(MIN_INCLUSIVE <= z) & (int)(x < MAX_EXCLUSIVE) & (int)(y < MAX_EXCLUSIVE) & (int)(z < MAX_EXCLUSIVE);
-    // (v_cvt_i32_f64 itself, which saturates: the C++ conversion of a value that does not fit is undefined, and the optimiser may act on that)
-    const double fx = floor(x), fy = floor(y), fz = floor(z);
-    asm("v_cvt_i32_f64 %0, %1" : "=v"(out[0]) : "v"(fx));
-    asm("v_cvt_i32_f64 %0, %1" : "=v"(out[1]) : "v"(fy));
-    asm("v_cvt_i32_f64 %0, %1" : "=v"(out[2]) : "v"(fz));
-    return ok != 0;
-}
-// `skip_ff_inside` (NEWRAY, AIC_NEWRAY_SKIP_FF): when every active lane's origin lies inside the bounds -- lo <= o <= hi on all three axes, as doubles; a NaN
-// fails -- the fast-forward and the cube of the fast-forwarded origin are skipped behind one wave-uniform branch. For such a lane every moving axis's signed
-// quotient is <= 0, so max_t is zero, `go` is false, t_start = +0 and `ff` is the origin, whose cube is at hand: the same bits by construction.
-AIC_DEV LvlLim lvl_init(double ox, double oy, double oz, const RayDir rd, bool bounded, int lox, int loy,
-                        int loz, int hix, int hiy, int hiz, bool include_exit, double half_over_len, bool skip_ff_inside = false) {
-    LvlLim out;
-    Lvl &s = out.s;
-    Lim &lim = out.lim;
-    int cube_o[3];
-    int valid = cube_containing_flat(ox, oy, oz, cube_o);
-    // MAXIMUM_BOUNDS.contains_cube (raycast.rs:485-499, 521-523); else State::EMPTY: produces nothing
-    // (c in [MIN + 1, MAX - 2]  <=>  (unsigned)(c - (MIN + 1)) < 2^32 - 3)
-    valid &= (int)((uint32_t)cube_o[0] - 0x80000001u < 0xfffffffdu) & (int)((uint32_t)cube_o[1] - 0x80000001u < 0xfffffffdu) & (int)((uint32_t)cube_o[2] - 0x80000001u < 0xfffffffdu);
-    // bounds = MAXIMUM_BOUNDS ∩ given (empty => ORIGIN_EMPTY, which contains no cube)
-    if (bounded) {
-        lox = max(lox, I32_MIN_ + 1); loy = max(loy, I32_MIN_ + 1); loz = max(loz, I32_MIN_ + 1);
-        hix = min(hix, I32_MAX_ - 1); hiy = min(hiy, I32_MAX_ - 1); hiz = min(hiz, I32_MAX_ - 1);
-    } else {
-        lox = loy = loz = I32_MIN_ + 1;
-        hix = hiy = hiz = I32_MAX_ - 1;
-    }
-    valid &= (int)(hix > lox) & (int)(hiy > loy) & (int)(hiz > loz);
-    // fast_forward (raycast.rs:632-704): plane_origin takes the upper bound on axes the ray descends, else the lower bound; one ray-plane
-    // intersection per moving axis. If the largest t is positive the ray starts again half a cube short of it (`t_start`), else where it is
-    // (t_start = +0: `ff` is the origin itself, and adding +0 to a t_max -- a quotient that is positive, +0 or infinite -- changes nothing).
-    // One copy of the t_max arithmetic serves both (round 6; it was written twice, each copy behind its own per-lane branch).
-    double t_start = 0.0;
-    double ffx = ox, ffy = oy, ffz = oz;
-    int cube[3] = {cube_o[0], cube_o[1], cube_o[2]};
-    bool need_ff = bounded;
-    if (bounded && skip_ff_inside) {
-        const bool inside = ((double)lox <= ox) & (ox <= (double)hix) & ((double)loy <= oy) & (oy <= (double)hiy) & ((double)loz <= oz) & (oz <= (double)hiz);
-        need_ff = __builtin_amdgcn_ballot_w64(!inside) != 0ull;
-    }
-    if (need_ff) {
-        // (the empty asm is here only to keep this a branch -- the arithmetic below is otherwise speculated and selected -- not because the path is
-        //  rare: a camera outside the space takes it at every NEWRAY)
-        if (skip_ff_inside) AIC_RARE_PATH();
-        const double pox = (double)((rd.sx < 0) ? hix : lox);
-        const double poy = (double)((rd.sy < 0) ? hiy : loy);
-        const double poz = (double)((rd.sz < 0) ? hiz : loz);
-        const double relx = pox - ox, rely = poy - oy, relz = poz - oz;
-        // ray_plane_intersection (raycast.rs:821-832) with an axis-aligned unit normal n = +-1:
-        // (rel.n)/(dir.n) == rel_a / dir_a exactly (the +-1 factors and the +-0 terms cancel for the
-        // finite values that reach this point). rel_a / dir_a = +-(rel_a / |dir_a|), the quotient by the reciprocal at hand (div_known_recip) for lanes
-        // whose rel_a is neither zero nor tiny (the origin is inside i32, so it is not huge); computed for every lane, used for the moving axes.
-        const int okx = f64_exp_in_512_1536(relx) | (rd.sx == 0), oky = f64_exp_in_512_1536(rely) | (rd.sy == 0), okz = f64_exp_in_512_1536(relz) | (rd.sz == 0);
-        const bool ff_fast = ((int)rd.fast & okx & oky & okz) != 0;
-        double qx = div_known_recip(relx, fabs(rd.dx), rd.tdx), qy = div_known_recip(rely, fabs(rd.dy), rd.tdy), qz = div_known_recip(relz, fabs(rd.dz), rd.tdz);
-        if (__builtin_amdgcn_ballot_w64(!ff_fast) != 0ull) {  // (never, in an ordinary frame)
-            AIC_RARE_PATH();
-            if (!ff_fast) { qx = relx / fabs(rd.dx); qy = rely / fabs(rd.dy); qz = relz / fabs(rd.dz); }
-        }
-        double max_t = 0.0;
-        max_t = rd.sx != 0 ? fmax(max_t, rd.sx < 0 ? -qx : qx) : max_t;
-        max_t = rd.sy != 0 ? fmax(max_t, rd.sy < 0 ? -qy : qy) : max_t;
-        max_t = rd.sz != 0 ? fmax(max_t, rd.sz < 0 ? -qz : qz) : max_t;
-        const bool go = max_t > 0.0;  // last_t_distance == 0 at this point
-        // 0.5 / direction.length() (raycast.rs:669) is a per-ray constant, computed once by the caller
-        double ts = max_t - half_over_len;
-        ts = isfinite(ts) ? ts : max_t;
-        t_start = go ? ts : 0.0;
-        ffx = go ? ox + rd.dx * ts : ox; ffy = go ? oy + rd.dy * ts : oy; ffz = go ? oz + rd.dz * ts : oz;
-    }
-    // the cube of the fast-forwarded origin; a fast-forwarded origin without one makes the level State::EMPTY (without a fast-forward it is the
-    // origin's own cube, which `valid` has already judged)
-    if (need_ff) valid &= (int)cube_containing_flat(ffx, ffy, ffz, cube);
-    {
-        // scale_to_integer_step on each axis (raycast.rs:797-819). The dividends are in [2^-53, 1] or +0: with a direction in the window (RayDir::fast)
-        // div_known_recip's precondition holds
-        const double ax = scale_step_dividend(ffx, rd.dx), ay = scale_step_dividend(ffy, rd.dy), az = scale_step_dividend(ffz, rd.dz);
-        double qx = div_known_recip(ax, fabs(rd.dx), rd.tdx), qy = div_known_recip(ay, fabs(rd.dy), rd.tdy), qz = div_known_recip(az, fabs(rd.dz), rd.tdz);
-        if (__builtin_amdgcn_ballot_w64(!rd.fast) != 0ull) {
-            AIC_RARE_PATH();
-            if (!rd.fast) { qx = ax / fabs(rd.dx); qy = ay / fabs(rd.dy); qz = az / fabs(rd.dz); }
-        }
-        s.tx = scale_step_result(qx, ffx, rd.dx) + t_start;
-        s.ty = scale_step_result(qy, ffy, rd.dy) + t_start;
-        s.tz = scale_step_result(qz, ffz, rd.dz) + t_start;
-    }
-    s.last_t = t_start;
-    s.cx = cube[0]; s.cy = cube[1]; s.cz = cube[2];
-    // exit coordinate once in bounds: moving up leaves at hi, moving down leaves at lo-1
-    lim.x = rd.sx > 0 ? hix : lox - 1;
-    lim.y = rd.sy > 0 ? hiy : loy - 1;
-    lim.z = rd.sz > 0 ? hiz : loz - 1;
-    s.st = valid ? (FL_BEGINNING | ((uint32_t)FACE_WITHIN << 2) | (include_exit ? 256u : 0u)) : FL_ENDED;
-    return out;
-}
-
-// The deferred State::step (raycast.rs:577-626) along the axis recorded in `pick`.
-AIC_DEV Lvl lvl_do_step(Lvl s, const RayDir rd) {
-    const uint32_t axis = (s.st >> 5) & 3u;
-    uint32_t face;
-    if (axis == 0) {
-        s.last_t = s.tx; s.tx += rd.tdx; s.cx += rd.sx; face = rd.sx > 0 ? 1u : 4u;
-    } else if (axis == 1) {
-        s.last_t = s.ty; s.ty += rd.tdy; s.cy += rd.sy; face = rd.sy > 0 ? 2u : 5u;
-    } else {
-        s.last_t = s.tz; s.tz += rd.tdz; s.cz += rd.sz; face = rd.sz > 0 ? 3u : 6u;
-    }
-    s.st = (s.st & ~(7u << 2) & ~128u) | (face << 2);  // FACE_TABLE; clears need_step
-    return s;
-}
-
-// Raycaster::next (raycast.rs:239-284). lo*/hi* are only consulted before the ray has entered
-// the bounds. Returns true if a step was produced: {c*, lvl_face, last_t, t*}; *is_exit tells
-// whether it is the include_exit step (the only produced step whose cube is out of bounds).
-struct NextResult {
-    Lvl s;
-    bool got, is_exit;
-};
-AIC_DEV NextResult lvl_next(Lvl s, const Lim lim, const RayDir rd, int lox, int loy, int loz, int hix, int hiy, int hiz) {
-    NextResult R;
-    R.got = false;
-    R.is_exit = false;
-    for (;;) {
-        const uint32_t fl = lvl_fl(s);
-        if (fl == FL_ENDED) { R.s = s; return R; }
-        const bool stepped = (s.st & 128u) != 0;
-        const uint32_t stepped_axis = (s.st >> 5) & 3u;
-        if (stepped) s = lvl_do_step(s, rd);
-        bool oob_enter = false, oob_exit = false;
-        if (fl == FL_INBOUNDS) {
-            // only the axis just stepped can have left; it can never be "not yet entered"
-            const int c = stepped_axis == 0 ? s.cx : (stepped_axis == 1 ? s.cy : s.cz);
-            const int l = stepped_axis == 0 ? lim.x : (stepped_axis == 1 ? lim.y : lim.z);
-            oob_exit = stepped && (c == l);
-        } else {
-            // is_out_of_bounds_ahead (raycast.rs:711-728)
-            {
-                const bool low = s.cx < lox, high = s.cx >= hix;
-                oob_enter |= rd.sx == 0 ? (low | high) : (rd.sx < 0 ? high : low);
-                oob_exit |= rd.sx == 0 ? (low | high) : (rd.sx < 0 ? low : high);
-            }
-            {
-                const bool low = s.cy < loy, high = s.cy >= hiy;
-                oob_enter |= rd.sy == 0 ? (low | high) : (rd.sy < 0 ? high : low);
-                oob_exit |= rd.sy == 0 ? (low | high) : (rd.sy < 0 ? low : high);
-            }
-            {
-                const bool low = s.cz < loz, high = s.cz >= hiz;
-                oob_enter |= rd.sz == 0 ? (low | high) : (rd.sz < 0 ? high : low);
-                oob_exit |= rd.sz == 0 ? (low | high) : (rd.sz < 0 ? low : high);
-            }
-        }
-        if (!oob_enter && !oob_exit) {
-            const int pick = pick_axis(s.tx, s.ty, s.tz);
-            const double tp = pick == 0 ? s.tx : (pick == 1 ? s.ty : s.tz);
-            // valid_for_stepping (raycast.rs:563-570): with NaN-free t_max (guaranteed for a
-            // non-EMPTY state) it is exactly "the smallest t_max is finite".
-            if (!isfinite(tp)) {
-                s.st = (s.st & ~3u) | FL_ENDED;
-                R.got = lvl_face(s) == FACE_WITHIN;
-                R.s = s;
-                return R;
-            }
-            s.st = (s.st & ~3u & ~(3u << 5)) | FL_INBOUNDS | ((uint32_t)pick << 5) | 128u;
-            R.got = true;
-            R.s = s;
-            return R;
-        } else if (fl == FL_BEGINNING && oob_enter && !oob_exit) {
-            const int pick = pick_axis(s.tx, s.ty, s.tz);
-            const double tp = pick == 0 ? s.tx : (pick == 1 ? s.ty : s.tz);
-            if (!isfinite(tp)) {
-                s.st = (s.st & ~3u) | FL_ENDED;
-                R.s = s;
-                return R;
-            }
-            const int c = pick == 0 ? s.cx : (pick == 1 ? s.cy : s.cz);
-            const int st = pick == 0 ? rd.sx : (pick == 1 ? rd.sy : rd.sz);
-            if ((st > 0 && c == I32_MAX_) || (st < 0 && c == I32_MIN_)) {  // checked_add failed
-                s.st = (s.st & ~3u) | FL_ENDED;
-                R.s = s;
-                return R;
-            }
-            s.st = (s.st & ~(3u << 5)) | ((uint32_t)pick << 5) | 128u;
-            continue;
-        } else if (fl == FL_INBOUNDS && !oob_enter && oob_exit) {
-            s.st = (s.st & ~3u) | FL_ENDED;
-            if (s.st & 256u) {
-                R.is_exit = true;
-                R.got = true;
-            }
-            R.s = s;
-            return R;
-        } else {
-            s.st = (s.st & ~3u) | FL_ENDED;
-            R.s = s;
-            return R;
-        }
-    }
-}
-
-// RaycastStep::intersection_point (raycast.rs:409-439) for the step currently held in `s`.
-//
-// Same arithmetic as the reference, written without per-axis control flow. For an axis the ray moves along
-// and that is not the face just crossed, the reference adds  1 - clamp((t_max - t) * d)  going up and
-// clamp(-((t_max - t) * d))  going down; -(x * d) == x * (-d) exactly, so both clamp the one product
-// (t_max - t) * |d|. That product is never NaN (t is finite, d finite and non-zero on this path), hence
-// f64::clamp(0, 1) == min(max(c, 0), 1); its only other freedom, the sign of a zero, cannot reach the result
-// (1 - +-0 == 1, and cube + +-0 == cube because an integer-valued cube coordinate is never -0).
-AIC_DEV double ip_axis(bool is_face_axis, bool within, int cube, double o, double d, double t_max, double last_t) {
-    const double cc = (double)cube;
-    const bool neg = d < 0.0;                        // signum_101(d) < 0
-    double c = (t_max - last_t) * fabs(d);
-    c = fmin(fmax(c, 0.0), 1.0);
-    const double moved = cc + (neg ? c : 1.0 - c);   // normal cube face hit
-    const double plane = cc + (neg ? 1.0 : 0.0);     // the plane just crossed
-    double v = is_face_axis ? plane : ((d == 0.0) ? o : moved);   // signum_101(d) == 0: the ray does not move from the origin
-    return within ? o : v;
-}
-AIC_DEV void intersection_point(const Lvl s, double ox, double oy, double oz, double dx, double dy, double dz, double out[3]) {
-    const int face = lvl_face(s);
-    const bool within = face == FACE_WITHIN;
-    const int face_axis = face > 3 ? face - 4 : face - 1;  // Face::axis(): NX NY NZ PX PY PZ = 1..6
-    out[0] = ip_axis(face_axis == 0, within, s.cx, ox, dx, s.tx, s.last_t);
-    out[1] = ip_axis(face_axis == 1, within, s.cy, oy, dy, s.ty, s.last_t);
-    out[2] = ip_axis(face_axis == 2, within, s.cz, oz, dz, s.tz, s.last_t);
-}
-
-// ---------------------------------------------------------------------------------------
-// colour helpers (f32, reference operation order)
-
-AIC_DEV float zo_clamped(float v) {                                        // restricted_number.rs:315-326
-    if (v > 0.f && v <= 1.f) return v;
-    if (v <= 0.f) return 0.f;
-    return 1.f;
-}
-
-// f32::powf as the reference's libm computes it on x86-64 Linux. Rust's `f32::powf` is the C library's
-// powf; glibc's (sysdeps/ieee754/flt-32/e_powf.c, from ARM's optimized-routines; not under
-// /root/reference, restated from the published algorithm) is: log2(x) by a 16-entry table and a
-// degree-4 polynomial, y*log2(x), exp2 by a 32-entry table and a cubic, all in f64, rounded to f32
-// once. Table and coefficient values are the published __powf_log2_data / __exp2f_data. The
-// multiply-adds are fused, as in the FMA build glibc selects on every current x86-64 CPU.
-// Domain: 0 < x < 1 normal, y > 0 finite (everything apply_transmittance feeds it); the caller
-// handles the rest of what can reach it (x == 0, x == 1, y == 0, y == +inf) itself. ~40 instructions instead of ~270; pinned against the host's
-// powf on a million inputs (tests/test_gpu_encode.py).
-__device__ const double kPowLog2Tab[16][2] = {
-    {0x1.661ec79f8f3bep+0, -0x1.efec65b963019p-2}, {0x1.571ed4aaf883dp+0, -0x1.b0b6832d4fca4p-2},
-    {0x1.49539f0f010bp+0, -0x1.7418b0a1fb77bp-2},  {0x1.3c995b0b80385p+0, -0x1.39de91a6dcf7bp-2},
-    {0x1.30d190c8864a5p+0, -0x1.01d9bf3f2b631p-2}, {0x1.25e227b0b8eap+0, -0x1.97c1d1b3b7afp-3},
-    {0x1.1bb4a4a1a343fp+0, -0x1.2f9e393af3c9fp-3}, {0x1.12358f08ae5bap+0, -0x1.960cbbf788d5cp-4},
-    {0x1.0953f419900a7p+0, -0x1.a6f9db6475fcep-5}, {0x1p+0, 0x0p+0},
-    {0x1.e608cfd9a47acp-1, 0x1.338ca9f24f53dp-4},  {0x1.ca4b31f026aap-1, 0x1.476a9543891bap-3},
-    {0x1.b2036576afce6p-1, 0x1.e840b4ac4e4d2p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.40645f0c6651cp-2},
-    {0x1.886e6037841edp-1, 0x1.88e9c2c1b9ff8p-2},  {0x1.767dcf5534862p-1, 0x1.ce0a44eb17bccp-2},
-};
-__device__ const unsigned long long kPowExp2Tab[32] = {
-    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
-    0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
-    0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull,
-    0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull,
-    0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
-    0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
-    0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
-    0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull,
-};
-// s_pow: [0,32) the log2 table as (invc, logc) pairs, [32,64) the exp2 table bit patterns
-AIC_DEV void pow_tables_to_lds(double *s_pow, uint32_t tid, uint32_t nthreads) {
-    for (uint32_t i = tid; i < 64u; i += nthreads)
-        s_pow[i] = i < 32u ? kPowLog2Tab[i >> 1][i & 1u] : __longlong_as_double((long long)kPowExp2Tab[i - 32u]);
-}
-AIC_DEV bool powf_table_domain(float x, float y) {  // 0 < x < 1 normal; y > 0 finite
-    const uint32_t ix = __float_as_uint(x), iy = __float_as_uint(y);
-    return ix >= 0x00800000u && ix < 0x3f800000u && iy > 0u && iy < 0x7f800000u;
-}
-// A 64-bit literal that is materialised where it is used (two s_mov). Left to itself the compiler hoists such constants out of
-// the persistent loop into VGPR pairs, runs out of registers, spills them to scratch at kernel start (every lane of every wave
-// storing the same 8 bytes: most of round 2's 46 MB of WRITE_SIZE per frame) and reloads them from memory in every SHADE event.
-AIC_DEV double KC(double v) { asm volatile("" : "+s"(v)); return v; }
 // population count of a wave mask as a 32-bit scalar (the compiler widens __popcll's result and then compares it on the VALU)
 AIC_DEV uint32_t wave_popc(unsigned long long m) {
     uint32_t n;
     asm volatile("s_bcnt1_i32_b64 %0, %1" : "=s"(n) : "s"(m) : "scc");
     return n;
 }
+// a float literal that is materialised where it is used (as KC, aic_colour.h, for a VGPR)
 AIC_DEV float KF(float v) { asm volatile("" : "+v"(v)); return v; }
-AIC_DEV float powf_table(float x, float y, const double *s_pow) {
-    const uint32_t ix = __float_as_uint(x);
-    // log2_inline
-    const uint32_t tmp = ix - 0x3f330000u;
-    const uint32_t i = (tmp >> 19) & 15u;
-    const uint32_t top = tmp & 0xff800000u;
-    const uint32_t iz = ix - top;
-    const int k = (int)top >> 23;
-    const double invc = s_pow[2u * i], logc = s_pow[2u * i + 1u];
-    const double z = (double)__uint_as_float(iz);
-    const double r = fma(z, invc, -1.0);
-    const double y0 = logc + (double)k;
-    const double r2 = r * r;
-    double yy = fma(KC(0x1.27616c9496e0bp-2), r, KC(-0x1.71969a075c67ap-2));
-    const double pp = fma(KC(0x1.ec70a6ca7baddp-2), r, KC(-0x1.7154748bef6c8p-1));
-    const double r4 = r2 * r2;
-    double q = fma(KC(0x1.71547652ab82bp+0), r, y0);
-    q = fma(pp, r2, q);
-    yy = fma(yy, r4, q);
-    const double ylogx = (double)y * yy;
-    // |y*log2(x)| >= 126: x < 1 and y > 0 make it negative -- underflow to 0 at <= -150, else the
-    // general path rounds into the subnormals by itself
-    if (ylogx <= -150.0) return 0.0f;
-    // exp2_inline
-    double kd = ylogx + KC(0x1.8p+47);
-    const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
-    kd -= KC(0x1.8p+47);
-    const double rr = ylogx - kd;
-    unsigned long long t = (unsigned long long)__double_as_longlong(s_pow[32u + (uint32_t)(ki & 31u)]);
-    t += ki << 47;
-    const double sc = __longlong_as_double((long long)t);
-    const double zz = fma(KC(0x1.c6af84b912394p-5), rr, KC(0x1.ebfce50fac4f3p-3));
-    const double rr2 = rr * rr;
-    double e = fma(KC(0x1.62e42ff0c52d6p-1), rr, 1.0);
-    e = fma(zz, rr2, e);
-    e = e * sc;
-    return (float)e;
-}
-// f32::exp as the reference's libm computes it (glibc sysdeps/ieee754/flt-32/e_expf.c, from ARM's optimized-routines; restated
-// from the published algorithm like powf_table above): x * 32/ln2 split into an integer and a remainder, 2^(k/32) from the
-// same 32-entry table as powf's exp2 step, a cubic in the remainder, all in f64, rounded to f32 once. Domain: |x| < 88 (the fog
-// term feeds it [-1.6, 0]); no overflow / underflow handling. Pinned against the host's expf on every f32 in [-1.6, 0]
-// (aic_probe_expf; tests/test_gpu_linear_parity.py).
-AIC_DEV float expf_table(float x, const double *s_pow) {
-    const double z = KC(0x1.71547652b82fep+5) * (double)x;  // InvLn2N = N / ln 2, N = 32
-    double kd = z + KC(0x1.8p+52);
-    const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
-    kd -= KC(0x1.8p+52);
-    const double r = z - kd;
-    unsigned long long t = (unsigned long long)__double_as_longlong(s_pow[32u + (uint32_t)(ki & 31u)]);
-    t += ki << 47;
-    const double sc = __longlong_as_double((long long)t);
-    const double zz = fma(KC(0x1.c6af84b912394p-20), r, KC(0x1.ebfce50fac4f3p-13));  // poly_scaled: C0 / N^3, C1 / N^2
-    const double r2 = r * r;
-    double y = fma(KC(0x1.62e42ff0c52d6p-6), r, 1.0);                                // C2 / N
-    y = fma(zz, r2, y);
-    y = y * sc;
-    return (float)y;
-}
-
-AIC_DEV void cb_add(ColorBuf &b, float s0, float s1, float s2, float st) {  // :87-92
-    b.l0 += s0 * b.t;
-    b.l1 += s1 * b.t;
-    b.l2 += s2 * b.t;
-    b.t *= st;
-}
-AIC_DEV bool cb_opaque(const ColorBuf &b) { return b.t < 1.0f / 256.0f; }  // :105-109
-
-
-
-
-// ---------------------------------------------------------------------------------------
-// light (space/light/data.rs, space/sky.rs, sr.rs:241-359)
-
-// The light volume of the layer as aic_lightmath.h sees it (every field a kernel argument: SGPRs)
-// Each field goes through an empty asm so that it is an opaque scalar: a select between elements of a kernel-argument array
-// (`axis == 0 ? L.lo[0] : ...`) is otherwise folded into ONE load with a selected address, and a kernel-argument array that is
-// indexed per lane gets copied to scratch memory.
-AIC_DEV int opaque_s(int v) { asm volatile("" : "+s"(v)); return v; }
-AIC_DEV uint32_t opaque_s(uint32_t v) { asm volatile("" : "+s"(v)); return v; }
-AIC_DEV float opaque_s(float v) { asm volatile("" : "+s"(v)); return v; }
-template <class LayerT>
-AIC_DEV LightGridView light_view(const LayerT &L) {
-    LightGridView G;
-    G.light = L.light;
-    G.lo_x = opaque_s(L.lo[0]); G.lo_y = opaque_s(L.lo[1]); G.lo_z = opaque_s(L.lo[2]);
-    G.size_x = opaque_s(L.size[0]); G.size_y = opaque_s(L.size[1]); G.size_z = opaque_s(L.size[2]);
-    G.sky_nx = opaque_s(L.block_sky[0]); G.sky_ny = opaque_s(L.block_sky[1]); G.sky_nz = opaque_s(L.block_sky[2]);
-    G.sky_px = opaque_s(L.block_sky[3]); G.sky_py = opaque_s(L.block_sky[4]); G.sky_pz = opaque_s(L.block_sky[5]);
-    G.sky_mean = opaque_s(L.block_sky[6]);
-    return G;
-}
-
-template <bool DIAG, class LayerT>
-AIC_DEV uint32_t get_packed_light(const LayerT &L, int cx, int cy, int cz, uint32_t &nlight) {  // sr.rs:241-246
-    if (DIAG) nlight++;
-    uint32_t dx = (uint32_t)cx - (uint32_t)L.lo[0];
-    uint32_t dy = (uint32_t)cy - (uint32_t)L.lo[1];
-    uint32_t dz = (uint32_t)cz - (uint32_t)L.lo[2];
-    if ((dx >= (uint32_t)L.size[0]) | (dy >= (uint32_t)L.size[1]) | (dz >= (uint32_t)L.size[2]))
-        return lm_light_outside(light_view(L), cx, cy, cz);
-    size_t idx = ((size_t)dx * (size_t)L.size[1] + dy) * (size_t)L.size[2] + dz;
-    return L.light[idx];
-}
-
-
-// ---------------------------------------------------------------------------------------
-// LightingOption::Bounce (surface.rs:119-166): the secondary rays.
-//
-// A fully opaque surface lit with Bounce { samples } sends `samples` rays in Lambert-distributed directions and averages what they
-// see; each of them is a whole SpaceRaytracer::trace_ray_impl(ray, accumulator = ColorBuf, include_sky = true,
-// allow_ray_bounce = false) under the SAME GraphicsOptions -- transparency mode, fog (with the secondary ray's own length), the
-// 1000-step cap, debug_pixel_cost -- whose surfaces are lit Flat (surface.rs:171-176: the bounce budget is one). It runs inside the
-// SHADE event of the lane that found the surface, one lane at a time through plain loops (the iterator stack of the reference
-// restated over lvl_init / lvl_next, as the oracle has it): Bounce is a quality option nobody streams frames with, so this path
-// is written for exactness and small code, not speed, and only the <.., LMODE = 3, ..> instantiations contain it.
-// The random directions: rand::rngs::SmallRng (xoshiro256++, seeded from the primary ray's direction bits through SplitMix64,
-// sr.rs:165-178) and rand_distr::UnitSphere -- rand 0.10.1 / rand_distr 0.6.0, neither under /root/reference: restated from the
-// published algorithms (the test oracle restates them separately), PARITY UNPINNED (the reference has no golden for Bounce).
-struct BounceRng {
-    unsigned long long s0, s1, s2, s3;
-};
-AIC_DEV unsigned long long rotl64(unsigned long long x, int k) { return (x << k) | (x >> (64 - k)); }
-AIC_DEV BounceRng bounce_rng_seed(unsigned long long state) {  // SeedableRng::seed_from_u64 of Xoshiro256PlusPlus
-    unsigned long long w[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        state += 0x9e3779b97f4a7c15ull;
-        unsigned long long z = state;
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        w[i] = z ^ (z >> 31);
-    }
-    return BounceRng{w[0], w[1], w[2], w[3]};
-}
-AIC_DEV unsigned long long bounce_rng_next(BounceRng &g) {
-    const unsigned long long result = rotl64(g.s0 + g.s3, 23) + g.s0;
-    const unsigned long long t = g.s1 << 17;
-    g.s2 ^= g.s0;
-    g.s3 ^= g.s1;
-    g.s1 ^= g.s2;
-    g.s0 ^= g.s3;
-    g.s2 ^= t;
-    g.s3 = rotl64(g.s3, 45);
-    return result;
-}
-AIC_DEV double bounce_uniform_m1_1(BounceRng &g) {  // Uniform::<f64>::new(-1., 1.).sample
-    const double value1_2 = __longlong_as_double((long long)((bounce_rng_next(g) >> 12) | 0x3ff0000000000000ull));
-    return (value1_2 - 1.0) * 2.0 + -1.0;
-}
-AIC_DEV void bounce_unit_sphere(BounceRng &g, double out[3]) {  // rand_distr::UnitSphere (Marsaglia)
-    for (;;) {
-        const double x1 = bounce_uniform_m1_1(g), x2 = bounce_uniform_m1_1(g);
-        const double sum = x1 * x1 + x2 * x2;
-        if (sum >= 1.0) continue;
-        const double factor = 2.0 * sqrt(1.0 - sum);
-        out[0] = x1 * factor; out[1] = x2 * factor; out[2] = 1.0 - 2.0 * sum;
-        return;
-    }
-}
-
-struct SecSurface {  // what a secondary ray's Surface needs (Flat lighting: no intersection point)
-    float r, g, b, a, e0, e1, e2;
-    int cx, cy, cz, face;
-    double t;
-};
-
-// trace_ray_impl(ray, ColorBuf, include_sky = true, allow_ray_bounce = false) -> Rgba::from(buf).to_rgb(); returns the ray's
-// cubes_traced. `sky_mem`: the layer's sky[8][3] as memory (a per-lane index into a kernel-argument array would put it in scratch).
-template <bool DIAG, class LayerT>
-AIC_DEV uint32_t bounce_secondary_ray(const LayerT &L, const float *sky_mem, const float *lut, const double *s_pow, bool big,
-                                      double ox, double oy, double oz, double dirx, double diry, double dirz, float out[3]) {
-    const auto &opt = L.opt;
-    const bool vol = opt.transparency == 1;
-    const uint32_t idx_mask = big ? 0xffffu : kCubeIndexMask;
-    const uint32_t oct = ((dirx >= 0.0) ? 4u : 0u) | ((diry >= 0.0) ? 2u : 0u) | ((dirz >= 0.0) ? 1u : 0u);  // Sky::sample (sky.rs:32-41)
-    float sky[3];
-    {
-        const float *p = sky_mem + (L.sky_kind != 0 ? 3u * oct : 0u);
-        sky[0] = p[0]; sky[1] = p[1]; sky[2] = p[2];
-    }
-    const double t_abs = sqrt(dirx * dirx + diry * diry + dirz * dirz);   // sr.rs:146
-    const float t_view = (float)(t_abs / opt.view_distance);              // sr.rs:149-151
-    const bool fog_on = opt.fog != 0;
-    const float fog_blend = opt.fog == 1 ? 1.0f : (opt.fog == 2 ? 0.5f : 0.0f);
-    const RayDir rd = raydir_init(dirx, diry, dirz);
-    const double half_over_len = 0.5 / t_abs;
-    const int olx = L.lo[0], oly = L.lo[1], olz = L.lo[2], osx = L.size[0], osy = L.size[1], osz = L.size[2];
-    const int ohx = olx + osx, ohy = oly + osy, ohz = olz + osz;
-    const LvlLim oi = lvl_init(ox, oy, oz, rd, true, olx, oly, olz, ohx, ohy, ohz, true, half_over_len);
-    Lvl os = oi.s;
-    const Lim ol = oi.lim;
-    // the block the ray is inside (VoxelSurfaceIter, surface.rs:361-411)
-    bool inb = false;
-    Lvl is = oi.s;
-    Lim il = oi.lim;
-    int ilx = 0, ily = 0, ilz = 0, isx = 1, isy = 1, isz = 1, bcx = 0, bcy = 0, bcz = 0;
-    uint32_t blk_res = 1u, vox_off = 0u, pal_off = 0u, n_inv = 0u;
-    ColorBuf acc;
-    acc.l0 = acc.l1 = acc.l2 = 0.f; acc.t = 1.0f;
-    uint32_t count = 0;
-    bool has_last = false;  // DepthIter.last_surface
-    SecSurface last;
-    last.r = last.g = last.b = last.a = last.e0 = last.e1 = last.e2 = 0.f; last.cx = last.cy = last.cz = last.face = 0; last.t = 0.0;
-
-    auto count_step_should_stop = [&]() -> bool {  // sr.rs:625-656 (the exception hits are transparent: no effect on a ColorBuf)
-        count++;
-        if (count > 1000u) return true;
-        return cb_opaque(acc);
-    };
-    // Surface::to_light with Flat illumination + trace_through_surface's accumulate (surface.rs:73-106, 171-176; sr.rs:697-717)
-    auto through_surface = [&](const SecSurface &sf) {
-        float r = sf.r, g = sf.g, b = sf.b, a = sf.a;
-        if (opt.transparency == 2) {  // limit_alpha
-            if (a > opt.threshold) a = 1.0f;
-            else { r = g = b = a = 0.f; }
-        }
-        if (a == 0.f && sf.e0 == 0.f && sf.e1 == 0.f && sf.e2 == 0.f) return;
-        int nx = 0, ny = 0, nz = 0;
-        if (sf.face == 1) nx = -1; else if (sf.face == 2) ny = -1; else if (sf.face == 3) nz = -1;
-        else if (sf.face == 4) nx = 1; else if (sf.face == 5) ny = 1; else if (sf.face == 6) nz = 1;
-        uint32_t nl = 0;
-        const uint32_t txl = get_packed_light<false>(L, sf.cx + nx, sf.cy + ny, sf.cz + nz, nl);
-        const float i0 = lut[txl & 255u], i1 = lut[(txl >> 8) & 255u], i2 = lut[(txl >> 16) & 255u];
-        float o0 = ps_mul(ps_mul(r, i0), a) + sf.e0, o1 = ps_mul(ps_mul(g, i1), a) + sf.e1, o2 = ps_mul(ps_mul(b, i2), a) + sf.e2;
-        float tr = 1.0f - a;
-        if (fog_on) {  // distance_fog (sr.rs:745-768), with THIS ray's t_to_view_distance and sky
-            float rel = (float)sf.t * t_view;
-            rel = rel < 0.0f ? 0.0f : (rel > 1.0f ? 1.0f : rel);
-            const float sq = rel * rel;
-            const float fog_exp = 1.0f - expf_table(-1.6f * rel, s_pow);
-            const float fudged = fog_exp / 0.79810348f;
-            const float amount = zo_clamped(fudged * (1.0f - fog_blend) + (sq * sq) * fog_blend);
-            const float comp = 1.0f - amount;
-            o0 = ps_mul(o0, comp) + ps_mul(sky[0], amount);
-            o1 = ps_mul(o1, comp) + ps_mul(sky[1], amount);
-            o2 = ps_mul(o2, comp) + ps_mul(sky[2], amount);
-            tr *= comp;
-        }
-        cb_add(acc, o0, o1, o2, tr);
-    };
-    // trace_through_span (sr.rs:720-740) + apply_transmittance (raytracer_components.rs:215-258)
-    auto through_span = [&](SecSurface sf, double exit_t) {
-        float thickness = (float)((exit_t - sf.t) * t_abs);
-        thickness = fmaxf(thickness, 0.0f);
-        float coeff;
-        if (thickness == 0.0f) {
-            if (sf.a == 1.0f) coeff = 1.0f;
-            else { sf.r = sf.g = sf.b = sf.a = 0.f; coeff = 0.0f; }
-        } else {
-            const float unit_t = 1.0f - sf.a;
-            float depth_t;
-            if (unit_t == 0.0f) depth_t = 0.0f;
-            else if (unit_t == 1.0f) depth_t = 1.0f;
-            else if (!(thickness < __uint_as_float(0x7f800000u))) depth_t = 0.0f;
-            else depth_t = powf_table(unit_t, thickness, s_pow);
-            sf.a = zo_clamped(1.0f - depth_t);
-            const float ec = (unit_t == 1.0f) ? thickness : (depth_t - 1.f) / (unit_t - 1.f);
-            coeff = fmaxf(ec, 0.0f);
-        }
-        const float c = ps_clamped(coeff);
-        sf.e0 = ps_mul(sf.e0, c); sf.e1 = ps_mul(sf.e1, c); sf.e2 = ps_mul(sf.e2, c);
-        through_surface(sf);
-    };
-
-    for (;;) {
-        // ---- SurfaceIter::next (surface.rs:283-354): 1 Invisible, 2 EnterSurface, 3 EnterBlock, 0 the ray is over ----
-        int kind = 0;
-        double t = 0.0;
-        SecSurface cur = last;
-        if (inb) {
-            const NextResult nr = lvl_next(is, il, rd, ilx, ily, ilz, ilx + isx, ily + isy, ilz + isz);
-            is = nr.s;
-            if (nr.got) {
-                const double as = __hiloint2double((int)((1023u - (31u - (uint32_t)__clz((int)blk_res))) << 20), 0);  // 1 / resolution
-                t = is.last_t * as;
-                kind = 1;
-                if (!nr.is_exit) {
-                    const uint32_t vi = (uint32_t)(((uint32_t)(is.cx - ilx) * (uint32_t)isy + (uint32_t)(is.cy - ily)) * (uint32_t)isz + (uint32_t)(is.cz - ilz));
-                    const uint32_t code = L.pool[(size_t)vox_off + vi];
-                    if (code >= n_inv) {
-                        const DevPaletteEntry *pe = &L.palette[pal_off + code];
-                        kind = 2;
-                        cur.r = pe->color[0]; cur.g = pe->color[1]; cur.b = pe->color[2]; cur.a = pe->color[3];
-                        cur.e0 = pe->emission[0]; cur.e1 = pe->emission[1]; cur.e2 = pe->emission[2];
-                        cur.cx = bcx; cur.cy = bcy; cur.cz = bcz; cur.face = lvl_face(is); cur.t = t;
-                    }
-                }
-            } else {
-                inb = false;
-            }
-        }
-        if (kind == 0) {
-            const NextResult nr = lvl_next(os, ol, rd, olx, oly, olz, ohx, ohy, ohz);
-            os = nr.s;
-            if (!nr.got) break;
-            t = os.last_t;
-            kind = 1;
-            if (!nr.is_exit) {
-                const size_t ci = ((size_t)(uint32_t)(os.cx - olx) * (size_t)osy + (size_t)(uint32_t)(os.cy - oly)) * (size_t)osz + (size_t)(uint32_t)(os.cz - olz);
-                const uint32_t entry = L.pool[ci];
-                const uint32_t bi = entry & idx_mask;
-                const uint32_t cls = big ? ((L.cls[bi >> 4] >> ((bi & 15u) << 1)) & 3u) : (entry >> kCubeClassShift);
-                const DevBlock *tb = &L.blocks[bi];
-                if (cls == 1u) {
-                    kind = 2;
-                    cur.r = tb->color[0]; cur.g = tb->color[1]; cur.b = tb->color[2]; cur.a = tb->color[3];
-                    cur.e0 = tb->emission[0]; cur.e1 = tb->emission[1]; cur.e2 = tb->emission[2];
-                    cur.cx = os.cx; cur.cy = os.cy; cur.cz = os.cz; cur.face = lvl_face(os); cur.t = t;
-                } else if (cls == 2u) {
-                    // RaycastStep::recursive_raycast (raycast.rs:458-476): the sub-ray keeps the direction
-                    kind = 3;
-                    blk_res = tb->kind & 255u;
-                    const uint32_t vlo = tb->vlo_packed, vsz = tb->vsize_packed;
-                    ilx = (int)(vlo & 255u); ily = (int)((vlo >> 8) & 255u); ilz = (int)((vlo >> 16) & 255u);
-                    isx = (int)(vsz & 255u); isy = (int)((vsz >> 8) & 255u); isz = (int)((vsz >> 16) & 255u);
-                    vox_off = tb->vox_off; pal_off = tb->pal_off; n_inv = tb->n_invisible;
-                    bcx = os.cx; bcy = os.cy; bcz = os.cz;
-                    const double kd = (double)blk_res;
-                    const LvlLim ii = lvl_init((ox - (double)bcx) * kd, (oy - (double)bcy) * kd, (oz - (double)bcz) * kd, rd, true, ilx, ily, ilz,
-                                               ilx + isx, ily + isy, ilz + isz, true, half_over_len);
-                    is = ii.s;
-                    il = ii.lim;
-                    inb = true;
-                }
-            }
-        }
-        // ---- the tracing loop's body (sr.rs:183-225), DepthIter (surface.rs:453-491) folded in for Volumetric ----
-        if (vol) {
-            if (count_step_should_stop()) break;
-            if (kind == 2) {
-                if (has_last) through_span(last, cur.t);
-                last = cur;
-                has_last = true;
-            } else {
-                if (has_last) { has_last = false; through_span(last, t); }
-                if (kind == 3 && count_step_should_stop()) break;  // the buffered EnterBlock step
-            }
-        } else {
-            if (count_step_should_stop()) break;
-            if (kind == 2) through_surface(cur);
-        }
-    }
-    // finish (sr.rs:658-693): the sky, then the optional cost visualisation
-    cb_add(acc, sky[0] * 1.0f, sky[1] * 1.0f, sky[2] * 1.0f, 0.0f);
-    if (opt.debug_pixel_cost) {
-        const float n = ps_clamped((float)count);
-        const float red = ps_clamped(ps_mul(0.02f, n) * 1.0f);
-        const float green = ps_clamped(ps_mul(0.002f, n) * 1.0f);
-        float cur_rgba[4];
-        cb_to_rgba(acc, cur_rgba);
-        const float blue = ps_clamped(luminance(cur_rgba[0], cur_rgba[1], cur_rgba[2]) * 0.2f);
-        acc.l0 = red; acc.l1 = green; acc.l2 = blue; acc.t = 0.0f;
-    }
-    float c[4];
-    cb_to_rgba(acc, c);
-    out[0] = c[0]; out[1] = c[1]; out[2] = c[2];
-    (void)DIAG;
-    return count;
-}
-
-// ---------------------------------------------------------------------------------------
-// The image kernel.
-//
-// Reference semantics per ray = SpaceRaytracer::trace_ray_impl (sr.rs:135-238) driven by
-// RtScene::trace_patch / trace_ray_through_layers and the draw_rgba encoder
-// (renderer.rs:282-308, 424-478, 516-556). Execution model (CDNA4-first):
-//
-//  * A wave64 runs its pixels through its 64 lanes persistently: a lane that finishes
-//    a ray is refilled with the next pixel of the wave's current 8x8 tile, and a new tile is pulled
-//    from the frame's queue when that one is used up (wave-level __ballot + prefix popcount), so
-//    lanes stay busy instead of idling behind the longest ray of a fixed packet.
-//  * Every lane is a small state machine. The *stepping* state is a tight loop body: one
-//    Amanatides-Woo step of whichever DDA level the lane is on (outer cube grid or inner block
-//    voxels share the code and the registers), one 2-byte lookup, the step bookkeeping. Anything
-//    expensive -- entering a block (a new bounded raycaster: divisions, sqrt), lighting a
-//    surface (8 light texels + f64 geometry), compositing a span (powf/exp), finishing a ray
-//    (sky, encode, store), starting a ray (unprojection) -- is an *event*: the lane parks, and
-//    the wave runs the event code only when at least half of its live lanes are parked (or none
-//    can step). Rare heavy paths therefore execute with well-filled waves instead of taxing
-//    every step of every lane.
-//  * The per-lane order of operations is exactly the reference's, so results are bit-identical
-//    to the sequential formulation (hit cubes, t values, step counts).
 
 struct Diag {
     uint32_t n_outer, n_inner, n_hits, n_light;
@@ -895,37 +127,6 @@ constexpr uint32_t EV_FRESH = 1u, EV_DEAD = 2u, EV_SHADE = 4u, EV_ENTER = 8u, EV
 //   22     ST_DIR_FAST: RayDir::fast of the ray's direction (divisions by it may use t_delta: div_known_recip)
 constexpr uint32_t ST_IN_BLOCK = 1u << 9, ST_HAS_LAST = 1u << 10, ST_OPAQUE = 1u << 12, ST_TRACED = 1u << 13, ST_OUTER_ALIVE = 1u << 21, ST_DIR_FAST = 1u << 22;
 
-#ifndef AIC_MIN_WAVES
-#define AIC_MIN_WAVES 4  // waves per SIMD the production variants are built for (128 VGPRs; cold lane state lives in LDS)
-#endif
-#ifndef AIC_T_BATCH
-#define AIC_T_BATCH 32  // run a kind of parked work once this many lanes wait on it
-#endif
-#ifndef AIC_N_FEW
-#define AIC_N_FEW 24    // ... or once at most this many lanes can still step (32 until the fast steps made stepping cheaper: r03 E)
-#endif
-#ifndef AIC_WG_THREADS
-#define AIC_WG_THREADS 256  // threads per persistent workgroup (a multiple of 64)
-#endif
-#ifndef AIC_STEP_REPS
-#define AIC_STEP_REPS 2  // full stepping passes per scheduler trip (3 until round 4; swept again with AIC_FAST_STEPS once no pending span kept lanes
-                         // out of the fast steps: profiles/r04_experiments.txt G)
-#endif
-#ifndef AIC_FAST_MIN
-#define AIC_FAST_MIN 16  // ... while at least this many lanes of the wave can take one
-#endif
-#ifndef AIC_FAST_STEPS
-#define AIC_FAST_STEPS 16  // bookkeeping-free steps a lane may take ahead of each full pass (0: none; 8 until round 4) ...
-#endif
-#ifndef AIC_FIRST_LOOKUP
-#define AIC_FIRST_LOOKUP 1  // ENTER and NEWRAY look up the first cube / voxel of the level they set up; an invisible one is counted there and the lane
-                            // leaves the event stepping instead of FRESH (!DIAG && !BIG only, with or without the lane exchange: the recording ones count lookups per level,
-                            // BIG needs the class table)
-#endif
-#ifndef AIC_NEWRAY_SKIP_FF
-#define AIC_NEWRAY_SKIP_FF 0  // 1: NEWRAY skips lvl_init's fast-forward when every lane's origin lies inside the space (a camera inside the hall). Off:
-                              // its counter pass (SQ_INSTS_VALU with and without it) has not been made; DESIGN.md 4.2 has the listing's static count
-#endif
 // Waits for a lookup issued into a register (`raw`, in the stepping trip) by an earlier asm statement. The loaded register goes in as a plain INPUT and the code comes
 // out in a fresh register, copied AFTER the wait: every later use depends on this statement. (Until round 4 this was
 // `asm("s_waitcnt vmcnt(0)" : "+v"(raw))`: a tied operand, for which the compiler may place a register copy in front of the
@@ -955,113 +156,8 @@ constexpr uint32_t ST_IN_BLOCK = 1u << 9, ST_HAS_LAST = 1u << 10, ST_OPAQUE = 1u
 // travels with the ray), and while the pool has free slots it parks such lanes and starts new pixels in them, so that the workgroup holds more rays
 // than lanes (the reservoir the sorting needs). Nothing ever waits for another wave: a claim that fails is simply not made. A ray is a pure
 // function of its own state, which moves as a whole, so frames are bit-identical for any pool size or policy.
-#ifndef AIC_EXCHANGE
-#define AIC_EXCHANGE 1
-#endif
-#ifndef AIC_XWG_THREADS
-#define AIC_XWG_THREADS 256  // threads of a workgroup of the exchanging variants (four per CU, a pool of 72 each: measured ahead of two workgroups of 512 with a pool of 160,
-                             // whose eight waves lose more claims to one another and fill the frame's tail worse -- profiles/r05_experiments.txt B)
-#endif
-#ifndef AIC_POOL
-#define AIC_POOL (AIC_XWG_THREADS >= 512 ? 160 : 64)  // parked rays per workgroup (<= 192: up to three tags per lane are scanned); what the CU's 160 KB leave room for beside 80-byte
-                                                       // columns (round 5: 72 slots beside 72-byte columns, the ray's origin and direction in global memory)
-#endif
-#ifndef AIC_XCHG_MIN_GAIN
-#define AIC_XCHG_MIN_GAIN 8  // a wave that has lanes of the chosen kind tops up only if the pool adds at least this many
-#endif
-#ifndef AIC_COLD_SCOPE
-#define AIC_COLD_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP  // (experiment: __HIP_MEMORY_SCOPE_WAVEFRONT = plain loads the CU's L1 may serve stale -- timing only)
-#endif
-#ifndef AIC_XCHG_FULL
-#define AIC_XCHG_FULL 48     // a wave with this many lanes of one kind runs it as it is
-#endif
-#ifndef AIC_XCHG_PARK_MIN
-#define AIC_XCHG_PARK_MIN 8  // an exchange that only parks (nothing to take) is made for at least this many lanes
-#endif
-#ifndef AIC_XCHG_DEPOSIT
-#define AIC_XCHG_DEPOSIT 3   // while slots are free: 0 park nothing, 2 park event lanes that do not run now, 3 stepping lanes too (tools/wave_sim: 3 > 2 > 1)
-#endif
 constexpr uint32_t TAG_FREE = 0u, TAG_STEP = 1u, TAG_SHADE = 2u, TAG_ENTER = 3u, TAG_RAY = 4u, TAG_BUSY = 7u;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// The first cube of a freshly initialised level, for the ENTER / RAY events: Raycaster::next run until it yields its first step or ends, so that the
-// stepping loop only ever sees levels that are already inside their bounds. Written like the stepping trip (round 6): wave masks for every decision, the per-lane state updated in place by
-// one exec-masked block -- lvl_next above, inlined into ENTER and NEWRAY, was compiled into ~600 instructions of nested exec-mask scaffolding with some
-// thirty register copies per turn of its loop. Raycaster::next from FirstLast::Beginning (raycast.rs:239-284) is: while the cube is outside the bounds on
-// the side the ray comes from and not past them (is_out_of_bounds_ahead, raycast.rs:711-728: "not yet entered"), step (State::step, raycast.rs:577-626:
-// along the axis of the smallest t_max, ties to the later axis; a level whose smallest t_max is not finite cannot step and ends); a cube inside the
-// bounds is emitted -- also by a level that cannot step, if it has not stepped yet (Face7::Within); anything else ends the level with nothing emitted.
-// (`checked_add` of the stepped coordinate cannot fail: a coordinate at i32::MAX with the ray going up, or at MIN going down, is past the bounds.)
-// Returns the emitted cube in the kernel's conventions: `lax` = the axis stepped along last, or 8 | Face7::Within for a cube emitted without a step.
-struct FirstCube {
-    double tx, ty, tz, last_t;
-    int cx, cy, cz;
-    uint32_t lax;
-    bool got, inbounds;  // emitted a cube; the level can go on (FirstLast::InBounds)
-};
-AIC_DEV FirstCube lvl_first_masks(const Lvl s0, const RayDir rd, int lox, int loy, int loz, int hix, int hiy, int hiz) {
-    typedef unsigned long long mask_t;
-    FirstCube f;
-    f.tx = s0.tx; f.ty = s0.ty; f.tz = s0.tz; f.last_t = s0.last_t;
-    f.cx = s0.cx; f.cy = s0.cy; f.cz = s0.cz;
-    f.lax = 8u | (uint32_t)FACE_WITHIN;
-    const mask_t negx = __builtin_amdgcn_ballot_w64(rd.sx < 0), posx = __builtin_amdgcn_ballot_w64(rd.sx > 0);
-    const mask_t negy = __builtin_amdgcn_ballot_w64(rd.sy < 0), posy = __builtin_amdgcn_ballot_w64(rd.sy > 0);
-    const mask_t negz = __builtin_amdgcn_ballot_w64(rd.sz < 0), posz = __builtin_amdgcn_ballot_w64(rd.sz > 0);
-    mask_t active = __builtin_amdgcn_ballot_w64(lvl_fl(s0) != FL_ENDED);
-    mask_t m_got = 0ull, m_inb = 0ull, m_stepped = 0ull;
-    const uint32_t finite_classes = 0x1f8u;  // v_cmp_class: -normal, -denormal, -0, +0, +denormal, +normal
-    while (active != 0ull) {
-        // is_out_of_bounds_ahead: per axis "not yet entered" is below the bounds going up, above going down, either for an axis the ray does not move
-        // along; "left" the other way round
-        const mask_t lowx = __builtin_amdgcn_ballot_w64(f.cx < lox), highx = __builtin_amdgcn_ballot_w64(f.cx >= hix);
-        const mask_t lowy = __builtin_amdgcn_ballot_w64(f.cy < loy), highy = __builtin_amdgcn_ballot_w64(f.cy >= hiy);
-        const mask_t lowz = __builtin_amdgcn_ballot_w64(f.cz < loz), highz = __builtin_amdgcn_ballot_w64(f.cz >= hiz);
-        const mask_t enter = (lowx & ~negx) | (highx & ~posx) | (lowy & ~negy) | (highy & ~posy) | (lowz & ~negz) | (highz & ~posz);
-        const mask_t exit_ = (lowx & ~posx) | (highx & ~negx) | (lowy & ~posy) | (highy & ~negy) | (lowz & ~posz) | (highz & ~negz);
-        const mask_t m_in = active & ~(enter | exit_), m_go = active & enter & ~exit_;
-        const mask_t m_any = m_in | m_go;
-        mask_t m_fin, sv, mx, m_stp;
-        double mn;
-        asm volatile(
-            "s_and_saveexec_b64 %[sv], %[any]\n\t"
-            "v_min_f64 %[mn], %[tx], %[ty]\n\t"
-            "v_min_f64 %[mn], %[mn], %[tz]\n\t"
-            "v_cmp_class_f64 %[fin], %[mn], %[cls]\n\t"   // valid_for_stepping (raycast.rs:563-570): the smallest t_max is finite
-            "s_and_b64 %[stp], %[fin], %[go]\n\t"          // the lanes that step
-            "s_mov_b64 exec, %[stp]\n\t"
-            "v_mov_b64 %[lt], %[mn]\n\t"
-            "v_cmp_eq_f64 %[mx], %[tz], %[mn]\n\t"         // Z
-            "v_cmp_eq_f64 vcc, %[ty], %[mn]\n\t"
-            "s_andn2_b64 vcc, vcc, %[mx]\n\t"              // Y
-            "s_mov_b64 exec, %[mx]\n\t"
-            "v_add_f64 %[tz], %[tz], %[tdz]\n\t"
-            "v_add_u32 %[cz], %[cz], %[sz]\n\t"
-            "v_mov_b32 %[lax], 2\n\t"
-            "s_or_b64 %[mx], %[mx], vcc\n\t"
-            "s_mov_b64 exec, vcc\n\t"
-            "v_add_f64 %[ty], %[ty], %[tdy]\n\t"
-            "v_add_u32 %[cy], %[cy], %[sy]\n\t"
-            "v_mov_b32 %[lax], 1\n\t"
-            "s_andn2_b64 exec, %[stp], %[mx]\n\t"          // X = stepping lanes that took neither
-            "v_add_f64 %[tx], %[tx], %[tdx]\n\t"
-            "v_add_u32 %[cx], %[cx], %[sx]\n\t"
-            "v_mov_b32 %[lax], 0\n\t"
-            "s_mov_b64 exec, %[sv]\n\t"
-            : [tx] "+v"(f.tx), [ty] "+v"(f.ty), [tz] "+v"(f.tz), [lt] "+v"(f.last_t), [cx] "+v"(f.cx), [cy] "+v"(f.cy), [cz] "+v"(f.cz), [lax] "+v"(f.lax),
-              [mn] "=&v"(mn), [sv] "=&s"(sv), [mx] "=&s"(mx), [fin] "=&s"(m_fin), [stp] "=&s"(m_stp)
-            : [tdx] "v"(rd.tdx), [tdy] "v"(rd.tdy), [tdz] "v"(rd.tdz), [sx] "v"(rd.sx), [sy] "v"(rd.sy), [sz] "v"(rd.sz), [any] "s"(m_any), [go] "s"(m_go),
-              [cls] "s"(finite_classes)
-            : "vcc", "scc");
-        m_got |= m_in & (m_fin | ~m_stepped);
-        m_inb |= m_in & m_fin;
-        m_stepped |= m_stp;
-        active = m_stp;
-    }
-    f.got = __builtin_amdgcn_inverse_ballot_w64(m_got);
-    f.inbounds = __builtin_amdgcn_inverse_ballot_w64(m_inb);
-    return f;
-}
 
 // How a DDA level is held in registers by the image kernel (both levels -- the cube grid and a block's
 // voxel volume -- use the same registers and the same stepping code):
@@ -1080,12 +176,12 @@ AIC_DEV FirstCube lvl_first_masks(const Lvl s0, const RayDir rd, int lox, int lo
 // carried in the state: it is a pure function of t[], which nothing modifies between steps.
 
 template <bool VOL, int LMODE, bool DIAG, bool BIG, bool XC>
-__global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC_WG_THREADS, (DIAG || LMODE == 3) ? 2 : AIC_MIN_WAVES) void trace_image_kernel(const DevFrame F) {
+__global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC_WG_THREADS, (DIAG || LMODE == 3) ? 2 : AIC_MIN_WAVES) void trace_image_kernel(const DevFrame F) {
     // XCHG: the production variants -- lanes are exchanged between the workgroup's waves through a pool of parked rays, and the part of a ray's
     // cold state that only ENTER / SHADE / FINISH touch (origin, direction, antialiasing sums) lives in global memory to make room for it.
     // The aux-recording and Bounce variants (more per-lane state, built for 2 waves per SIMD) keep everything in LDS and exchange nothing.
     // (XC: the production variants exist with and without the exchange; the launcher picks by the frame's size -- DevFrame::exchange)
-    constexpr bool XCHG = AIC_EXCHANGE && XC && !DIAG && LMODE != 3;
+    constexpr bool XCHG = XC && !DIAG && LMODE != 3;
     constexpr uint32_t WGT = XCHG ? (uint32_t)AIC_XWG_THREADS : (uint32_t)AIC_WG_THREADS;  // threads per workgroup
     constexpr uint32_t NPOOL = XCHG ? (uint32_t)AIC_POOL : 0u;                            // pool slots
     constexpr uint32_t NCOL = WGT + NPOOL;                                                // LDS columns: one per lane and one per slot
@@ -1383,13 +479,13 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
             AIC_TICK(19);
             const int dry_i = __builtin_amdgcn_readfirstlane((int)dry);
             const int alive = n_step + c_shade + c_enter + c_ray, parked = pk_step + pk_shade + pk_enter + pk_ray;
-            const int n_others = alive - mine - ((AIC_XCHG_DEPOSIT < 3 && run != 0u) ? n_step : 0);  // lanes holding a ray that will not run now (and may be parked)
+            const int n_others = alive - mine;  // lanes holding a ray that will not run now (and may be parked)
             // An exchange costs a few hundred instructions: it is made for a top-up of at least AIC_XCHG_MIN_GAIN lanes, for a kind the wave has none of, or -- while
             // the image has pixels left and the pool a free slot -- to park at least AIC_XCHG_PARK_MIN lanes:
             //     best - mine >= MIN_GAIN  ||  mine == 0  ||  (!dry && parked < NPOOL && n_others >= PARK_MIN)
             // as one comparison of integers that are >= 0 where their term holds (a dozen scalar instructions; as booleans every term is a compare, a 64-bit
             // select and a 64-bit and / or)
-            static_assert(AIC_XCHG_PARK_MIN > 0 && AIC_XCHG_DEPOSIT != 0, "parking wants lanes to park");
+            static_assert(AIC_XCHG_PARK_MIN > 0, "parking wants lanes to park");
             const int park_room = (int)NPOOL - 1 - parked, not_dry = -dry_i;
             const int park_ok_i = park_room < not_dry ? park_room : not_dry;                             // >= 0: parking is possible
             const int t_park = n_others - AIC_XCHG_PARK_MIN, t_gain = best - mine - AIC_XCHG_MIN_GAIN, t_none = -opaque_s(mine);  // (opaque: else the negation is made on the vector unit, for the carry that says mine != 0)
@@ -1449,7 +545,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                 // a giver of rank < n_take takes a parked ray; the rays of the ranks after that are parked while slots are free
                 const bool takes = giver & (rank < n_take);
                 const uint32_t j_ = rank - n_take;
-                const bool parks = giver & !empty & (AIC_XCHG_DEPOSIT >= 3 || my_tag != TAG_STEP) & (rank >= n_take) & (j_ < n_free);  // (n_free is 0 unless may_park)
+                const bool parks = giver & !empty & (rank >= n_take) & (j_ < n_free);  // (n_free is 0 unless may_park)
                 const uint32_t expect = takes ? want : TAG_FREE;
                 const uint32_t slot = (takes | parks) ? (uint32_t)(takes ? pick_w : pick_f)[takes ? rank : (j_ & 63u)] : 0u;
                 bool got = false;
@@ -1587,12 +683,6 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
             // thresholds scale with the lanes still alive, so that a wave that is running out of rays
             // (the frame's tail) keeps batching instead of running every event for a lane or two
             const int alive = n_step + c_shade + c_enter + c_ray;
-#ifndef AIC_FRAC_T
-#define AIC_FRAC_T 4  // eighths of the lanes alive
-#endif
-#ifndef AIC_FRAC_N
-#define AIC_FRAC_N 3
-#endif
             const int part_t = (alive * AIC_FRAC_T) >> 3, part_n = (alive * AIC_FRAC_N) >> 3;
             const int t_lo = opaque_s(part_t > 0 ? part_t : 1);  // (kept apart from the min: fused, the pair becomes a v_med3 and a v_readfirstlane)
             const int t_batch = t_lo < AIC_T_BATCH ? t_lo : AIC_T_BATCH;
@@ -1791,7 +881,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
             auto cold_direction = [&](double &dx, double &dy, double &dz) { dx = c64[C_DX][col]; dy = c64[C_DY][col]; dz = c64[C_DZ][col]; };
             auto cold_sums_load = [&](float v[4]) {
                 if constexpr (XCHG) {
-                    for (uint32_t k = 0; k < 4u; k++) v[k] = __uint_as_float(__hip_atomic_load(reinterpret_cast<uint32_t *>(cold_wg + off32(k)), __ATOMIC_RELAXED, AIC_COLD_SCOPE));
+                    for (uint32_t k = 0; k < 4u; k++) v[k] = __uint_as_float(__hip_atomic_load(reinterpret_cast<uint32_t *>(cold_wg + off32(k)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                 } else {
                     v[0] = __uint_as_float(c32[XCHG ? 0 : (int)K_S0][col]); v[1] = __uint_as_float(c32[XCHG ? 0 : (int)K_S1][col]);
                     v[2] = __uint_as_float(c32[XCHG ? 0 : (int)K_S2][col]); v[3] = __uint_as_float(c32[XCHG ? 0 : (int)K_ST][col]);
@@ -2025,21 +1115,15 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                 if (VOL) {
                     // DepthIter.last_surface: applied when the next TraceStep is counted
                     if (will_flush) {
-#ifndef AIC_EARLY_APPLY
-#define AIC_EARLY_APPLY 1
-#endif
                         // The span is applied when the ray's next TraceStep is counted and passes the stop check (sr.rs:625-656).
                         // For a lane whose level can step and that is below the step cap that is CERTAIN: its next step (a lookup or the
                         // exit step) is produced, counted (count + 1 <= 1000) and not stopped (the ray is not opaque, or it would not be
                         // shading). Nothing reads the accumulator in between, so the same additions can be made now -- unless they make
                         // the ray opaque: the stop check of that next step still has to see it transparent, so then the span waits as
                         // before. A lane without a pending span takes the bookkeeping-free fast steps at once.
-                        bool early = AIC_EARLY_APPLY && !DIAG && !(ev & EV_DEAD) && count <= 999u;
+                        bool early = !DIAG && !(ev & EV_DEAD) && count <= 999u;
                         const float n0 = acc.l0 + o0 * acc.t, n1 = acc.l1 + o1 * acc.t, n2 = acc.l2 + o2 * acc.t, nt = acc.t * tr;
                         early = early && !(nt < 1.0f / 256.0f);
-#ifndef AIC_OPAQUE_SHORTCUT
-#define AIC_OPAQUE_SHORTCUT 1
-#endif
                         // A span that makes the ray opaque decides the rest of the ray, whatever lies behind it: the ray's next step is
                         // counted and applies the span (the accumulator is opaque from there), the step after that -- if the iterators
                         // still yield one -- is counted and stops the ray (sr.rs:183-189, 625-656). What those two steps find is
@@ -2048,7 +1132,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                         // next step is the exit step of the cube grid, or of a block whose enclosing grid level has ended. So the lane
                         // finishes here: two lookups, two full stepping passes and a scheduler round trip less for every ray that ends
                         // on a solid. (Not the aux-recording variant: its per-level lookup counters follow the reference's iterators.)
-                        const bool finish_now = AIC_OPAQUE_SHORTCUT && !DIAG && !(ev & EV_DEAD) && count <= 998u && (nt < 1.0f / 256.0f);
+                        const bool finish_now = !DIAG && !(ev & EV_DEAD) && count <= 998u && (nt < 1.0f / 256.0f);
                         if (finish_now) {
                             const int pk = pick_axis(tx, ty, tz);
                             const uint32_t r_next = pk == 0 ? rx : (pk == 1 ? ry : rz);  // steps left on that axis minus one: 0 = the exit step is next
@@ -2070,7 +1154,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     if (cb_opaque(acc)) {
                         st |= ST_OPAQUE;
                         // (as above, Surface transparency: the ray's next step is counted and stops it; a level that is not over yields one)
-                        if (AIC_OPAQUE_SHORTCUT && !DIAG && !(ev & EV_DEAD) && count <= 999u) {
+                        if (!DIAG && !(ev & EV_DEAD) && count <= 999u) {
                             count += 1u;
                             ev = (ev & EV_SHADE) | EV_FINISH;
                         }
@@ -2125,7 +1209,7 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                 boff = 2u * (vox_off + (uint32_t)(((uint32_t)vcx * (uint32_t)isy + (uint32_t)vcy) * (uint32_t)isz + (uint32_t)vcz));
                 // The first voxel's lookup, taken here where the stepping trip would count it and do nothing else: the level goes on, no span is pending
                 // (DepthIter), the ray is not opaque and the step stays under the 1000-step cap (count_step_should_stop, sr.rs:625-656).
-                constexpr bool first_lookup = AIC_FIRST_LOOKUP && !DIAG && !BIG;
+                constexpr bool first_lookup = !DIAG && !BIG;
                 const bool first_elig = first_lookup && f.got && f.inbounds && !(st & (ST_HAS_LAST | ST_OPAQUE)) && count <= 999u;
                 uint32_t first_raw = 0u;  // (a register of its own: `raw` keeps the live range it has without this lookup)
                 if constexpr (first_lookup) { AIC_ISSUE_FIRST_LOOKUP(first_elig, first_raw); }
@@ -2463,13 +1547,13 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
                     const int ohx = olx + osx_i, ohy = oly + osy_i, ohz = olz + osz_i;
                     // the sanitised direction equals the original unless it was zeroed, in which case no fast-forward happens
                     const double half_over_len = 0.5 / t_abs;
-                    const LvlLim ll = lvl_init(ox, oy, oz, rd, true, olx, oly, olz, ohx, ohy, ohz, true, half_over_len, AIC_NEWRAY_SKIP_FF != 0);
+                    const LvlLim ll = lvl_init(ox, oy, oz, rd, true, olx, oly, olz, ohx, ohy, ohz, true, half_over_len);
                     const FirstCube fs = lvl_first_masks(ll.s, rd, olx, oly, olz, ohx, ohy, ohz);
                     const int ccx = fs.cx - olx, ccy = fs.cy - oly, ccz = fs.cz - olz;
                     boff = 2u * (uint32_t)(((uint32_t)ccx * (uint32_t)osy_i + (uint32_t)ccy) * (uint32_t)osz_i + (uint32_t)ccz);
                     // the first cube's lookup, as in ENTER: a new ray has no span pending and its count is zero; one that starts opaque (the backdrop, the UI
                     // pass's pixel) stays FRESH and ends in the stepping trip with its one step
-                    constexpr bool first_lookup = AIC_FIRST_LOOKUP && !DIAG && !BIG;
+                    constexpr bool first_lookup = !DIAG && !BIG;
                     const bool first_elig = first_lookup && fs.got && fs.inbounds && !cb_opaque(acc);
                     uint32_t first_raw = 0u;  // (a register of its own: `raw` keeps the live range it has without this lookup)
                     if constexpr (first_lookup) { AIC_ISSUE_FIRST_LOOKUP(first_elig, first_raw); }
@@ -2555,17 +1639,13 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
             AIC_PROF(25, __popcll(m_step & ~(m_hl | m_opq) & m_far_from_cap));
 #endif
             mask_t m_pre_exit = 0ull, m_pre_look = 0ull;  // lanes whose step of this pass was taken here: left the bounds / looked something up
-            if (!BIG && AIC_FAST_STEPS > 0) {
+            if (!BIG) {
                 mask_t m_f = m_step & ~(m_hl | m_opq) & m_far_from_cap;
 #pragma unroll
                 for (int f = 0; f < AIC_FAST_STEPS; f++) {
-#if AIC_FAST_MIN > 0
                     // a fast step costs the same however few lanes take it: too few, and their steps are cheaper taken by
                     // the full passes that run anyway
                     if (wave_popc(m_f) < fast_min) break;
-#else
-                    if (m_f == 0ull) break;
-#endif
                     mask_t m_fx, m_fe, m_fb;
                     if (DIAG) {
                         m_fx = dda_step(m_f);
@@ -2891,225 +1971,14 @@ __global__ __launch_bounds__((AIC_EXCHANGE && XC && !DIAG && LMODE != 3) ? AIC_X
 }
 
 // ---------------------------------------------------------------------------------------
-// small kernels
-
-// aic_update_cubes: scatter of SpaceChange::{CubeBlock,CubeLight} (updating.rs:146-166)
-__global__ void scatter_cubes_kernel(uint16_t *grid, uint32_t *light, const int32_t *xyz, const uint16_t *bi,
-                                     const uint32_t *lt, uint32_t n, int lx, int ly, int lz, int sx, int sy, int sz,
-                                     const uint32_t *cls) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t dx = (uint32_t)xyz[3 * i + 0] - (uint32_t)lx;
-    uint32_t dy = (uint32_t)xyz[3 * i + 1] - (uint32_t)ly;
-    uint32_t dz = (uint32_t)xyz[3 * i + 2] - (uint32_t)lz;
-    if ((dx >= (uint32_t)sx) | (dy >= (uint32_t)sy) | (dz >= (uint32_t)sz)) return;
-    size_t idx = ((size_t)dx * sy + dy) * sz + dz;
-    if (bi) {
-        uint32_t b = bi[i];
-        if (cls) b |= ((cls[b >> 4] >> ((b & 15u) << 1)) & 3u) << kCubeClassShift;  // cls != null: tagged grid
-        grid[idx] = (uint16_t)b;
-    }
-    if (lt) light[idx] = lt[i];
-}
-
-// (re)writes the class bits of every cube-grid entry from the class table (aic_device.h)
-__global__ void tag_cubes_kernel(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t b = grid[i];
-    if (from_tagged) b &= kCubeIndexMask;
-    if (to_tagged) b |= ((cls[b >> 4] >> ((b & 15u) << 1)) & 3u) << kCubeClassShift;
-    grid[i] = (uint16_t)b;
-}
-
-// Orders the tiles of the next frame by the cost the previous frame measured for them (its longest
-// ray, in steps), costliest first: the rays most likely to be long start early instead of landing
-// in the frame's tail, where a wave with two live lanes still pays a whole event phase for each.
-// One workgroup: histogram over 1024 cost buckets per queue, prefix sum, scatter. Order inside a bucket is
-// whatever the atomics give -- every pixel is traced exactly once either way.
-//
-// Queues (round 4): each XCD has its own L2, and with one dispenser for the chip the 4 waves' worth of rays of a macro tile and of
-// its neighbours run on all eight at once -- every L2 fetches the same lines. With n_queues > 1 the macro tiles are dealt to queues
-// by the super-block (2^sb_shift macro tiles on a side) they lie in, a workgroup serves the queue of the XCD it runs on (and helps
-// the others when its own is empty), and `order` comes out as n_queues segments, each costliest first; queue_start[q] is where
-// segment q begins. cost == nullptr: no record to go by (index order inside a queue, as far as the atomics keep it).
-__device__ __forceinline__ uint32_t tile_queue_of(uint32_t mt, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues) {
-    // mt / macros_x without the ~40-instruction integer division (this runs twice per macro tile on one workgroup, ahead of every frame):
-    // a float quotient is within one of the truth for these sizes (mt < 2^24), corrected exactly
-    uint32_t my = (uint32_t)((float)mt * __builtin_amdgcn_rcpf((float)macros_x));
-    if (my * macros_x > mt) my--;
-    else if ((my + 1u) * macros_x <= mt) my++;
-    const uint32_t mx = mt - my * macros_x;
-    const uint32_t v = (mx >> sb_shift) + 3u * (my >> sb_shift);
-    return (n_queues & (n_queues - 1u)) == 0u ? (v & (n_queues - 1u)) : v % n_queues;
-}
-// One workgroup of kOrderThreads = 256 threads (four waves, 33 KB of LDS): what ONE retiring workgroup of a trace kernel leaves free on a CU. With 1024
-// threads it needed a whole CU to drain, and while frames are streamed every CU is full of persistent trace workgroups: rocprofv3 showed it
-// waiting 0.14 ms (C2) / 1.6 ms (C3) for a place to run (profiles/r04_experiments.txt L).
-constexpr uint32_t kOrderThreads = 256;
-// (a workgroup per job -- OrderJobs, aic_device.h: the frames of a batch, aic_render_submit_batch, are ordered by one launch)
-__global__ __launch_bounds__(kOrderThreads) void order_tiles_kernel(const OrderJobs jobs, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues,
-                                                                    uint32_t clear_the_cost, uint32_t n_clear_words) {
-    const uint32_t *__restrict__ const cost = jobs.cost[blockIdx.x];
-    uint32_t *__restrict__ const order = jobs.order[blockIdx.x];
-    uint32_t *__restrict__ const queue_start = jobs.queue_start[blockIdx.x];
-    uint32_t *const clear_cost = (clear_the_cost && cost) ? const_cast<uint32_t *>(cost) : nullptr;
-    uint32_t *const clear_words = jobs.clear_words[blockIdx.x];
-    __shared__ uint32_t hist[kMaxTileQueues * 1024];
-    __shared__ uint32_t scan[kOrderThreads];
-    // (behind a frame this launch also does the slot's clearing -- the frame's counters, and below the cost record once it has been read -- instead of two
-    //  fill launches that would each wait for room on a CU)
-    if (clear_words) for (uint32_t i = threadIdx.x; i < n_clear_words; i += kOrderThreads) clear_words[i] = 0u;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t n_bins = n_queues * 1024u;
-    const uint32_t per_thread = n_bins / kOrderThreads;  // 4 * n_queues consecutive buckets each
-    const uint32_t *const cp = cost ? cost : order;  // no record: any readable words, masked away
-    const uint32_t use = cost ? ~0u : 0u;
-    for (uint32_t b = tid; b < n_bins; b += kOrderThreads) hist[b] = 0;
-    __syncthreads();
-    // (eight tiles per thread at a time: the eight cost fetches are issued together, not one ahead of each atomic)
-    for (uint32_t base = tid; base < n_tiles; base += 8u * kOrderThreads) {
-        uint32_t c[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) c[k] = cp[min(base + k * kOrderThreads, n_tiles - 1u)] & use;  // (unconditional: nothing keeps the eight fetches apart)
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) {
-            const uint32_t t = base + k * kOrderThreads;
-            if (t < n_tiles) atomicAdd(&hist[tile_queue_of(t, macros_x, sb_shift, n_queues) * 1024u + 1023u - (c[k] < 1023u ? c[k] : 1023u)], 1u);
-        }
-    }
-    __syncthreads();
-    // exclusive prefix sum over the n_queues * 1024 buckets: thread `tid` owns `per_thread` consecutive buckets
-    uint32_t mine = 0;
-    for (uint32_t k = 0; k < per_thread; k++) mine += hist[tid * per_thread + k];
-    scan[tid] = mine;
-    __syncthreads();
-    for (uint32_t off = 1; off < kOrderThreads; off <<= 1) {  // Hillis-Steele over the partial sums
-        const uint32_t v = tid >= off ? scan[tid - off] : 0u;
-        __syncthreads();
-        scan[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = scan[tid] - mine;
-    for (uint32_t k = 0; k < per_thread; k++) {
-        const uint32_t h = hist[tid * per_thread + k];
-        hist[tid * per_thread + k] = run;  // start of each bucket
-        run += h;
-    }
-    __syncthreads();
-    if (queue_start && tid <= n_queues) queue_start[tid] = tid < n_queues ? hist[tid * 1024u] : n_tiles;
-    __syncthreads();
-    for (uint32_t base = tid; base < n_tiles; base += 8u * kOrderThreads) {
-        uint32_t c[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) c[k] = cp[min(base + k * kOrderThreads, n_tiles - 1u)] & use;
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) {
-            const uint32_t t = base + k * kOrderThreads;
-            if (t < n_tiles) {
-                const uint32_t pos = atomicAdd(&hist[tile_queue_of(t, macros_x, sb_shift, n_queues) * 1024u + 1023u - (c[k] < 1023u ? c[k] : 1023u)], 1u);
-                order[pos] = t;
-                if (clear_cost) clear_cost[t] = 0u;
-            }
-        }
-    }
-}
-
-// aic_assemble_strips: [n_parts][max_rows][w] compacted strips -> [h][w]
-__global__ void assemble_strips_kernel(const uint32_t *gathered, uint32_t *out, uint32_t w, uint32_t h, uint32_t strip_rows,
-                                       uint32_t n_parts, uint32_t max_rows) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)w * h) return;
-    uint32_t y = (uint32_t)(i / w), x = (uint32_t)(i % w);
-    uint32_t strip = y / strip_rows;
-    uint32_t part = strip % n_parts;
-    uint32_t lrow = (strip / n_parts) * strip_rows + (y % strip_rows);
-    out[i] = gathered[((size_t)part * max_rows + lrow) * w + x];
-}
-
-// aic_probe_raycast: the device Raycaster, one ray
-__global__ void probe_raycast_kernel(const double *od, int use_bounds, const int *lohi, int include_exit, uint32_t max_steps,
-                                     double *out_rec, uint32_t *n_out, int *ended) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const double ox = od[0], oy = od[1], oz = od[2], dx = od[3], dy = od[4], dz = od[5];
-    int lo[3] = {lohi[0], lohi[1], lohi[2]}, hi[3] = {lohi[3], lohi[4], lohi[5]};
-    if (!use_bounds) {
-        lo[0] = lo[1] = lo[2] = I32_MIN_ + 1;
-        hi[0] = hi[1] = hi[2] = I32_MAX_ - 1;
-    }
-    const RayDir rd = raydir_init(dx, dy, dz);
-    const LvlLim ll = lvl_init(ox, oy, oz, rd, use_bounds != 0, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], include_exit != 0,
-                               0.5 / sqrt(rd.dx * rd.dx + rd.dy * rd.dy + rd.dz * rd.dz));
-    Lvl s = ll.s;
-    const Lim lim = ll.lim;
-    uint32_t n = 0;
-    *ended = 0;
-    // A bounded raycaster with its exit step -- what the image kernel's events set up -- takes its first step through the events' own code
-    // (lvl_first_masks), so that the reference's step tables pin that too; lvl_next goes on from the state it leaves.
-    bool first_by_masks = use_bounds != 0 && include_exit != 0;
-    while (n < max_steps) {
-        NextResult nr;
-        if (first_by_masks) {
-            first_by_masks = false;
-            const FirstCube f = lvl_first_masks(s, rd, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
-            nr.got = f.got; nr.is_exit = false;
-            nr.s.tx = f.tx; nr.s.ty = f.ty; nr.s.tz = f.tz; nr.s.last_t = f.last_t;
-            nr.s.cx = f.cx; nr.s.cy = f.cy; nr.s.cz = f.cz;
-            const uint32_t face = (f.lax & 8u) ? (f.lax & 7u) : (((f.lax == 0u ? rd.sx : (f.lax == 1u ? rd.sy : rd.sz)) > 0 ? 1u : 4u) + f.lax);
-            // "emitted, step scheduled" as lvl_next leaves it: InBounds | pick | need_step, or Ended
-            nr.s.st = (face << 2) | 256u | (f.inbounds ? (FL_INBOUNDS | ((uint32_t)pick_axis(f.tx, f.ty, f.tz) << 5) | 128u) : FL_ENDED);
-        } else {
-            nr = lvl_next(s, lim, rd, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
-        }
-        s = nr.s;
-        if (!nr.got) {
-            *ended = 1;
-            break;
-        }
-        double ip[3];
-        intersection_point(s, ox, oy, oz, dx, dy, dz, ip);
-        double *r = out_rec + 8 * (size_t)n;
-        // record: cube[3] as doubles, face, t, ip[3]
-        r[0] = (double)s.cx; r[1] = (double)s.cy; r[2] = (double)s.cz;
-        r[3] = (double)lvl_face(s); r[4] = s.last_t; r[5] = ip[0]; r[6] = ip[1]; r[7] = ip[2];
-        n++;
-    }
-    *n_out = n;
-}
-
-// f32::powf evaluated in f64 and rounded once: only for the probe below, outside powf_table's domain (the trace kernel never
-// leaves that domain)
-AIC_DEV float powf_exact(float x, float y) { return (float)pow((double)x, (double)y); }
-
-// aic_probe_powf: the device's powf (table path where its domain allows, as the trace kernel chooses)
-__global__ void probe_powf_kernel(const float *x, const float *y, float *out, uint32_t n) {
-    __shared__ double s_pow[64];
-    pow_tables_to_lds(s_pow, threadIdx.x, blockDim.x);
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = powf_table_domain(x[i], y[i]) ? powf_table(x[i], y[i], s_pow) : powf_exact(x[i], y[i]);
-}
-
-// aic_probe_expf: the device's expf as distance_fog uses it (expf_table; its domain, |x| < 88, is the caller's to keep)
-__global__ void probe_expf_kernel(const float *x, float *out, uint32_t n) {
-    __shared__ double s_pow[64];
-    pow_tables_to_lds(s_pow, threadIdx.x, blockDim.x);
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = expf_table(x[i], s_pow);
-}
-
-// ---------------------------------------------------------------------------------------
-// host-callable launchers (used by aic_abi.cpp)
+// the image kernel's launchers (declared in aic_launch.h)
 
 template <bool VOL, int LMODE, bool DIAG, bool BIG, bool XC>
 static void launch_trace_x(const DevFrame &F, hipStream_t stream) {
     // persistent waves: enough workgroups to fill the chip at the kernel's occupancy, never more
     // waves than tiles (each wave pulls 8x8-pixel tiles from counters->tile_next)
     const uint32_t n_tiles = F.tiles_x * F.tiles_y;
-    constexpr bool XCHG = AIC_EXCHANGE && XC && !DIAG && LMODE != 3;
+    constexpr bool XCHG = XC && !DIAG && LMODE != 3;
     constexpr uint32_t WGT = XCHG ? (uint32_t)AIC_XWG_THREADS : (uint32_t)AIC_WG_THREADS;
     const uint32_t wg_waves = WGT / 64u;
     const uint32_t n_sub = F.n_sub > 1u ? F.n_sub : 1u;  // frames of this launch (DevSub): each gets an equal share of the resident grid
@@ -3137,7 +2006,7 @@ static void launch_trace_x(const DevFrame &F, hipStream_t stream) {
 // (DevFrame::exchange == 0: a frame of a tile or two per wave -- a rank's share of a multi-GPU frame, the test images -- which the pool only costs).
 template <bool VOL, int LMODE, bool DIAG, bool BIG>
 static void launch_trace(const DevFrame &F, hipStream_t stream) {
-    if constexpr (AIC_EXCHANGE && !DIAG && LMODE != 3) {
+    if constexpr (!DIAG && LMODE != 3) {
         if (F.exchange && (F.ray_cold || !F.antialias)) { launch_trace_x<VOL, LMODE, DIAG, BIG, true>(F, stream); return; }
     }
     launch_trace_x<VOL, LMODE, DIAG, BIG, false>(F, stream);
@@ -3160,7 +2029,6 @@ static void launch_trace_diag(const DevFrame &F, bool vol, int lmode, hipStream_
 
 // DevFrame::ray_cold of the exchanging variants (antialiased frames): 16 bytes per LDS column (a lane's or a pool slot's) of every workgroup of the resident grid
 size_t trace_ray_cold_bytes(uint32_t n_cus, uint32_t *groups) {
-    if (!AIC_EXCHANGE) { *groups = 0; return 0; }
     const uint32_t g = n_cus * 4u * (uint32_t)AIC_MIN_WAVES / ((uint32_t)AIC_XWG_THREADS / 64u);
     *groups = g;
     return (size_t)g * ((size_t)AIC_XWG_THREADS + (size_t)AIC_POOL) * 16u;
@@ -3178,57 +2046,6 @@ void launch_trace_image(const DevFrame &F, bool diag, hipStream_t stream) {
         if (big) launch_trace_diag<false, true>(F, vol, lmode, stream);
         else launch_trace_diag<false, false>(F, vol, lmode, stream);
     }
-}
-
-void launch_tag_cubes(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged, hipStream_t stream) {
-    if (!n) return;
-    hipLaunchKernelGGL(tag_cubes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, grid, n, cls, from_tagged, to_tagged);
-}
-
-void launch_scatter_cubes(uint16_t *grid, uint32_t *light, const int32_t *xyz, const uint16_t *bi, const uint32_t *lt,
-                          uint32_t n, const int lo[3], const int size[3], const uint32_t *cls, hipStream_t stream) {
-    if (!n) return;
-    hipLaunchKernelGGL(scatter_cubes_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, grid, light, xyz, bi, lt, n, lo[0],
-                       lo[1], lo[2], size[0], size[1], size[2], cls);
-}
-
-void launch_probe_powf(const float *x, const float *y, float *out, uint32_t n, hipStream_t stream) {
-    if (!n) return;
-    hipLaunchKernelGGL(probe_powf_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, x, y, out, n);
-}
-
-void launch_probe_expf(const float *x, float *out, uint32_t n, hipStream_t stream) {
-    if (!n) return;
-    hipLaunchKernelGGL(probe_expf_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, x, out, n);
-}
-
-void launch_order_tiles_jobs(const OrderJobs &jobs, uint32_t n_jobs, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, hipStream_t stream,
-                             bool clear_cost, uint32_t n_clear_words) {
-    if (!n_tiles || !n_jobs) return;
-    if (n_queues < 1u) n_queues = 1u;
-    if (n_queues > kMaxTileQueues) n_queues = kMaxTileQueues;
-    hipLaunchKernelGGL(order_tiles_kernel, dim3(n_jobs), dim3(kOrderThreads), 0, stream, jobs, n_tiles, macros_x ? macros_x : 1u, sb_shift, n_queues, clear_cost ? 1u : 0u,
-                       n_clear_words);
-}
-void launch_order_tiles(const uint32_t *cost, uint32_t *order, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, uint32_t *queue_start,
-                        hipStream_t stream, bool clear_cost, uint32_t *clear_words, uint32_t n_clear_words) {
-    OrderJobs jobs{};
-    jobs.cost[0] = cost; jobs.order[0] = order; jobs.queue_start[0] = queue_start; jobs.clear_words[0] = clear_words;
-    launch_order_tiles_jobs(jobs, 1u, n_tiles, macros_x, sb_shift, n_queues, stream, clear_cost, n_clear_words);
-}
-
-void launch_assemble_strips(const uint32_t *gathered, uint32_t *out, uint32_t w, uint32_t h, uint32_t strip_rows,
-                            uint32_t n_parts, uint32_t max_rows, hipStream_t stream) {
-    size_t n = (size_t)w * h;
-    if (!n) return;
-    hipLaunchKernelGGL(assemble_strips_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, gathered, out, w, h,
-                       strip_rows, n_parts, max_rows);
-}
-
-void launch_probe_raycast(const double *od, int use_bounds, const int *lohi, int include_exit, uint32_t max_steps,
-                          double *out_rec, uint32_t *n_out, int *ended, hipStream_t stream) {
-    hipLaunchKernelGGL(probe_raycast_kernel, dim3(1), dim3(64), 0, stream, od, use_bounds, lohi, include_exit, max_steps, out_rec,
-                       n_out, ended);
 }
 
 }  // namespace aic

@@ -54,7 +54,7 @@ def _host_powf(x, y):
 
 def test_device_powf_equals_libm_powf():
     """apply_transmittance's powf (raytracer_components.rs:215-258) on the device -- glibc's table
-    algorithm restated (aic_trace.hip powf_table) -- against the host libm, bit for bit."""
+    algorithm restated (aic_colour.h powf_table) -- against the host libm, bit for bit."""
     rng = np.random.default_rng(11)
     n = 400_000
     x = np.concatenate([

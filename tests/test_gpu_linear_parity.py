@@ -1,7 +1,7 @@
 """The trace kernel's colour against the CPU oracle bit for bit (run with -m gpu on an MI355X).
 
 The kernel is built with -ffp-contract=off, does its colour arithmetic in f32 in the reference's order and restates the C
-library's powf / expf (aic_trace.hip powf_table, expf_table), as the oracle calls them. So the linear Rgba the frame hands
+library's powf / expf (aic_colour.h powf_table, expf_table), as the oracle calls them. So the linear Rgba the frame hands
 over before exposure and tone mapping (AIC_FRAME_OUT_LINEAR, Rgba::from(ColorBuf): raytracer_components.rs:141-163) must
 carry the oracle's exact bits, and the encoded RGBA8 must equal the oracle's with no tolerance. A +-1 level bar lets relative
 errors of up to about 1 % through; these tests do not. Every option of the colour path (fog, transparency, lighting, Bounce,

@@ -135,7 +135,7 @@ def test_probe_raycast_random_vs_oracle(ctx):
 
 
 def test_probe_raycast_extreme_exponents_vs_oracle(ctx):
-    """Rays whose operands leave the exponent windows of the cheap divisions (aic_trace.hip div_known_recip: quotients by a direction through its t_delta, taken only for
+    """Rays whose operands leave the exponent windows of the cheap divisions (aic_raycast.h div_known_recip: quotients by a direction through its t_delta, taken only for
     exponents far from the ends of the range) -- tiny and huge direction components, origins a denormal's width from a bounding plane or exactly on it, origins far away --
     so that the generic division behind the guard, and the guard itself, are compared with the oracle bit for bit like the ordinary rays above."""
     rng = np.random.default_rng(4242)
@@ -306,7 +306,7 @@ def test_bounce_with_octant_sky_ui_layer_and_antialiasing(ctx):
 
 def test_xcd_local_tile_queues_trace_every_pixel_once(ctx, synth_space):
     """The persistent kernel's waves take their tiles from one queue per XCD (macro tiles dealt to queues by super-block, a workgroup
-    starting on its XCD's queue and moving on when it is empty: csrc/aic_trace.hip order_tiles_kernel). Whatever the number of queues
+    starting on its XCD's queue and moving on when it is empty: csrc/aic_scene_kernels.h order_tiles_kernel). Whatever the number of queues
     and the block size, and with or without the previous frame's cost record, the frame is the one the single dispenser gives --
     pixels, per-pixel step counts and totals -- and the oracle's."""
     opt = oracle.make_options(fog=1, transparency=1, lighting=2)

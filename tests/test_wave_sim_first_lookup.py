@@ -1,5 +1,5 @@
 """The wave-scheduler model's SIM_FIRST_LOOKUP switch (tools/wave_sim): the ENTER and RAY phases consume a leading 'l' token -- the first lookup of the
-level they set up, when it finds nothing -- of the lane they serve, as the kernel's AIC_FIRST_LOOKUP does. CPU only; the `small` workload."""
+level they set up, when it finds nothing -- of the lane they serve, as the kernel's ENTER and NEWRAY events do. CPU only; the `small` workload."""
 import ctypes
 import os
 import sys
@@ -9,7 +9,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, os.path.join(ROOT, "tools", "wave_sim"))
 
-# the kernel's policy as built (the exchange constants of aic_trace.hip), and no exchange at all
+# the kernel's policy as built (the exchange constants of aic_tunables.h), and no exchange at all
 SETTINGS = (dict(pool=64, reservoir=1, policy=3, deposit_free=3, min_gain=8, c_xchg_base=75, c_xchg_move=450, c_pass=120), dict())
 
 

@@ -4,6 +4,10 @@
 # AIC_PATCH=<file>: the variants are built from a copy of csrc/ with that patch applied (e.g. profiles/scripts_r04/experiments_r01_r04.patch, which
 # puts the measured-negative experiments of rounds 1-4 -- AIC_SPEC_STEPS, AIC_SHADE_STEP, AIC_PRIO_SHIFT, AIC_HURRY_STEPS, AIC_RAY_MIGRATION, AIC_LDS_PAD,
 # AIC_SCHED_SIMPLE, AIC_TRIP_MIN -- back into aic_trace.hip as it stood at the commit that removed them: `git log -- profiles/scripts_r04/experiments_r01_r04.patch`).
+# profiles/scripts_r07/retired_switches.patch does the same for the switches whose defaults won and whose other values nobody builds -- AIC_NEWRAY_SKIP_FF,
+# AIC_EARLY_APPLY, AIC_OPAQUE_SHORTCUT, AIC_FIRST_LOOKUP, AIC_EXCHANGE, AIC_XCHG_DEPOSIT, AIC_COLD_SCOPE, AIC_FAST_STEPS=0, AIC_FAST_MIN=0 -- on top of the commit
+# that retired them (aic_trace.hip and the headers compiled with it, which are copied along: the whole of csrc/ is):
+#   AIC_PATCH=profiles/scripts_r07/retired_switches.patch tools/build_variants.sh "ff:-DAIC_NEWRAY_SKIP_FF=1"
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p variants

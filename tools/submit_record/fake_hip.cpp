@@ -13,6 +13,7 @@
 
 #include "aic_bloom.h"
 #include "aic_device.h"
+#include "aic_launch.h"
 #include "record.h"
 
 namespace {

@@ -181,7 +181,7 @@ extern "C" int simulate(const char *tok, const long *off, const Params *Pp, Out 
     // (SIM_COST=<file of n_macro int32>: another cost record -- e.g. an estimate made before the frame -- in place of the true one; a policy experiment)
     if (const char *cf = getenv("SIM_COST")) { if (FILE *f = fopen(cf, "rb")) { size_t got = fread(cost.data(), 4, (size_t)n_macro, f); fclose(f); if (got != (size_t)n_macro) return 7; } }
     // (SIM_FIRST_LOOKUP=1: the event that sets a level up takes the level's first lookup itself when it finds nothing -- ENTER and RAY consume a leading 'l'
-    //  token of the lane they serve, as the kernel's AIC_FIRST_LOOKUP does; the lane leaves the event as an ordinary stepping lane)
+    //  token of the lane they serve, as the kernel's ENTER and NEWRAY events do; the lane leaves the event as an ordinary stepping lane)
     const char *fl_env = getenv("SIM_FIRST_LOOKUP");
     const bool first_lookup = fl_env && atoi(fl_env) != 0;
     // queues: super-blocks of 128 px (8 macro tiles), (bx + 3 by) mod 8
