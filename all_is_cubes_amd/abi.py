@@ -25,6 +25,8 @@ FRAME_BLOOM = 64  # AIC_FRAME_BLOOM: bloom the frame when the world options' blo
 FRAME_OUT_SPLIT = 512  # AIC_FRAME_OUT_SPLIT: an f16x4 colour plane and an f32 depth plane (12 bytes per pixel), raytrace_to_texture's two texels
 RAYS_NO_SKY, RAYS_DEVICE = 128, 256  # aic_trace_rays only: include_sky = false; rays / out / aux are device pointers
 MAX_RAYS = 2048 * 65535  # rays in one aic_trace_rays call
+PIXELS_DEVICE, PIXELS_IN_PLACE = 1, 2  # aic_trace_pixels' mode: pixels / out / aux are device pointers; out is a whole frame written at the listed pixels
+MAX_PIXELS = 2048 * 65535  # pixels in one aic_trace_pixels call
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
@@ -66,7 +68,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
@@ -112,6 +114,21 @@ def light_chart():
     ch = np.zeros((n, 6), np.uint32)
     lib.aic_light_chart(w.ctypes.data, ch.ctypes.data, C.byref(depth))
     return w, ch, int(depth.value)
+
+
+def pixel_order(width: int, height: int):
+    """PixelPicker::new (raytrace_to_texture.rs:856-891) through aic_pixel_order: (order [width * height] uint32 -- the pixel indices y * width + x, centre
+    first and dithered --, central, cycle_length). Pick k of the sequence is order[(k // 2) % central] for even k and
+    order[central + (k // 2) % (count - central)] for odd k; with central = 0, order[k % count]. Host-only: needs no device or context."""
+    lib = load()
+    lib.aic_pixel_order.restype = C.c_int
+    lib.aic_pixel_order.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    order = np.zeros(int(width) * int(height), np.uint32)
+    central, cycle = C.c_uint32(0), C.c_uint64(0)
+    rc = lib.aic_pixel_order(int(width), int(height), order.ctypes.data if order.size else None, C.byref(central), C.byref(cycle))
+    if rc != 0:
+        raise AicError(rc, f"aic_pixel_order({width}, {height})")
+    return order, int(central.value), int(cycle.value)
 
 
 class SpaceDesc(C.Structure):
@@ -198,6 +215,7 @@ def load() -> C.CDLL:
         lib.aic_render_wait_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FrameInfo)]
         lib.aic_trace_patches.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_trace_rays.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
+        lib.aic_trace_pixels.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_read_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -517,6 +535,34 @@ class Context:
         info = FrameInfo()
         self._check(self._lib.aic_trace_rays(self._h, int(layer), int(n), C.c_void_p(rays_ptr), flags, float(exposure), C.c_void_p(out_ptr),
                                              C.c_void_p(aux_ptr or None), C.byref(info)))
+        return info
+
+    def trace_pixels(self, frame: FrameDesc, pixels, want_aux: bool = False):
+        """The listed pixels of `frame` (indices y * width + x, host memory), each traced exactly as render() traces it, results in list order
+        (aic_trace_pixels, compact mode). Returns dict(rgba8 [n,4] uint8 or float32 by frame.flags, aux or None, info); for a FRAME_OUT_SPLIT frame
+        dict(color_f16 [n,4] float16, depth [n] float32, aux, info)."""
+        px = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        n = len(px)
+        floats = bool(frame.flags & (FRAME_OUT_LINEAR | FRAME_OUT_COLORBUF))
+        split = bool(frame.flags & FRAME_OUT_SPLIT) and not floats
+        out = np.zeros(n * 3, np.uint32) if split else np.zeros((n, 4), np.float32 if floats else np.uint8)
+        aux = np.zeros(n, PIXEL_AUX_DTYPE) if want_aux else None
+        info = FrameInfo()
+        self._check(self._lib.aic_trace_pixels(self._h, C.byref(frame), n, _ptr(px), 0, _ptr(out), _ptr(aux), C.byref(info)))
+        if split:
+            planes = split_planes(out, 1, n)
+            return {"color_f16": planes["color_f16"].reshape(n, 4), "depth": planes["depth"].reshape(n), "aux": aux, "info": info}
+        return {"rgba8": out, "aux": aux, "info": info}
+
+    def trace_pixels_device(self, frame: FrameDesc, n: int, pixels_ptr: int, out_ptr: int, aux_ptr: int = 0, in_place: bool = False) -> FrameInfo:
+        """The same with the list ([n] uint32), the results and (aux_ptr != 0) the [n] first-hit records in HBM on the context's device, e.g. torch
+        tensors' data_ptr() (AIC_PIXELS_DEVICE). in_place: `out_ptr` is a whole frame of frame.width x frame.height as render_to_device leaves it (Split:
+        the depth plane at byte offset width * height * 8); result i goes to pixel pixels[i] and every other texel stays (AIC_PIXELS_IN_PLACE) -- the
+        resident textures of raytrace_to_texture's incremental loop. Returns once the batch is done."""
+        mode = PIXELS_DEVICE | (PIXELS_IN_PLACE if in_place else 0)
+        info = FrameInfo()
+        self._check(self._lib.aic_trace_pixels(self._h, C.byref(frame), int(n), C.c_void_p(pixels_ptr or None), mode, C.c_void_p(out_ptr or None),
+                                               C.c_void_p(aux_ptr or None), C.byref(info)))
         return info
 
     def render_submit(self, frame: FrameDesc, device_ptr: int, slot: int) -> None:

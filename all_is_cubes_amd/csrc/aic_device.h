@@ -197,7 +197,7 @@ struct DevFrame {
     uint32_t ray_cold_groups;
     // How the kernel derives a ray from its pixel (aic_trace.hip ray_of_pixel), decided by the launcher from the fields above so that the common cameras take ONE scalar
     // fetch and branch instead of a chain of five dependent ones (round 6): 0 = the layer holds a space, pixel grid, edge tables, one part; 1 = the same with the strip
-    // partition (n_parts > 1); 2 = anything else (pixel centres, patch rectangles, orthographic views, no tables, no space).
+    // partition (n_parts > 1); 2 = anything else (pixel centres, patch rectangles, pixel lists, orthographic views, no tables, no space).
     uint32_t ray_mode;
     uint32_t exchange;       // host-side: launch the exchanging variant (aic_trace.hip "lane exchange") -- a frame with several tiles per persistent wave; a frame of
                              // about one tile per wave (a rank's share at N >= 4, small images) runs the variant without the pool, which it would only pay for
@@ -206,6 +206,13 @@ struct DevFrame {
     double depth_zw[4];                // {m33, m43, m34, m44} of the depth transform (aic_set_depth_transform)
     double *split_depth[kMaxSub];      // per frame: [samples][local_rows][width] DepthBuf of every sample after the UI pre-pass (written by it, read by the world pass), or null
     float split_ui_exposure[kMaxSub];  // per frame: the UI Camera::exposure() (the world's is DevSub::exposure)
+    // aic_trace_pixels (the recording variants only; appended like the Split fields): batch position i = row-major index of the batch's image, as for patches and
+    // rays, traces pixel pixels[i] = y * px_width + x of a TARGET frame of px_width x px_height -- the edge tables are that frame's -- and n_patches is the list's
+    // length. An entry >= px_width * px_height has no ray and no store. acc_buf, split_depth and aux stay indexed by batch position; the result goes to `out` at
+    // pixels[i] with the target frame's plane layout (px_in_place) or at i with planes of n_patches texels.
+    const uint32_t *pixels;
+    uint32_t px_width, px_height;
+    uint32_t px_in_place;
 };
 
 // order_tiles_kernel's jobs: one workgroup each -- the cost record to read (null: index order), the order and the queues' starts to write, and words to clear

@@ -1,7 +1,7 @@
 // aic_frame.cpp -- the frame path of the C ABI declared in include/aic_hip.h: everything that submits a trace or waits for one.
 //
 // submit_frames queues the frames of one launch on a slot's stream as a sequence of named steps (DESIGN.md 4.3 "One frame, step by step"); wait_frame
-// collects them. The entry points -- aic_render, aic_render_orthographic, aic_trace_patches, aic_trace_rays, aic_render_submit(_batch),
+// collects them. The entry points -- aic_render, aic_render_orthographic, aic_trace_patches, aic_trace_rays, aic_trace_pixels, aic_render_submit(_batch),
 // aic_render_wait(_batch) -- say what is traced (Traced) and where the result goes. Of aic_abi.cpp it uses what aic_ctx.h declares.
 // Built with -ffp-contract=off, like the kernels: the pixel-edge table is the reference's own f64 operations (bind_pixel_edges).
 
@@ -80,8 +80,8 @@ bool cameras_close(const double a[16], const double b[16]) {
     return true;
 }
 
-// What one launch traces. Whole frames (k of them: all pointers null) go through the pixel grid, the tile queues and the cost feedback; the other three replace the
-// camera and take none of those. A patch batch (aic_trace_patches): n NDC rectangles on the device, one per pixel of the batch's image. Orthographic views
+// What one launch traces. Whole frames (k of them: all pointers null) go through the pixel grid, the tile queues and the cost feedback; the other four replace the
+// camera (a pixel list: the pixel grid) and take none of those. A patch batch (aic_trace_patches): n NDC rectangles on the device, one per pixel of the batch's image. Orthographic views
 // (aic_render_orthographic): ortho_n views on the device. A ray batch (aic_trace_rays): n world-space rays on the device replace the camera; the space traced is
 // the launch's world layer (the caller swaps it in, as aic_render_orthographic does), labelled `layer` in first-hit records, which go to `aux_target` when the
 // caller's own device buffer receives them.
@@ -92,13 +92,23 @@ struct RayBatch {
     uint32_t layer;
     DevAux *aux_target;
 };
+// A pixel list (aic_trace_pixels): n pixel indices on the device, one per pixel of the batch's image, each a pixel of the target frame of width x height, whose
+// cameras, edge tables and plane layout (in_place) the launch uses; the recording variants only. First-hit records go to `aux_target` as for a ray batch.
+struct PixelList {
+    const uint32_t *pixels;
+    uint32_t n, width, height;
+    bool in_place;
+    DevAux *aux_target;
+};
 struct Traced {
     const double *patches = nullptr;
     uint32_t n_patches = 0;
     const DevOrthoView *ortho = nullptr;
     int32_t ortho_n = 0;
     const RayBatch *rb = nullptr;
-    bool whole_frame() const { return !patches && !rb && !ortho_n; }
+    const PixelList *px = nullptr;
+    bool whole_frame() const { return !patches && !rb && !px && !ortho_n; }
+    DevAux *aux_target() const { return rb ? rb->aux_target : (px ? px->aux_target : nullptr); }
 };
 
 // What the steps of one submit hand to each other (submit_frames is the list of steps).
@@ -148,7 +158,7 @@ int validate_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32
         if (P.npix && !out_devices[j]) return fail(c, AIC_ERR_INVALID, "aic_render: output buffer is null");
         if (P.split && ((uintptr_t)out_devices[j] & 7u)) return fail(c, AIC_ERR_INVALID, "aic_render: an AIC_FRAME_OUT_SPLIT buffer starts at an 8-byte boundary");
     }
-    if (!what.patches && !what.rb)
+    if (!what.patches && !what.rb && !what.px)
         for (uint32_t j = 0; j < k; j++) dump_record(c, DUMP_FRAME, slot, {{&frames[j], sizeof(frames[j])}});
     if (f->width > 65535u || P.local_rows > 65535u) return fail(c, AIC_ERR_INVALID, "aic_render: frame dimensions above 65535 are not supported");
     for (uint32_t j = 0; j < k; j++)  // Camera::exposure() is a PositiveSign<f32> (camera_struct.rs:365-367)
@@ -194,7 +204,13 @@ void plan_geometry(const aic_ctx *c, uint32_t k, const aic_frame_desc *f, uint32
     F.out_mode = P.split ? 3 : ((f->flags & AIC_FRAME_OUT_LINEAR) ? 1 : ((f->flags & AIC_FRAME_OUT_COLORBUF) || P.bloom ? 2 : 0));  // (a bloomed frame: its ColorBuf, into the slot's scratch)
     std::memcpy(F.depth_zw, c->depth_zw, sizeof(F.depth_zw));
     F.patches = what.patches;
-    F.n_patches = what.rb ? what.rb->n : what.n_patches;
+    F.n_patches = what.rb ? what.rb->n : (what.px ? what.px->n : what.n_patches);
+    if (what.px) {
+        F.pixels = what.px->pixels;
+        F.px_width = what.px->width;
+        F.px_height = what.px->height;
+        F.px_in_place = what.px->in_place ? 1u : 0u;
+    }
     F.ortho = what.ortho;
     F.ortho_n = what.ortho_n;
     F.rays = what.rb ? what.rb->rays : nullptr;
@@ -242,7 +258,7 @@ void plan_geometry(const aic_ctx *c, uint32_t k, const aic_frame_desc *f, uint32
 void plan_dispatch(const aic_ctx *c, uint32_t k, const aic_frame_desc *f, bool allow_aux, const Traced &what, FramePlan &P) {
     DevFrame &F = P.F;
     P.want_aux = allow_aux && (f->flags & AIC_FRAME_AUX) != 0;
-    P.diag = P.want_aux || P.split || (f->flags & AIC_FRAME_COUNTERS) != 0;  // (the Split's depth and layer live in the recording variants only)
+    P.diag = P.want_aux || P.split || what.px || (f->flags & AIC_FRAME_COUNTERS) != 0;  // (the Split's depth and layer, and pixel lists, live in the recording variants only)
     P.n_tiles = F.macros_x * F.macros_y;  // the feedback works on macro tiles
     // XCD-local tile queues (aic_scene_kernels.h order_tiles_kernel): one per XCD (32 CUs each on this part), a macro tile in the queue of the
     // 2^sb_shift-macro-tile super-block it lies in. One queue (aic_frame_desc.tuning) is the single dispenser of rounds 1-3.
@@ -367,10 +383,9 @@ int bind_sub_frame(aic_ctx *c, aic_ctx::FrameSlot &fs, uint32_t j, const aic_fra
     return AIC_OK;
 }
 
-// Step 5 (whole frames): Viewport's pixel edges (viewport.rs:104-113), once per frame shape: x / width * 2 - 1 and -(y / height * 2 - 1) in the reference's own f64
+// Step 5 (whole frames, and pixel lists for their target frame): Viewport's pixel edges (viewport.rs:104-113), once per frame shape: x / width * 2 - 1 and -(y / height * 2 - 1) in the reference's own f64
 // operations (this file is built with -ffp-contract=off, like the kernels), so that the kernel reads them instead of dividing per ray
-int bind_pixel_edges(aic_ctx *c, aic_ctx::FrameSlot &fs, DevFrame &F) {
-    const uint32_t width = F.width, height = F.height;
+int bind_pixel_edges(aic_ctx *c, aic_ctx::FrameSlot &fs, DevFrame &F, const uint32_t width, const uint32_t height) {
     if (fs.edges_w != width || fs.edges_h != height || !fs.edges.p) {
         std::vector<double> host((size_t)width + 1 + (size_t)height + 1);
         for (uint32_t x = 0; x <= width; x++) host[x] = ((double)x) / (double)width * 2.0 - 1.0;
@@ -520,13 +535,14 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     fs.variant = fs.tile_queues = 0;
     if (allow_aux) c->aux_records = 0;
     if (!P.npix) return AIC_OK;
-    const bool own_aux = P.want_aux && !(what.rb && what.rb->aux_target);  // the first-hit records go to the context's buffer (aic_read_aux)
+    const bool own_aux = P.want_aux && !what.aux_target();  // the first-hit records go to the context's buffer (aic_read_aux)
     hipError_t e;
     if (own_aux && (e = c->aux.ensure(P.npix)) != hipSuccess) return hip_fail(c, "alloc aux", e);
-    if (P.want_aux) F.aux = own_aux ? c->aux.p : what.rb->aux_target;
+    if (P.want_aux) F.aux = own_aux ? c->aux.p : what.aux_target();
     STEP(ensure_static_order(c, fs, k, frames, P));
     for (uint32_t j = 0; j < k; j++) STEP(bind_sub_frame(c, fs, j, frames[j], out_devices[j], P));
-    if (what.whole_frame()) STEP(bind_pixel_edges(c, fs, F));
+    if (what.whole_frame()) STEP(bind_pixel_edges(c, fs, F, F.width, F.height));
+    if (what.px) STEP(bind_pixel_edges(c, fs, F, what.px->width, what.px->height));
     if (F.exchange && F.antialias) {  // the exchanging variants' antialiasing sums (DevFrame::ray_cold)
         if ((e = fs.ray_cold.ensure(P.ray_cold_bytes / sizeof(uint4))) != hipSuccess) return hip_fail(c, "alloc ray state", e);
         F.ray_cold = fs.ray_cold.p;
@@ -871,6 +887,84 @@ int aic_trace_rays(aic_ctx *c, int layer, uint32_t n, const double *rays, uint32
     if (rc != AIC_OK) return rc;
     if (aux && !on_device) HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
     if (info) info->rows_rendered = n;
+    return AIC_OK;
+}
+
+int aic_trace_pixels(aic_ctx *c, const aic_frame_desc *f, uint32_t n, const uint32_t *pixels, uint32_t mode, void *out, aic_pixel_aux *aux,
+                     aic_frame_info *info) {
+    if (!c || !f || (n && (!pixels || !out))) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    const bool on_device = (mode & AIC_PIXELS_DEVICE) != 0, in_place = (mode & AIC_PIXELS_IN_PLACE) != 0;
+    const bool split = (f->flags & AIC_FRAME_OUT_SPLIT) != 0, floats = (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) != 0;
+    if (in_place && !on_device) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: AIC_PIXELS_IN_PLACE needs AIC_PIXELS_DEVICE");
+    if (f->flags & AIC_FRAME_BLOOM) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_pixels: AIC_FRAME_BLOOM needs a whole frame");
+    if (f->partition.n_parts > 1u) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_pixels: the pixels are those of the whole frame (partition.n_parts <= 1)");
+    if (split && floats) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: AIC_FRAME_OUT_SPLIT excludes AIC_FRAME_OUT_LINEAR and AIC_FRAME_OUT_COLORBUF");
+    if (f->width > 65535u || f->height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: frame dimensions above 65535 are not supported");
+    if (!(f->world.exposure >= 0.f) || !(f->ui.exposure >= 0.f)) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: exposure is negative or NaN");
+    const size_t out_align = split ? 8u : (floats ? 16u : 4u);
+    if (on_device && (((uintptr_t)pixels & 3u) || ((uintptr_t)out & (out_align - 1u)) || ((uintptr_t)aux & 7u)))
+        return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: AIC_PIXELS_DEVICE wants pixels, out and aux at their element's boundary (Split: 8 bytes, float outputs: 16)");
+    if (!n) return AIC_OK;
+    const uint32_t count = f->width * f->height;  // (< 2^32: both at most 65535)
+    if (!on_device)
+        for (uint32_t i = 0; i < n; i++)
+            if (pixels[i] >= count) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: a listed pixel is outside the frame");
+    // the batch is laid out as an image of up to 2048 columns, like a patch batch; pixel i of that image traces pixel pixels[i] of the frame
+    aic_frame_desc g = *f;
+    g.width = n < 2048u ? n : 2048u;
+    g.height = (n + g.width - 1u) / g.width;
+    if (g.height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: more than 2048 x 65535 pixels in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (!count) return AIC_OK;  // (a device list over an empty viewport: every entry is outside it)
+    g.partition = aic_partition{0, 1, 0, 0};
+    g.flags = (f->flags & (AIC_FRAME_COUNTERS | AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF | AIC_FRAME_OUT_SPLIT | AIC_FRAME_PIXEL_CENTERS)) | (aux ? AIC_FRAME_AUX : 0u);
+    g.tuning = 0;
+    PixelList px{pixels, n, f->width, f->height, in_place, on_device ? reinterpret_cast<DevAux *>(aux) : nullptr};
+    uint32_t *target = (uint32_t *)out;
+    hipStream_t stream = c->slots[0].stream;
+    const size_t px_words = floats ? 4 : (split ? 3 : 1);  // (compact Split: [n] colour texels, then [n] depths -- contiguous, one copy)
+    hipError_t e;
+    if (!on_device) {
+        if ((e = c->out.ensure((size_t)n * px_words)) != hipSuccess) return hip_fail(c, "alloc output", e);
+        if ((e = c->staging.ensure((size_t)n * 4)) != hipSuccess) return hip_fail(c, "alloc staging", e);
+        HIP_TRY(c, hipMemcpyAsync(c->staging.p, pixels, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        px.pixels = (const uint32_t *)c->staging.p;
+        target = c->out.p;
+    }
+    Traced batch;
+    batch.px = &px;
+    int rc = submit_frame(c, &g, target, 0, true, batch);
+    if (rc != AIC_OK) return rc;
+    if (!on_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, (size_t)n * px_words * 4, hipMemcpyDeviceToHost, stream));
+    rc = wait_frame(c, 0, info, !on_device);
+    if (rc != AIC_OK) return rc;
+    if (aux && !on_device) HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
+    if (info) info->rows_rendered = n;
+    return AIC_OK;
+}
+
+// PixelPicker::new (raytrace_to_texture.rs:856-891). sort_by_key is stable; the keys are small non-negative integers, so a counting sort gives the same order.
+int aic_pixel_order(uint32_t width, uint32_t height, uint32_t *order, uint32_t *central, uint64_t *cycle_length) {
+    const uint64_t count = (uint64_t)width * height;
+    if (count > 0xffffffffull) return AIC_ERR_INVALID;  // (a pixel index is a uint32_t)
+    const uint64_t n_central = std::min<uint64_t>(60000u, count / 4u);
+    if (central) *central = (uint32_t)n_central;
+    if (cycle_length) *cycle_length = std::max(n_central, count - n_central) * 2u;
+    if (!order || !count) return AIC_OK;
+    const double cx = (double)width / 2.0 - 0.5, cy = (double)height / 2.0 - 0.5;
+    auto key_of = [&](uint32_t x, uint32_t y) -> int64_t {
+        const double blend = (double)(((x ^ y) % 4u) * 2u);
+        const double square_radius = std::fmax(std::fabs((double)x - cx), std::fabs((double)y - cy));
+        return (int64_t)(square_radius + blend);
+    };
+    std::vector<uint32_t> start((size_t)std::max(width, height) / 2u + 9u, 0u);  // key <= max(cx, cy) + 6
+    for (uint32_t y = 0; y < height; y++)
+        for (uint32_t x = 0; x < width; x++) start[(size_t)key_of(x, y) + 1u]++;
+    for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
+    for (uint32_t y = 0; y < height; y++)
+        for (uint32_t x = 0; x < width; x++) order[start[(size_t)key_of(x, y)]++] = y * width + x;
     return AIC_OK;
 }
 

@@ -796,10 +796,19 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                     const uint32_t strip = lrow / srows;
                     y = (F.part + strip * F.n_parts) * srows + (lrow - strip * srows);
                 }
+                // aic_trace_pixels (the recording variants): the batch position names a pixel of the target frame, and from here on the image path runs on that
+                // pixel and that frame's shape -- its edge tables, its width and height for pixel centres (the tile decode has checked the entry's range)
+                const bool listed = DIAG && F.pixels;
+                uint32_t gx = x;
+                if (listed) {
+                    const uint32_t p_ = F.pixels[pix], pw_ = opaque_s(F.px_width);
+                    y = p_ / pw_;
+                    gx = p_ - y * pw_;
+                }
                 double px, py;  // renderer.rs:428-433 sample points, else the patch centre
                 if (F.pixel_centers) {  // Viewport::normalize_fb_x / _y (viewport.rs:89-99): the text renderer's rays
-                    const uint32_t fw = opaque_s(F.width), fh = opaque_s(F.height);
-                    px = ((double)x + 0.5) / (double)fw * 2.0 - 1.0;
+                    const uint32_t fw = opaque_s(listed ? F.px_width : F.width), fh = opaque_s(listed ? F.px_height : F.height);
+                    px = ((double)gx + 0.5) / (double)fw * 2.0 - 1.0;
                     py = -(((double)y + 0.5) / (double)fh * 2.0 - 1.0);
                 } else {
                     double x0, x1, y0, y1;  // the pixel's NdcRect {min: (x0, y0), max: (x1, y1)} (renderer.rs:537-550)
@@ -808,10 +817,10 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                         x0 = r[0]; y0 = r[1]; x1 = r[2]; y1 = r[3];
                     } else if (F.edge_x) {
                         // fb_x_edge / fb_y_edge of the pixel's two edges each, from the frame's tables (DevFrame::edge_x: made by the same operations)
-                        x0 = F.edge_x[x]; x1 = F.edge_x[x + 1u]; y0 = F.edge_y[y]; y1 = F.edge_y[y + 1u];
+                        x0 = F.edge_x[gx]; x1 = F.edge_x[gx + 1u]; y0 = F.edge_y[y]; y1 = F.edge_y[y + 1u];
                     } else {
                         const uint32_t fw = opaque_s(F.width), fh = opaque_s(F.height);
-                        x0 = fb_x_edge(fw, x); x1 = fb_x_edge(fw, x + 1);
+                        x0 = fb_x_edge(fw, gx); x1 = fb_x_edge(fw, gx + 1);
                         y0 = fb_y_edge(fh, y); y1 = fb_y_edge(fh, y + 1);
                     }
                     if (n_samples == 4) {
@@ -835,13 +844,13 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                     int vsel = -1;
                     for (int v = 0; v < F.ortho_n; v++) {
                         const uint32_t vx = F.ortho[v].x0, vy = F.ortho[v].y0, vw = F.ortho[v].w, vh = F.ortho[v].h;
-                        if (vsel < 0 && x >= vx && y >= vy && x - vx < vw && y - vy < vh) vsel = v;
+                        if (vsel < 0 && gx >= vx && y >= vy && gx - vx < vw && y - vy < vh) vsel = v;
                     }
                     have_ray = false;
                     if (vsel >= 0) {
                         const DevOrthoView *V = &F.ortho[vsel];
                         double p[3];
-                        unproject(V->m, (double)(x - V->x0), (double)(y - V->y0), 0.0, p);
+                        unproject(V->m, (double)(gx - V->x0), (double)(y - V->y0), 0.0, p);
                         int cube[3];
                         if (cube_containing(p, cube)) {
                             have_ray = true;
@@ -1325,6 +1334,14 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                         // encoder: Camera::post_process_color(Rgba::from(buf)).to_srgb8()
                         float c[4];
                         cb_to_rgba(pixel, c);
+                        // where the pixel's result goes: its place in the image, or -- a pixel list (the recording variants) -- entry pixels[i] of the target
+                        // frame in place, else i, with the Split's depth plane behind the target frame's or the list's colour texels. The entry is loaded again
+                        // here, not carried from NEWRAY in a register.
+                        size_t opix = pix, depth_plane = npix * 8u;
+                        if (DIAG && F.pixels) {
+                            if (F.px_in_place) { opix = F.pixels[pix]; depth_plane = (size_t)F.px_width * F.px_height * 8u; }
+                            else depth_plane = (size_t)F.n_patches * 8u;
+                        }
                         if (DIAG && F.out_mode == 3) {
                             // Split: the two texels raytrace_to_texture stores (raytrace_to_texture.rs:646-674) -- one 8-byte and one 4-byte store
                             const uint32_t sub_ = F.n_sub > 1u ? (blockIdx.x & (F.n_sub - 1u)) : 0u;
@@ -1334,7 +1351,7 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                             a = a < 0.0f ? 0.0f : a;
                             a = a > 1.0f ? 1.0f : a;
                             auto f16_bits = [](float v) -> uint32_t { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)v); };  // half::f16::from_f32: to nearest even, overflow to infinity
-                            reinterpret_cast<uint2 *>(S.out)[pix] =
+                            reinterpret_cast<uint2 *>(S.out)[opix] =
                                 make_uint2(f16_bits(pixel.l0 * e) | (f16_bits(pixel.l1 * e) << 16), f16_bits(pixel.l2 * e) | (f16_bits(a) << 16));
                             double d = sp_px;  // depth_buf.depth().clamp(0.0, 1.0)
                             d = d < 0.0 ? 0.0 : d;
@@ -1343,9 +1360,9 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                             const double z_ = ((0.0 * 0.0 + 0.0 * 0.0) + d * F.depth_zw[0]) + F.depth_zw[1];
                             const double w_ = ((0.0 * 0.0 + 0.0 * 0.0) + d * F.depth_zw[2]) + F.depth_zw[3];
                             const float layer_factor = pl == SPLIT_WORLD ? 1.0f : -1.0f;  // layer.unwrap_or(InLayer::Ui) as i8
-                            reinterpret_cast<float *>(reinterpret_cast<char *>(S.out) + npix * 8u)[pix] = (float)(z_ / w_) * layer_factor;
+                            reinterpret_cast<float *>(reinterpret_cast<char *>(S.out) + depth_plane)[opix] = (float)(z_ / w_) * layer_factor;
                         } else if (F.out_mode != 0) {  // float outputs: the linear Rgba, or the ColorBuf as it is
-                            reinterpret_cast<float4 *>(S.out)[pix] =
+                            reinterpret_cast<float4 *>(S.out)[opix] =
                                 F.out_mode == 1 ? make_float4(c[0], c[1], c[2], c[3]) : make_float4(pixel.l0, pixel.l1, pixel.l2, pixel.t);
                         } else {
                         const float ex = S.exposure;
@@ -1364,7 +1381,7 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                         uint32_t R, G, B;
                         srgb8_rgb(r, g, bl, s_thr, R, G, B);
                         const uint32_t A = round_sat_u8(c[3] * 255.0f);
-                        S.out[pix] = R | (G << 8) | (B << 16) | (A << 24);
+                        S.out[opix] = R | (G << 8) | (B << 16) | (A << 24);
                         }
                     }
                     if (DIAG) {
@@ -1467,8 +1484,11 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                         const uint32_t x = tile_x0 + (pidx & 7u) + (((pidx >> 6) & 1u) << 3);
                         const uint32_t lrow = tile_y0 + ((pidx >> 3) & 7u) + (((pidx >> 7) & 1u) << 3);
                         if (x < F.width && lrow < F.local_rows && (!F.n_patches || lrow * F.width + x < F.n_patches)) {  // pixels of partial tiles outside the image are skipped
-                            pxy = x | (lrow << 16);
-                            want = false;
+                            // (a pixel list's entry outside its target frame -- a device list, which the host cannot check -- is skipped like them: no ray, no store)
+                            if (!(DIAG && F.pixels) || F.pixels[lrow * F.width + x] < F.px_width * F.px_height) {
+                                pxy = x | (lrow << 16);
+                                want = false;
+                            }
                         }
                     }
                     const uint32_t n_need = wave_popc(need);
@@ -1998,7 +2018,7 @@ static void launch_trace_x(const DevFrame &F, hipStream_t stream) {
     grid *= n_sub;
     if (grid == 0) return;
     DevFrame G = F;
-    G.ray_mode = (F.layer.present && !F.pixel_centers && !F.patches && !F.rays && !F.ortho_n && F.edge_x && F.edge_y) ? (F.n_parts > 1u ? 1u : 0u) : 2u;  // (DevFrame::ray_mode)
+    G.ray_mode = (F.layer.present && !F.pixel_centers && !F.patches && !F.rays && !F.pixels && !F.ortho_n && F.edge_x && F.edge_y) ? (F.n_parts > 1u ? 1u : 0u) : 2u;  // (DevFrame::ray_mode)
     hipLaunchKernelGGL((trace_image_kernel<VOL, LMODE, DIAG, BIG, XC>), dim3(grid), dim3(WGT), 0, stream, G);
 }
 

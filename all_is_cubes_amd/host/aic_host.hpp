@@ -22,6 +22,7 @@
 
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <limits>
 #include <memory>
@@ -296,6 +297,45 @@ struct StandardCameras {  // stdcam.rs:90-180, reduced to values the caller sets
 };
 struct Cursor {};
 
+// PixelPicker (all-is-cubes-gpu/src/raytrace_to_texture.rs:838-908): the order in which the incremental renderer takes a frame's pixels -- centre first and
+// dithered (aic_pixel_order), the central pixels interleaved with the rest and so picked more often. take(n) is n calls of Iterator::next, as pixel indices
+// y * width + x; after cycle_length() picks every pixel has been picked. Host-only.
+class PixelPicker {
+  public:
+    PixelPicker(uint32_t width, uint32_t height) : width_(width), height_(height), order_((size_t)width * height) {
+        if (aic_pixel_order(width, height, order_.empty() ? nullptr : order_.data(), &central_, &cycle_length_) != AIC_OK)
+            throw std::invalid_argument("PixelPicker: more than 2^32 - 1 pixels");
+    }
+    void resize(uint32_t width, uint32_t height) {
+        if (width != width_ || height != height_) *this = PixelPicker(width, height);
+    }
+    std::vector<uint32_t> take(size_t n) {
+        std::vector<uint32_t> out;
+        const uint64_t count = order_.size();
+        if (!count) return out;  // (the reference's iterator panics on an empty viewport; nothing to pick here)
+        out.reserve(n);
+        for (size_t i = 0; i < n; i++, next_++) {
+            const uint64_t half = next_ / 2u;
+            // itertools::Interleave of the two cycles; with no central pixels the inner side is empty and every pick is the outer's
+            if (!central_) out.push_back(order_[next_ % count]);
+            else out.push_back((next_ & 1u) ? order_[central_ + half % (count - central_)] : order_[half % central_]);
+        }
+        return out;
+    }
+    uint64_t cycle_length() const { return cycle_length_; }
+    uint32_t central() const { return central_; }
+    uint32_t width() const { return width_; }
+    uint32_t height() const { return height_; }
+    const std::vector<uint32_t> &order() const { return order_; }
+
+  private:
+    uint32_t width_, height_;
+    std::vector<uint32_t> order_;
+    uint32_t central_ = 0;
+    uint64_t cycle_length_ = 0;
+    uint64_t next_ = 0;  // picks made so far
+};
+
 class HeadlessRenderer {  // headless.rs:17-44
   public:
     virtual ~HeadlessRenderer() = default;
@@ -341,6 +381,18 @@ class HipRtRenderer : public HeadlessRenderer {
         ImageInfo info;
     };
     RayResults trace_rays(int layer, const std::vector<Ray> &rays, bool include_sky = true);
+    // One round of raytrace_to_texture's do_some_tracing (raytrace_to_texture.rs:591-751; aic_trace_pixels): the listed pixels (y * width + x) of the frame
+    // draw_split() renders, each traced exactly as there. trace_pixels returns the Split texels in list order; trace_pixels_into stores them at the pixels'
+    // positions of a resident Split frame in device memory (width * height colour texels, then the depth plane) and leaves every other texel as it is --
+    // `device_pixels` is the list in device memory on the renderer's device.
+    struct PixelResults {
+        std::vector<uint16_t> color;  // [n][4] f16 bits
+        std::vector<float> depth;     // [n]
+        std::vector<aic_pixel_aux> hits;
+        ImageInfo info;
+    };
+    PixelResults trace_pixels(const std::vector<uint32_t> &pixels);
+    ImageInfo trace_pixels_into(void *device_frame, const uint32_t *device_pixels, uint32_t n);
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)
     ImageInfo draw_rows_to_device(void *device_out, uint32_t strip_rows, uint32_t n_parts, uint32_t part, bool counters = false,
                                   bool no_feedback = false);
@@ -421,6 +473,42 @@ inline HipRtRenderer::RayResults HipRtRenderer::trace_rays(int layer, const std:
     i.cubes_traced = fi.cubes_traced; i.n_outer = fi.n_outer; i.n_inner = fi.n_inner; i.n_hits = fi.n_hits; i.n_light = fi.n_light;
     i.kernel_ms = fi.kernel_ms; i.total_ms = fi.total_ms; i.width = (uint32_t)rays.size(); i.height = 1; i.rows_rendered = fi.rows_rendered;
     return out;
+}
+
+inline HipRtRenderer::PixelResults HipRtRenderer::trace_pixels(const std::vector<uint32_t> &pixels) {
+    if (pixels.size() > 2048u * 65535u) throw RenderError(AIC_ERR_INVALID, "trace_pixels: more than 2048 x 65535 pixels in one call");
+    aic_frame_desc f = make_frame();
+    f.flags |= AIC_FRAME_OUT_SPLIT;
+    const std::array<double, 4> zw = world_camera_.depth_transform_zw();
+    check(aic_set_depth_transform(ctx_, zw.data()), "aic_set_depth_transform");
+    const size_t n = pixels.size();
+    PixelResults out;
+    out.hits.resize(n);
+    std::vector<uint32_t> planes(n * 3, 0u);  // 8 bytes of colour per pixel, then 4 of depth
+    aic_frame_info fi;
+    check(aic_trace_pixels(ctx_, &f, (uint32_t)n, pixels.data(), 0u, planes.data(), out.hits.data(), &fi), "aic_trace_pixels");
+    out.color.resize(n * 4);
+    out.depth.resize(n);
+    if (n) {
+        std::memcpy(out.color.data(), planes.data(), n * 8);
+        std::memcpy(out.depth.data(), planes.data() + n * 2, n * 4);
+    }
+    ImageInfo &i = out.info;
+    i.cubes_traced = fi.cubes_traced; i.n_outer = fi.n_outer; i.n_inner = fi.n_inner; i.n_hits = fi.n_hits; i.n_light = fi.n_light;
+    i.kernel_ms = fi.kernel_ms; i.total_ms = fi.total_ms; i.width = f.width; i.height = f.height; i.rows_rendered = fi.rows_rendered;
+    return out;
+}
+inline ImageInfo HipRtRenderer::trace_pixels_into(void *device_frame, const uint32_t *device_pixels, uint32_t n) {
+    aic_frame_desc f = make_frame();
+    f.flags |= AIC_FRAME_OUT_SPLIT;
+    const std::array<double, 4> zw = world_camera_.depth_transform_zw();
+    check(aic_set_depth_transform(ctx_, zw.data()), "aic_set_depth_transform");
+    aic_frame_info fi;
+    check(aic_trace_pixels(ctx_, &f, n, device_pixels, AIC_PIXELS_DEVICE | AIC_PIXELS_IN_PLACE, device_frame, nullptr, &fi), "aic_trace_pixels");
+    ImageInfo i;
+    i.cubes_traced = fi.cubes_traced; i.n_outer = fi.n_outer; i.n_inner = fi.n_inner; i.n_hits = fi.n_hits; i.n_light = fi.n_light;
+    i.kernel_ms = fi.kernel_ms; i.total_ms = fi.total_ms; i.width = f.width; i.height = f.height; i.rows_rendered = fi.rows_rendered;
+    return i;
 }
 
 }  // namespace aic::host

@@ -226,6 +226,18 @@ PYBIND11_MODULE(_host, m) {
 
     py::class_<Cursor>(m, "Cursor").def(py::init<>());
 
+    py::class_<PixelPicker>(m, "PixelPicker")
+        .def(py::init<uint32_t, uint32_t>(), py::arg("width"), py::arg("height"))
+        .def("take", [](PixelPicker &p, size_t n) {
+            const std::vector<uint32_t> v = p.take(n);
+            py::array_t<uint32_t> a((py::ssize_t)v.size());
+            if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * 4);
+            return a;
+        }, py::arg("n"))
+        .def("resize", &PixelPicker::resize, py::arg("width"), py::arg("height"))
+        .def("cycle_length", &PixelPicker::cycle_length)
+        .def_property_readonly("central", &PixelPicker::central);
+
     py::class_<HipRtRenderer>(m, "HipRtRenderer")
         .def(py::init([](std::shared_ptr<StandardCameras> cams, py::object policy, int device_id) {
             HipRtRenderer::SizePolicy sp = nullptr;
@@ -252,6 +264,28 @@ PYBIND11_MODULE(_host, m) {
             d["colorbuf"] = colors; d["hits"] = hits; d["info"] = res.info;
             return d;
         }, py::arg("layer"), py::arg("rays"), py::arg("include_sky") = true)
+        .def("trace_pixels", [](HipRtRenderer &r, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> pixels) {
+            // pixels [n] = y * width + x -> dict(color_f16_bits [n, 4] u16 -- view it as numpy float16 --, depth [n] f32, hits [n, sizeof(aic_pixel_aux)] u8, info)
+            std::vector<uint32_t> v((size_t)pixels.size());
+            if (!v.empty()) std::memcpy(v.data(), pixels.data(), v.size() * 4);
+            HipRtRenderer::PixelResults res;
+            { py::gil_scoped_release rel; res = r.trace_pixels(v); }
+            py::array_t<uint16_t> color({(py::ssize_t)v.size(), (py::ssize_t)4});
+            py::array_t<float> depth((py::ssize_t)v.size());
+            py::array_t<uint8_t> hits({(py::ssize_t)v.size(), (py::ssize_t)sizeof(aic_pixel_aux)});
+            if (!v.empty()) {
+                std::memcpy(color.mutable_data(), res.color.data(), v.size() * 8);
+                std::memcpy(depth.mutable_data(), res.depth.data(), v.size() * 4);
+                std::memcpy(hits.mutable_data(), res.hits.data(), v.size() * sizeof(aic_pixel_aux));
+            }
+            py::dict d;
+            d["color_f16_bits"] = color; d["depth"] = depth; d["hits"] = hits; d["info"] = res.info;
+            return d;
+        }, py::arg("pixels"))
+        .def("trace_pixels_into", [](HipRtRenderer &r, uintptr_t frame_ptr, uintptr_t pixels_ptr, uint32_t n) {
+            py::gil_scoped_release rel;
+            return r.trace_pixels_into(reinterpret_cast<void *>(frame_ptr), reinterpret_cast<const uint32_t *>(pixels_ptr), n);
+        }, py::arg("device_ptr"), py::arg("pixels_ptr"), py::arg("n"))
         .def("set_world_camera_override", [](HipRtRenderer &r, py::object inv, float exposure) {
             if (inv.is_none()) { r.set_world_camera_override(nullptr, 1.0f); return; }
             const auto m = inv.cast<std::array<double, 16>>();

@@ -327,6 +327,35 @@ int aic_trace_patches(aic_ctx *ctx, const aic_frame_desc *frame, uint32_t n, con
                               * boundary -- an allocation's start, or any whole number of rays into one */
 int aic_trace_rays(aic_ctx *ctx, int layer, uint32_t n, const double *rays, uint32_t flags, float exposure, void *out, aic_pixel_aux *aux,
                    aic_frame_info *info);
+/* replaces: one round of Inner::do_some_tracing (all-is-cubes-gpu/src/raytrace_to_texture.rs:591-751) -- RtScene::trace_patch on each listed pixel's
+ * own rectangle and the store of its texels at that pixel's position. pixels[i] = y * frame->width + x names pixel (x, y) of `frame`, which is traced
+ * exactly as aic_render traces it for the same `frame` (layers, UI pre-pass, backdrop, the four antialiasing samples, AIC_FRAME_PIXEL_CENTERS, the
+ * frame's pixel edges): the same bits. The output kind follows frame->flags as in aic_render: RGBA8, AIC_FRAME_OUT_LINEAR, AIC_FRAME_OUT_COLORBUF or
+ * AIC_FRAME_OUT_SPLIT. AIC_FRAME_COUNTERS is honoured; info->rows_rendered = n, info->variant = AIC_VARIANT_RECORDING (pixel lists always run the
+ * recording variants, as Split frames do).
+ * mode 0 (compact): out = [n] results in list order, host memory; for Split [n] colour texels, then [n] f32 depths at byte offset n * 8.
+ * AIC_PIXELS_DEVICE: `pixels`, `out` and `aux` are device pointers on the context's device (no staging copy, no read-back).
+ * AIC_PIXELS_IN_PLACE (needs AIC_PIXELS_DEVICE): out is a whole frame as aic_render with no partition lays it out (Split: the depth plane at byte
+ * offset width * height * 8); result i goes to pixel pixels[i] and every other texel is left as it is -- the resident textures of raytrace_to_texture.
+ * aux (may be NULL) = [n] first-hit records in list order, whatever the mode. A pixel may be listed more than once (PixelPicker's inner cycle
+ * repeats pixels): every store of it carries the same value. The call returns when the batch is done (slot 0, like aic_trace_patches). n = 0 is AIC_OK.
+ * AIC_ERR_INVALID: a frame still occupies slot 0; a host list with an entry >= width * height; more than 2048 x 65535 pixels; width or height above
+ * 65535; AIC_PIXELS_IN_PLACE without AIC_PIXELS_DEVICE; AIC_FRAME_OUT_SPLIT with a float flag; a device `out` that is not at its element's boundary
+ * (8 bytes for Split, 16 for the float outputs); a negative or NaN exposure. AIC_ERR_UNSUPPORTED: AIC_FRAME_BLOOM, partition.n_parts > 1. The
+ * context stays usable after either. A device list cannot be checked by the host: an entry >= width * height gets no ray and no store and counts
+ * nothing (its aux record is left as it is). */
+#define AIC_PIXELS_DEVICE 1u   /* `pixels`, `out` and `aux` are device pointers on the context's device */
+#define AIC_PIXELS_IN_PLACE 2u /* `out` is a whole frame of frame->width x frame->height; result i goes to pixel pixels[i], every other texel is left
+                                * as it is. Needs AIC_PIXELS_DEVICE */
+int aic_trace_pixels(aic_ctx *ctx, const aic_frame_desc *frame, uint32_t n, const uint32_t *pixels, uint32_t mode, void *out, aic_pixel_aux *aux,
+                     aic_frame_info *info);
+/* replaces: PixelPicker::new (raytrace_to_texture.rs:838-908), the order in which do_some_tracing takes a frame's pixels: centre first, dithered, the
+ * central pixels interleaved with the rest. Host-only, like aic_light_chart. order (may be NULL) = [width * height]: the pixel indices y * width + x
+ * stably sorted by (int64)(max(|x - cx|, |y - cy|) + ((x ^ y) % 4) * 2) evaluated in f64, c = size / 2 - 0.5. *central = min(60000, count / 4);
+ * *cycle_length = 2 * max(central, count - central) (either may be NULL). The pick sequence, k = 0, 1, 2, ...: pick k is order[(k / 2) % central] for
+ * even k and order[central + (k / 2) % (count - central)] for odd k; with central = 0 every pick k is order[k % count] (itertools::Interleave with one
+ * side empty). The first cycle_length picks cover every pixel. An empty viewport gives AIC_OK, zeros, and nothing written. */
+int aic_pixel_order(uint32_t width, uint32_t height, uint32_t *order, uint32_t *central, uint64_t *cycle_length);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

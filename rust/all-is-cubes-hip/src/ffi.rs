@@ -27,6 +27,8 @@ pub const AIC_FRAME_BLOOM: u32 = 64;
 pub const AIC_FRAME_OUT_SPLIT: u32 = 512;
 pub const AIC_RAYS_NO_SKY: u32 = 128;
 pub const AIC_RAYS_DEVICE: u32 = 256;
+pub const AIC_PIXELS_DEVICE: u32 = 1;
+pub const AIC_PIXELS_IN_PLACE: u32 = 2;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
 pub const AIC_MULTI_MAX_IN_FLIGHT: u32 = 8;
 pub const AIC_TUNE_QUEUES_SHIFT: u32 = 0;
@@ -219,6 +221,8 @@ unsafe extern "C" {
     pub fn aic_assemble_strips_async(ctx: *mut aic_ctx, gathered_device: *const c_void, out_device: *mut c_void, width: u32, height: u32, strip_rows: u32, n_parts: u32) -> c_int;
     pub fn aic_assemble_strips_on(ctx: *mut aic_ctx, gathered_device: *const c_void, out_device: *mut c_void, width: u32, height: u32, strip_rows: u32, n_parts: u32, hip_stream: *mut c_void) -> c_int;
     pub fn aic_trace_rays(ctx: *mut aic_ctx, layer: c_int, n: u32, rays: *const f64, flags: u32, exposure: f32, out: *mut c_void, aux: *mut aic_pixel_aux, info: *mut aic_frame_info) -> c_int;
+    pub fn aic_trace_pixels(ctx: *mut aic_ctx, frame: *const aic_frame_desc, n: u32, pixels: *const u32, mode: u32, out: *mut c_void, aux: *mut aic_pixel_aux, info: *mut aic_frame_info) -> c_int;
+    pub fn aic_pixel_order(width: u32, height: u32, order: *mut u32, central: *mut u32, cycle_length: *mut u64) -> c_int;
     pub fn aic_read_aux(ctx: *mut aic_ctx, out: *mut aic_pixel_aux, n_records: u64) -> c_int;
     pub fn aic_synchronize(ctx: *mut aic_ctx) -> c_int;
     pub fn aic_stream(ctx: *mut aic_ctx) -> *mut c_void;

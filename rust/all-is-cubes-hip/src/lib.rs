@@ -620,6 +620,41 @@ impl HipRtRenderer {
         Ok((colors, hits))
     }
 
+    /// One round of `raytrace_to_texture`'s `do_some_tracing` (raytrace_to_texture.rs:591-751): the listed pixels (`y * width + x`) of the frame
+    /// `draw_split` renders, each traced exactly as there (`RtScene::trace_patch` on the pixel's own rectangle). Returns the two texels per pixel in list
+    /// order -- the f16 colour bits and the signed depth -- for the caller to write at those pixels of its resident textures. A pixel may be listed more
+    /// than once, as [`PixelPicker`]'s inner cycle does.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures; a listed pixel outside the viewport is an error.
+    ///
+    /// # Panics
+    /// On a multi-device renderer, or more than 2048 x 65535 pixels.
+    pub fn trace_pixels(&mut self, pixels: &[u32]) -> Result<(Vec<[u16; 4]>, Vec<f32>), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("trace_pixels needs a single-device renderer") };
+        let (_, mut frame) = self.frame_desc();
+        frame.flags = ffi::AIC_FRAME_OUT_SPLIT;
+        let camera = &self.cameras.cameras().world;
+        let depth_scale = -(camera.view_distance().into_inner() - camera.near_plane_distance().into_inner());
+        let depth_bias = -camera.near_plane_distance().into_inner();
+        let p = camera.projection_matrix();
+        let zw = [depth_scale * p.m33, depth_bias * p.m33 + p.m43, depth_scale * p.m34, depth_bias * p.m34 + p.m44];
+        // SAFETY: the context is live; `zw` holds the four coefficients the call copies
+        self.device.check(unsafe { ffi::aic_set_depth_transform(ctx.as_ptr(), zw.as_ptr()) })?;
+        let n = pixels.len();
+        let n32 = u32::try_from(n).expect("more than u32::MAX pixels");
+        // one allocation of u64 words, as in draw_split: n of colour, then n / 2 rounded up of depth
+        let mut planes = vec![0u64; n + n.div_ceil(2)];
+        let mut info = ffi::aic_frame_info::default();
+        // SAFETY: the context is live; `pixels` holds n indices, `planes` the 12 bytes per pixel the call writes; the call returns when the batch is done
+        self.device.check(unsafe {
+            ffi::aic_trace_pixels(ctx.as_ptr(), &frame, n32, pixels.as_ptr(), 0, planes.as_mut_ptr().cast(), core::ptr::null_mut(), &mut info)
+        })?;
+        let color = planes[..n].iter().map(|t| [*t as u16, (*t >> 16) as u16, (*t >> 32) as u16, (*t >> 48) as u16]).collect();
+        let depth = (0..n).map(|i| f32::from_bits((planes[n + i / 2] >> (32 * (i % 2))) as u32)).collect();
+        Ok((color, depth))
+    }
+
     fn light_params(maximum_distance: u8, fast: bool, epsilon: u8, n_queue: i32, max_updates: u64) -> ffi::aic_light_params {
         ffi::aic_light_params {
             maximum_distance: i32::from(maximum_distance),
@@ -694,6 +729,67 @@ impl HipRtRenderer {
         let mut info = ffi::aic_light_info::default();
         self.device.evaluate_light_wait(ffi::AIC_LAYER_WORLD, &mut info)?;
         Ok((info.updates, info.queue_left))
+    }
+}
+
+/// `PixelPicker` of raytrace_to_texture.rs:838-908: the order in which the incremental renderer takes a frame's pixels -- centre first and dithered
+/// (`aic_pixel_order`), the central pixels interleaved with the rest. An iterator over pixel indices `y * width + x` that never ends; after
+/// `cycle_length()` picks every pixel has been picked. Feed `take(rays_per_frame)` of it to [`HipRtRenderer::trace_pixels`].
+#[derive(Clone, Debug)]
+pub struct PixelPicker {
+    size: (u32, u32),
+    order: Box<[u32]>,
+    central: u64,
+    cycle_length: u64,
+    next: u64,
+}
+
+impl PixelPicker {
+    /// # Panics
+    /// If the viewport has more than `u32::MAX` pixels.
+    pub fn new(width: u32, height: u32) -> Self {
+        let mut order = vec![0u32; (width as usize) * (height as usize)].into_boxed_slice();
+        let (mut central, mut cycle_length) = (0u32, 0u64);
+        // SAFETY: `order` holds width * height entries (a null pointer asks for none); the other two are valid out-pointers
+        let rc = unsafe {
+            ffi::aic_pixel_order(width, height, if order.is_empty() { core::ptr::null_mut() } else { order.as_mut_ptr() }, &mut central, &mut cycle_length)
+        };
+        assert_eq!(rc, ffi::AIC_OK, "aic_pixel_order({width}, {height})");
+        Self { size: (width, height), order, central: u64::from(central), cycle_length, next: 0 }
+    }
+
+    /// Starts over with the new size, if it differs (as the reference's `resize`).
+    pub fn resize(&mut self, width: u32, height: u32) {
+        if self.size != (width, height) {
+            *self = Self::new(width, height);
+        }
+    }
+
+    /// After at least this many picks, the entire image has been covered.
+    pub fn cycle_length(&self) -> u64 {
+        self.cycle_length
+    }
+}
+
+impl Iterator for PixelPicker {
+    type Item = u32;
+
+    fn next(&mut self) -> Option<u32> {
+        let count = self.order.len() as u64;
+        if count == 0 {
+            return None;
+        }
+        let (k, half) = (self.next, self.next / 2);
+        self.next += 1;
+        // itertools::Interleave of the two cycles; with no central pixels the inner side is empty and every pick is the outer's
+        let index = if self.central == 0 {
+            k % count
+        } else if k % 2 == 0 {
+            half % self.central
+        } else {
+            self.central + half % (count - self.central)
+        };
+        Some(self.order[index as usize])
     }
 }
 
