@@ -27,6 +27,8 @@ RAYS_NO_SKY, RAYS_DEVICE = 128, 256  # aic_trace_rays only: include_sky = false;
 MAX_RAYS = 2048 * 65535  # rays in one aic_trace_rays call
 PIXELS_DEVICE, PIXELS_IN_PLACE = 1, 2  # aic_trace_pixels' mode: pixels / out / aux are device pointers; out is a whole frame written at the listed pixels
 MAX_PIXELS = 2048 * 65535  # pixels in one aic_trace_pixels call
+REPROJECT_KEEP_SPLATS = 1  # AIC_REPROJECT_KEEP_SPLATS: reprojected texels stay at full resolution; only the gaps take the fill
+REPROJECT_MAX_LEVELS = 12  # AIC_REPROJECT_MAX_LEVELS
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
@@ -68,7 +70,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
@@ -131,6 +133,19 @@ def pixel_order(width: int, height: int):
     return order, int(central.value), int(cycle.value)
 
 
+def reproject_geometry(width: int, height: int):
+    """The gap-fill chain of aic_reproject_split for a width x height frame (aic_reproject_geometry): (levels L, (T0x, T0y), bytes of context scratch the
+    call allocates). Host-only: needs no device or context."""
+    lib = load()
+    lib.aic_reproject_geometry.restype = C.c_int
+    lib.aic_reproject_geometry.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    levels, t0, scratch = C.c_uint32(0), (C.c_uint32 * 2)(0, 0), C.c_uint64(0)
+    rc = lib.aic_reproject_geometry(int(width), int(height), C.byref(levels), t0, C.byref(scratch))
+    if rc != 0:
+        raise AicError(rc, f"aic_reproject_geometry({width}, {height})")
+    return int(levels.value), (int(t0[0]), int(t0[1])), int(scratch.value)
+
+
 class SpaceDesc(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("size", C.c_int32 * 3), ("block_index", C.c_void_p), ("light", C.c_void_p),
                 ("n_blocks", C.c_uint32), ("blocks", C.c_void_p), ("voxels", C.c_void_p), ("n_voxels", C.c_uint64),
@@ -162,6 +177,16 @@ class FrameInfo(C.Structure):
     _fields_ = [("cubes_traced", C.c_uint64), ("n_outer", C.c_uint64), ("n_inner", C.c_uint64), ("n_hits", C.c_uint64),
                 ("n_light", C.c_uint64), ("kernel_ms", C.c_float), ("total_ms", C.c_float), ("rows_rendered", C.c_uint32),
                 ("flaws", C.c_uint32), ("variant", C.c_uint32), ("tile_queues", C.c_uint32)]
+
+
+class ReprojectDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("reprojection", C.c_float * 16), ("inverse_projection_zw", C.c_float * 4),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ReprojectInfo(C.Structure):
+    _fields_ = [("n_splats", C.c_uint64), ("n_dropped", C.c_uint64), ("n_gaps", C.c_uint64), ("n_unfilled", C.c_uint64),
+                ("kernel_ms", C.c_float), ("levels", C.c_uint32), ("t0", C.c_uint32 * 2)]
 
 
 PIXEL_AUX_DTYPE = np.dtype(
@@ -216,6 +241,7 @@ def load() -> C.CDLL:
         lib.aic_trace_patches.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_trace_rays.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_trace_pixels.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
+        lib.aic_reproject_split.argtypes = [C.c_void_p, C.POINTER(ReprojectDesc), C.c_void_p, C.c_void_p, C.POINTER(ReprojectInfo)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_read_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -563,6 +589,19 @@ class Context:
         info = FrameInfo()
         self._check(self._lib.aic_trace_pixels(self._h, C.byref(frame), int(n), C.c_void_p(pixels_ptr or None), mode, C.c_void_p(out_ptr or None),
                                                C.c_void_p(aux_ptr or None), C.byref(info)))
+        return info
+
+    def reproject_split(self, width: int, height: int, matrix, ipzw, src_ptr: int, dst_ptr: int, flags: int = 0) -> ReprojectInfo:
+        """A resident Split frame drawn into a new camera and gap-filled (aic_reproject_split). `src_ptr` and `dst_ptr` are whole Split frames of
+        width x height in HBM on the context's device (the depth plane at byte offset width * height * 8) that do not overlap; `matrix` = the 16 floats of
+        ReprojectionUniforms.reprojection_matrix, column-major ([c*4+r]; clip_new = M clip_old); `ipzw` = {ipz.z, ipw.z, ipz.w, ipw.w} of the current
+        camera's inverse projection; flags: REPROJECT_KEEP_SPLATS. Returns once dst is written."""
+        d = ReprojectDesc()
+        d.width, d.height, d.flags = int(width), int(height), int(flags)
+        d.reprojection[:] = [float(v) for v in np.asarray(matrix, np.float32).reshape(16)]
+        d.inverse_projection_zw[:] = [float(v) for v in np.asarray(ipzw, np.float32).reshape(4)]
+        info = ReprojectInfo()
+        self._check(self._lib.aic_reproject_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(dst_ptr or None), C.byref(info)))
         return info
 
     def render_submit(self, frame: FrameDesc, device_ptr: int, slot: int) -> None:

@@ -28,6 +28,7 @@
 #include "aic_ctx.h"
 #include "aic_device.h"
 #include "aic_launch.h"
+#include "aic_reproject.h"
 
 using namespace aic;
 
@@ -359,7 +360,7 @@ void aic_destroy(aic_ctx *c) {
         if (i > 0 && fs.stream) (void)hipStreamDestroy(fs.stream);
     }
     for (auto &l : c->layers) l.release();
-    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release();
+    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release();
     if (c->dump) std::fclose(c->dump);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -918,6 +919,63 @@ int aic_probe_bloom(aic_ctx *c, uint32_t width, uint32_t height, const float *co
     if (out_mip0) HIP_TRY(c, hipMemcpyAsync(out_mip0, sb.bloom_mips.p, (size_t)geom.mw[0] * geom.mh[0] * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (mip0_size) { mip0_size[0] = geom.mw[0]; mip0_size[1] = geom.mh[0]; }
+    return AIC_OK;
+}
+
+int aic_reproject_geometry(uint32_t width, uint32_t height, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes) {
+    if (width > 65535u || height > 65535u) return AIC_ERR_INVALID;
+    const ReprojectGeom g = reproject_geometry(width, height);
+    if (levels) *levels = g.levels;
+    if (t0) { t0[0] = g.mw[0]; t0[1] = g.mh[0]; }
+    if (scratch_bytes) *scratch_bytes = g.scratch_bytes();
+    return AIC_OK;
+}
+
+int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src, void *dst, aic_reproject_info *info) {
+    if (!c || !d || !src || !dst) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (d->width > 65535u || d->height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: frame dimensions above 65535 are not supported");
+    if (d->flags & ~AIC_REPROJECT_KEEP_SPLATS) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: unknown flag bits");
+    if (((uintptr_t)src & 7u) || ((uintptr_t)dst & 7u)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a Split frame starts at an 8-byte boundary");
+    for (float v : d->reprojection)
+        if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a component of the reprojection matrix is not finite");
+    for (float v : d->inverse_projection_zw)
+        if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a component of inverse_projection_zw is not finite");
+    const ReprojectGeom g = reproject_geometry(d->width, d->height);
+    const size_t npix = g.npix(), frame_bytes = npix * 12;
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    if (s0 == d0 || (s0 < d0 + frame_bytes && d0 < s0 + frame_bytes)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: src and dst overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (!npix) return AIC_OK;
+    hipError_t e = c->reproject_scratch.ensure(g.scratch_bytes());
+    if (e != hipSuccess) return hip_fail(c, "alloc reprojection scratch", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    ReprojectParams rp;
+    rp.src_color = (const uint2 *)src;
+    rp.src_depth = (const float *)((const unsigned char *)src + npix * 8);
+    rp.dst_color = (uint2 *)dst;
+    rp.dst_depth = (float *)((unsigned char *)dst + npix * 8);
+    rp.scratch = c->reproject_scratch.p;
+    std::memcpy(rp.m, d->reprojection, sizeof(rp.m));
+    std::memcpy(rp.ipzw, d->inverse_projection_zw, sizeof(rp.ipzw));
+    rp.keep_splats = (d->flags & AIC_REPROJECT_KEEP_SPLATS) ? 1u : 0u;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_reproject(g, rp, fs.stream)) != hipSuccess) return hip_fail(c, "launch reprojection", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    ReprojectCounts counts;
+    HIP_TRY(c, hipMemcpyAsync(&counts, reproject_counts(g, c->reproject_scratch.p), sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    if (info) {
+        info->n_splats = counts.n_splats;
+        info->n_dropped = counts.n_dropped;
+        info->n_gaps = counts.n_gaps;
+        info->n_unfilled = counts.n_unfilled;
+        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+        info->levels = g.levels;
+        info->t0[0] = g.mw[0];
+        info->t0[1] = g.mh[0];
+    }
     return AIC_OK;
 }
 

@@ -59,3 +59,9 @@
 #ifndef AIC_XCHG_PARK_MIN
 #define AIC_XCHG_PARK_MIN 8  // an exchange that only parks (nothing to take) is made for at least this many lanes
 #endif
+
+// ---- the reprojection post-process (aic_reproject.hip). Unlike everything above this one is part of what is computed (decision 3), and
+// tests/reproject_ref.py carries the same value
+#ifndef AIC_REPROJECT_RATIO_CAP
+#define AIC_REPROJECT_RATIO_CAP 8.0f  // the largest sprite scale: a sample just in front of the new camera covers a disc of at most 9.2 pixels, not the screen
+#endif

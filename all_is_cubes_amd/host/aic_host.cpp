@@ -246,6 +246,20 @@ std::array<double, 4> Camera::depth_transform_zw() const {  // raytrace_to_textu
     const Mat4 &p = projection_;
     return {depth_scale * MM(p, 3, 3), depth_bias * MM(p, 3, 3) + MM(p, 4, 3), depth_scale * MM(p, 3, 4), depth_bias * MM(p, 3, 4) + MM(p, 4, 4)};
 }
+std::array<float, 16> Camera::reprojection_matrix(const Camera &traced_with, const Camera &current) {
+    Mat4 old_inverse;
+    Mat4 m;
+    if (traced_with.view_matrix().then(traced_with.projection_matrix()).inverse(&old_inverse))
+        m = old_inverse.then(current.view_matrix()).then(current.projection_matrix());
+    std::array<float, 16> out;
+    for (int i = 0; i < 16; i++) out[i] = (float)m.m[i];
+    return out;
+}
+std::array<float, 4> Camera::inverse_projection_zw() const {
+    Mat4 ip;
+    if (!projection_.inverse(&ip)) ip = Mat4();
+    return {(float)MM(ip, 3, 3), (float)MM(ip, 4, 3), (float)MM(ip, 3, 4), (float)MM(ip, 4, 4)};
+}
 Vec3 Camera::project_ndc3_into_world(const Vec3 &ndc) const {
     Vec3 out;
     if (!inverse_projection_view_.transform_point3d(ndc, &out)) {
@@ -625,6 +639,21 @@ Rendering HipRtRenderer::draw_rgba(const std::string &info_text) {  // renderer.
         draw_info_text(r.data.data(), f.width, f.height, black, white, info_text);
     }
     return r;
+}
+
+aic_reproject_info HipRtRenderer::reproject_split(const void *src, void *dst, const Camera &traced_with, uint32_t flags) {
+    const Viewport vp = world_camera_.viewport();
+    aic_reproject_desc d{};
+    d.width = vp.framebuffer_width;
+    d.height = vp.framebuffer_height;
+    const std::array<float, 16> m = Camera::reprojection_matrix(traced_with, world_camera_);
+    const std::array<float, 4> zw = world_camera_.inverse_projection_zw();
+    std::memcpy(d.reprojection, m.data(), sizeof(d.reprojection));
+    std::memcpy(d.inverse_projection_zw, zw.data(), sizeof(d.inverse_projection_zw));
+    d.flags = flags;
+    aic_reproject_info info;
+    check(aic_reproject_split(ctx_, &d, src, dst, &info), "aic_reproject_split");
+    return info;
 }
 
 SplitRendering HipRtRenderer::draw_split() {

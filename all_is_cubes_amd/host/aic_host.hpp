@@ -142,6 +142,14 @@ class Camera {
     std::array<double, 4> depth_transform_zw() const;
     Mat4 view_matrix() const { return world_to_eye_; }
     Mat4 inverse_projection_view() const { return inverse_projection_view_; }
+    // ReprojectionUniforms.reprojection_matrix from the camera an image was traced with to the camera it is shown in (raytrace_to_texture.rs:446-453):
+    // (view_old . proj_old)^-1 . view_new . proj_new in f64 and euclid's row-vector order, converted to f32 as camera::convert_matrix lays it out --
+    // column-major for WGSL's column vectors, [c*4+r], which is this Mat4's own element order. The identity where the old product is singular (the reference
+    // unwraps there).
+    static std::array<float, 16> reprojection_matrix(const Camera &traced_with, const Camera &current);
+    // {ipz.z, ipw.z, ipz.w, ipw.w} of the inverse projection (rt-copy.wgsl:210-223): what linearize_depth_value reads; the identity's when the projection
+    // is singular (raytrace_to_texture.rs:460-465)
+    std::array<float, 4> inverse_projection_zw() const;
     Vec3 view_position() const { return view_position_; }
     Ray project_ndc_into_world(double ndc_x, double ndc_y) const;
     Vec3 project_ndc3_into_world(const Vec3 &ndc) const;
@@ -393,6 +401,13 @@ class HipRtRenderer : public HeadlessRenderer {
     };
     PixelResults trace_pixels(const std::vector<uint32_t> &pixels);
     ImageInfo trace_pixels_into(void *device_frame, const uint32_t *device_pixels, uint32_t n);
+    // raytrace_to_texture's prepare_frame when the camera has moved (raytrace_to_texture.rs:433-540; aic_reproject_split): the resident Split frame `src`,
+    // traced with the camera `traced_with`, drawn into the current world camera as depth-tested point sprites and gap-filled, into `dst` -- again a
+    // resident Split frame, which trace_pixels_into refines. Both are device memory on the renderer's device, of the current viewport's size, and do
+    // not overlap. `flags`: AIC_REPROJECT_*.
+    aic_reproject_info reproject_split(const void *src, void *dst, const Camera &traced_with, uint32_t flags = 0);
+    // the world camera of the last update(): what to keep beside a resident frame as its `traced_with`
+    const Camera &world_camera() const { return world_camera_; }
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)
     ImageInfo draw_rows_to_device(void *device_out, uint32_t strip_rows, uint32_t n_parts, uint32_t part, bool counters = false,
                                   bool no_feedback = false);

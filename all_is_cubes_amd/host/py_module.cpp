@@ -99,6 +99,8 @@ PYBIND11_MODULE(_host, m) {
         .def("depth_transform_zw", &Camera::depth_transform_zw)
         .def("view_matrix", [](const Camera &c) { return mat(c.view_matrix()); })
         .def("inverse_projection_view", [](const Camera &c) { return mat(c.inverse_projection_view()); })
+        .def_static("reprojection_matrix", &Camera::reprojection_matrix, py::arg("traced_with"), py::arg("current"))
+        .def("inverse_projection_zw", &Camera::inverse_projection_zw)
         .def("view_position", [](const Camera &c) { return a3(c.view_position()); })
         .def("project_ndc_into_world", [](const Camera &c, double x, double y) { Ray r = c.project_ndc_into_world(x, y); return py::make_tuple(a3(r.origin), a3(r.direction)); })
         .def("project_ndc3_into_world", [](const Camera &c, const std::array<double, 3> &p) { return a3(c.project_ndc3_into_world(v3(p))); })
@@ -286,6 +288,16 @@ PYBIND11_MODULE(_host, m) {
             py::gil_scoped_release rel;
             return r.trace_pixels_into(reinterpret_cast<void *>(frame_ptr), reinterpret_cast<const uint32_t *>(pixels_ptr), n);
         }, py::arg("device_ptr"), py::arg("pixels_ptr"), py::arg("n"))
+        .def("reproject_split", [](HipRtRenderer &r, uintptr_t src_ptr, uintptr_t dst_ptr, const Camera &traced_with, uint32_t flags) {
+            // -> dict(n_splats, n_dropped, n_gaps, n_unfilled, kernel_ms, levels, t0)
+            aic_reproject_info i;
+            { py::gil_scoped_release rel; i = r.reproject_split(reinterpret_cast<const void *>(src_ptr), reinterpret_cast<void *>(dst_ptr), traced_with, flags); }
+            py::dict d;
+            d["n_splats"] = i.n_splats; d["n_dropped"] = i.n_dropped; d["n_gaps"] = i.n_gaps; d["n_unfilled"] = i.n_unfilled;
+            d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]);
+            return d;
+        }, py::arg("src_ptr"), py::arg("dst_ptr"), py::arg("traced_with"), py::arg("flags") = 0u)
+        .def("world_camera", [](const HipRtRenderer &r) { return Camera(r.world_camera()); })
         .def("set_world_camera_override", [](HipRtRenderer &r, py::object inv, float exposure) {
             if (inv.is_none()) { r.set_world_camera_override(nullptr, 1.0f); return; }
             const auto m = inv.cast<std::array<double, 16>>();

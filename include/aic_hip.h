@@ -356,6 +356,49 @@ int aic_trace_pixels(aic_ctx *ctx, const aic_frame_desc *frame, uint32_t n, cons
  * even k and order[central + (k / 2) % (count - central)] for odd k; with central = 0 every pick k is order[k % count] (itertools::Interleave with one
  * side empty). The first cycle_length picks cover every pixel. An empty viewport gives AIC_OK, zeros, and nothing written. */
 int aic_pixel_order(uint32_t width, uint32_t height, uint32_t *order, uint32_t *central, uint64_t *cycle_length);
+/* replaces: the reprojection of raytrace_to_texture's resident textures into the current camera when it has moved since they were traced
+ * (all-is-cubes-gpu/src/raytrace_to_texture.rs:433-540 prepare_frame; shaders/rt-copy.wgsl:73-223 rt_reproject_vertex / rt_reproject_fragment, drawn
+ * with a LessEqual depth test, pipelines.rs:633-674), followed by the gap fill (shaders/resampling.wgsl:119-176 through mip_ping with 12 levels and
+ * one repetition, raytrace_to_texture.rs:150-172 and 326-335). Every pixel of `src` becomes one depth-tested point sprite in the new view; the pixels no
+ * sprite covers are filled from a nearest-sampled mip pyramid. DESIGN.md 4.10 restates every operation (all f32, one rounding each, in the order
+ * written there) and the five decisions taken where the reference leaves room; tests/reproject_ref.py is that text in NumPy and the device equals it
+ * bit for bit.
+ * src_device, dst_device: whole Split frames of width x height as aic_render with no partition lays them out: the colour plane [height][width] of
+ * four f16, then the depth plane [height][width] of f32 at byte offset width * height * 8 (sign bit set: a UI pixel). dst is again such a frame -- it
+ * can be handed to aic_trace_pixels in place, or reprojected again: colour = the winning sprite's texel or the fill, alpha -1 where nothing is known
+ * (the marker 0, 0, 0, -1); depth = the winning fragment's depth in the new view (sign bit: the winner was a UI pixel), 1.0 where no sprite landed.
+ * The call blocks and runs on slot 0, like aic_trace_pixels. Scratch belongs to the context, is allocated on first use and again when a frame needs more:
+ * the depth-test keys (8 bytes a pixel), the splat image (8 bytes a pixel), mips 1 .. L-1 of the chain (8 bytes a texel; mip 0 is never stored) and four
+ * counters -- aic_reproject_geometry reports it; 1920 x 1080 (L = 11, T0 = 2048 x 2048): 33 177 600 + 11 184 800 + 32 = 44 362 432 bytes.
+ * Rejected before anything is queued, with AIC_ERR_INVALID and the context still usable: a frame still occupying slot 0; a NULL pointer; src or dst not
+ * at an 8-byte boundary; src and dst ranges that overlap (equal pointers included); width or height above 65535; a matrix or inverse_projection_zw
+ * component that is not finite; unknown flag bits. A width or height of 0 is AIC_OK, writes nothing and zeroes the info. */
+#define AIC_REPROJECT_KEEP_SPLATS 1u  /* a pixel some sprite covered with a valid texel keeps that texel at full resolution; without it (the reference's
+                                       * behaviour) the last upsample returns mip 1 wherever that is valid, which halves the image's resolution */
+#define AIC_REPROJECT_MAX_LEVELS 12u  /* raytrace_to_texture.rs:331 */
+typedef struct aic_reproject_desc {
+    uint32_t width, height;      /* size of BOTH frames (the reference reprojects at the render viewport's own size) */
+    float reprojection[16];      /* ReprojectionUniforms.reprojection_matrix as WGSL holds it: column-major, [c*4+r];
+                                    clip_new = M * clip_old (column vector) */
+    float inverse_projection_zw[4]; /* {ipz.z, ipw.z, ipz.w, ipw.w} of the CURRENT camera's inverse projection
+                                       (rt-copy.wgsl:210-223) */
+    uint32_t flags;              /* AIC_REPROJECT_* */
+    uint32_t reserved;
+} aic_reproject_desc;
+typedef struct aic_reproject_info {
+    uint64_t n_splats;    /* source pixels that drew a sprite */
+    uint64_t n_dropped;   /* source pixels that drew none (behind the camera, degenerate) */
+    uint64_t n_gaps;      /* pixels no sprite covered, before the fill */
+    uint64_t n_unfilled;  /* pixels of the result whose colour is still the invalid marker */
+    float kernel_ms;      /* HIP events around the whole post-process */
+    uint32_t levels;      /* L */
+    uint32_t t0[2];       /* T0 */
+} aic_reproject_info;
+int aic_reproject_split(aic_ctx *ctx, const aic_reproject_desc *desc, const void *src_device, void *dst_device, aic_reproject_info *info);
+/* host-only, like aic_pixel_order: levels L = min(12, ilog2(min(width, height)) + 1), T0 = (width, height) each rounded up to a multiple of 2^L, and
+ * the bytes of context scratch the call needs (any of the three may be NULL). An empty viewport gives zeros. AIC_ERR_INVALID: width or height
+ * above 65535. */
+int aic_reproject_geometry(uint32_t width, uint32_t height, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

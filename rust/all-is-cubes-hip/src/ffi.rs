@@ -29,6 +29,8 @@ pub const AIC_RAYS_NO_SKY: u32 = 128;
 pub const AIC_RAYS_DEVICE: u32 = 256;
 pub const AIC_PIXELS_DEVICE: u32 = 1;
 pub const AIC_PIXELS_IN_PLACE: u32 = 2;
+pub const AIC_REPROJECT_KEEP_SPLATS: u32 = 1;
+pub const AIC_REPROJECT_MAX_LEVELS: u32 = 12;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
 pub const AIC_MULTI_MAX_IN_FLIGHT: u32 = 8;
 pub const AIC_TUNE_QUEUES_SHIFT: u32 = 0;
@@ -136,6 +138,29 @@ pub struct aic_frame_info {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct aic_reproject_desc {
+    pub width: u32,
+    pub height: u32,
+    pub reprojection: [f32; 16],
+    pub inverse_projection_zw: [f32; 4],
+    pub flags: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_reproject_info {
+    pub n_splats: u64,
+    pub n_dropped: u64,
+    pub n_gaps: u64,
+    pub n_unfilled: u64,
+    pub kernel_ms: f32,
+    pub levels: u32,
+    pub t0: [u32; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct aic_pixel_aux {
     pub hit: i32,
     pub cube: [i32; 3],
@@ -222,6 +247,8 @@ unsafe extern "C" {
     pub fn aic_assemble_strips_on(ctx: *mut aic_ctx, gathered_device: *const c_void, out_device: *mut c_void, width: u32, height: u32, strip_rows: u32, n_parts: u32, hip_stream: *mut c_void) -> c_int;
     pub fn aic_trace_rays(ctx: *mut aic_ctx, layer: c_int, n: u32, rays: *const f64, flags: u32, exposure: f32, out: *mut c_void, aux: *mut aic_pixel_aux, info: *mut aic_frame_info) -> c_int;
     pub fn aic_trace_pixels(ctx: *mut aic_ctx, frame: *const aic_frame_desc, n: u32, pixels: *const u32, mode: u32, out: *mut c_void, aux: *mut aic_pixel_aux, info: *mut aic_frame_info) -> c_int;
+    pub fn aic_reproject_split(ctx: *mut aic_ctx, desc: *const aic_reproject_desc, src_device: *const c_void, dst_device: *mut c_void, info: *mut aic_reproject_info) -> c_int;
+    pub fn aic_reproject_geometry(width: u32, height: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
     pub fn aic_pixel_order(width: u32, height: u32, order: *mut u32, central: *mut u32, cycle_length: *mut u64) -> c_int;
     pub fn aic_read_aux(ctx: *mut aic_ctx, out: *mut aic_pixel_aux, n_records: u64) -> c_int;
     pub fn aic_synchronize(ctx: *mut aic_ctx) -> c_int;

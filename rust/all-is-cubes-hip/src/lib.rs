@@ -655,6 +655,54 @@ impl HipRtRenderer {
         Ok((color, depth))
     }
 
+    /// `raytrace_to_texture`'s `prepare_frame` when the camera has moved since its textures were traced (raytrace_to_texture.rs:433-540): the resident
+    /// Split frame at `src_device`, traced with `traced_with`, is drawn into the current world camera as depth-tested point sprites
+    /// (`rt_reproject_vertex` / `rt_reproject_fragment`) and gap-filled (`gap_fill_downsample` / `gap_fill_upsample`), into `dst_device` -- again a
+    /// resident Split frame (colour plane, then the depth plane at byte offset `width * height * 8`), which a round of tracing refines in place.
+    /// `flags`: `ffi::AIC_REPROJECT_*`.
+    ///
+    /// # Safety
+    /// `src_device` and `dst_device` are device memory on the renderer's device, each `width * height * 12` bytes of the current viewport, 8-byte
+    /// aligned and not overlapping.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub unsafe fn reproject_split(
+        &mut self,
+        src_device: *const core::ffi::c_void,
+        dst_device: *mut core::ffi::c_void,
+        traced_with: &Camera,
+        flags: u32,
+    ) -> Result<ffi::aic_reproject_info, RenderError> {
+        let Device::One(ctx) = self.device else { panic!("reproject_split needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let camera = &self.cameras.cameras().world;
+        // raytrace_to_texture.rs:446-453, and camera::convert_matrix: euclid's rows become WGSL's columns
+        let m = traced_with
+            .view_matrix()
+            .then(&traced_with.projection_matrix())
+            .inverse()
+            .unwrap_or_default()
+            .then(&camera.view_matrix())
+            .then(&camera.projection_matrix());
+        let ip = camera.projection_matrix().inverse().unwrap_or_default();
+        let desc = ffi::aic_reproject_desc {
+            width: viewport.framebuffer_size.width,
+            height: viewport.framebuffer_size.height,
+            reprojection: m.to_array().map(|v| v as f32),
+            inverse_projection_zw: [ip.m33 as f32, ip.m43 as f32, ip.m34 as f32, ip.m44 as f32],
+            flags,
+            reserved: 0,
+        };
+        let mut info = ffi::aic_reproject_info::default();
+        // SAFETY: the context is live; the caller vouches for the two frames; the call returns when dst is written
+        self.device.check(unsafe { ffi::aic_reproject_split(ctx.as_ptr(), &desc, src_device, dst_device, &mut info) })?;
+        Ok(info)
+    }
+
     fn light_params(maximum_distance: u8, fast: bool, epsilon: u8, n_queue: i32, max_updates: u64) -> ffi::aic_light_params {
         ffi::aic_light_params {
             maximum_distance: i32::from(maximum_distance),

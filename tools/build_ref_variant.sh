@@ -25,6 +25,10 @@ if [ -f $C/aic_bloom.hip ]; then  # (revisions from the bloom post-process on)
   /opt/rocm/bin/hipcc $F -c $C/aic_bloom.hip -o $D/bloom.o &
   OBJS="$OBJS $D/bloom.o"
 fi
+if [ -f $C/aic_reproject.hip ]; then  # (revisions from the reprojection post-process on)
+  /opt/rocm/bin/hipcc $F -c $C/aic_reproject.hip -o $D/reproject.o &
+  OBJS="$OBJS $D/reproject.o"
+fi
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -Wl,--no-undefined -o variants/libaic_hip_$NAME.so $OBJS
 rm -f $D/*.o
