@@ -29,6 +29,8 @@ PIXELS_DEVICE, PIXELS_IN_PLACE = 1, 2  # aic_trace_pixels' mode: pixels / out / 
 MAX_PIXELS = 2048 * 65535  # pixels in one aic_trace_pixels call
 REPROJECT_KEEP_SPLATS = 1  # AIC_REPROJECT_KEEP_SPLATS: reprojected texels stay at full resolution; only the gaps take the fill
 REPROJECT_MAX_LEVELS = 12  # AIC_REPROJECT_MAX_LEVELS
+PRESENT_OUT_F16 = 1  # AIC_PRESENT_OUT_F16: the presented image as four f16 per pixel, linear, alpha 1.0, instead of sRGB RGBA8
+PRESENT_MAX_PIXELS = 1 << 31  # AIC_PRESENT_MAX_PIXELS
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
@@ -70,7 +72,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_present_split", "aic_present_geometry", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
@@ -146,6 +148,19 @@ def reproject_geometry(width: int, height: int):
     return int(levels.value), (int(t0[0]), int(t0[1])), int(scratch.value)
 
 
+def present_geometry(src_size, out_size):
+    """The bloom chain of aic_present_split for a (width, height) Split frame shown in an (width, height) window (aic_present_geometry): (levels L,
+    (T0x, T0y), bytes of context scratch a call with bloom_intensity > 0 allocates; a call with 0 allocates none). Host-only: needs no device or context."""
+    lib = load()
+    lib.aic_present_geometry.restype = C.c_int
+    lib.aic_present_geometry.argtypes = [C.c_uint32] * 4 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    levels, t0, scratch = C.c_uint32(0), (C.c_uint32 * 2)(0, 0), C.c_uint64(0)
+    rc = lib.aic_present_geometry(int(src_size[0]), int(src_size[1]), int(out_size[0]), int(out_size[1]), C.byref(levels), t0, C.byref(scratch))
+    if rc != 0:
+        raise AicError(rc, f"aic_present_geometry({tuple(src_size)}, {tuple(out_size)})")
+    return int(levels.value), (int(t0[0]), int(t0[1])), int(scratch.value)
+
+
 class SpaceDesc(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("size", C.c_int32 * 3), ("block_index", C.c_void_p), ("light", C.c_void_p),
                 ("n_blocks", C.c_uint32), ("blocks", C.c_void_p), ("voxels", C.c_void_p), ("n_voxels", C.c_uint64),
@@ -187,6 +202,15 @@ class ReprojectDesc(C.Structure):
 class ReprojectInfo(C.Structure):
     _fields_ = [("n_splats", C.c_uint64), ("n_dropped", C.c_uint64), ("n_gaps", C.c_uint64), ("n_unfilled", C.c_uint64),
                 ("kernel_ms", C.c_float), ("levels", C.c_uint32), ("t0", C.c_uint32 * 2)]
+
+
+class PresentDesc(C.Structure):
+    _fields_ = [("src_width", C.c_uint32), ("src_height", C.c_uint32), ("out_width", C.c_uint32), ("out_height", C.c_uint32),
+                ("bloom_intensity", C.c_float), ("tone_mapping", C.c_int32), ("maximum_intensity", C.c_float), ("flags", C.c_uint32)]
+
+
+class PresentInfo(C.Structure):
+    _fields_ = [("kernel_ms", C.c_float), ("levels", C.c_uint32), ("t0", C.c_uint32 * 2), ("bloomed", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 PIXEL_AUX_DTYPE = np.dtype(
@@ -242,6 +266,7 @@ def load() -> C.CDLL:
         lib.aic_trace_rays.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_trace_pixels.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_reproject_split.argtypes = [C.c_void_p, C.POINTER(ReprojectDesc), C.c_void_p, C.c_void_p, C.POINTER(ReprojectInfo)]
+        lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_read_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -603,6 +628,25 @@ class Context:
         info = ReprojectInfo()
         self._check(self._lib.aic_reproject_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(dst_ptr or None), C.byref(info)))
         return info
+
+    def present_split(self, src_ptr: int, src_size, out_size, bloom_intensity: float, tone_mapping: int, maximum_intensity: float, flags: int = 0,
+                      out_device: int | None = None):
+        """A resident Split frame shown in a window (aic_present_split): stretched with a linear ClampToEdge filter from `src_size` = (width, height) to
+        `out_size`, bloomed when `bloom_intensity` > 0, tone-mapped, and encoded as sRGB RGBA8 or, with PRESENT_OUT_F16, as four linear f16 with alpha
+        1.0. `src_ptr` is the whole frame in HBM on the context's device; only its colour plane's three colour halves are used. Returns (image, info):
+        the image is [height][width][4] uint8 (or uint16: f16 bit patterns) read back to the host, or None when `out_device` -- a device pointer the
+        image is written to instead -- is given. Returns once the image is written."""
+        d = PresentDesc()
+        d.src_width, d.src_height = int(src_size[0]), int(src_size[1])
+        d.out_width, d.out_height = int(out_size[0]), int(out_size[1])
+        d.bloom_intensity, d.tone_mapping, d.maximum_intensity, d.flags = float(bloom_intensity), int(tone_mapping), float(maximum_intensity), int(flags)
+        info = PresentInfo()
+        if out_device is not None:
+            self._check(self._lib.aic_present_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(out_device or None), 1, C.byref(info)))
+            return None, info
+        image = np.zeros((d.out_height, d.out_width, 4), np.uint16 if flags & PRESENT_OUT_F16 else np.uint8)
+        self._check(self._lib.aic_present_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), image.ctypes.data_as(C.c_void_p), 0, C.byref(info)))
+        return image, info
 
     def render_submit(self, frame: FrameDesc, device_ptr: int, slot: int) -> None:
         """Queues a frame on `slot` (0..MAX_IN_FLIGHT-1); returns without waiting (aic_render_submit). A FRAME_OUT_SPLIT frame leaves 12 bytes per

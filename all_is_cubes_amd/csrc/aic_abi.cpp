@@ -360,7 +360,7 @@ void aic_destroy(aic_ctx *c) {
         if (i > 0 && fs.stream) (void)hipStreamDestroy(fs.stream);
     }
     for (auto &l : c->layers) l.release();
-    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release();
+    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->present_scratch.release();
     if (c->dump) std::fclose(c->dump);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -975,6 +975,86 @@ int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src
         info->levels = g.levels;
         info->t0[0] = g.mw[0];
         info->t0[1] = g.mh[0];
+    }
+    return AIC_OK;
+}
+
+namespace {
+// the checks aic_present_geometry and aic_present_split share; nullptr: the sizes are fine
+const char *present_sizes_invalid(uint32_t sw, uint32_t sh, uint32_t ow, uint32_t oh) {
+    if (sw > 65535u || sh > 65535u || ow > 65535u || oh > 65535u) return "dimensions above 65535 are not supported";
+    if ((uint64_t)ow * oh > AIC_PRESENT_MAX_PIXELS) return "an output of more than 2^31 pixels is not supported";
+    if (ow && oh && (!sw || !sh)) return "a source of zero size cannot fill an output";
+    return nullptr;
+}
+size_t present_scratch_texels(const BloomGeom &g, uint32_t sw, uint32_t sh) {
+    return (size_t)g.texels + ((sw != g.width || sh != g.height) ? (size_t)g.width * g.height : 0);
+}
+}  // namespace
+
+int aic_present_geometry(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes) {
+    if (present_sizes_invalid(src_w, src_h, out_w, out_h)) return AIC_ERR_INVALID;
+    const bool empty = !out_w || !out_h;
+    const BloomGeom g = bloom_geometry(out_w, out_h);
+    if (levels) *levels = empty ? 0u : g.levels;
+    if (t0) { t0[0] = empty ? 0u : g.mw[0]; t0[1] = empty ? 0u : g.mh[0]; }
+    if (scratch_bytes) *scratch_bytes = empty ? 0u : (uint64_t)present_scratch_texels(g, src_w, src_h) * 8u;
+    return AIC_OK;
+}
+
+int aic_present_split(aic_ctx *c, const aic_present_desc *d, const void *src, void *out, int out_is_device, aic_present_info *info) {
+    if (!c || !d || !src || !out) return fail(c, AIC_ERR_INVALID, "aic_present_split: bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (const char *why = present_sizes_invalid(d->src_width, d->src_height, d->out_width, d->out_height)) {
+        const std::string msg = std::string("aic_present_split: ") + why;
+        return fail(c, AIC_ERR_INVALID, msg.c_str());
+    }
+    if (d->flags & ~AIC_PRESENT_OUT_F16) return fail(c, AIC_ERR_INVALID, "aic_present_split: unknown flag bits");
+    if (!(d->bloom_intensity >= 0.f) || std::isinf(d->bloom_intensity)) return fail(c, AIC_ERR_INVALID, "aic_present_split: bloom_intensity is NaN, negative or infinite");
+    if (!(d->maximum_intensity >= 0.f)) return fail(c, AIC_ERR_INVALID, "aic_present_split: maximum_intensity is NaN or negative");
+    if (d->tone_mapping != 0 && d->tone_mapping != 1) return fail(c, AIC_ERR_INVALID, "aic_present_split: tone_mapping is neither 0 (Clamp) nor 1 (Reinhard)");
+    const bool f16 = (d->flags & AIC_PRESENT_OUT_F16) != 0;
+    const size_t px_bytes = f16 ? 8 : 4;
+    const size_t npix = (size_t)d->out_width * d->out_height, src_bytes = (size_t)d->src_width * d->src_height * 12, out_bytes = npix * px_bytes;
+    if ((uintptr_t)src & 7u) return fail(c, AIC_ERR_INVALID, "aic_present_split: a Split frame starts at an 8-byte boundary");
+    if (out_is_device) {
+        const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
+        if (o0 & (px_bytes - 1)) return fail(c, AIC_ERR_INVALID, "aic_present_split: a device out starts at its element's boundary (4 bytes for RGBA8, 8 for f16)");
+        if (s0 < o0 + out_bytes && o0 < s0 + src_bytes) return fail(c, AIC_ERR_INVALID, "aic_present_split: out overlaps src");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_present_split: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (!npix) return AIC_OK;
+    const BloomGeom g = bloom_geometry(d->out_width, d->out_height);
+    const bool bloomed = d->bloom_intensity > 0.f;
+    hipError_t e;
+    if (bloomed && (e = c->present_scratch.ensure(present_scratch_texels(g, d->src_width, d->src_height))) != hipSuccess) return hip_fail(c, "alloc presentation scratch", e);
+    if (!out_is_device && (e = c->out.ensure(out_bytes / 4)) != hipSuccess) return hip_fail(c, "alloc output", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    PresentParams pp;
+    pp.src = (const uint2 *)src;
+    pp.src_width = d->src_width;
+    pp.src_height = d->src_height;
+    pp.mips = bloomed ? c->present_scratch.p : nullptr;
+    pp.scene = bloomed ? c->present_scratch.p + g.texels : nullptr;
+    pp.out = out_is_device ? out : (void *)c->out.p;
+    pp.intensity = d->bloom_intensity;
+    pp.tone_mapping = d->tone_mapping;
+    pp.maximum_intensity = d->maximum_intensity;
+    pp.srgb_thr = c->srgb_thr.p;
+    pp.out_f16 = f16;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    launch_present(g, pp, fs.stream);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(c, "launch presentation", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    if (!out_is_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, out_bytes, hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    if (info) {
+        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+        info->levels = g.levels;
+        info->t0[0] = g.mw[0];
+        info->t0[1] = g.mh[0];
+        info->bloomed = bloomed ? 1u : 0u;
     }
     return AIC_OK;
 }

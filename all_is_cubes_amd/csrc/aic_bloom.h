@@ -58,5 +58,26 @@ struct BloomParams {
 // Queues the whole post-process on `stream`: the chain (downsample 0 from the ColorBuf, then the stages of mip_ping.rs:301-420) and the composite into
 // p.out. Launches: one per stage, 6 L - 5 of them (31 at L = 6: a 1080p or 4K frame), then the composite.
 void launch_bloom(const BloomGeom &g, const BloomParams &p, hipStream_t stream);
+// Every stage of the chain but the first: with mip 0 of `mips` already queued as downsample 0 of the scene -- from whatever holds it --, queues
+// downsample 1 .. L-1, upsample L-2 .. 0 and the two further repetitions, which read mips only (mip_ping.rs:301-420). 6 L - 6 launches.
+void launch_bloom_stages(const BloomGeom &g, uint2 *mips, hipStream_t stream);
+
+// Presentation of a resident Split frame (aic_present_split): the reference's per-frame draw of its resident textures, raytrace_to_texture.rs:546-568 with
+// shaders/rt-copy.wgsl:41-71 (the linear ClampToEdge stretch into the scene texture, alpha 1), then the same chain and postprocess.wgsl:140-158, 251-276.
+struct PresentParams {
+    const uint2 *src;                 // the frame's colour plane [src_height][src_width] f16 x 4 (its depth plane is not read)
+    uint32_t src_width, src_height;
+    uint2 *scene;                     // S, [geom.height][geom.width]: written and read only when bloomed AND the sizes differ
+    uint2 *mips;                      // [geom.texels]: only when bloomed
+    void *out;                        // [geom.height][geom.width] RGBA8, or four f16 with out_f16
+    float intensity;                  // > 0: bloomed
+    int32_t tone_mapping;
+    float maximum_intensity;
+    const float *srgb_thr;
+    bool out_f16;                     // AIC_PRESENT_OUT_F16
+};
+// Queues the presentation on `stream`; `g` = bloom_geometry of the OUTPUT size, at most 2^31 pixels (the kernels' texel indices are 32-bit). Launches:
+// the composite alone at intensity 0; else the chain's 6 L - 5 stages before it, and the stretch into S before those when the sizes differ.
+void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stream);
 
 }  // namespace aic

@@ -120,6 +120,7 @@ struct aic_ctx {
     DevBuf<unsigned char> staging;  // scratch for scatter updates / probes
     DevBuf<DevOrthoView> ortho_views;  // aic_render_orthographic
     DevBuf<unsigned char> reproject_scratch;  // aic_reproject_split: keys, splat image, mips, counters (aic_reproject.h)
+    DevBuf<uint2> present_scratch;  // aic_present_split with bloom: the chain's mips, then the scene texture of a stretched frame (aic_bloom.h)
     uint64_t aux_records = 0;
     double depth_zw[4] = {1.0, 0.0, 0.0, 1.0};  // aic_set_depth_transform: the Split frames' depth transform
     bool streaming_submit = false;  // set around aic_render_submit: frames meant to overlap are sized for throughput, synchronous ones for latency

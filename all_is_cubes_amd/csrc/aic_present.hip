@@ -1,0 +1,125 @@
+// aic_present.hip -- presentation of a resident Split frame on gfx950 (aic_present_split; aic_bloom.h, DESIGN.md "Presentation"): what the reference's
+// incremental raytracer does with its resident textures every displayed frame.
+//
+//  * The frame's f16 colour texels, saturated at 65504 and with alpha 1, ARE the scene texture S when the window has the frame's size, and the
+//    ClampToEdge bilinear stretch of them, rounded to f16, when it has not (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71).
+//  * The bloom chain runs from that S: downsample 0 through SrcSplit here, every later stage by the chain's own kernels. The composite
+//    x = s (1 - i) + B i needs no division: alpha is 1 everywhere (postprocess.wgsl:140-158).
+//  * S is stored only for a stretched AND bloomed frame (downsample 0 reads each of its texels five times over); otherwise the composite forms it
+//    where it reads it. The bits are the same either way.
+//  * Everything else -- the f16 texel, the sampler, the chain's stages from mip 1 on, the tone map and the encoder -- is the bloom post-process's own
+//    (aic_bloom_device.h, launch_bloom_stages, aic_encode.h). A texel per lane, 256-thread workgroups, one 8-byte load or store per colour texel.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "aic_bloom.h"
+#include "aic_bloom_device.h"
+#include "aic_encode.h"
+
+namespace aic {
+
+namespace {
+
+// A resident Split frame's colour plane as the scene texture reads it (rt_frame_copy_fragment, rt-copy.wgsl:56-71: alpha discarded, 1.0 written):
+// colour saturated at 65504 (a Split frame stores overflow as infinity; the chain's convention is saturation, and inf x 0 weights would make NaN).
+// The alpha half travels in the 8-byte load and is dropped; the depth plane is never addressed.
+struct SrcSplit {
+    const uint2 *__restrict__ p;
+    AIC_DEV float4 at(int x, int y, int w) const {
+        const uint2 v = p[(uint32_t)y * (uint32_t)w + (uint32_t)x];
+        return make_float4(fminf(f16_value(v.x & 0xffffu), 65504.0f), fminf(f16_value(v.x >> 16), 65504.0f), fminf(f16_value(v.y & 0xffffu), 65504.0f), 1.0f);
+    }
+};
+
+// S(x, y) of an ow x oh window stretched from an sw x sh Split frame: the linear ClampToEdge sampler of the frame-copy pipeline at the window pixel's
+// centre, stored as the Rgba16Float scene texture stores it
+AIC_DEV uint2 stretch_texel(const SrcSplit &s, int sw, int sh, int ow, int oh, int x, int y) {
+    const float u = ((float)x + 0.5f) / (float)ow, v = ((float)y + 0.5f) / (float)oh;
+    float4 r = sample<false>(s, sw, sh, u, v);
+    r.w = 1.0f;
+    return pack_texel(r);
+}
+__global__ void __launch_bounds__(256) present_stretch_kernel(const uint2 *__restrict__ src, int sw, int sh, uint2 *__restrict__ out, int ow, int oh) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= (uint32_t)ow * (uint32_t)oh) return;
+    out[t] = stretch_texel(SrcSplit{src}, sw, sh, ow, oh, (int)(t % (uint32_t)ow), (int)(t / (uint32_t)ow));
+}
+// downsample 0 of a presented frame: `scene` is the Split frame itself (window of the frame's size) or the stored S; sw x sh is S's size either way
+__global__ void __launch_bounds__(256) present_down0_kernel(const uint2 *__restrict__ scene, int sw, int sh, uint2 *__restrict__ out, int ow, int oh) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= (uint32_t)(ow * oh)) return;
+    out[t] = downsample_texel(SrcSplit{scene}, sw, sh, ow, oh, (int)(t % (uint32_t)ow), (int)(t / (uint32_t)ow));
+}
+
+// postprocess_fragment (postprocess.wgsl:140-158, 251-276) on an opaque scene: mix(S, B, i), the tone map, then sRGB8 with alpha byte 255 or (F16) the
+// linear colour as four f16 with alpha 1.0. STRETCH: S is formed here from an sw x sh frame; otherwise `src` holds S's texels at the window's size.
+template <bool STRETCH, bool F16>
+__global__ void __launch_bounds__(256) present_composite_kernel(const uint2 *__restrict__ src, int sw, int sh, const uint2 *__restrict__ mip0, int w, int h, int t0x,
+                                                                int t0y, float intensity, int32_t tone_mapping, float m, const float *__restrict__ thr,
+                                                                void *__restrict__ out) {
+    __shared__ float s_thr[F16 ? 1u : kSrgbWindowWords];
+    if (!F16) {
+        srgb_window_to_lds(s_thr, thr, threadIdx.x, 256u);
+        __syncthreads();
+    }
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;
+    const uint32_t pix = t < npix ? t : npix - 1u;  // (every lane of the wave runs srgb8_rgb's ballot; only the real pixels store)
+    const int x = (int)(pix % (uint32_t)w), y = (int)(pix / (uint32_t)w);
+    const SrcSplit s{src};
+    const float4 c = STRETCH ? unpack_texel(stretch_texel(s, sw, sh, w, h, x, y)) : s.at(x, y, w);
+    float r = c.x, g = c.y, bl = c.z;
+    if (mip0) {  // (launch-uniform: bloom_intensity > 0)
+        const float u = ((float)x + 0.5f) / (float)w, v = ((float)y + 0.5f) / (float)h;
+        const float4 B = sample<false>(SrcGlobal{mip0}, t0x, t0y, u, v);
+        const float keep = 1.0f - intensity;
+        r = r * keep + B.x * intensity;
+        g = g * keep + B.y * intensity;
+        bl = bl * keep + B.z * intensity;
+    }
+    if (isfinite(m)) {  // ToneMappingOperator::apply (graphics_options.rs:352-368), as the trace kernels apply it
+        if (tone_mapping == 0) {
+            r = r < 0.f ? 0.f : (r > m ? m : r);
+            g = g < 0.f ? 0.f : (g > m ? m : g);
+            bl = bl < 0.f ? 0.f : (bl > m ? m : bl);
+        } else {
+            const float scale = ps_clamped(1.0f / (1.0f + luminance(r, g, bl) / m));
+            r = ps_mul(r, scale); g = ps_mul(g, scale); bl = ps_mul(bl, scale);
+        }
+    }
+    if (F16) {
+        if (t < npix) ((uint2 *)out)[t] = pack_texel(make_float4(r, g, bl, 1.0f));
+    } else {
+        uint32_t R, G, B;
+        srgb8_rgb(r, g, bl, s_thr, R, G, B);
+        if (t < npix) ((uint32_t *)out)[t] = R | (G << 8) | (B << 16) | 0xff000000u;
+    }
+}
+
+}  // namespace
+
+void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stream) {
+    if (!g.width || !g.height || !g.levels) return;
+    const int w = (int)g.width, h = (int)g.height, sw = (int)p.src_width, sh = (int)p.src_height;
+    const uint32_t blocks = bloom_blocks_of(g.width * g.height);
+    const bool bloomed = p.intensity > 0.0f;
+    bool stretch = sw != w || sh != h;
+    const uint2 *scene = p.src;
+    if (bloomed) {
+        if (stretch) {  // S is read five times over by downsample 0 and once by the composite: store it
+            present_stretch_kernel<<<blocks, 256, 0, stream>>>(p.src, sw, sh, p.scene, w, h);
+            scene = p.scene;
+            stretch = false;
+        }
+        present_down0_kernel<<<bloom_blocks_of(g.mw[0] * g.mh[0]), 256, 0, stream>>>(scene, w, h, p.mips + g.off[0], (int)g.mw[0], (int)g.mh[0]);
+        launch_bloom_stages(g, p.mips, stream);
+    }
+    const uint2 *const mip0 = bloomed ? p.mips + g.off[0] : nullptr;
+    const int cw = stretch ? sw : w, ch = stretch ? sh : h;
+    auto composite = stretch ? (p.out_f16 ? present_composite_kernel<true, true> : present_composite_kernel<true, false>)
+                             : (p.out_f16 ? present_composite_kernel<false, true> : present_composite_kernel<false, false>);
+    composite<<<blocks, 256, 0, stream>>>(scene, cw, ch, mip0, w, h, (int)g.mw[0], (int)g.mh[0], p.intensity, p.tone_mapping, p.maximum_intensity, p.srgb_thr, p.out);
+}
+
+}  // namespace aic

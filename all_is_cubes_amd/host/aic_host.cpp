@@ -656,6 +656,44 @@ aic_reproject_info HipRtRenderer::reproject_split(const void *src, void *dst, co
     return info;
 }
 
+aic_present_desc HipRtRenderer::present_desc(uint32_t out_width, uint32_t out_height, uint32_t flags) const {
+    const Viewport vp = world_camera_.viewport();
+    const GraphicsOptions &o = world_camera_.options();
+    aic_present_desc d{};
+    d.src_width = vp.framebuffer_width;
+    d.src_height = vp.framebuffer_height;
+    d.out_width = out_width;
+    d.out_height = out_height;
+    d.bloom_intensity = o.bloom_intensity;
+    d.tone_mapping = (int32_t)o.tone_mapping;
+    d.maximum_intensity = o.maximum_intensity;
+    d.flags = flags;
+    return d;
+}
+
+Rendering HipRtRenderer::present_split(const void *src_device, uint32_t out_width, uint32_t out_height) {
+    const aic_present_desc d = present_desc(out_width, out_height, 0);
+    Rendering r;
+    r.width = out_width;
+    r.height = out_height;
+    r.data.assign((size_t)out_width * out_height * 4, 0);
+    uint8_t none = 0;  // (an empty window: the library still wants a pointer)
+    aic_present_info pi;
+    check(aic_present_split(ctx_, &d, src_device, r.data.empty() ? &none : r.data.data(), 0, &pi), "aic_present_split");
+    r.info.kernel_ms = pi.kernel_ms;
+    r.info.width = out_width;
+    r.info.height = out_height;
+    r.info.rows_rendered = out_height;
+    return r;
+}
+
+aic_present_info HipRtRenderer::present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags) {
+    const aic_present_desc d = present_desc(out_width, out_height, flags);
+    aic_present_info pi;
+    check(aic_present_split(ctx_, &d, src_device, out_device, 1, &pi), "aic_present_split");
+    return pi;
+}
+
 SplitRendering HipRtRenderer::draw_split() {
     aic_frame_desc f = make_frame();
     f.flags |= AIC_FRAME_OUT_SPLIT;

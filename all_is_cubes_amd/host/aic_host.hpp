@@ -406,6 +406,14 @@ class HipRtRenderer : public HeadlessRenderer {
     // resident Split frame, which trace_pixels_into refines. Both are device memory on the renderer's device, of the current viewport's size, and do
     // not overlap. `flags`: AIC_REPROJECT_*.
     aic_reproject_info reproject_split(const void *src, void *dst, const Camera &traced_with, uint32_t flags = 0);
+    // raytrace_to_texture's per-frame presentation of its resident textures (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71, bloom.rs:41-60,
+    // shaders/postprocess.wgsl:140-158 and 251-276; aic_present_split): the resident Split frame `src_device` -- of raytracer's viewport, i.e. the current
+    // (size-policy-modified) viewport -- stretched with a linear filter to out_width x out_height, bloomed, tone-mapped and encoded, with bloom_intensity,
+    // tone_mapping and maximum_intensity of the renderer's GraphicsOptions. The Rendering is the window's sRGB RGBA8 image (no flaws: nothing is left
+    // out; draw_info_text stays a separate host step, as it is for draw); the device form writes RGBA8 or, with AIC_PRESENT_OUT_F16, four linear f16
+    // per pixel to `out_device`, which must not overlap the frame.
+    Rendering present_split(const void *src_device, uint32_t out_width, uint32_t out_height);
+    aic_present_info present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags = 0);
     // the world camera of the last update(): what to keep beside a resident frame as its `traced_with`
     const Camera &world_camera() const { return world_camera_; }
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)
@@ -457,6 +465,7 @@ class HipRtRenderer : public HeadlessRenderer {
     bool sync_space(int layer, const std::shared_ptr<Space> &space, const GraphicsOptions &options);
     void upload_full(int layer, const Space &space);
     void check(int rc, const char *what);
+    aic_present_desc present_desc(uint32_t out_width, uint32_t out_height, uint32_t flags) const;
     aic_frame_desc make_frame() const;
     std::shared_ptr<StandardCameras> cameras_;
     SizePolicy size_policy_;

@@ -297,6 +297,20 @@ PYBIND11_MODULE(_host, m) {
             d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]);
             return d;
         }, py::arg("src_ptr"), py::arg("dst_ptr"), py::arg("traced_with"), py::arg("flags") = 0u)
+        .def("present_split", [](HipRtRenderer &r, uintptr_t src_ptr, uint32_t out_width, uint32_t out_height, uint32_t flags, uintptr_t out_ptr) -> py::object {
+            // out_ptr = 0: the Rendering (RGBA8; flags must be 0); else the image is written to that device pointer -> dict(kernel_ms, levels, t0, bloomed)
+            if (!out_ptr) {
+                if (flags) throw std::invalid_argument("present_split: a host Rendering is RGBA8; AIC_PRESENT_OUT_F16 needs out_ptr");
+                Rendering out;
+                { py::gil_scoped_release rel; out = r.present_split(reinterpret_cast<const void *>(src_ptr), out_width, out_height); }
+                return py::cast(std::move(out));
+            }
+            aic_present_info i;
+            { py::gil_scoped_release rel; i = r.present_split_to_device(reinterpret_cast<const void *>(src_ptr), reinterpret_cast<void *>(out_ptr), out_width, out_height, flags); }
+            py::dict d;
+            d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]); d["bloomed"] = i.bloomed;
+            return std::move(d);
+        }, py::arg("src_ptr"), py::arg("out_width"), py::arg("out_height"), py::arg("flags") = 0u, py::arg("out_ptr") = (uintptr_t)0)
         .def("world_camera", [](const HipRtRenderer &r) { return Camera(r.world_camera()); })
         .def("set_world_camera_override", [](HipRtRenderer &r, py::object inv, float exposure) {
             if (inv.is_none()) { r.set_world_camera_override(nullptr, 1.0f); return; }

@@ -399,6 +399,54 @@ int aic_reproject_split(aic_ctx *ctx, const aic_reproject_desc *desc, const void
  * the bytes of context scratch the call needs (any of the three may be NULL). An empty viewport gives zeros. AIC_ERR_INVALID: width or height
  * above 65535. */
 int aic_reproject_geometry(uint32_t width, uint32_t height, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes);
+/* replaces: what raytrace_to_texture does with its resident textures every displayed frame: RaytraceToTexture::draw
+ * (all-is-cubes-gpu/src/raytrace_to_texture.rs:546-568) draws rt_frame_copy_vertex / rt_frame_copy_fragment (shaders/rt-copy.wgsl:41-71) into the linear
+ * scene texture -- the pipeline's linear ClampToEdge sampler stretches the frame to the viewport (the reference traces at half the nominal size,
+ * raytracer_size_policy, raytrace_to_texture.rs:985-990), alpha is discarded and 1.0 written --; bloom.rs:41-60 and mip_ping.rs:301-420 run the
+ * dual-filter chain on that texture; postprocess_fragment (shaders/postprocess.wgsl:140-158, 251-276) mixes mix(scene, bloom, bloom_intensity), tone-maps
+ * and converts to the output colour space. DESIGN.md 4.11 restates every operation (all f32, one rounding each, in the order written there) and the
+ * decisions taken; tests/present_ref.py is that text in NumPy.
+ * src_device: a whole Split frame of src_width x src_height in device memory as aic_render with no partition lays it out (AIC_FRAME_OUT_SPLIT). Only the
+ * three colour halves of each texel are used: a colour above 65504 (Split stores overflow as infinity) reads as 65504; source alpha and the whole depth
+ * plane have no influence, so the marker texel (0, 0, 0, -1) of an unfilled reprojection shows black. A NaN colour gives whatever the arithmetic gives.
+ * out: [out_height][out_width] RGBA8 (4 bytes a pixel), or four f16 (8 bytes) with AIC_PRESENT_OUT_F16; as in aic_render a device pointer when
+ * out_is_device != 0, host memory the call reads back into otherwise. The output may equal, exceed or fall below the source in either axis; at equal
+ * size the scene texel is the source texel itself.
+ * The call blocks and runs on slot 0, like aic_reproject_split. Scratch belongs to the context, is allocated on first use, again when a call needs
+ * more, and released in aic_destroy: aic_present_geometry reports it.
+ * Rejected before anything is queued, with AIC_ERR_INVALID and the context still usable: a frame still occupying slot 0; a NULL pointer; src not at an
+ * 8-byte boundary; a device out not at its element's boundary (4 bytes for RGBA8, 8 for f16); a device out overlapping the src_width * src_height * 12
+ * bytes of src; any dimension above 65535; an output of more than AIC_PRESENT_MAX_PIXELS pixels (the kernels' texel indices are 32-bit); src of zero
+ * size with a non-empty output; bloom_intensity NaN, negative or infinite; maximum_intensity NaN or negative; tone_mapping other than 0 or 1; unknown
+ * flag bits. An empty output (out_width or out_height 0) is AIC_OK, writes nothing and zeroes the info. */
+#define AIC_PRESENT_OUT_F16 1u   /* out = [out_height][out_width] of four f16: the mixed, tone-mapped LINEAR colour and alpha 1.0 (the reference's
+                                  * color_space_id 0 on an Rgba16Float surface, postprocess.wgsl:251-276), saturated at 65504; default: sRGB RGBA8 as
+                                  * aic_render writes it, alpha byte 255 */
+#define AIC_PRESENT_MAX_PIXELS 2147483648ull  /* out_width * out_height at most 2^31 */
+typedef struct aic_present_desc {
+    uint32_t src_width, src_height;   /* the resident Split frame (no partition; layout as AIC_FRAME_OUT_SPLIT) */
+    uint32_t out_width, out_height;   /* the window's framebuffer; may equal, exceed or fall below the source (rt-copy.wgsl:41-71) */
+    float bloom_intensity;            /* GraphicsOptions::bloom_intensity (postprocess.wgsl:140-158); 0 skips the chain */
+    int32_t tone_mapping;             /* 0 Clamp, 1 Reinhard (graphics_options.rs:352-368) */
+    float maximum_intensity;          /* may be +inf: no tone mapping */
+    uint32_t flags;                   /* AIC_PRESENT_* */
+} aic_present_desc;
+typedef struct aic_present_info {
+    float kernel_ms;      /* HIP events around the whole post-process */
+    uint32_t levels;      /* L of the bloom chain on the output size (bloom.rs:41-60, mip_ping.rs:460-481) */
+    uint32_t t0[2];       /* T0 */
+    uint32_t bloomed;     /* 1: the chain ran (bloom_intensity > 0) */
+    uint32_t reserved[3];
+} aic_present_info;
+int aic_present_split(aic_ctx *ctx, const aic_present_desc *desc, const void *src_device, void *out, int out_is_device, aic_present_info *info);
+/* host-only, like aic_reproject_geometry: levels L and T0 of the bloom chain on the OUTPUT size (mip_ping.rs:460-481 on bloom.rs:50-53's half-size
+ * request: R = ceil(out / 2), L = min(6, ilog2(min(R)) + 1), T0 = R rounded up to a multiple of 2^L), and the bytes of context scratch a call with
+ * bloom_intensity > 0 allocates: the chain's mips (8 bytes a texel) and, when the output size differs from the source's, the scene texture (8 bytes an
+ * output pixel); 1920 x 1080 from 1920 x 1080: 5 896 800; from 960 x 540: 22 485 600. bloom_intensity is known only at call time: a call with 0 needs and
+ * allocates none of it. Not counted: the staging of a host-target call, which is the context's output buffer that aic_render uses. Any of the three may
+ * be NULL. An empty output gives zeros. AIC_ERR_INVALID: a dimension above 65535, more than AIC_PRESENT_MAX_PIXELS output pixels, src of zero size
+ * with a non-empty output. */
+int aic_present_geometry(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

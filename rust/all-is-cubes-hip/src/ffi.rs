@@ -31,6 +31,8 @@ pub const AIC_PIXELS_DEVICE: u32 = 1;
 pub const AIC_PIXELS_IN_PLACE: u32 = 2;
 pub const AIC_REPROJECT_KEEP_SPLATS: u32 = 1;
 pub const AIC_REPROJECT_MAX_LEVELS: u32 = 12;
+pub const AIC_PRESENT_OUT_F16: u32 = 1;
+pub const AIC_PRESENT_MAX_PIXELS: u64 = 2147483648;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
 pub const AIC_MULTI_MAX_IN_FLIGHT: u32 = 8;
 pub const AIC_TUNE_QUEUES_SHIFT: u32 = 0;
@@ -161,6 +163,29 @@ pub struct aic_reproject_info {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct aic_present_desc {
+    pub src_width: u32,
+    pub src_height: u32,
+    pub out_width: u32,
+    pub out_height: u32,
+    pub bloom_intensity: f32,
+    pub tone_mapping: i32,
+    pub maximum_intensity: f32,
+    pub flags: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_present_info {
+    pub kernel_ms: f32,
+    pub levels: u32,
+    pub t0: [u32; 2],
+    pub bloomed: u32,
+    pub reserved: [u32; 3],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct aic_pixel_aux {
     pub hit: i32,
     pub cube: [i32; 3],
@@ -249,6 +274,8 @@ unsafe extern "C" {
     pub fn aic_trace_pixels(ctx: *mut aic_ctx, frame: *const aic_frame_desc, n: u32, pixels: *const u32, mode: u32, out: *mut c_void, aux: *mut aic_pixel_aux, info: *mut aic_frame_info) -> c_int;
     pub fn aic_reproject_split(ctx: *mut aic_ctx, desc: *const aic_reproject_desc, src_device: *const c_void, dst_device: *mut c_void, info: *mut aic_reproject_info) -> c_int;
     pub fn aic_reproject_geometry(width: u32, height: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
+    pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;
+    pub fn aic_present_geometry(src_w: u32, src_h: u32, out_w: u32, out_h: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
     pub fn aic_pixel_order(width: u32, height: u32, order: *mut u32, central: *mut u32, cycle_length: *mut u64) -> c_int;
     pub fn aic_read_aux(ctx: *mut aic_ctx, out: *mut aic_pixel_aux, n_records: u64) -> c_int;
     pub fn aic_synchronize(ctx: *mut aic_ctx) -> c_int;

@@ -703,6 +703,46 @@ impl HipRtRenderer {
         Ok(info)
     }
 
+    /// What `raytrace_to_texture` does with its resident textures every displayed frame (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71,
+    /// bloom.rs:41-60, shaders/postprocess.wgsl:140-158 and 251-276): the resident Split frame at `src_device`, of the renderer's own viewport, is
+    /// stretched with a linear filter to `out_size`, bloomed with the world options' `bloom_intensity`, tone-mapped and written to `out_device` as sRGB
+    /// RGBA8 (4 bytes a pixel) or, with `ffi::AIC_PRESENT_OUT_F16`, as four linear f16 (8 bytes a pixel). The info text is not drawn.
+    ///
+    /// # Safety
+    /// `src_device` is a whole Split frame of the current viewport in device memory on the renderer's device, 8-byte aligned; `out_device` is device
+    /// memory there of `out_size.width * out_size.height` elements, aligned to its element, not overlapping the frame.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub unsafe fn present_split(
+        &mut self,
+        src_device: *const core::ffi::c_void,
+        out_device: *mut core::ffi::c_void,
+        out_size: [u32; 2],
+        flags: u32,
+    ) -> Result<ffi::aic_present_info, RenderError> {
+        let Device::One(ctx) = self.device else { panic!("present_split needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let options = options_of(self.cameras.cameras().world.options());
+        let desc = ffi::aic_present_desc {
+            src_width: viewport.framebuffer_size.width,
+            src_height: viewport.framebuffer_size.height,
+            out_width: out_size[0],
+            out_height: out_size[1],
+            bloom_intensity: options.bloom_intensity,
+            tone_mapping: options.tone_mapping,
+            maximum_intensity: options.maximum_intensity,
+            flags,
+        };
+        let mut info = ffi::aic_present_info::default();
+        // SAFETY: the context is live; the caller vouches for the frame and the target; the call returns when the image is written
+        self.device.check(unsafe { ffi::aic_present_split(ctx.as_ptr(), &desc, src_device, out_device, 1, &mut info) })?;
+        Ok(info)
+    }
+
     fn light_params(maximum_distance: u8, fast: bool, epsilon: u8, n_queue: i32, max_updates: u64) -> ffi::aic_light_params {
         ffi::aic_light_params {
             maximum_distance: i32::from(maximum_distance),

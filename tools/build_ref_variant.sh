@@ -25,6 +25,10 @@ if [ -f $C/aic_bloom.hip ]; then  # (revisions from the bloom post-process on)
   /opt/rocm/bin/hipcc $F -c $C/aic_bloom.hip -o $D/bloom.o &
   OBJS="$OBJS $D/bloom.o"
 fi
+if [ -f $C/aic_present.hip ]; then  # (revisions from the presentation post-process on)
+  /opt/rocm/bin/hipcc $F -c $C/aic_present.hip -o $D/present.o &
+  OBJS="$OBJS $D/present.o"
+fi
 if [ -f $C/aic_reproject.hip ]; then  # (revisions from the reprojection post-process on)
   /opt/rocm/bin/hipcc $F -c $C/aic_reproject.hip -o $D/reproject.o &
   OBJS="$OBJS $D/reproject.o"

@@ -30,6 +30,10 @@ for spec in "$@"; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_light.hip -o variants/light_$name.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $flags -x hip -c $C/aic_multi.cpp -o variants/multi_$name.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_bloom.hip -o variants/bloom_$name.o &&
+    if [ -f $C/aic_present.hip ]; then  # (the presentation post-process; an AIC_PATCH tree of an older revision has none)
+      OBJS="$OBJS variants/present_$name.o"
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_present.hip -o variants/present_$name.o
+    fi &&
     if [ -f $C/aic_reproject.hip ]; then  # (the reprojection post-process; an AIC_PATCH tree of an older revision has none)
       OBJS="$OBJS variants/reproject_$name.o"
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_reproject.hip -o variants/reproject_$name.o
