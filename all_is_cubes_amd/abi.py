@@ -72,7 +72,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_present_split", "aic_present_geometry", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
@@ -204,6 +204,16 @@ class ReprojectInfo(C.Structure):
                 ("kernel_ms", C.c_float), ("levels", C.c_uint32), ("t0", C.c_uint32 * 2)]
 
 
+class PickDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n", C.c_uint32), ("max_unknown", C.c_uint32), ("skip_unknown", C.c_uint64),
+                ("cursor", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PickInfo(C.Structure):
+    _fields_ = [("n_unknown", C.c_uint64), ("next_cursor", C.c_uint64), ("n_from_unknown", C.c_uint32), ("n_from_order", C.c_uint32),
+                ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
 class PresentDesc(C.Structure):
     _fields_ = [("src_width", C.c_uint32), ("src_height", C.c_uint32), ("out_width", C.c_uint32), ("out_height", C.c_uint32),
                 ("bloom_intensity", C.c_float), ("tone_mapping", C.c_int32), ("maximum_intensity", C.c_float), ("flags", C.c_uint32)]
@@ -266,6 +276,7 @@ def load() -> C.CDLL:
         lib.aic_trace_rays.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_trace_pixels.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_reproject_split.argtypes = [C.c_void_p, C.POINTER(ReprojectDesc), C.c_void_p, C.c_void_p, C.POINTER(ReprojectInfo)]
+        lib.aic_pick_pixels.argtypes = [C.c_void_p, C.POINTER(PickDesc), C.c_void_p, C.c_void_p, C.POINTER(PickInfo)]
         lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -627,6 +638,21 @@ class Context:
         d.inverse_projection_zw[:] = [float(v) for v in np.asarray(ipzw, np.float32).reshape(4)]
         info = ReprojectInfo()
         self._check(self._lib.aic_reproject_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(dst_ptr or None), C.byref(info)))
+        return info
+
+    def pick_pixels(self, width: int, height: int, n: int, order_ptr: int, out_ptr: int, cursor: int = 0, max_unknown: int = 0, skip_unknown: int = 0,
+                    flags: int = 0) -> PickInfo:
+        """The next `n` pixel indices of a width x height frame written to `out_ptr` ([n] uint32 in HBM on the context's device), ready for
+        trace_pixels_device(..., in_place=True) (aic_pick_pixels). `order_ptr`: pixel_order()'s order resident on the device ([width * height] uint32),
+        or 0: row-major. The list holds first up to `max_unknown` of the pixels the context's last reproject_split of this size knows nothing about
+        (the texels of its splat image with !(alpha > -0.5)), in the order's ranks, past the first `skip_unknown` of them; then the picker's picks
+        `cursor`, `cursor` + 1, ... With max_unknown = 0 it is PixelPicker's sequence and the reprojection is not looked at. Returns once the list is
+        written; the info's next_cursor and n_from_unknown are what the next call's cursor and skip_unknown advance by."""
+        d = PickDesc()
+        d.width, d.height, d.n, d.max_unknown = int(width), int(height), int(n), int(max_unknown)
+        d.skip_unknown, d.cursor, d.flags = int(skip_unknown), int(cursor), int(flags)
+        info = PickInfo()
+        self._check(self._lib.aic_pick_pixels(self._h, C.byref(d), C.c_void_p(order_ptr or None), C.c_void_p(out_ptr or None), C.byref(info)))
         return info
 
     def present_split(self, src_ptr: int, src_size, out_size, bloom_intensity: float, tone_mapping: int, maximum_intensity: float, flags: int = 0,

@@ -28,6 +28,7 @@
 #include "aic_ctx.h"
 #include "aic_device.h"
 #include "aic_launch.h"
+#include "aic_pick.h"
 #include "aic_reproject.h"
 
 using namespace aic;
@@ -360,7 +361,7 @@ void aic_destroy(aic_ctx *c) {
         if (i > 0 && fs.stream) (void)hipStreamDestroy(fs.stream);
     }
     for (auto &l : c->layers) l.release();
-    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->present_scratch.release();
+    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->pick_scratch.release(); c->present_scratch.release();
     if (c->dump) std::fclose(c->dump);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -947,9 +948,12 @@ int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src
     if (s0 == d0 || (s0 < d0 + frame_bytes && d0 < s0 + frame_bytes)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: src and dst overlap");
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a submitted frame still occupies slot 0 (aic_render_wait it first)");
-    if (!npix) return AIC_OK;
+    if (!npix) return AIC_OK;  // (nothing written: the splat image of an earlier call stays what aic_pick_pixels reads)
+    const unsigned char *scratch_before = c->reproject_scratch.p;
     hipError_t e = c->reproject_scratch.ensure(g.scratch_bytes());
     if (e != hipSuccess) return hip_fail(c, "alloc reprojection scratch", e);
+    // a new allocation has lost the splat image aic_pick_pixels reads: if this call then fails, there is none
+    if (c->reproject_scratch.p != scratch_before) c->reproject_valid_w = c->reproject_valid_h = 0u;
     aic_ctx::FrameSlot &fs = c->slots[0];
     ReprojectParams rp;
     rp.src_color = (const uint2 *)src;
@@ -966,6 +970,8 @@ int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src
     ReprojectCounts counts;
     HIP_TRY(c, hipMemcpyAsync(&counts, reproject_counts(g, c->reproject_scratch.p), sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
     HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    c->reproject_valid_w = d->width;
+    c->reproject_valid_h = d->height;
     if (info) {
         info->n_splats = counts.n_splats;
         info->n_dropped = counts.n_dropped;
@@ -976,6 +982,53 @@ int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src
         info->t0[0] = g.mw[0];
         info->t0[1] = g.mh[0];
     }
+    return AIC_OK;
+}
+
+int aic_pick_pixels(aic_ctx *c, const aic_pick_desc *d, const uint32_t *order, uint32_t *pixels_out, aic_pick_info *info) {
+    if (!c || !d || !info) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: bad argument");
+    std::memset(info, 0, sizeof(*info));
+    if (d->width > 65535u || d->height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: frame dimensions above 65535 are not supported");
+    if (d->flags) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: unknown flag bits");
+    if (d->n > 2048u * 65535u) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: more than 2048 x 65535 picks");
+    if (d->n && !pixels_out) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: no list to write the picks to");
+    if (((uintptr_t)pixels_out & 3u) || ((uintptr_t)order & 3u)) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: a list starts at a 4-byte boundary");
+    const uint64_t count = (uint64_t)d->width * d->height;
+    if (d->n && !count) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: an empty frame has no pixel to pick");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (!d->n) return AIC_OK;  // (and so count == 0)
+    if (d->max_unknown && (!c->reproject_scratch.p || c->reproject_valid_w != d->width || c->reproject_valid_h != d->height))
+        return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: max_unknown needs the context's last successful aic_reproject_split to be of this size");
+    hipError_t e;
+    if (d->max_unknown && (e = c->pick_scratch.ensure(pick_scratch_words(count))) != hipSuccess) return hip_fail(c, "alloc pick scratch", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    PickParams pp;
+    pp.R = d->max_unknown ? (const uint2 *)(c->reproject_scratch.p + reproject_geometry(d->width, d->height).keys_bytes()) : nullptr;
+    pp.order = order;
+    pp.out = pixels_out;
+    pp.scratch = d->max_unknown ? c->pick_scratch.p : nullptr;
+    pp.count = (uint32_t)count;  // at most 65535^2
+    pp.n = d->n;
+    pp.max_unknown = d->max_unknown;
+    pp.skip_unknown = d->skip_unknown;
+    pp.cursor = d->cursor;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_pick(pp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    PickRecord rec = {};
+    if (d->max_unknown) {
+        HIP_TRY(c, hipMemcpyAsync(&rec, c->pick_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
+    } else {  // nothing was looked at: the whole list is the picker's
+        rec.n_from_order = d->n;
+        rec.next_cursor = d->cursor + d->n;
+    }
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    info->n_unknown = rec.n_unknown;
+    info->next_cursor = rec.next_cursor;
+    info->n_from_unknown = rec.n_from_unknown;
+    info->n_from_order = rec.n_from_order;
+    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
     return AIC_OK;
 }
 

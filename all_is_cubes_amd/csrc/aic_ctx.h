@@ -120,6 +120,9 @@ struct aic_ctx {
     DevBuf<unsigned char> staging;  // scratch for scatter updates / probes
     DevBuf<DevOrthoView> ortho_views;  // aic_render_orthographic
     DevBuf<unsigned char> reproject_scratch;  // aic_reproject_split: keys, splat image, mips, counters (aic_reproject.h)
+    // the size of the last successful aic_reproject_split: the splat image R it left in reproject_scratch is what aic_pick_pixels reads (0 x 0: none)
+    uint32_t reproject_valid_w = 0, reproject_valid_h = 0;
+    DevBuf<uint32_t> pick_scratch;  // aic_pick_pixels: the record read back, then the scan blocks' counts and offsets (aic_pick.h)
     DevBuf<uint2> present_scratch;  // aic_present_split with bloom: the chain's mips, then the scene texture of a stretched frame (aic_bloom.h)
     uint64_t aux_records = 0;
     double depth_zw[4] = {1.0, 0.0, 0.0, 1.0};  // aic_set_depth_transform: the Split frames' depth transform

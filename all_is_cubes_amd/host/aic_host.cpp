@@ -653,6 +653,28 @@ aic_reproject_info HipRtRenderer::reproject_split(const void *src, void *dst, co
     d.flags = flags;
     aic_reproject_info info;
     check(aic_reproject_split(ctx_, &d, src, dst, &info), "aic_reproject_split");
+    pick_skip_unknown_ = 0;  // the unknown pixels are those of this reprojection now
+    return info;
+}
+
+aic_pick_info HipRtRenderer::pick_pixels(const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n, uint32_t max_unknown) {
+    const Viewport vp = world_camera_.viewport();
+    if (vp.framebuffer_width != pick_width_ || vp.framebuffer_height != pick_height_) {
+        pick_width_ = vp.framebuffer_width;
+        pick_height_ = vp.framebuffer_height;
+        pick_cursor_ = pick_skip_unknown_ = 0;
+    }
+    aic_pick_desc d{};
+    d.width = pick_width_;
+    d.height = pick_height_;
+    d.n = n;
+    d.max_unknown = max_unknown;
+    d.skip_unknown = pick_skip_unknown_;
+    d.cursor = pick_cursor_;
+    aic_pick_info info;
+    check(aic_pick_pixels(ctx_, &d, device_order, device_pixels_out, &info), "aic_pick_pixels");
+    pick_cursor_ = info.next_cursor;
+    pick_skip_unknown_ += info.n_from_unknown;
     return info;
 }
 

@@ -406,6 +406,15 @@ class HipRtRenderer : public HeadlessRenderer {
     // resident Split frame, which trace_pixels_into refines. Both are device memory on the renderer's device, of the current viewport's size, and do
     // not overlap. `flags`: AIC_REPROJECT_*.
     aic_reproject_info reproject_split(const void *src, void *dst, const Camera &traced_with, uint32_t flags = 0);
+    // PixelPicker::take on the device (aic_pick_pixels): the next `n` picks written to `device_pixels_out` ([n] u32 on the renderer's device), ready for
+    // trace_pixels_into. `device_order`: aic_pixel_order's result for the current viewport, resident once ([width * height] u32), or nullptr: row-major.
+    // With max_unknown > 0 the list begins with up to that many of the pixels the last reproject_split knows nothing about, in picker order -- those
+    // not handed out since --, which the reference does not do; with 0 it is the reference's sequence. The renderer keeps the picker's cursor and the
+    // count of unknown pixels handed out: reproject_split sets the latter back to 0, a change of the viewport's size both. Its host PixelPicker class
+    // is a separate object with a cursor of its own.
+    aic_pick_info pick_pixels(const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n, uint32_t max_unknown = 0);
+    uint64_t pick_cursor() const { return pick_cursor_; }
+    uint64_t pick_skip_unknown() const { return pick_skip_unknown_; }
     // raytrace_to_texture's per-frame presentation of its resident textures (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71, bloom.rs:41-60,
     // shaders/postprocess.wgsl:140-158 and 251-276; aic_present_split): the resident Split frame `src_device` -- of raytracer's viewport, i.e. the current
     // (size-policy-modified) viewport -- stretched with a linear filter to out_width x out_height, bloomed, tone-mapped and encoded, with bloom_intensity,
@@ -476,6 +485,8 @@ class HipRtRenderer : public HeadlessRenderer {
     float cam_override_exposure_ = 1.0f;
     bool had_cursor_ = false;
     bool bloom_ = false;  // set_bloom
+    uint64_t pick_cursor_ = 0, pick_skip_unknown_ = 0;  // pick_pixels
+    uint32_t pick_width_ = 0, pick_height_ = 0;         // ... and the viewport they belong to
     // snapshot taken by update(): draw() must not touch the scene objects (headless.rs:33-39)
     Camera world_camera_, ui_camera_;
     float backdrop_[4] = {0, 0, 0, 0};

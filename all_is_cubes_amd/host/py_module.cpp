@@ -297,6 +297,17 @@ PYBIND11_MODULE(_host, m) {
             d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]);
             return d;
         }, py::arg("src_ptr"), py::arg("dst_ptr"), py::arg("traced_with"), py::arg("flags") = 0u)
+        .def("pick_pixels", [](HipRtRenderer &r, uintptr_t order_ptr, uintptr_t out_ptr, uint32_t n, uint32_t max_unknown) {
+            // -> dict(n_unknown, next_cursor, n_from_unknown, n_from_order, kernel_ms)
+            aic_pick_info i;
+            { py::gil_scoped_release rel; i = r.pick_pixels(reinterpret_cast<const uint32_t *>(order_ptr), reinterpret_cast<uint32_t *>(out_ptr), n, max_unknown); }
+            py::dict d;
+            d["n_unknown"] = i.n_unknown; d["next_cursor"] = i.next_cursor; d["n_from_unknown"] = i.n_from_unknown; d["n_from_order"] = i.n_from_order;
+            d["kernel_ms"] = i.kernel_ms;
+            return d;
+        }, py::arg("order_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("max_unknown") = 0u)
+        .def_property_readonly("pick_cursor", &HipRtRenderer::pick_cursor)
+        .def_property_readonly("pick_skip_unknown", &HipRtRenderer::pick_skip_unknown)
         .def("present_split", [](HipRtRenderer &r, uintptr_t src_ptr, uint32_t out_width, uint32_t out_height, uint32_t flags, uintptr_t out_ptr) -> py::object {
             // out_ptr = 0: the Rendering (RGBA8; flags must be 0); else the image is written to that device pointer -> dict(kernel_ms, levels, t0, bloomed)
             if (!out_ptr) {

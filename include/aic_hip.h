@@ -399,6 +399,44 @@ int aic_reproject_split(aic_ctx *ctx, const aic_reproject_desc *desc, const void
  * the bytes of context scratch the call needs (any of the three may be NULL). An empty viewport gives zeros. AIC_ERR_INVALID: width or height
  * above 65535. */
 int aic_reproject_geometry(uint32_t width, uint32_t height, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes);
+/* replaces: PixelPicker::take (all-is-cubes-gpu/src/raytrace_to_texture.rs:838-908) on the device -- the next n pixel indices written into device
+ * memory, ready for aic_trace_pixels(..., AIC_PIXELS_DEVICE | AIC_PIXELS_IN_PLACE) -- and adds what the reference does not have: on request the list
+ * begins with the pixels the context's last reprojection knows nothing about. Opt-in through max_unknown, as AIC_REPROJECT_KEEP_SPLATS is: with
+ * max_unknown = 0 the list is exactly the pick sequence written out under aic_pixel_order. DESIGN.md 4.12; tests/pick_ref.py is that text in NumPy and
+ * the device equals it entry for entry, on every run.
+ * count = width * height. order_device = [count], the result of aic_pixel_order uploaded once by the caller; NULL: row-major, order[r] = r. It is
+ * not checked: an entry >= count is never unknown, and in the picker part it is written as it is (aic_trace_pixels ignores such an entry of a device
+ * list). Unknown set U: the pixels p whose texel of the splat image R that the context's last successful aic_reproject_split left in its scratch has
+ * !(alpha > -0.5), the gap fill's validity test: no sprite covered p, the winning sprite carried the marker texel, or its alpha is NaN. Rank list
+ * u_0, u_1, ...: the pixels order[r], r ascending, that are in U; n_unknown = |U|. g = min(n, max_unknown, max(n_unknown - skip_unknown, 0)).
+ * pixels_out[i] = u_(skip_unknown + i) for i < g; pixels_out[g + j] = pick(cursor + j) for j < n - g, pick k being order[(k / 2) % central] for even
+ * k and order[central + (k / 2) % (count - central)] for odd k, central = min(60000, count / 4); with central = 0, order[k % count]; all 64-bit.
+ * Nothing beyond pixels_out[n) is written; R, the frames and the keys are only read. With max_unknown = 0 R is not looked at and n_unknown is 0.
+ * The call blocks and runs on slot 0, like aic_reproject_split. Scratch of its own (8 bytes per 256 pixels and a 32-byte record) belongs to the
+ * context, is allocated on first use with max_unknown > 0, again when a frame needs more, and released in aic_destroy.
+ * Rejected before anything is queued, with AIC_ERR_INVALID and the context still usable: a NULL desc or info; a NULL pixels_out_device with n > 0;
+ * pixels_out_device or order_device not at a 4-byte boundary; n > 0 with count = 0; width or height above 65535; n above 2048 x 65535
+ * (aic_trace_pixels' limit); non-zero flags; a frame still occupying slot 0; max_unknown > 0 when the context's last successful aic_reproject_split
+ * was not of exactly width x height (one of another size replaces that state; a failed, a rejected or an empty one leaves it as it was). n = 0 is AIC_OK,
+ * writes nothing and zeroes the info. */
+typedef struct aic_pick_desc {
+    uint32_t width, height;  /* the resident frame */
+    uint32_t n;              /* picks to write */
+    uint32_t max_unknown;    /* at most this many of them from the unknown pixels of the last reprojection; 0: none */
+    uint64_t skip_unknown;   /* unknown pixels (in rank order) already handed out since that reprojection */
+    uint64_t cursor;         /* pick index k of the first picker pick */
+    uint32_t flags;          /* none defined: must be 0 */
+    uint32_t reserved;
+} aic_pick_desc;
+typedef struct aic_pick_info {
+    uint64_t n_unknown;      /* unknown pixels of the last reprojection (0 when max_unknown == 0: not looked at) */
+    uint64_t next_cursor;    /* cursor + n_from_order */
+    uint32_t n_from_unknown; /* g */
+    uint32_t n_from_order;   /* n - g */
+    float kernel_ms;         /* HIP events around the launches */
+    uint32_t reserved;
+} aic_pick_info;
+int aic_pick_pixels(aic_ctx *ctx, const aic_pick_desc *desc, const uint32_t *order_device, uint32_t *pixels_out_device, aic_pick_info *info);
 /* replaces: what raytrace_to_texture does with its resident textures every displayed frame: RaytraceToTexture::draw
  * (all-is-cubes-gpu/src/raytrace_to_texture.rs:546-568) draws rt_frame_copy_vertex / rt_frame_copy_fragment (shaders/rt-copy.wgsl:41-71) into the linear
  * scene texture -- the pipeline's linear ClampToEdge sampler stretches the frame to the viewport (the reference traces at half the nominal size,

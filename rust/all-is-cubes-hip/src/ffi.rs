@@ -163,6 +163,30 @@ pub struct aic_reproject_info {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct aic_pick_desc {
+    pub width: u32,
+    pub height: u32,
+    pub n: u32,
+    pub max_unknown: u32,
+    pub skip_unknown: u64,
+    pub cursor: u64,
+    pub flags: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_pick_info {
+    pub n_unknown: u64,
+    pub next_cursor: u64,
+    pub n_from_unknown: u32,
+    pub n_from_order: u32,
+    pub kernel_ms: f32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct aic_present_desc {
     pub src_width: u32,
     pub src_height: u32,
@@ -274,6 +298,7 @@ unsafe extern "C" {
     pub fn aic_trace_pixels(ctx: *mut aic_ctx, frame: *const aic_frame_desc, n: u32, pixels: *const u32, mode: u32, out: *mut c_void, aux: *mut aic_pixel_aux, info: *mut aic_frame_info) -> c_int;
     pub fn aic_reproject_split(ctx: *mut aic_ctx, desc: *const aic_reproject_desc, src_device: *const c_void, dst_device: *mut c_void, info: *mut aic_reproject_info) -> c_int;
     pub fn aic_reproject_geometry(width: u32, height: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
+    pub fn aic_pick_pixels(ctx: *mut aic_ctx, desc: *const aic_pick_desc, order_device: *const u32, pixels_out_device: *mut u32, info: *mut aic_pick_info) -> c_int;
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;
     pub fn aic_present_geometry(src_w: u32, src_h: u32, out_w: u32, out_h: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
     pub fn aic_pixel_order(width: u32, height: u32, order: *mut u32, central: *mut u32, cycle_length: *mut u64) -> c_int;

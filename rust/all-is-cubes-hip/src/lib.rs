@@ -703,6 +703,48 @@ impl HipRtRenderer {
         Ok(info)
     }
 
+    /// `PixelPicker::take` on the device (raytrace_to_texture.rs:838-908): the next `n` pixel indices of the renderer's viewport written to
+    /// `pixels_out_device`, ready for `aic_trace_pixels` with `AIC_PIXELS_DEVICE | AIC_PIXELS_IN_PLACE`. With `max_unknown > 0` the list begins with up
+    /// to that many of the pixels the last [`Self::reproject_split`] knows nothing about, in picker order, skipping the first `skip_unknown` of them
+    /// (those already handed out); the rest is the reference's pick sequence from pick index `cursor`. The caller keeps `cursor` (the info's
+    /// `next_cursor`) and `skip_unknown` (add `n_from_unknown`; zero after a reprojection).
+    ///
+    /// # Safety
+    /// `order_device` is null (row-major) or `width * height` `u32` of device memory on the renderer's device holding `aic_pixel_order`'s result for the
+    /// current viewport; `pixels_out_device` is `n` `u32` of device memory there; both 4-byte aligned.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures; `max_unknown > 0` without a reprojection of the current viewport's size behind it is rejected.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub unsafe fn pick_pixels(
+        &mut self,
+        order_device: *const u32,
+        pixels_out_device: *mut u32,
+        n: u32,
+        max_unknown: u32,
+        skip_unknown: u64,
+        cursor: u64,
+    ) -> Result<ffi::aic_pick_info, RenderError> {
+        let Device::One(ctx) = self.device else { panic!("pick_pixels needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let desc = ffi::aic_pick_desc {
+            width: viewport.framebuffer_size.width,
+            height: viewport.framebuffer_size.height,
+            n,
+            max_unknown,
+            skip_unknown,
+            cursor,
+            flags: 0,
+            reserved: 0,
+        };
+        let mut info = ffi::aic_pick_info::default();
+        // SAFETY: the context is live; the caller vouches for the two lists; the call returns when the list is written
+        self.device.check(unsafe { ffi::aic_pick_pixels(ctx.as_ptr(), &desc, order_device, pixels_out_device, &mut info) })?;
+        Ok(info)
+    }
+
     /// What `raytrace_to_texture` does with its resident textures every displayed frame (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71,
     /// bloom.rs:41-60, shaders/postprocess.wgsl:140-158 and 251-276): the resident Split frame at `src_device`, of the renderer's own viewport, is
     /// stretched with a linear filter to `out_size`, bloomed with the world options' `bloom_intensity`, tone-mapped and written to `out_device` as sRGB

@@ -14,6 +14,7 @@
 #include "aic_bloom.h"
 #include "aic_device.h"
 #include "aic_launch.h"
+#include "aic_pick.h"
 #include "aic_reproject.h"
 #include "record.h"
 
@@ -233,6 +234,7 @@ void launch_tag_cubes(uint16_t *grid, size_t n, const uint32_t *cls, int from_ta
 // (what the scenarios never reach: scene updates, strip assembly, the probes)
 void launch_scatter_cubes(uint16_t *, uint32_t *, const int32_t *, const uint16_t *, const uint32_t *, uint32_t, const int[3], const int[3], const uint32_t *, hipStream_t) { rec("launch_scatter_cubes"); }
 hipError_t launch_reproject(const ReprojectGeom &, const ReprojectParams &, hipStream_t) { rec("launch_reproject"); return hipSuccess; }
+hipError_t launch_pick(const PickParams &, hipStream_t) { rec("launch_pick"); return hipSuccess; }
 void launch_present(const BloomGeom &, const PresentParams &, hipStream_t) { rec("launch_present"); }
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
