@@ -31,6 +31,9 @@ REPROJECT_KEEP_SPLATS = 1  # AIC_REPROJECT_KEEP_SPLATS: reprojected texels stay 
 REPROJECT_MAX_LEVELS = 12  # AIC_REPROJECT_MAX_LEVELS
 PRESENT_OUT_F16 = 1  # AIC_PRESENT_OUT_F16: the presented image as four f16 per pixel, linear, alpha 1.0, instead of sRGB RGBA8
 PRESENT_MAX_PIXELS = 1 << 31  # AIC_PRESENT_MAX_PIXELS
+LINES_DEVICE = 1  # AIC_LINES_DEVICE: the line vertices are a device pointer
+LINES_MAX = 1 << 20  # AIC_LINES_MAX
+CURSOR_MAX_LINES = 28  # AIC_CURSOR_MAX_LINES
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
@@ -72,7 +75,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
@@ -161,6 +164,19 @@ def present_geometry(src_size, out_size):
     return int(levels.value), (int(t0[0]), int(t0[1])), int(scratch.value)
 
 
+def present_lines_scratch(src_size, out_size, n_lines: int) -> int:
+    """Bytes of line scratch an aic_present_split_lines call with `n_lines` host vertices pairs allocates on top of present_geometry's figure
+    (aic_present_lines_scratch). Host-only: needs no device or context."""
+    lib = load()
+    lib.aic_present_lines_scratch.restype = C.c_int
+    lib.aic_present_lines_scratch.argtypes = [C.c_uint32] * 5 + [C.POINTER(C.c_uint64)]
+    scratch = C.c_uint64(0)
+    rc = lib.aic_present_lines_scratch(int(src_size[0]), int(src_size[1]), int(out_size[0]), int(out_size[1]), int(n_lines), C.byref(scratch))
+    if rc != 0:
+        raise AicError(rc, f"aic_present_lines_scratch({tuple(src_size)}, {tuple(out_size)}, {n_lines})")
+    return int(scratch.value)
+
+
 class SpaceDesc(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("size", C.c_int32 * 3), ("block_index", C.c_void_p), ("light", C.c_void_p),
                 ("n_blocks", C.c_uint32), ("blocks", C.c_void_p), ("voxels", C.c_void_p), ("n_voxels", C.c_uint64),
@@ -223,6 +239,41 @@ class PresentInfo(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("levels", C.c_uint32), ("t0", C.c_uint32 * 2), ("bloomed", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class LinesDesc(C.Structure):
+    _fields_ = [("view_projection", C.c_float * 16), ("n_lines", C.c_uint32), ("flags", C.c_uint32), ("vertices", C.c_void_p)]
+
+
+class LinesInfo(C.Structure):
+    _fields_ = [("n_clipped_away", C.c_uint64), ("n_fragments", C.c_uint64), ("n_passed", C.c_uint64), ("n_pixels", C.c_uint64)]
+
+
+class CursorDesc(C.Structure):
+    _fields_ = [("cube", C.c_int32 * 3), ("face_entered", C.c_int32), ("face_selected", C.c_int32), ("point_entered", C.c_double * 3),
+                ("distance_to_point", C.c_double), ("voxel_lo", C.c_int32 * 3), ("voxel_size", C.c_int32 * 3), ("resolution", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+LINE_VERTEX_DTYPE = np.dtype([("position", "<f4", (3,)), ("color", "<f4", (4,))])  # aic_line_vertex: 28 bytes
+
+
+def cursor_wireframe(cube, face_entered: int, face_selected: int, point_entered, distance_to_point: float, voxel_lo=(0, 0, 0), voxel_size=(1, 1, 1),
+                     resolution: int = 1):
+    """The cursor's line list (aic_cursor_wireframe; impl Wireframe for Cursor, cursor.rs:219-278): [2 n] LINE_VERTEX_DTYPE records, n = 12, 16, 24 or
+    28. Faces are Face7 discriminants; voxel_lo / voxel_size / resolution are the hit block's voxels_bounds() and resolution. Host-only."""
+    lib = load()
+    lib.aic_cursor_wireframe.restype = C.c_int
+    lib.aic_cursor_wireframe.argtypes = [C.POINTER(CursorDesc), C.c_void_p, C.POINTER(C.c_uint32)]
+    d = CursorDesc()
+    d.cube[:], d.point_entered[:], d.voxel_lo[:], d.voxel_size[:] = [int(v) for v in cube], [float(v) for v in point_entered], [int(v) for v in voxel_lo], [int(v) for v in voxel_size]
+    d.face_entered, d.face_selected, d.distance_to_point, d.resolution = int(face_entered), int(face_selected), float(distance_to_point), int(resolution)
+    out = np.zeros(2 * CURSOR_MAX_LINES, LINE_VERTEX_DTYPE)
+    n = C.c_uint32(0)
+    rc = lib.aic_cursor_wireframe(C.byref(d), out.ctypes.data_as(C.c_void_p), C.byref(n))
+    if rc != 0:
+        raise AicError(rc, "aic_cursor_wireframe")
+    return out[:2 * n.value].copy()
+
+
 PIXEL_AUX_DTYPE = np.dtype(
     [("hit", "<i4"), ("cube", "<i4", (3,)), ("voxel", "<i4", (3,)), ("resolution", "<i4"), ("face", "<i4"),
      ("block_index", "<i4"), ("cubes_traced", "<u4"), ("layer", "<u4"), ("t_distance", "<f8")],
@@ -278,6 +329,8 @@ def load() -> C.CDLL:
         lib.aic_reproject_split.argtypes = [C.c_void_p, C.POINTER(ReprojectDesc), C.c_void_p, C.c_void_p, C.POINTER(ReprojectInfo)]
         lib.aic_pick_pixels.argtypes = [C.c_void_p, C.POINTER(PickDesc), C.c_void_p, C.c_void_p, C.POINTER(PickInfo)]
         lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
+        lib.aic_present_split_lines.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo),
+                                                C.POINTER(LinesInfo)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_read_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -673,6 +726,35 @@ class Context:
         image = np.zeros((d.out_height, d.out_width, 4), np.uint16 if flags & PRESENT_OUT_F16 else np.uint8)
         self._check(self._lib.aic_present_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), image.ctypes.data_as(C.c_void_p), 0, C.byref(info)))
         return image, info
+
+    def present_split_lines(self, src_ptr: int, src_size, out_size, bloom_intensity: float, tone_mapping: int, maximum_intensity: float, view_projection,
+                            vertices=None, n_lines: int | None = None, flags: int = 0, out_device: int | None = None):
+        """present_split with a line list drawn into the scene before bloom and tone mapping, depth-tested against the frame's depth plane
+        (aic_present_split_lines). `view_projection` = [16] column-major projection x view; `vertices` = [2 n] line vertices on the host (anything
+        np.asarray turns into n x 2 x 7 float32: LINE_VERTEX_DTYPE records, or position + linear RGBA rows), or a device pointer (an int) with
+        `n_lines`; None: no lines. Returns (image or None, info, lines_info) as present_split does."""
+        d = PresentDesc()
+        d.src_width, d.src_height = int(src_size[0]), int(src_size[1])
+        d.out_width, d.out_height = int(out_size[0]), int(out_size[1])
+        d.bloom_intensity, d.tone_mapping, d.maximum_intensity, d.flags = float(bloom_intensity), int(tone_mapping), float(maximum_intensity), int(flags)
+        ld = LinesDesc()
+        ld.view_projection[:] = [float(v) for v in np.asarray(view_projection, np.float32).reshape(16)]
+        keep = None
+        if isinstance(vertices, int):
+            ld.vertices, ld.n_lines, ld.flags = vertices, int(n_lines), LINES_DEVICE
+        elif vertices is not None:
+            keep = np.asarray(vertices)
+            keep = np.ascontiguousarray(keep.view(np.float32) if keep.dtype == LINE_VERTEX_DTYPE else keep, np.float32).reshape(-1, 2, 7)
+            ld.vertices, ld.n_lines = keep.ctypes.data, len(keep) if n_lines is None else int(n_lines)
+        info, lines_info = PresentInfo(), LinesInfo()
+        if out_device is not None:
+            self._check(self._lib.aic_present_split_lines(self._h, C.byref(d), C.byref(ld), C.c_void_p(src_ptr or None), C.c_void_p(out_device or None), 1,
+                                                          C.byref(info), C.byref(lines_info)))
+            return None, info, lines_info
+        image = np.zeros((d.out_height, d.out_width, 4), np.uint16 if flags & PRESENT_OUT_F16 else np.uint8)
+        self._check(self._lib.aic_present_split_lines(self._h, C.byref(d), C.byref(ld), C.c_void_p(src_ptr or None), image.ctypes.data_as(C.c_void_p), 0,
+                                                      C.byref(info), C.byref(lines_info)))
+        return image, info, lines_info
 
     def render_submit(self, frame: FrameDesc, device_ptr: int, slot: int) -> None:
         """Queues a frame on `slot` (0..MAX_IN_FLIGHT-1); returns without waiting (aic_render_submit). A FRAME_OUT_SPLIT frame leaves 12 bytes per

@@ -29,6 +29,7 @@
 #include "aic_device.h"
 #include "aic_launch.h"
 #include "aic_pick.h"
+#include "aic_present_lines.h"
 #include "aic_reproject.h"
 
 using namespace aic;
@@ -260,6 +261,7 @@ aic_ctx *aic_create(int device_id, int *status) {
         c->sw.macro = env_int("AIC_MACRO", 0);
         c->sw.feedback = env_int("AIC_TILE_FEEDBACK", 1) != 0;
         c->sw.wait_whole_stream = env_int("AIC_WAIT_WHOLE_STREAM", 0) != 0;
+        c->sw.lines_clear_keys = env_int("AIC_LINES_CLEAR_KEYS", 0) != 0;
         c->sw.tiles_per_wave = (uint32_t)std::max(0, env_int("AIC_TILES_PER_WAVE", 0));
         if (const char *p = std::getenv("AIC_WAVE_PROF")) c->sw.wave_prof = p;
     }
@@ -361,7 +363,7 @@ void aic_destroy(aic_ctx *c) {
         if (i > 0 && fs.stream) (void)hipStreamDestroy(fs.stream);
     }
     for (auto &l : c->layers) l.release();
-    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->pick_scratch.release(); c->present_scratch.release();
+    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->pick_scratch.release(); c->present_scratch.release(); c->lines_scratch.release();
     if (c->dump) std::fclose(c->dump);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1102,6 +1104,125 @@ int aic_present_split(aic_ctx *c, const aic_present_desc *d, const void *src, vo
     HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
     if (!out_is_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, out_bytes, hipMemcpyDeviceToHost, fs.stream));
     HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    if (info) {
+        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+        info->levels = g.levels;
+        info->t0[0] = g.mw[0];
+        info->t0[1] = g.mh[0];
+        info->bloomed = bloomed ? 1u : 0u;
+    }
+    return AIC_OK;
+}
+
+namespace {
+// aic_present_split's own rejections of its arguments, in its order, for aic_present_split_lines (aic_present_split keeps its code as it stands); 0: none
+int present_args_invalid(aic_ctx *c, const aic_present_desc *d, const void *src, const void *out, int out_is_device, aic_present_info *info, const char *who) {
+    const auto reject = [&](const char *why) { return fail(c, AIC_ERR_INVALID, (std::string(who) + ": " + why).c_str()); };
+    if (!c || !d || !src || !out) return reject("bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (const char *why = present_sizes_invalid(d->src_width, d->src_height, d->out_width, d->out_height)) return reject(why);
+    if (d->flags & ~AIC_PRESENT_OUT_F16) return reject("unknown flag bits");
+    if (!(d->bloom_intensity >= 0.f) || std::isinf(d->bloom_intensity)) return reject("bloom_intensity is NaN, negative or infinite");
+    if (!(d->maximum_intensity >= 0.f)) return reject("maximum_intensity is NaN or negative");
+    if (d->tone_mapping != 0 && d->tone_mapping != 1) return reject("tone_mapping is neither 0 (Clamp) nor 1 (Reinhard)");
+    const size_t px_bytes = (d->flags & AIC_PRESENT_OUT_F16) ? 8 : 4;
+    const size_t src_bytes = (size_t)d->src_width * d->src_height * 12, out_bytes = (size_t)d->out_width * d->out_height * px_bytes;
+    if ((uintptr_t)src & 7u) return reject("a Split frame starts at an 8-byte boundary");
+    if (out_is_device) {
+        const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
+        if (o0 & (px_bytes - 1)) return reject("a device out starts at its element's boundary (4 bytes for RGBA8, 8 for f16)");
+        if (s0 < o0 + out_bytes && o0 < s0 + src_bytes) return reject("out overlaps src");
+    }
+    return 0;
+}
+}  // namespace
+
+int aic_present_lines_scratch(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t n_lines, uint64_t *bytes) {
+    if (present_sizes_invalid(src_w, src_h, out_w, out_h) || n_lines > AIC_LINES_MAX) return AIC_ERR_INVALID;
+    if (bytes) *bytes = (n_lines && out_w && out_h) ? (uint64_t)lines_layout(out_w, out_h, n_lines).bytes : 0u;
+    return AIC_OK;
+}
+
+int aic_present_split_lines(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const void *src, void *out, int out_is_device, aic_present_info *info,
+                            aic_lines_info *lines_info) {
+    if (lines_info) std::memset(lines_info, 0, sizeof(*lines_info));
+    if (c && ld) {  // (the rejections this call adds; a NULL ctx is aic_present_split's to report)
+        if (info) std::memset(info, 0, sizeof(*info));
+        if (ld->flags & ~AIC_LINES_DEVICE) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: unknown line flag bits");
+        if (ld->n_lines > AIC_LINES_MAX) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: more than AIC_LINES_MAX lines");
+        if (ld->n_lines && !ld->vertices) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: no vertices");
+        if (ld->n_lines && (ld->flags & AIC_LINES_DEVICE) && ((uintptr_t)ld->vertices & 3u))
+            return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: device vertices start at a 4-byte boundary");
+        for (float v : ld->view_projection)
+            if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: a component of view_projection is not finite");
+    }
+    if (!c || !ld || !ld->n_lines) return aic_present_split(c, d, src, out, out_is_device, info);
+    if (const int rc = present_args_invalid(c, d, src, out, out_is_device, info, "aic_present_split_lines")) return rc;
+    const bool f16 = (d->flags & AIC_PRESENT_OUT_F16) != 0;
+    const size_t npix = (size_t)d->out_width * d->out_height, out_bytes = npix * (f16 ? 8 : 4);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (!npix) return AIC_OK;
+    const BloomGeom g = bloom_geometry(d->out_width, d->out_height);
+    const bool bloomed = d->bloom_intensity > 0.f, staged = !(ld->flags & AIC_LINES_DEVICE);
+    const LinesLayout lay = lines_layout(d->out_width, d->out_height, staged ? ld->n_lines : 0u);
+    hipError_t e;
+    // (S is the line scratch's: the chain reads it as a frame of the output's size, so the presentation scratch holds the mips alone)
+    if (bloomed && (e = c->present_scratch.ensure(g.texels)) != hipSuccess) return hip_fail(c, "alloc presentation scratch", e);
+    const unsigned char *scratch_before = c->lines_scratch.p;
+    if ((e = c->lines_scratch.ensure(lay.bytes)) != hipSuccess) return hip_fail(c, "alloc line scratch", e);
+    if (c->lines_scratch.p != scratch_before) c->lines_keys_clean = 0;
+    if (!out_is_device && (e = c->out.ensure(out_bytes / 4)) != hipSuccess) return hip_fail(c, "alloc output", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    unsigned char *const ls = c->lines_scratch.p;
+    PresentParams pp;
+    pp.src = (const uint2 *)src;
+    pp.src_width = d->src_width;
+    pp.src_height = d->src_height;
+    pp.mips = bloomed ? c->present_scratch.p : nullptr;
+    pp.scene = (uint2 *)(ls + lay.scene);
+    pp.out = out_is_device ? out : (void *)c->out.p;
+    pp.intensity = d->bloom_intensity;
+    pp.tone_mapping = d->tone_mapping;
+    pp.maximum_intensity = d->maximum_intensity;
+    pp.srgb_thr = c->srgb_thr.p;
+    pp.out_f16 = f16;
+    LinesParams lp;
+    lp.vertices = staged ? (const float *)(ls + lay.vertices) : (const float *)ld->vertices;
+    lp.n_lines = ld->n_lines;
+    std::memcpy(lp.m, ld->view_projection, sizeof(lp.m));
+    lp.depth = (const uint32_t *)((const unsigned char *)src + (size_t)d->src_width * d->src_height * 8);
+    lp.src_width = d->src_width;
+    lp.src_height = d->src_height;
+    lp.width = d->out_width;
+    lp.height = d->out_height;
+    lp.keys = (unsigned long long *)(ls + lay.keys);
+    lp.scene = pp.scene;
+    lp.counts = (LinesCounts *)(ls + lay.counts);
+    lp.reset_keys = !c->sw.lines_clear_keys;
+    lp.clear_keys = !lp.reset_keys || c->lines_keys_clean < npix;
+    c->lines_keys_clean = 0;  // until the call has finished
+    if (staged) HIP_TRY(c, hipMemcpyAsync(ls + lay.vertices, ld->vertices, (size_t)ld->n_lines * sizeof(aic_line_vertex) * 2, hipMemcpyHostToDevice, fs.stream));
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    launch_present_scene(g, pp, fs.stream);
+    if ((e = launch_present_lines(lp, fs.stream)) != hipSuccess) return hip_fail(c, "launch line pass", e);
+    pp.src = pp.scene;  // S' shown at its own size
+    pp.src_width = d->out_width;
+    pp.src_height = d->out_height;
+    launch_present(g, pp, fs.stream);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(c, "launch presentation", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    LinesCounts counts;
+    HIP_TRY(c, hipMemcpyAsync(&counts, lp.counts, sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
+    if (!out_is_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, out_bytes, hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    if (lp.reset_keys) c->lines_keys_clean = npix;
+    if (lines_info) {
+        lines_info->n_clipped_away = counts.n_clipped_away;
+        lines_info->n_fragments = counts.n_fragments;
+        lines_info->n_passed = counts.n_passed;
+        lines_info->n_pixels = counts.n_pixels;
+    }
     if (info) {
         HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
         info->levels = g.levels;

@@ -79,5 +79,8 @@ struct PresentParams {
 // Queues the presentation on `stream`; `g` = bloom_geometry of the OUTPUT size, at most 2^31 pixels (the kernels' texel indices are 32-bit). Launches:
 // the composite alone at intensity 0; else the chain's 6 L - 5 stages before it, and the stretch into S before those when the sizes differ.
 void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stream);
+// Queues S alone, stored into p.scene whatever the sizes: the stretch when they differ, the source texels (saturated, alpha 1) when they do not. What a
+// pass that draws into the scene before the chain runs (aic_present_lines.h) starts from; launch_present then takes p.scene as a frame of the output's size.
+void launch_present_scene(const BloomGeom &g, const PresentParams &p, hipStream_t stream);
 
 }  // namespace aic

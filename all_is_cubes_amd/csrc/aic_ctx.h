@@ -124,6 +124,11 @@ struct aic_ctx {
     uint32_t reproject_valid_w = 0, reproject_valid_h = 0;
     DevBuf<uint32_t> pick_scratch;  // aic_pick_pixels: the record read back, then the scan blocks' counts and offsets (aic_pick.h)
     DevBuf<uint2> present_scratch;  // aic_present_split with bloom: the chain's mips, then the scene texture of a stretched frame (aic_bloom.h)
+    // aic_present_split_lines: the key image, the stored scene, the counters, the staged vertices of a host list (aic_present_lines.h)
+    DevBuf<unsigned char> lines_scratch;
+    // the first lines_keys_clean keys of lines_scratch are all ones (cleared once after an allocation; every finished call leaves them so). 0 after an
+    // allocation and while a call that may have failed between its draw and its resolve is the last one: the next call clears first
+    size_t lines_keys_clean = 0;
     uint64_t aux_records = 0;
     double depth_zw[4] = {1.0, 0.0, 0.0, 1.0};  // aic_set_depth_transform: the Split frames' depth transform
     bool streaming_submit = false;  // set around aic_render_submit: frames meant to overlap are sized for throughput, synchronous ones for latency
@@ -206,6 +211,7 @@ struct aic_ctx {
         bool wait_whole_stream = false;  // AIC_WAIT_WHOLE_STREAM=1: aic_render_wait drains the slot's stream (rounds 1-3)
         uint32_t tiles_per_wave = 0;     // AIC_TILES_PER_WAVE: grid sizing of streamed frames smaller than the chip
         std::string wave_prof;           // AIC_WAVE_PROF (-DAIC_PROFILE builds): file for the per-wave clocks
+        bool lines_clear_keys = false;   // AIC_LINES_CLEAR_KEYS=1: every aic_present_split_lines clears its whole key image first instead of resetting the keys it touched
     } sw;
 };
 

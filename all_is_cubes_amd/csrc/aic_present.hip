@@ -45,6 +45,12 @@ __global__ void __launch_bounds__(256) present_stretch_kernel(const uint2 *__res
     if (t >= (uint32_t)ow * (uint32_t)oh) return;
     out[t] = stretch_texel(SrcSplit{src}, sw, sh, ow, oh, (int)(t % (uint32_t)ow), (int)(t / (uint32_t)ow));
 }
+// S of a window of the frame's own size, stored: the source texel itself, saturated, alpha 1 (what SrcSplit reads, as the scene texture holds it)
+__global__ void __launch_bounds__(256) present_copy_kernel(const uint2 *__restrict__ src, uint2 *__restrict__ out, uint32_t npix, int w) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= npix) return;
+    out[t] = pack_texel(SrcSplit{src}.at((int)(t % (uint32_t)w), (int)(t / (uint32_t)w), w));
+}
 // downsample 0 of a presented frame: `scene` is the Split frame itself (window of the frame's size) or the stored S; sw x sh is S's size either way
 __global__ void __launch_bounds__(256) present_down0_kernel(const uint2 *__restrict__ scene, int sw, int sh, uint2 *__restrict__ out, int ow, int oh) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -98,6 +104,14 @@ __global__ void __launch_bounds__(256) present_composite_kernel(const uint2 *__r
 }
 
 }  // namespace
+
+void launch_present_scene(const BloomGeom &g, const PresentParams &p, hipStream_t stream) {
+    if (!g.width || !g.height) return;
+    const int w = (int)g.width, h = (int)g.height, sw = (int)p.src_width, sh = (int)p.src_height;
+    const uint32_t blocks = bloom_blocks_of(g.width * g.height);
+    if (sw != w || sh != h) present_stretch_kernel<<<blocks, 256, 0, stream>>>(p.src, sw, sh, p.scene, w, h);
+    else present_copy_kernel<<<blocks, 256, 0, stream>>>(p.src, p.scene, g.width * g.height, w);
+}
 
 void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stream) {
     if (!g.width || !g.height || !g.levels) return;

@@ -568,7 +568,9 @@ bool HipRtRenderer::sync_space(int layer, const std::shared_ptr<Space> &space, c
 }
 
 bool HipRtRenderer::update_scene(const Cursor *cursor) {  // renderer.rs:96-161
+    std::vector<aic_line_vertex> lines = cursor ? cursor->wireframe() : std::vector<aic_line_vertex>();  // (throws before anything has changed)
     had_cursor_ = cursor != nullptr;
+    cursor_lines_ = std::move(lines);
     const StandardCameras &sc = *cameras_;
     const Viewport vp = modified_viewport();
     world_camera_ = Camera(sc.graphics_options, vp);
@@ -713,6 +715,59 @@ aic_present_info HipRtRenderer::present_split_to_device(const void *src_device, 
     const aic_present_desc d = present_desc(out_width, out_height, flags);
     aic_present_info pi;
     check(aic_present_split(ctx_, &d, src_device, out_device, 1, &pi), "aic_present_split");
+    return pi;
+}
+
+std::vector<aic_line_vertex> Cursor::wireframe() const {
+    aic_cursor_desc d{};
+    std::memcpy(d.cube, cube, sizeof(d.cube));
+    d.face_entered = face_entered;
+    d.face_selected = face_selected;
+    std::memcpy(d.point_entered, point_entered, sizeof(d.point_entered));
+    d.distance_to_point = distance_to_point;
+    std::memcpy(d.voxel_lo, voxel_lo, sizeof(d.voxel_lo));
+    std::memcpy(d.voxel_size, voxel_size, sizeof(d.voxel_size));
+    d.resolution = resolution;
+    std::vector<aic_line_vertex> v(2 * AIC_CURSOR_MAX_LINES);
+    uint32_t n = 0;
+    if (aic_cursor_wireframe(&d, v.data(), &n) != AIC_OK) throw std::invalid_argument("Cursor::wireframe: a face outside 0..6, resolution < 1 or a negative voxel_size");
+    v.resize(2 * (size_t)n);
+    return v;
+}
+
+aic_lines_desc HipRtRenderer::lines_desc(const std::vector<aic_line_vertex> *lines) const {
+    const std::vector<aic_line_vertex> &v = lines ? *lines : cursor_lines_;
+    aic_lines_desc l{};
+    const Mat4 m = world_camera_.view_matrix().then(world_camera_.projection_matrix());  // (row-vector order: WGSL's projection * view, column-major)
+    for (int i = 0; i < 16; i++) l.view_projection[i] = (float)m.m[i];
+    l.n_lines = (uint32_t)(v.size() / 2);
+    l.vertices = v.empty() ? nullptr : v.data();
+    return l;
+}
+
+Rendering HipRtRenderer::present_split(const void *src_device, uint32_t out_width, uint32_t out_height, const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info) {
+    const aic_present_desc d = present_desc(out_width, out_height, 0);
+    const aic_lines_desc l = lines_desc(lines);
+    Rendering r;
+    r.width = out_width;
+    r.height = out_height;
+    r.data.assign((size_t)out_width * out_height * 4, 0);
+    uint8_t none = 0;
+    aic_present_info pi;
+    check(aic_present_split_lines(ctx_, &d, &l, src_device, r.data.empty() ? &none : r.data.data(), 0, &pi, lines_info), "aic_present_split_lines");
+    r.info.kernel_ms = pi.kernel_ms;
+    r.info.width = out_width;
+    r.info.height = out_height;
+    r.info.rows_rendered = out_height;
+    return r;
+}
+
+aic_present_info HipRtRenderer::present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags,
+                                                        const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info) {
+    const aic_present_desc d = present_desc(out_width, out_height, flags);
+    const aic_lines_desc l = lines_desc(lines);
+    aic_present_info pi;
+    check(aic_present_split_lines(ctx_, &d, &l, src_device, out_device, 1, &pi, lines_info), "aic_present_split_lines");
     return pi;
 }
 

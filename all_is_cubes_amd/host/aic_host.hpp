@@ -303,7 +303,19 @@ struct StandardCameras {  // stdcam.rs:90-180, reduced to values the caller sets
     float measured_exposure = 1.0f;
     UiViewState ui;
 };
-struct Cursor {};
+// Cursor (all-is-cubes/src/character/cursor.rs): what of it the renderer draws. The application makes it (cursor_raycast needs the `selectable`
+// attribute, which the scene handed to the device does not carry); wireframe() is impl Wireframe for Cursor (cursor.rs:219-278) through
+// aic_cursor_wireframe: 12, 16, 24 or 28 lines in palette::CURSOR_OUTLINE. update(cursor) takes the wireframe before it touches the scene, so a Cursor
+// that has none (a face outside 0..6, resolution < 1, a negative voxel_size) makes update throw std::invalid_argument with nothing changed.
+struct Cursor {
+    int32_t cube[3] = {0, 0, 0};
+    int32_t face_entered = 0, face_selected = 0;  // Face7 discriminants: 0 Within, 1-3 NX NY NZ, 4-6 PX PY PZ
+    double point_entered[3] = {0.0, 0.0, 0.0};
+    double distance_to_point = 0.0;
+    int32_t voxel_lo[3] = {0, 0, 0}, voxel_size[3] = {1, 1, 1};  // the hit block's EvaluatedBlock::voxels_bounds()
+    int32_t resolution = 1;
+    std::vector<aic_line_vertex> wireframe() const;
+};
 
 // PixelPicker (all-is-cubes-gpu/src/raytrace_to_texture.rs:838-908): the order in which the incremental renderer takes a frame's pixels -- centre first and
 // dithered (aic_pixel_order), the central pixels interleaved with the rest and so picked more often. take(n) is n calls of Iterator::next, as pixel indices
@@ -423,6 +435,12 @@ class HipRtRenderer : public HeadlessRenderer {
     // per pixel to `out_device`, which must not overlap the frame.
     Rendering present_split(const void *src_device, uint32_t out_width, uint32_t out_height);
     aic_present_info present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags = 0);
+    // The same with the lines pass of EverythingRenderer::draw_frame_linear (all-is-cubes-gpu/src/everything.rs:616-658; aic_present_split_lines): `lines`
+    // -- pairs of vertices; nullptr: the wireframe of the cursor last given to update(), none if there was none -- is drawn into the scene before bloom
+    // and tone mapping, depth-tested against the frame's depth plane, under the world camera's projection x view (formed in f64, rounded to f32).
+    Rendering present_split(const void *src_device, uint32_t out_width, uint32_t out_height, const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info = nullptr);
+    aic_present_info present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags,
+                                             const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info = nullptr);
     // the world camera of the last update(): what to keep beside a resident frame as its `traced_with`
     const Camera &world_camera() const { return world_camera_; }
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)
@@ -484,6 +502,8 @@ class HipRtRenderer : public HeadlessRenderer {
     double cam_override_inv_[16] = {0};
     float cam_override_exposure_ = 1.0f;
     bool had_cursor_ = false;
+    std::vector<aic_line_vertex> cursor_lines_;  // the wireframe of the cursor of the last update()
+    aic_lines_desc lines_desc(const std::vector<aic_line_vertex> *lines) const;
     bool bloom_ = false;  // set_bloom
     uint64_t pick_cursor_ = 0, pick_skip_unknown_ = 0;  // pick_pixels
     uint32_t pick_width_ = 0, pick_height_ = 0;         // ... and the viewport they belong to

@@ -226,7 +226,26 @@ PYBIND11_MODULE(_host, m) {
     flaws.attr("OTHER") = Flaws::OTHER; flaws.attr("UNSUPPORTED") = Flaws::UNSUPPORTED; flaws.attr("NO_BLOOM") = Flaws::NO_BLOOM;
     flaws.attr("NO_CURSOR") = Flaws::NO_CURSOR; flaws.attr("OUT_OF_MEMORY") = Flaws::OUT_OF_MEMORY;
 
-    py::class_<Cursor>(m, "Cursor").def(py::init<>());
+    py::class_<Cursor>(m, "Cursor")
+        .def(py::init<>())
+        .def_property("cube", [](const Cursor &c) { return std::array<int32_t, 3>{c.cube[0], c.cube[1], c.cube[2]}; },
+                      [](Cursor &c, std::array<int32_t, 3> v) { std::copy(v.begin(), v.end(), c.cube); })
+        .def_readwrite("face_entered", &Cursor::face_entered)
+        .def_readwrite("face_selected", &Cursor::face_selected)
+        .def_property("point_entered", [](const Cursor &c) { return std::array<double, 3>{c.point_entered[0], c.point_entered[1], c.point_entered[2]}; },
+                      [](Cursor &c, std::array<double, 3> v) { std::copy(v.begin(), v.end(), c.point_entered); })
+        .def_readwrite("distance_to_point", &Cursor::distance_to_point)
+        .def_property("voxel_lo", [](const Cursor &c) { return std::array<int32_t, 3>{c.voxel_lo[0], c.voxel_lo[1], c.voxel_lo[2]}; },
+                      [](Cursor &c, std::array<int32_t, 3> v) { std::copy(v.begin(), v.end(), c.voxel_lo); })
+        .def_property("voxel_size", [](const Cursor &c) { return std::array<int32_t, 3>{c.voxel_size[0], c.voxel_size[1], c.voxel_size[2]}; },
+                      [](Cursor &c, std::array<int32_t, 3> v) { std::copy(v.begin(), v.end(), c.voxel_size); })
+        .def_readwrite("resolution", &Cursor::resolution)
+        .def("wireframe", [](const Cursor &c) {  // [2 n, 7] f32: position, linear RGBA
+            const std::vector<aic_line_vertex> v = c.wireframe();
+            py::array_t<float> a({(py::ssize_t)v.size(), (py::ssize_t)7});
+            if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(aic_line_vertex));
+            return a;
+        });
 
     py::class_<PixelPicker>(m, "PixelPicker")
         .def(py::init<uint32_t, uint32_t>(), py::arg("width"), py::arg("height"))
@@ -246,7 +265,11 @@ PYBIND11_MODULE(_host, m) {
             if (!policy.is_none()) sp = policy.cast<HipRtRenderer::SizePolicy>();
             return std::make_unique<HipRtRenderer>(std::move(cams), sp, device_id);
         }), py::arg("cameras"), py::arg("size_policy") = py::none(), py::arg("device_id") = -1)
-        .def("update", [](HipRtRenderer &r, py::object cursor) { Cursor c; return r.update_scene(cursor.is_none() ? nullptr : &c); }, py::arg("cursor") = py::none())
+        .def("update", [](HipRtRenderer &r, py::object cursor) {
+            if (cursor.is_none()) return r.update_scene(nullptr);
+            const Cursor c = cursor.cast<Cursor>();
+            return r.update_scene(&c);
+        }, py::arg("cursor") = py::none())
         .def("draw", [](HipRtRenderer &r, const std::string &t) { py::gil_scoped_release rel; return r.draw(t); }, py::arg("info_text") = "")
         .def("draw_text", [](HipRtRenderer &r, const std::string &le) { py::gil_scoped_release rel; return r.draw_text(le); }, py::arg("line_ending") = "\n")
         .def("trace_rays", [](HipRtRenderer &r, int layer, py::array_t<double, py::array::c_style | py::array::forcecast> rays, bool include_sky) {
@@ -322,6 +345,35 @@ PYBIND11_MODULE(_host, m) {
             d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]); d["bloomed"] = i.bloomed;
             return std::move(d);
         }, py::arg("src_ptr"), py::arg("out_width"), py::arg("out_height"), py::arg("flags") = 0u, py::arg("out_ptr") = (uintptr_t)0)
+        .def("present_split_lines", [](HipRtRenderer &r, uintptr_t src_ptr, uint32_t out_width, uint32_t out_height, py::object lines, uint32_t flags, uintptr_t out_ptr) {
+            // lines = None: the cursor of the last update(); else [2 n, 7] f32 (position, linear RGBA). -> (present_split's result, dict(n_clipped_away,
+            // n_fragments, n_passed, n_pixels))
+            std::vector<aic_line_vertex> v;
+            if (!lines.is_none()) {
+                const auto a = lines.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                if (a.size() % 14 != 0) throw std::invalid_argument("lines: [2 n, 7] floats");
+                v.resize((size_t)a.size() / 7);
+                if (!v.empty()) std::memcpy(v.data(), a.data(), v.size() * sizeof(aic_line_vertex));
+            }
+            const std::vector<aic_line_vertex> *given = lines.is_none() ? nullptr : &v;
+            aic_lines_info li{};
+            py::object first;
+            if (!out_ptr) {
+                if (flags) throw std::invalid_argument("present_split_lines: a host Rendering is RGBA8; AIC_PRESENT_OUT_F16 needs out_ptr");
+                Rendering out;
+                { py::gil_scoped_release rel; out = r.present_split(reinterpret_cast<const void *>(src_ptr), out_width, out_height, given, &li); }
+                first = py::cast(std::move(out));
+            } else {
+                aic_present_info i;
+                { py::gil_scoped_release rel; i = r.present_split_to_device(reinterpret_cast<const void *>(src_ptr), reinterpret_cast<void *>(out_ptr), out_width, out_height, flags, given, &li); }
+                py::dict d;
+                d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]); d["bloomed"] = i.bloomed;
+                first = std::move(d);
+            }
+            py::dict l;
+            l["n_clipped_away"] = li.n_clipped_away; l["n_fragments"] = li.n_fragments; l["n_passed"] = li.n_passed; l["n_pixels"] = li.n_pixels;
+            return py::make_tuple(first, l);
+        }, py::arg("src_ptr"), py::arg("out_width"), py::arg("out_height"), py::arg("lines") = py::none(), py::arg("flags") = 0u, py::arg("out_ptr") = (uintptr_t)0)
         .def("world_camera", [](const HipRtRenderer &r) { return Camera(r.world_camera()); })
         .def("set_world_camera_override", [](HipRtRenderer &r, py::object inv, float exposure) {
             if (inv.is_none()) { r.set_world_camera_override(nullptr, 1.0f); return; }

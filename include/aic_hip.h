@@ -485,6 +485,64 @@ int aic_present_split(aic_ctx *ctx, const aic_present_desc *desc, const void *sr
  * be NULL. An empty output gives zeros. AIC_ERR_INVALID: a dimension above 65535, more than AIC_PRESENT_MAX_PIXELS output pixels, src of zero size
  * with a non-empty output. */
 int aic_present_geometry(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes);
+/* replaces: the lines pass of EverythingRenderer::draw_frame_linear (all-is-cubes-gpu/src/everything.rs:616-658): after the traced frame is drawn into
+ * the scene texture with its depth as frag_depth (shaders/rt-copy.wgsl:55-71) and before bloom and tone mapping, the line list -- the cursor's wireframe
+ * and debug lines -- is drawn with lines_vertex / lines_fragment (shaders/blocks-and-lines.wgsl:902-919) by a LineList pipeline with
+ * CompareFunction::Less, depth write and no blend (pipelines.rs:453-487). aic_present_split_lines is aic_present_split with that pass: the lines are
+ * drawn into the scene texture S on the device, depth-tested against the resident Split frame's depth plane, and bloom and composite run on the result.
+ * WebGPU leaves line rasterisation to the implementation; the rule here is DESIGN.md 4.13's (clip coordinates, Liang-Barsky clipping, one fragment per
+ * major-axis pixel centre in [p0, p1), nearest depth texel, least depth wins and among equal depths the lowest line), tests/present_lines_ref.py is that
+ * text in NumPy and the device equals it bit for bit. A fragment passes iff its depth texel has a clear sign bit, is not NaN and f < min(texel, 1):
+ * the negative depth of a UI pixel or of a pixel of no layer hides every line, as frag_depth clamped to 0 does in the reference. Colours are linear RGBA
+ * interpolated in screen space and written as f16 with alpha 1; nothing is written to src.
+ * lines == NULL or n_lines == 0: the call is aic_present_split itself -- the same launches, no extra scratch, lines_info zeroed.
+ * vertices: host memory, copied into context scratch before the call returns, or with AIC_LINES_DEVICE a device pointer. Their contents are not
+ * checked: a line with a non-finite position or r, g, b component is dropped and counted in n_clipped_away; alpha is never read, whatever it holds.
+ * The line scratch is the context's own: the 64-bit key image and the stored scene (8 bytes an output pixel each), a 32-byte record and the staged
+ * vertices of a host list; allocated on first use, again when a call needs more, released in aic_destroy. aic_present_lines_scratch reports it.
+ * Rejected like aic_present_split, and also: NULL vertices with n_lines > 0; n_lines above AIC_LINES_MAX; a device vertices pointer off a 4-byte
+ * boundary; unknown flag bits; a non-finite component of view_projection. All AIC_ERR_INVALID, before anything is queued, the context still usable. */
+typedef struct aic_line_vertex {
+    float position[3];  /* world space */
+    float color[4];     /* linear RGBA (WgpuLinesVertex, all-is-cubes-gpu/src/in_wgpu/vertex.rs:386-410); alpha is not used: no blend */
+} aic_line_vertex;
+#define AIC_LINES_DEVICE 1u      /* `vertices` is a device pointer on the context's device (4-byte aligned) */
+#define AIC_LINES_MAX 1048576u   /* lines per call */
+typedef struct aic_lines_desc {
+    float view_projection[16];   /* camera.projection * camera.view_matrix as WGSL holds it: column-major [c*4+r]; clip = M * (x, y, z, 1) */
+    uint32_t n_lines;            /* line i = vertices[2i], vertices[2i+1] (LineList) */
+    uint32_t flags;              /* AIC_LINES_* */
+    const aic_line_vertex *vertices;
+} aic_lines_desc;
+typedef struct aic_lines_info {
+    uint64_t n_clipped_away;     /* lines that produced no segment: a non-finite position, r, g, b or clip coordinate, clipped away whole, w <= 0 at a clipped end */
+    uint64_t n_fragments;        /* fragments generated inside the window */
+    uint64_t n_passed;           /* ... that passed the depth test against the frame */
+    uint64_t n_pixels;           /* output pixels that show a line */
+} aic_lines_info;
+int aic_present_split_lines(aic_ctx *ctx, const aic_present_desc *desc, const aic_lines_desc *lines, const void *src_device, void *out, int out_is_device,
+                            aic_present_info *info, aic_lines_info *lines_info);
+/* host-only, like aic_present_geometry: the bytes of line scratch a call with n_lines > 0 host vertices allocates, on top of what aic_present_geometry
+ * reports (of which such a call never needs the stored scene: it keeps its own). A device list needs n_lines * 56 fewer. 1920 x 1080 with the cursor's
+ * 28 lines: 33 179 200. AIC_ERR_INVALID as aic_present_geometry, or n_lines above AIC_LINES_MAX. n_lines = 0 or an empty output gives 0. */
+int aic_present_lines_scratch(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t n_lines, uint64_t *bytes);
+/* replaces: impl Wireframe for Cursor (all-is-cubes/src/character/cursor.rs:219-278), host-only, in f64 and in the reference's order: the 12 edges of
+ * the hit block's voxel bounds (scaled by 1 / resolution, translated to the cube, expanded by 0.001 * distance_to_point) in Aab::wireframe_points' order
+ * (all-is-cubes-base/src/math/aab.rs:569-588); if face_selected is a real face, the 12 edges of that box shrunk by 1/128 and flattened onto the face;
+ * if face_entered is a real face, the 4-line diamond with tips at 1/32 around point_entered + face * offset. 12, 16, 24 or 28 lines; positions as f32,
+ * colour palette::CURSOR_OUTLINE = linear (0, 0, 0, 1). Making the Cursor (cursor_raycast) stays the application's: it needs the `selectable`
+ * attribute, which the scene of this ABI does not carry. AIC_ERR_INVALID: a NULL pointer, a face outside 0..6, resolution < 1, a negative voxel_size. */
+typedef struct aic_cursor_desc {
+    int32_t cube[3];
+    int32_t face_entered, face_selected;   /* Face7 discriminants, as aic_pixel_aux.face */
+    double point_entered[3];
+    double distance_to_point;
+    int32_t voxel_lo[3], voxel_size[3];    /* EvaluatedBlock::voxels_bounds() */
+    int32_t resolution;
+    int32_t reserved;
+} aic_cursor_desc;
+#define AIC_CURSOR_MAX_LINES 28u
+int aic_cursor_wireframe(const aic_cursor_desc *cursor, aic_line_vertex *out /* [2 * 28] */, uint32_t *n_lines);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

@@ -33,6 +33,9 @@ pub const AIC_REPROJECT_KEEP_SPLATS: u32 = 1;
 pub const AIC_REPROJECT_MAX_LEVELS: u32 = 12;
 pub const AIC_PRESENT_OUT_F16: u32 = 1;
 pub const AIC_PRESENT_MAX_PIXELS: u64 = 2147483648;
+pub const AIC_LINES_DEVICE: u32 = 1;
+pub const AIC_LINES_MAX: u32 = 1048576;
+pub const AIC_CURSOR_MAX_LINES: u32 = 28;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
 pub const AIC_MULTI_MAX_IN_FLIGHT: u32 = 8;
 pub const AIC_TUNE_QUEUES_SHIFT: u32 = 0;
@@ -209,6 +212,45 @@ pub struct aic_present_info {
 }
 
 #[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct aic_line_vertex {
+    pub position: [f32; 3],
+    pub color: [f32; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct aic_lines_desc {
+    pub view_projection: [f32; 16],
+    pub n_lines: u32,
+    pub flags: u32,
+    pub vertices: *const aic_line_vertex,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct aic_lines_info {
+    pub n_clipped_away: u64,
+    pub n_fragments: u64,
+    pub n_passed: u64,
+    pub n_pixels: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_cursor_desc {
+    pub cube: [i32; 3],
+    pub face_entered: i32,
+    pub face_selected: i32,
+    pub point_entered: [f64; 3],
+    pub distance_to_point: f64,
+    pub voxel_lo: [i32; 3],
+    pub voxel_size: [i32; 3],
+    pub resolution: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct aic_pixel_aux {
     pub hit: i32,
@@ -301,6 +343,9 @@ unsafe extern "C" {
     pub fn aic_pick_pixels(ctx: *mut aic_ctx, desc: *const aic_pick_desc, order_device: *const u32, pixels_out_device: *mut u32, info: *mut aic_pick_info) -> c_int;
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;
     pub fn aic_present_geometry(src_w: u32, src_h: u32, out_w: u32, out_h: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
+    pub fn aic_present_split_lines(ctx: *mut aic_ctx, desc: *const aic_present_desc, lines: *const aic_lines_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info, lines_info: *mut aic_lines_info) -> c_int;
+    pub fn aic_present_lines_scratch(src_w: u32, src_h: u32, out_w: u32, out_h: u32, n_lines: u32, bytes: *mut u64) -> c_int;
+    pub fn aic_cursor_wireframe(cursor: *const aic_cursor_desc, out: *mut aic_line_vertex, n_lines: *mut u32) -> c_int;
     pub fn aic_pixel_order(width: u32, height: u32, order: *mut u32, central: *mut u32, cycle_length: *mut u64) -> c_int;
     pub fn aic_read_aux(ctx: *mut aic_ctx, out: *mut aic_pixel_aux, n_records: u64) -> c_int;
     pub fn aic_synchronize(ctx: *mut aic_ctx) -> c_int;

@@ -267,6 +267,22 @@ pub struct HipRtRenderer {
 // which every entry point performs itself.
 unsafe impl Send for HipRtRenderer {}
 
+/// `impl Wireframe for Cursor` (all-is-cubes/src/character/cursor.rs:219-278) as the line list [`HipRtRenderer::present_split_lines`] draws: the hit
+/// block's voxel bounds, the selected face's frame and the diamond at the point of entry, 12 to 28 lines in `palette::CURSOR_OUTLINE`. Host-only.
+/// `None`: a face discriminant outside 0..=6, a resolution below 1 or a negative voxel size.
+#[must_use]
+pub fn cursor_wireframe(cursor: &ffi::aic_cursor_desc) -> Option<Vec<[ffi::aic_line_vertex; 2]>> {
+    let mut out = vec![[ffi::aic_line_vertex::default(); 2]; ffi::AIC_CURSOR_MAX_LINES as usize];
+    let mut n = 0u32;
+    // SAFETY: `out` holds 2 * AIC_CURSOR_MAX_LINES vertices, the most the call writes
+    let rc = unsafe { ffi::aic_cursor_wireframe(cursor, out.as_mut_ptr().cast(), &mut n) };
+    if rc != 0 {
+        return None;
+    }
+    out.truncate(n as usize);
+    Some(out)
+}
+
 fn options_of(o: &GraphicsOptions) -> ffi::aic_options {
     let (transparency, threshold) = match o.transparency {
         TransparencyOption::Surface => (0, 0.5),
@@ -783,6 +799,57 @@ impl HipRtRenderer {
         // SAFETY: the context is live; the caller vouches for the frame and the target; the call returns when the image is written
         self.device.check(unsafe { ffi::aic_present_split(ctx.as_ptr(), &desc, src_device, out_device, 1, &mut info) })?;
         Ok(info)
+    }
+
+    /// [`Self::present_split`] with the lines pass of `EverythingRenderer::draw_frame_linear` (all-is-cubes-gpu/src/everything.rs:616-658): `lines`,
+    /// pairs of world-space vertices with a linear RGBA colour -- the cursor's wireframe from [`cursor_wireframe`], debug lines --, are drawn into the
+    /// scene before bloom and tone mapping, depth-tested against the resident frame's depth plane, under the world camera's projection x view.
+    /// Returns the presentation's report and how many lines, fragments and pixels were drawn.
+    ///
+    /// # Safety
+    /// As [`Self::present_split`].
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer, or with more than `ffi::AIC_LINES_MAX` lines.
+    pub unsafe fn present_split_lines(
+        &mut self,
+        src_device: *const core::ffi::c_void,
+        out_device: *mut core::ffi::c_void,
+        out_size: [u32; 2],
+        flags: u32,
+        lines: &[[ffi::aic_line_vertex; 2]],
+    ) -> Result<(ffi::aic_present_info, ffi::aic_lines_info), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("present_split_lines needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let camera = &self.cameras.cameras().world;
+        let options = options_of(camera.options());
+        let desc = ffi::aic_present_desc {
+            src_width: viewport.framebuffer_size.width,
+            src_height: viewport.framebuffer_size.height,
+            out_width: out_size[0],
+            out_height: out_size[1],
+            bloom_intensity: options.bloom_intensity,
+            tone_mapping: options.tone_mapping,
+            maximum_intensity: options.maximum_intensity,
+            flags,
+        };
+        // (euclid's row-vector order is WGSL's column-major one: all-is-cubes-gpu/src/camera.rs convert_matrix)
+        let view_projection = camera.view_matrix().then(&camera.projection_matrix()).to_array().map(|v| v as f32);
+        let lines_desc = ffi::aic_lines_desc {
+            view_projection,
+            n_lines: u32::try_from(lines.len()).expect("too many lines"),
+            flags: 0,
+            vertices: lines.as_ptr().cast(),
+        };
+        let mut info = ffi::aic_present_info::default();
+        let mut lines_info = ffi::aic_lines_info::default();
+        // SAFETY: the context is live; the caller vouches for the frame and the target; `lines` is copied before the call returns, and the call
+        // returns when the image is written
+        self.device.check(unsafe { ffi::aic_present_split_lines(ctx.as_ptr(), &desc, &lines_desc, src_device, out_device, 1, &mut info, &mut lines_info) })?;
+        Ok((info, lines_info))
     }
 
     fn light_params(maximum_distance: u8, fast: bool, epsilon: u8, n_queue: i32, max_updates: u64) -> ffi::aic_light_params {

@@ -15,6 +15,7 @@
 #include "aic_device.h"
 #include "aic_launch.h"
 #include "aic_pick.h"
+#include "aic_present_lines.h"
 #include "aic_reproject.h"
 #include "record.h"
 
@@ -236,6 +237,12 @@ void launch_scatter_cubes(uint16_t *, uint32_t *, const int32_t *, const uint16_
 hipError_t launch_reproject(const ReprojectGeom &, const ReprojectParams &, hipStream_t) { rec("launch_reproject"); return hipSuccess; }
 hipError_t launch_pick(const PickParams &, hipStream_t) { rec("launch_pick"); return hipSuccess; }
 void launch_present(const BloomGeom &, const PresentParams &, hipStream_t) { rec("launch_present"); }
+void launch_present_scene(const BloomGeom &, const PresentParams &, hipStream_t) { rec("launch_present_scene"); }
+hipError_t launch_present_lines(const LinesParams &p, hipStream_t) {
+    rec("launch_present_lines vertices %s n_lines %u keys %s scene %s counts %s clear_keys %d reset_keys %d", P(p.vertices), p.n_lines, P(p.keys), P(p.scene), P(p.counts),
+        (int)p.clear_keys, (int)p.reset_keys);
+    return hipSuccess;
+}
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
 void launch_assemble_strips(const uint32_t *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t) { rec("launch_assemble_strips"); }
