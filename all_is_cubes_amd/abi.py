@@ -542,6 +542,8 @@ class Context:
 
     def replace_blocks(self, layer: int, items) -> None:
         """`items`: list of (index, flat.BlockDef) -- a batch of BlockEvaluation changes under one synchronisation."""
+        from . import flat
+
         n = len(items)
         idx = np.ascontiguousarray([i for i, _ in items], np.uint32)
         descs = (BlockDesc * max(n, 1))()

@@ -445,7 +445,10 @@ int aic_upload_space(aic_ctx *c, int layer, const aic_space_desc *s) {
     if (!vox.empty()) HIP_TRY(c, hipMemcpyAsync(l.pool.p + n, vox.data(), vox.size() * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(l.cls.p, cls.data(), cls.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     const bool cls_in_code = s->n_blocks <= kCubeIndexMask + 1u;
-    if (cls_in_code) launch_tag_cubes(l.pool.p, n, l.cls.p, 0, 1, c->stream);
+    if (cls_in_code) {
+        launch_tag_cubes(l.pool.p, n, l.cls.p, 0, 1, c->stream);
+        launch_open_cubes(l.pool.p, s->size, c->stream);
+    }
     if (!pal.empty()) HIP_TRY(c, hipMemcpyAsync(l.palette.p, pal.data(), pal.size() * sizeof(DevPaletteEntry), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // host buffers may be released on return
 
@@ -511,6 +514,8 @@ int aic_update_cubes(aic_ctx *c, int layer, uint32_t n, const int32_t *xyz, cons
     light_state_cubes_updated(l.lstate, l.version - 1, l.version, n, xyz, block_index, light);
     launch_scatter_cubes(l.pool.p, l.light.p, (const int32_t *)base, block_index ? (const uint16_t *)(base + b_xyz) : nullptr,
                          light ? (const uint32_t *)(base + b_xyz + b_bi) : nullptr, n, l.lo, l.size, l.cls_in_code ? l.cls.p : nullptr, c->stream);
+    // the scatter leaves no changed cube OPEN; whether it and its six neighbours are is decided now, from the grid with every change in (no frame is in flight)
+    if (block_index && l.cls_in_code) launch_open_changed_cubes(l.pool.p, (const int32_t *)base, n, l.lo, l.size, c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     {
@@ -661,12 +666,14 @@ int replace_one(aic_ctx *c, int layer, Layer &l, uint32_t index, const aic_block
     HIP_TRY(c, hipMemcpy(l.cls.p + index / 16u, &l.host_cls[index / 16u], sizeof(uint32_t), hipMemcpyHostToDevice));
     if (l.cls_in_code) {
         // the cube grid carries class bits: drop them if the table outgrew 14-bit indices, refresh
-        // them if an existing block changed class (cubes already holding this index must follow)
+        // them if an existing block changed class (cubes already holding this index must follow, and
+        // the OPEN tags around them: the retag leaves none, the pass behind it decides them all again)
         if (l.host_blocks.size() > kCubeIndexMask + 1u) {
             launch_tag_cubes(l.pool.p, l.n_cubes(), l.cls.p, 1, 0, c->stream);
             l.cls_in_code = false;
         } else if (class_changed) {
             launch_tag_cubes(l.pool.p, l.n_cubes(), l.cls.p, 1, 1, c->stream);
+            launch_open_cubes(l.pool.p, l.size, c->stream);
         }
         HIP_TRY(c, hipGetLastError());
     }

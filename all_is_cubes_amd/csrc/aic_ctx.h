@@ -87,7 +87,7 @@ struct Layer {
     uint32_t block_sky[7] = {};
     aic_options opt;
     bool opt_set = false;
-    bool cls_in_code = false;  // cube-grid entries carry the block class in bits 14-15 (aic_device.h)
+    bool cls_in_code = false;  // cube-grid entries carry a tag in bits 14-15: the block class, and which invisible cubes are open (aic_device.h)
     uint64_t version = 0;      // bumped by every scene mutation; the light updater's host mirrors follow it
     uint64_t upload_serial = 0;  // bumped by aic_upload_space only: the light update queue lives as long as one upload
     LightState *lstate = nullptr;

@@ -79,11 +79,22 @@ struct DevLayer {
 };
 
 // Cube-grid entries of the pool when DevLayer.cls_in_code != 0 (block table of at most 16384 entries):
-//   bits 0-13 block index, bits 14-15 the block's class (0 invisible single voxel, 1 visible single
-//   voxel, 2 recursive) -- so the trace kernel classifies a cube with no second lookup.
-// Larger block tables store the plain 16-bit index and the kernel consults the class table in LDS.
+//   bits 0-13 block index, bits 14-15 the cube's TAG: the block's class plus one (1 invisible single voxel, 2 visible
+//   single voxel, 3 recursive) -- so the trace kernel classifies a cube with no second lookup, "found something" being
+//   one unsigned compare (entry >= kCubeTagVisible << kCubeClassShift) -- and 0 for an OPEN cube: an invisible one that
+//   is not on the grid's outermost layer and whose six face neighbours are invisible too. A step out of an open cube,
+//   along any axis, lands on an in-bounds invisible cube: the production trace kernels take it without looking that cube up.
+//   A tag of 0 that is stale is a wrong picture (rays walk through a block); a tag of 1 on a cube that is open is only slow:
+//   whoever changes a cube's class leaves the cube and its six neighbours at 1 or recomputed (aic_scene_kernels.h) before a frame runs.
+// Larger block tables store the plain 16-bit index and the kernel consults the class table.
 static constexpr uint32_t kCubeClassShift = 14u;
 static constexpr uint32_t kCubeIndexMask = (1u << kCubeClassShift) - 1u;
+static constexpr uint32_t kCubeTagOpen = 0u, kCubeTagInvisible = 1u, kCubeTagVisible = 2u, kCubeTagRecursive = 3u;
+// the block's class (DevLayer::cls: 0 / 1 / 2) of a tagged entry
+__host__ __device__ inline uint32_t cube_entry_class(uint32_t entry) {
+    const uint32_t tag = entry >> kCubeClassShift;
+    return tag > kCubeTagInvisible ? tag - 1u : 0u;
+}
 
 constexpr uint32_t kMaxTileQueues = 8;  // one per XCD
 

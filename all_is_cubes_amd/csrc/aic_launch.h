@@ -23,6 +23,9 @@ size_t trace_ray_cold_bytes(uint32_t n_cus, uint32_t *groups);
 void launch_scatter_cubes(uint16_t *grid, uint32_t *light, const int32_t *xyz, const uint16_t *bi, const uint32_t *lt,
                           uint32_t n, const int lo[3], const int size[3], const uint32_t *cls, hipStream_t stream);
 void launch_tag_cubes(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged, hipStream_t stream);
+// the OPEN tags (aic_device.h) of a tagged grid: all of them, behind launch_tag_cubes; those of `n` changed cubes (xyz: device memory) and their neighbours, behind the scatter
+void launch_open_cubes(uint16_t *grid, const int size[3], hipStream_t stream);
+void launch_open_changed_cubes(uint16_t *grid, const int32_t *xyz, uint32_t n, const int lo[3], const int size[3], hipStream_t stream);
 void launch_order_tiles(const uint32_t *cost, uint32_t *order, uint32_t n_tiles, uint32_t macros_x, uint32_t sb_shift, uint32_t n_queues, uint32_t *queue_start,
                         hipStream_t stream, bool clear_cost = false, uint32_t *clear_words = nullptr, uint32_t n_clear_words = 0);
 // the same for the frames of a batch, one workgroup each, in ONE launch (OrderJobs: aic_device.h)

@@ -244,7 +244,7 @@ AIC_DEV uint32_t bounce_secondary_ray(const LayerT &L, const float *sky_mem, con
                 const size_t ci = ((size_t)(uint32_t)(os.cx - olx) * (size_t)osy + (size_t)(uint32_t)(os.cy - oly)) * (size_t)osz + (size_t)(uint32_t)(os.cz - olz);
                 const uint32_t entry = L.pool[ci];
                 const uint32_t bi = entry & idx_mask;
-                const uint32_t cls = big ? ((L.cls[bi >> 4] >> ((bi & 15u) << 1)) & 3u) : (entry >> kCubeClassShift);
+                const uint32_t cls = big ? ((L.cls[bi >> 4] >> ((bi & 15u) << 1)) & 3u) : cube_entry_class(entry);
                 const DevBlock *tb = &L.blocks[bi];
                 if (cls == 1u) {
                     kind = 2;

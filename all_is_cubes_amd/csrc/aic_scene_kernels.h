@@ -1,7 +1,8 @@
 // aic_scene_kernels.h -- the small kernels that maintain the device's copy of a scene and a frame's bookkeeping, with their launchers (part of the
 // aic_trace.hip translation unit: DESIGN.md 4 says why they are not compiled on their own):
 //   scatter_cubes_kernel   aic_update_cubes: SpaceChange::{CubeBlock, CubeLight} (all-is-cubes-render/src/raytracer/updating.rs:146-166)
-//   tag_cubes_kernel       the class bits of the cube grid (aic_device.h)
+//   tag_cubes_kernel       the tag bits of the cube grid (aic_device.h): the block classes ...
+//   open_cubes_kernel, open_changed_cubes_kernel   ... and which invisible cubes are OPEN, for the whole grid / around changed cubes
 //   order_tiles_kernel     the tile queues of the next frame, costliest tiles first (no counterpart in the reference: DESIGN.md 4.2)
 //   assemble_strips_kernel aic_assemble_strips: a multi-device frame's strips into one image
 #pragma once
@@ -13,6 +14,9 @@
 #include "aic_launch.h"
 
 namespace aic {
+
+// the tag of a cube holding block `b`, short of OPEN (aic_device.h): the block's class plus one
+__device__ __forceinline__ uint32_t cube_tag_of(const uint32_t *cls, uint32_t b) { return ((cls[b >> 4] >> ((b & 15u) << 1)) & 3u) + 1u; }
 
 // aic_update_cubes: scatter of SpaceChange::{CubeBlock,CubeLight} (updating.rs:146-166)
 __global__ void scatter_cubes_kernel(uint16_t *grid, uint32_t *light, const int32_t *xyz, const uint16_t *bi,
@@ -27,20 +31,57 @@ __global__ void scatter_cubes_kernel(uint16_t *grid, uint32_t *light, const int3
     size_t idx = ((size_t)dx * sy + dy) * sz + dz;
     if (bi) {
         uint32_t b = bi[i];
-        if (cls) b |= ((cls[b >> 4] >> ((b & 15u) << 1)) & 3u) << kCubeClassShift;  // cls != null: tagged grid
+        if (cls) b |= cube_tag_of(cls, b) << kCubeClassShift;  // cls != null: tagged grid (never OPEN: open_changed_cubes_kernel decides that, after every cube is in)
         grid[idx] = (uint16_t)b;
     }
     if (lt) light[idx] = lt[i];
 }
 
-// (re)writes the class bits of every cube-grid entry from the class table (aic_device.h)
+// (re)writes the class bits of every cube-grid entry from the class table (aic_device.h); no entry comes out OPEN
 __global__ void tag_cubes_kernel(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t b = grid[i];
     if (from_tagged) b &= kCubeIndexMask;
-    if (to_tagged) b |= ((cls[b >> 4] >> ((b & 15u) << 1)) & 3u) << kCubeClassShift;
+    if (to_tagged) b |= cube_tag_of(cls, b) << kCubeClassShift;
     grid[i] = (uint16_t)b;
+}
+
+// The OPEN tag (aic_device.h) of cube (x, y, z) of a tagged grid, decided from the grid as it stands: an invisible cube inside the outermost layer whose six
+// face neighbours are invisible. Only the tag bit between OPEN and INVISIBLE is ever written, with a value that depends on nobody's tag bit but on classes
+// alone (tag <= INVISIBLE), so threads that decide neighbouring cubes -- or the same cube twice -- at the same time write what a serial pass would.
+__device__ __forceinline__ void decide_open(uint16_t *grid, int x, int y, int z, int sx, int sy, int sz) {
+    const size_t i = ((size_t)x * sy + y) * sz + z;
+    const uint32_t b = grid[i];
+    if ((b >> kCubeClassShift) > kCubeTagInvisible) return;
+    bool open = x > 0 && y > 0 && z > 0 && x < sx - 1 && y < sy - 1 && z < sz - 1;
+    if (open) {
+        const size_t stx = (size_t)sy * sz, sty = (size_t)sz;
+        const uint32_t worst = max(max(max((uint32_t)grid[i - stx], (uint32_t)grid[i + stx]), max((uint32_t)grid[i - sty], (uint32_t)grid[i + sty])),
+                                   max((uint32_t)grid[i - 1], (uint32_t)grid[i + 1]));
+        open = (worst >> kCubeClassShift) <= kCubeTagInvisible;
+    }
+    const uint32_t nb = (b & kCubeIndexMask) | ((open ? kCubeTagOpen : kCubeTagInvisible) << kCubeClassShift);
+    if (nb != b) grid[i] = (uint16_t)nb;
+}
+
+// every cube of a tagged grid (after tag_cubes_kernel: upload, a block that changed class)
+__global__ void open_cubes_kernel(uint16_t *grid, int sx, int sy, int sz) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)sx * sy * sz) return;
+    const int z = (int)(i % (size_t)sz), y = (int)((i / (size_t)sz) % (size_t)sy), x = (int)(i / ((size_t)sz * sy));
+    decide_open(grid, x, y, z, sx, sy, sz);
+}
+
+// aic_update_cubes, after the scatter: the changed cubes and their six face neighbours (thread = change * 8 + which of the seven)
+__global__ void open_changed_cubes_kernel(uint16_t *grid, const int32_t *xyz, uint32_t n, int lx, int ly, int lz, int sx, int sy, int sz) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = t >> 3, k = t & 7u;
+    if (i >= n || k == 7u) return;
+    // (in 64 bits: a change may name any i32 cube, inside the space or not)
+    long long x = (long long)xyz[3 * i + 0] - lx, y = (long long)xyz[3 * i + 1] - ly, z = (long long)xyz[3 * i + 2] - lz;
+    if (k == 1u) x--; else if (k == 2u) x++; else if (k == 3u) y--; else if (k == 4u) y++; else if (k == 5u) z--; else if (k == 6u) z++;
+    if (x < 0 || y < 0 || z < 0 || x >= sx || y >= sy || z >= sz) return;
+    decide_open(grid, (int)x, (int)y, (int)z, sx, sy, sz);
 }
 
 // Orders the tiles of the next frame by the cost the previous frame measured for them (its longest
@@ -151,6 +192,18 @@ __global__ void assemble_strips_kernel(const uint32_t *gathered, uint32_t *out, 
 void launch_tag_cubes(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged, hipStream_t stream) {
     if (!n) return;
     hipLaunchKernelGGL(tag_cubes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, grid, n, cls, from_tagged, to_tagged);
+}
+
+// the OPEN tags of a whole tagged grid / of the cubes around `n` changes (device array of xyz triples): after the tags themselves, on the same stream
+void launch_open_cubes(uint16_t *grid, const int size[3], hipStream_t stream) {
+    const size_t n = (size_t)size[0] * (size_t)size[1] * (size_t)size[2];
+    if (!n) return;
+    hipLaunchKernelGGL(open_cubes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, grid, size[0], size[1], size[2]);
+}
+void launch_open_changed_cubes(uint16_t *grid, const int32_t *xyz, uint32_t n, const int lo[3], const int size[3], hipStream_t stream) {
+    if (!n) return;
+    hipLaunchKernelGGL(open_changed_cubes_kernel, dim3((unsigned)(((size_t)n * 8 + 255) / 256)), dim3(256), 0, stream, grid, xyz, n, lo[0], lo[1], lo[2], size[0], size[1],
+                       size[2]);
 }
 
 void launch_scatter_cubes(uint16_t *grid, uint32_t *light, const int32_t *xyz, const uint16_t *bi, const uint32_t *lt,

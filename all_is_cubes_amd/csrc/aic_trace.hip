@@ -171,7 +171,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 //          Stepping adds ss[axis]: no index arithmetic in the loop, and the lookup is a
 //          scalar-base + 32-bit-offset load (the pool is at most 4 GiB: aic_upload_space checks).
 //   thr    a looked-up code >= thr is a visible surface (voxels: the block's first visible palette code;
-//          cubes with class bits: 0x4000, i.e. class >= 1)
+//          cubes with tag bits: 0x8000, i.e. tag >= kCubeTagVisible)
 // The axis to step along is recomputed from t[] at every step (two v_min_f64, two compares) instead of being
 // carried in the state: it is a pure function of t[], which nothing modifies between steps.
 
@@ -214,7 +214,7 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
     asm volatile("s_mov_b64 %0, %1" : "=s"(pool_bits) : "s"(pool_bits));
     // BIG: block tables past 16384 entries -- plain 16-bit indices in the grid, classes from L.cls
     const uint32_t idx_mask = BIG ? 0xffffu : kCubeIndexMask;
-    const uint32_t outer_thr = BIG ? 0x10000u : (1u << kCubeClassShift);
+    const uint32_t outer_thr = BIG ? 0x10000u : (kCubeTagVisible << kCubeClassShift);
 
     // ---- per-lane state, hot: lives in registers across the stepping loop ----
     double tx = 0, ty = 0, tz = 0, last_t = 0;   // t_max of the current level, t of the step that entered the current cube
@@ -1627,9 +1627,10 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
         mask_t m_inb = __builtin_amdgcn_ballot_w64((st & ST_IN_BLOCK) != 0u);
         mask_t m_opq = __builtin_amdgcn_ballot_w64((st & ST_OPAQUE) != 0u);
         mask_t m_hl = VOL ? __builtin_amdgcn_ballot_w64((st & ST_HAS_LAST) != 0u) : 0ull;
-        // a trip adds at most AIC_STEP_REPS * (AIC_FAST_STEPS + 2) to a lane's step count: lanes this far below the 1000-step cap
-        // (count_step_should_stop, sr.rs:639-651) cannot reach it during the trip
-        const mask_t m_far_from_cap = __builtin_amdgcn_ballot_w64(count < 1000u - (uint32_t)(AIC_STEP_REPS * (AIC_FAST_STEPS + 2)));
+        // a trip adds at most AIC_STEP_REPS * (2 * AIC_FAST_STEPS + 2) to a lane's step count (a fast step may bring a bonus step with it): lanes this
+        // far below the 1000-step cap (count_step_should_stop, sr.rs:639-651) cannot reach it during the trip
+        static_assert(AIC_STEP_REPS * (2 * AIC_FAST_STEPS + 2) < 1000, "the fast steps of a trip stay below the step cap");
+        const mask_t m_far_from_cap = __builtin_amdgcn_ballot_w64(count < 1000u - (uint32_t)(AIC_STEP_REPS * (2 * AIC_FAST_STEPS + 2)));
         // what the trip decides for each lane is collected in masks and written to the event words once, after the loop
         mask_t t_shade = 0ull, t_enter = 0ull, t_fin = 0ull, t_deadpark = 0ull;
         // Fast steps need AIC_FAST_MIN takers while the frame is in full swing (other waves want the issue slots); once this wave has
@@ -1691,7 +1692,20 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                         // level's threshold under the same mask, and the count under the lanes that found nothing. (Left to the compiler,
                         // the pieces come with hazard nops between them, a vector compare for the loop's 64-bit population count,
                         // and six more mask operations.)
+                        // Then the BONUS step. A cube-grid entry that came back OPEN (aic_device.h) says that all six face neighbours are in bounds and
+                        // invisible: whichever way the lane steps next it produces an Invisible TraceStep, so it takes that step here -- the same DDA
+                        // arithmetic, addition by addition, and the count -- with no bounds test (the steps-left counters still decrement), no lookup
+                        // and no wait. Taken when at least AIC_BONUS_MIN lanes can (the block is issued for the whole wave). The lane goes on as after
+                        // any fast step: last_t and lax are the bonus step's, and `raw` is not read again before the lane's next lookup.
                         mask_t sv, mx, by, bx;
+#if AIC_BONUS_MIN > 1
+                        uint32_t bn;
+#define AIC_BONUS_GATE "s_bcnt1_i32_b64 %[bn], %[bx]\n\t" "s_cmp_lt_u32 %[bn], %[bmin]\n\t" "s_cbranch_scc1 1f\n\t"
+#define AIC_BONUS_GATE_OUT , [bn] "=&s"(bn)
+#else
+#define AIC_BONUS_GATE "s_cbranch_scc0 1f\n\t"  // (SCC of the s_andn2: some lane is left)
+#define AIC_BONUS_GATE_OUT
+#endif
                         asm volatile(
                             "s_and_saveexec_b64 %[sv], %[m]\n\t"
                             "v_min_f64 %[lt], %[tx], %[ty]\n\t"
@@ -1725,13 +1739,43 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                             "s_andn2_b64 exec, exec, vcc\n\t"             // an Invisible TraceStep: counted, nothing else
                             "s_mov_b64 %[fb], exec\n\t"
                             "v_add_u32 %[cnt], 1, %[cnt]\n\t"
+                            "v_cmp_gt_u32 vcc, %[inv], %[raw]\n\t"        // tag OPEN ...
+                            "s_andn2_b64 %[bx], vcc, %[inb]\n\t"          // ... of a cube, not a voxel code: the bonus lanes
+                            AIC_BONUS_GATE
+                            "s_mov_b64 exec, %[bx]\n\t"
+                            "v_min_f64 %[lt], %[tx], %[ty]\n\t"
+                            "v_min_f64 %[lt], %[lt], %[tz]\n\t"
+                            "v_cmp_eq_f64 %[mx], %[tz], %[lt]\n\t"        // Z
+                            "v_cmp_eq_f64 vcc, %[ty], %[lt]\n\t"
+                            "s_andn2_b64 vcc, vcc, %[mx]\n\t"             // Y
+                            "s_mov_b64 exec, %[mx]\n\t"
+                            "v_add_f64 %[tz], %[tz], %[tdz]\n\t"
+                            "v_add_u32 %[rz], -1, %[rz]\n\t"
+                            "v_add_u32 %[bo], %[bo], %[ssz]\n\t"
+                            "v_mov_b32 %[lax], 2\n\t"
+                            "s_or_b64 %[mx], %[mx], vcc\n\t"
+                            "s_mov_b64 exec, vcc\n\t"
+                            "v_add_f64 %[ty], %[ty], %[tdy]\n\t"
+                            "v_add_u32 %[ry], -1, %[ry]\n\t"
+                            "v_add_u32 %[bo], %[bo], %[ssy]\n\t"
+                            "v_mov_b32 %[lax], 1\n\t"
+                            "s_andn2_b64 exec, %[bx], %[mx]\n\t"          // X
+                            "v_add_f64 %[tx], %[tx], %[tdx]\n\t"
+                            "v_add_u32 %[rx], -1, %[rx]\n\t"
+                            "v_add_u32 %[bo], %[bo], %[ssx]\n\t"
+                            "v_mov_b32 %[lax], 0\n\t"
+                            "s_mov_b64 exec, %[bx]\n\t"
+                            "v_add_u32 %[cnt], 1, %[cnt]\n\t"
+                            "1:\n\t"
                             "s_mov_b64 exec, %[sv]\n\t"
                             : [tx] "+v"(tx), [ty] "+v"(ty), [tz] "+v"(tz), [lt] "+v"(last_t), [rx] "+v"(rx), [ry] "+v"(ry), [rz] "+v"(rz),
                               [bo] "+v"(boff), [lax] "+v"(lax), [raw] "+v"(raw), [cnt] "+v"(count), [sv] "=&s"(sv), [mx] "=&s"(mx),
-                              [fx] "=&s"(m_fx), [by] "=&s"(by), [bx] "=&s"(bx), [fe] "=&s"(m_fe), [fb] "=&s"(m_fb)
+                              [fx] "=&s"(m_fx), [by] "=&s"(by), [bx] "=&s"(bx), [fe] "=&s"(m_fe), [fb] "=&s"(m_fb) AIC_BONUS_GATE_OUT
                             : [tdx] "v"(tdx), [tdy] "v"(tdy), [tdz] "v"(tdz), [ssx] "v"(ssx), [ssy] "v"(ssy), [ssz] "v"(ssz), [m] "s"(m_f),
-                              [pool] "s"(pool_bits), [thr] "v"(thr)
+                              [pool] "s"(pool_bits), [thr] "v"(thr), [inb] "s"(m_inb), [inv] "n"(kCubeTagInvisible << kCubeClassShift), [bmin] "n"(AIC_BONUS_MIN)
                             : "memory", "vcc", "scc");
+#undef AIC_BONUS_GATE
+#undef AIC_BONUS_GATE_OUT
                     }
                     AIC_PROF(20, 1);
                     AIC_PROF(21, __popcll(m_f));
@@ -1780,7 +1824,7 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                 m_blk = __builtin_amdgcn_ballot_w64(cls == 2u);
                 m_surf = (__builtin_amdgcn_ballot_w64(raw >= thr) & m_lookup & m_inb) | __builtin_amdgcn_ballot_w64(cls == 1u);
             } else {
-                m_blk = __builtin_amdgcn_ballot_w64(raw >= (2u << kCubeClassShift)) & m_lookup & ~m_inb;
+                m_blk = __builtin_amdgcn_ballot_w64(raw >= (kCubeTagRecursive << kCubeClassShift)) & m_lookup & ~m_inb;
                 m_surf = __builtin_amdgcn_ballot_w64(raw >= thr) & m_lookup & ~m_blk;
             }
             const mask_t m_some = m_blk | m_surf;
@@ -1837,7 +1881,7 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                     : [tx] "+v"(tx), [ty] "+v"(ty), [tz] "+v"(tz), [rx] "+v"(rx), [ry] "+v"(ry), [rz] "+v"(rz),
                       [bo] "+v"(boff), [ssx] "+v"(ssx), [ssy] "+v"(ssy), [ssz] "+v"(ssz), [thr] "+v"(thr), [lax] "+v"(lax), [st] "+v"(st),
                       [t] "=&v"(t_), [sv] "=&s"(sv), [nd] "=&s"(m_newdead)
-                    : [a64] "v"(lds64), [a32] "v"(lds32), [m] "s"(m_leave), [osx] "s"(ostx), [osy] "s"(osty), [othr] "n"(BIG ? 0x10000u : (1u << kCubeClassShift)),
+                    : [a64] "v"(lds64), [a32] "v"(lds32), [m] "s"(m_leave), [osx] "s"(ostx), [osy] "s"(osty), [othr] "n"(BIG ? 0x10000u : (kCubeTagVisible << kCubeClassShift)),
                       [alive] "n"(ST_OUTER_ALIVE), [notinb] "n"(~ST_IN_BLOCK),
                       [o0] "n"(C_STX * NCOL * 8), [o1] "n"(C_STY * NCOL * 8), [o2] "n"(C_STZ * NCOL * 8),
                       [p0] "n"(K_SRX * NCOL * 4), [p1] "n"(K_SRY * NCOL * 4),

@@ -41,6 +41,10 @@
 #define AIC_FAST_MIN 16  // ... while at least this many lanes of the wave can take one (at least 1)
 #endif
 
+#ifndef AIC_BONUS_MIN
+#define AIC_BONUS_MIN 1  // a fast step that found OPEN cubes (aic_device.h) takes their lanes one step further without a lookup if at least this many lanes can (1 .. 64)
+#endif
+
 // ---- the lane exchange between the waves of a workgroup (the XC variants; aic_trace.hip "Lane exchange")
 #ifndef AIC_XWG_THREADS
 #define AIC_XWG_THREADS 256  // threads of a workgroup of the exchanging variants (four per CU, a pool of 72 each: measured ahead of two workgroups of 512 with a pool of 160,

@@ -232,8 +232,10 @@ void launch_bloom(const BloomGeom &g, const BloomParams &p, hipStream_t stream) 
 void launch_tag_cubes(uint16_t *grid, size_t n, const uint32_t *cls, int from_tagged, int to_tagged, hipStream_t stream) {
     rec("launch_tag_cubes %s n %zu cls %s %d %d %s", P(grid), n, P(cls), from_tagged, to_tagged, S(stream));
 }
+void launch_open_cubes(uint16_t *grid, const int size[3], hipStream_t stream) { rec("launch_open_cubes %s size %d %d %d %s", P(grid), size[0], size[1], size[2], S(stream)); }
 // (what the scenarios never reach: scene updates, strip assembly, the probes)
 void launch_scatter_cubes(uint16_t *, uint32_t *, const int32_t *, const uint16_t *, const uint32_t *, uint32_t, const int[3], const int[3], const uint32_t *, hipStream_t) { rec("launch_scatter_cubes"); }
+void launch_open_changed_cubes(uint16_t *, const int32_t *, uint32_t, const int[3], const int[3], hipStream_t) { rec("launch_open_changed_cubes"); }
 hipError_t launch_reproject(const ReprojectGeom &, const ReprojectParams &, hipStream_t) { rec("launch_reproject"); return hipSuccess; }
 hipError_t launch_pick(const PickParams &, hipStream_t) { rec("launch_pick"); return hipSuccess; }
 void launch_present(const BloomGeom &, const PresentParams &, hipStream_t) { rec("launch_present"); }
