@@ -5,8 +5,8 @@
 // (all-is-cubes-render/src/raytracer/renderer.rs:35-54), and launches the kernels of
 // aic_trace.hip (aic_launch.h) on a private HIP stream. No CPU rendering path exists here: every entry
 // point fails with AIC_ERR_NO_DEVICE / AIC_ERR_DEVICE when HIP is unusable.
-// Here: the context, scene upload and update, options, strip assembly, synchronisation and the probes. The frame
-// path -- everything that submits or waits for a trace -- is aic_frame.cpp, the light updater aic_light_host.cpp.
+// Here: the context, scene upload and update, options, strip assembly, synchronisation and the probes. The frame path -- everything that submits or
+// waits for a trace -- is aic_frame.cpp, what acts on a resident Split frame aic_split_ops.cpp, the light updater aic_light_host.cpp.
 
 #include <hip/hip_runtime.h>
 
@@ -28,9 +28,6 @@
 #include "aic_ctx.h"
 #include "aic_device.h"
 #include "aic_launch.h"
-#include "aic_pick.h"
-#include "aic_present_lines.h"
-#include "aic_reproject.h"
 
 using namespace aic;
 
@@ -929,314 +926,6 @@ int aic_probe_bloom(aic_ctx *c, uint32_t width, uint32_t height, const float *co
     if (out_mip0) HIP_TRY(c, hipMemcpyAsync(out_mip0, sb.bloom_mips.p, (size_t)geom.mw[0] * geom.mh[0] * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (mip0_size) { mip0_size[0] = geom.mw[0]; mip0_size[1] = geom.mh[0]; }
-    return AIC_OK;
-}
-
-int aic_reproject_geometry(uint32_t width, uint32_t height, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes) {
-    if (width > 65535u || height > 65535u) return AIC_ERR_INVALID;
-    const ReprojectGeom g = reproject_geometry(width, height);
-    if (levels) *levels = g.levels;
-    if (t0) { t0[0] = g.mw[0]; t0[1] = g.mh[0]; }
-    if (scratch_bytes) *scratch_bytes = g.scratch_bytes();
-    return AIC_OK;
-}
-
-int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src, void *dst, aic_reproject_info *info) {
-    if (!c || !d || !src || !dst) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: bad argument");
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (d->width > 65535u || d->height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: frame dimensions above 65535 are not supported");
-    if (d->flags & ~AIC_REPROJECT_KEEP_SPLATS) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: unknown flag bits");
-    if (((uintptr_t)src & 7u) || ((uintptr_t)dst & 7u)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a Split frame starts at an 8-byte boundary");
-    for (float v : d->reprojection)
-        if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a component of the reprojection matrix is not finite");
-    for (float v : d->inverse_projection_zw)
-        if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a component of inverse_projection_zw is not finite");
-    const ReprojectGeom g = reproject_geometry(d->width, d->height);
-    const size_t npix = g.npix(), frame_bytes = npix * 12;
-    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
-    if (s0 == d0 || (s0 < d0 + frame_bytes && d0 < s0 + frame_bytes)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: src and dst overlap");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a submitted frame still occupies slot 0 (aic_render_wait it first)");
-    if (!npix) return AIC_OK;  // (nothing written: the splat image of an earlier call stays what aic_pick_pixels reads)
-    const unsigned char *scratch_before = c->reproject_scratch.p;
-    hipError_t e = c->reproject_scratch.ensure(g.scratch_bytes());
-    if (e != hipSuccess) return hip_fail(c, "alloc reprojection scratch", e);
-    // a new allocation has lost the splat image aic_pick_pixels reads: if this call then fails, there is none
-    if (c->reproject_scratch.p != scratch_before) c->reproject_valid_w = c->reproject_valid_h = 0u;
-    aic_ctx::FrameSlot &fs = c->slots[0];
-    ReprojectParams rp;
-    rp.src_color = (const uint2 *)src;
-    rp.src_depth = (const float *)((const unsigned char *)src + npix * 8);
-    rp.dst_color = (uint2 *)dst;
-    rp.dst_depth = (float *)((unsigned char *)dst + npix * 8);
-    rp.scratch = c->reproject_scratch.p;
-    std::memcpy(rp.m, d->reprojection, sizeof(rp.m));
-    std::memcpy(rp.ipzw, d->inverse_projection_zw, sizeof(rp.ipzw));
-    rp.keep_splats = (d->flags & AIC_REPROJECT_KEEP_SPLATS) ? 1u : 0u;
-    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
-    if ((e = launch_reproject(g, rp, fs.stream)) != hipSuccess) return hip_fail(c, "launch reprojection", e);
-    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
-    ReprojectCounts counts;
-    HIP_TRY(c, hipMemcpyAsync(&counts, reproject_counts(g, c->reproject_scratch.p), sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
-    HIP_TRY(c, hipStreamSynchronize(fs.stream));
-    c->reproject_valid_w = d->width;
-    c->reproject_valid_h = d->height;
-    if (info) {
-        info->n_splats = counts.n_splats;
-        info->n_dropped = counts.n_dropped;
-        info->n_gaps = counts.n_gaps;
-        info->n_unfilled = counts.n_unfilled;
-        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
-        info->levels = g.levels;
-        info->t0[0] = g.mw[0];
-        info->t0[1] = g.mh[0];
-    }
-    return AIC_OK;
-}
-
-int aic_pick_pixels(aic_ctx *c, const aic_pick_desc *d, const uint32_t *order, uint32_t *pixels_out, aic_pick_info *info) {
-    if (!c || !d || !info) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: bad argument");
-    std::memset(info, 0, sizeof(*info));
-    if (d->width > 65535u || d->height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: frame dimensions above 65535 are not supported");
-    if (d->flags) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: unknown flag bits");
-    if (d->n > 2048u * 65535u) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: more than 2048 x 65535 picks");
-    if (d->n && !pixels_out) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: no list to write the picks to");
-    if (((uintptr_t)pixels_out & 3u) || ((uintptr_t)order & 3u)) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: a list starts at a 4-byte boundary");
-    const uint64_t count = (uint64_t)d->width * d->height;
-    if (d->n && !count) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: an empty frame has no pixel to pick");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: a submitted frame still occupies slot 0 (aic_render_wait it first)");
-    if (!d->n) return AIC_OK;  // (and so count == 0)
-    if (d->max_unknown && (!c->reproject_scratch.p || c->reproject_valid_w != d->width || c->reproject_valid_h != d->height))
-        return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: max_unknown needs the context's last successful aic_reproject_split to be of this size");
-    hipError_t e;
-    if (d->max_unknown && (e = c->pick_scratch.ensure(pick_scratch_words(count))) != hipSuccess) return hip_fail(c, "alloc pick scratch", e);
-    aic_ctx::FrameSlot &fs = c->slots[0];
-    PickParams pp;
-    pp.R = d->max_unknown ? (const uint2 *)(c->reproject_scratch.p + reproject_geometry(d->width, d->height).keys_bytes()) : nullptr;
-    pp.order = order;
-    pp.out = pixels_out;
-    pp.scratch = d->max_unknown ? c->pick_scratch.p : nullptr;
-    pp.count = (uint32_t)count;  // at most 65535^2
-    pp.n = d->n;
-    pp.max_unknown = d->max_unknown;
-    pp.skip_unknown = d->skip_unknown;
-    pp.cursor = d->cursor;
-    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
-    if ((e = launch_pick(pp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick", e);
-    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
-    PickRecord rec = {};
-    if (d->max_unknown) {
-        HIP_TRY(c, hipMemcpyAsync(&rec, c->pick_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
-    } else {  // nothing was looked at: the whole list is the picker's
-        rec.n_from_order = d->n;
-        rec.next_cursor = d->cursor + d->n;
-    }
-    HIP_TRY(c, hipStreamSynchronize(fs.stream));
-    info->n_unknown = rec.n_unknown;
-    info->next_cursor = rec.next_cursor;
-    info->n_from_unknown = rec.n_from_unknown;
-    info->n_from_order = rec.n_from_order;
-    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
-    return AIC_OK;
-}
-
-namespace {
-// the checks aic_present_geometry and aic_present_split share; nullptr: the sizes are fine
-const char *present_sizes_invalid(uint32_t sw, uint32_t sh, uint32_t ow, uint32_t oh) {
-    if (sw > 65535u || sh > 65535u || ow > 65535u || oh > 65535u) return "dimensions above 65535 are not supported";
-    if ((uint64_t)ow * oh > AIC_PRESENT_MAX_PIXELS) return "an output of more than 2^31 pixels is not supported";
-    if (ow && oh && (!sw || !sh)) return "a source of zero size cannot fill an output";
-    return nullptr;
-}
-size_t present_scratch_texels(const BloomGeom &g, uint32_t sw, uint32_t sh) {
-    return (size_t)g.texels + ((sw != g.width || sh != g.height) ? (size_t)g.width * g.height : 0);
-}
-}  // namespace
-
-int aic_present_geometry(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes) {
-    if (present_sizes_invalid(src_w, src_h, out_w, out_h)) return AIC_ERR_INVALID;
-    const bool empty = !out_w || !out_h;
-    const BloomGeom g = bloom_geometry(out_w, out_h);
-    if (levels) *levels = empty ? 0u : g.levels;
-    if (t0) { t0[0] = empty ? 0u : g.mw[0]; t0[1] = empty ? 0u : g.mh[0]; }
-    if (scratch_bytes) *scratch_bytes = empty ? 0u : (uint64_t)present_scratch_texels(g, src_w, src_h) * 8u;
-    return AIC_OK;
-}
-
-int aic_present_split(aic_ctx *c, const aic_present_desc *d, const void *src, void *out, int out_is_device, aic_present_info *info) {
-    if (!c || !d || !src || !out) return fail(c, AIC_ERR_INVALID, "aic_present_split: bad argument");
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (const char *why = present_sizes_invalid(d->src_width, d->src_height, d->out_width, d->out_height)) {
-        const std::string msg = std::string("aic_present_split: ") + why;
-        return fail(c, AIC_ERR_INVALID, msg.c_str());
-    }
-    if (d->flags & ~AIC_PRESENT_OUT_F16) return fail(c, AIC_ERR_INVALID, "aic_present_split: unknown flag bits");
-    if (!(d->bloom_intensity >= 0.f) || std::isinf(d->bloom_intensity)) return fail(c, AIC_ERR_INVALID, "aic_present_split: bloom_intensity is NaN, negative or infinite");
-    if (!(d->maximum_intensity >= 0.f)) return fail(c, AIC_ERR_INVALID, "aic_present_split: maximum_intensity is NaN or negative");
-    if (d->tone_mapping != 0 && d->tone_mapping != 1) return fail(c, AIC_ERR_INVALID, "aic_present_split: tone_mapping is neither 0 (Clamp) nor 1 (Reinhard)");
-    const bool f16 = (d->flags & AIC_PRESENT_OUT_F16) != 0;
-    const size_t px_bytes = f16 ? 8 : 4;
-    const size_t npix = (size_t)d->out_width * d->out_height, src_bytes = (size_t)d->src_width * d->src_height * 12, out_bytes = npix * px_bytes;
-    if ((uintptr_t)src & 7u) return fail(c, AIC_ERR_INVALID, "aic_present_split: a Split frame starts at an 8-byte boundary");
-    if (out_is_device) {
-        const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
-        if (o0 & (px_bytes - 1)) return fail(c, AIC_ERR_INVALID, "aic_present_split: a device out starts at its element's boundary (4 bytes for RGBA8, 8 for f16)");
-        if (s0 < o0 + out_bytes && o0 < s0 + src_bytes) return fail(c, AIC_ERR_INVALID, "aic_present_split: out overlaps src");
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_present_split: a submitted frame still occupies slot 0 (aic_render_wait it first)");
-    if (!npix) return AIC_OK;
-    const BloomGeom g = bloom_geometry(d->out_width, d->out_height);
-    const bool bloomed = d->bloom_intensity > 0.f;
-    hipError_t e;
-    if (bloomed && (e = c->present_scratch.ensure(present_scratch_texels(g, d->src_width, d->src_height))) != hipSuccess) return hip_fail(c, "alloc presentation scratch", e);
-    if (!out_is_device && (e = c->out.ensure(out_bytes / 4)) != hipSuccess) return hip_fail(c, "alloc output", e);
-    aic_ctx::FrameSlot &fs = c->slots[0];
-    PresentParams pp;
-    pp.src = (const uint2 *)src;
-    pp.src_width = d->src_width;
-    pp.src_height = d->src_height;
-    pp.mips = bloomed ? c->present_scratch.p : nullptr;
-    pp.scene = bloomed ? c->present_scratch.p + g.texels : nullptr;
-    pp.out = out_is_device ? out : (void *)c->out.p;
-    pp.intensity = d->bloom_intensity;
-    pp.tone_mapping = d->tone_mapping;
-    pp.maximum_intensity = d->maximum_intensity;
-    pp.srgb_thr = c->srgb_thr.p;
-    pp.out_f16 = f16;
-    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
-    launch_present(g, pp, fs.stream);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(c, "launch presentation", e);
-    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
-    if (!out_is_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, out_bytes, hipMemcpyDeviceToHost, fs.stream));
-    HIP_TRY(c, hipStreamSynchronize(fs.stream));
-    if (info) {
-        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
-        info->levels = g.levels;
-        info->t0[0] = g.mw[0];
-        info->t0[1] = g.mh[0];
-        info->bloomed = bloomed ? 1u : 0u;
-    }
-    return AIC_OK;
-}
-
-namespace {
-// aic_present_split's own rejections of its arguments, in its order, for aic_present_split_lines (aic_present_split keeps its code as it stands); 0: none
-int present_args_invalid(aic_ctx *c, const aic_present_desc *d, const void *src, const void *out, int out_is_device, aic_present_info *info, const char *who) {
-    const auto reject = [&](const char *why) { return fail(c, AIC_ERR_INVALID, (std::string(who) + ": " + why).c_str()); };
-    if (!c || !d || !src || !out) return reject("bad argument");
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (const char *why = present_sizes_invalid(d->src_width, d->src_height, d->out_width, d->out_height)) return reject(why);
-    if (d->flags & ~AIC_PRESENT_OUT_F16) return reject("unknown flag bits");
-    if (!(d->bloom_intensity >= 0.f) || std::isinf(d->bloom_intensity)) return reject("bloom_intensity is NaN, negative or infinite");
-    if (!(d->maximum_intensity >= 0.f)) return reject("maximum_intensity is NaN or negative");
-    if (d->tone_mapping != 0 && d->tone_mapping != 1) return reject("tone_mapping is neither 0 (Clamp) nor 1 (Reinhard)");
-    const size_t px_bytes = (d->flags & AIC_PRESENT_OUT_F16) ? 8 : 4;
-    const size_t src_bytes = (size_t)d->src_width * d->src_height * 12, out_bytes = (size_t)d->out_width * d->out_height * px_bytes;
-    if ((uintptr_t)src & 7u) return reject("a Split frame starts at an 8-byte boundary");
-    if (out_is_device) {
-        const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
-        if (o0 & (px_bytes - 1)) return reject("a device out starts at its element's boundary (4 bytes for RGBA8, 8 for f16)");
-        if (s0 < o0 + out_bytes && o0 < s0 + src_bytes) return reject("out overlaps src");
-    }
-    return 0;
-}
-}  // namespace
-
-int aic_present_lines_scratch(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t n_lines, uint64_t *bytes) {
-    if (present_sizes_invalid(src_w, src_h, out_w, out_h) || n_lines > AIC_LINES_MAX) return AIC_ERR_INVALID;
-    if (bytes) *bytes = (n_lines && out_w && out_h) ? (uint64_t)lines_layout(out_w, out_h, n_lines).bytes : 0u;
-    return AIC_OK;
-}
-
-int aic_present_split_lines(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const void *src, void *out, int out_is_device, aic_present_info *info,
-                            aic_lines_info *lines_info) {
-    if (lines_info) std::memset(lines_info, 0, sizeof(*lines_info));
-    if (c && ld) {  // (the rejections this call adds; a NULL ctx is aic_present_split's to report)
-        if (info) std::memset(info, 0, sizeof(*info));
-        if (ld->flags & ~AIC_LINES_DEVICE) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: unknown line flag bits");
-        if (ld->n_lines > AIC_LINES_MAX) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: more than AIC_LINES_MAX lines");
-        if (ld->n_lines && !ld->vertices) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: no vertices");
-        if (ld->n_lines && (ld->flags & AIC_LINES_DEVICE) && ((uintptr_t)ld->vertices & 3u))
-            return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: device vertices start at a 4-byte boundary");
-        for (float v : ld->view_projection)
-            if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: a component of view_projection is not finite");
-    }
-    if (!c || !ld || !ld->n_lines) return aic_present_split(c, d, src, out, out_is_device, info);
-    if (const int rc = present_args_invalid(c, d, src, out, out_is_device, info, "aic_present_split_lines")) return rc;
-    const bool f16 = (d->flags & AIC_PRESENT_OUT_F16) != 0;
-    const size_t npix = (size_t)d->out_width * d->out_height, out_bytes = npix * (f16 ? 8 : 4);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: a submitted frame still occupies slot 0 (aic_render_wait it first)");
-    if (!npix) return AIC_OK;
-    const BloomGeom g = bloom_geometry(d->out_width, d->out_height);
-    const bool bloomed = d->bloom_intensity > 0.f, staged = !(ld->flags & AIC_LINES_DEVICE);
-    const LinesLayout lay = lines_layout(d->out_width, d->out_height, staged ? ld->n_lines : 0u);
-    hipError_t e;
-    // (S is the line scratch's: the chain reads it as a frame of the output's size, so the presentation scratch holds the mips alone)
-    if (bloomed && (e = c->present_scratch.ensure(g.texels)) != hipSuccess) return hip_fail(c, "alloc presentation scratch", e);
-    const unsigned char *scratch_before = c->lines_scratch.p;
-    if ((e = c->lines_scratch.ensure(lay.bytes)) != hipSuccess) return hip_fail(c, "alloc line scratch", e);
-    if (c->lines_scratch.p != scratch_before) c->lines_keys_clean = 0;
-    if (!out_is_device && (e = c->out.ensure(out_bytes / 4)) != hipSuccess) return hip_fail(c, "alloc output", e);
-    aic_ctx::FrameSlot &fs = c->slots[0];
-    unsigned char *const ls = c->lines_scratch.p;
-    PresentParams pp;
-    pp.src = (const uint2 *)src;
-    pp.src_width = d->src_width;
-    pp.src_height = d->src_height;
-    pp.mips = bloomed ? c->present_scratch.p : nullptr;
-    pp.scene = (uint2 *)(ls + lay.scene);
-    pp.out = out_is_device ? out : (void *)c->out.p;
-    pp.intensity = d->bloom_intensity;
-    pp.tone_mapping = d->tone_mapping;
-    pp.maximum_intensity = d->maximum_intensity;
-    pp.srgb_thr = c->srgb_thr.p;
-    pp.out_f16 = f16;
-    LinesParams lp;
-    lp.vertices = staged ? (const float *)(ls + lay.vertices) : (const float *)ld->vertices;
-    lp.n_lines = ld->n_lines;
-    std::memcpy(lp.m, ld->view_projection, sizeof(lp.m));
-    lp.depth = (const uint32_t *)((const unsigned char *)src + (size_t)d->src_width * d->src_height * 8);
-    lp.src_width = d->src_width;
-    lp.src_height = d->src_height;
-    lp.width = d->out_width;
-    lp.height = d->out_height;
-    lp.keys = (unsigned long long *)(ls + lay.keys);
-    lp.scene = pp.scene;
-    lp.counts = (LinesCounts *)(ls + lay.counts);
-    lp.reset_keys = !c->sw.lines_clear_keys;
-    lp.clear_keys = !lp.reset_keys || c->lines_keys_clean < npix;
-    c->lines_keys_clean = 0;  // until the call has finished
-    if (staged) HIP_TRY(c, hipMemcpyAsync(ls + lay.vertices, ld->vertices, (size_t)ld->n_lines * sizeof(aic_line_vertex) * 2, hipMemcpyHostToDevice, fs.stream));
-    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
-    launch_present_scene(g, pp, fs.stream);
-    if ((e = launch_present_lines(lp, fs.stream)) != hipSuccess) return hip_fail(c, "launch line pass", e);
-    pp.src = pp.scene;  // S' shown at its own size
-    pp.src_width = d->out_width;
-    pp.src_height = d->out_height;
-    launch_present(g, pp, fs.stream);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(c, "launch presentation", e);
-    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
-    LinesCounts counts;
-    HIP_TRY(c, hipMemcpyAsync(&counts, lp.counts, sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
-    if (!out_is_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, out_bytes, hipMemcpyDeviceToHost, fs.stream));
-    HIP_TRY(c, hipStreamSynchronize(fs.stream));
-    if (lp.reset_keys) c->lines_keys_clean = npix;
-    if (lines_info) {
-        lines_info->n_clipped_away = counts.n_clipped_away;
-        lines_info->n_fragments = counts.n_fragments;
-        lines_info->n_passed = counts.n_passed;
-        lines_info->n_pixels = counts.n_pixels;
-    }
-    if (info) {
-        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
-        info->levels = g.levels;
-        info->t0[0] = g.mw[0];
-        info->t0[1] = g.mh[0];
-        info->bloomed = bloomed ? 1u : 0u;
-    }
     return AIC_OK;
 }
 

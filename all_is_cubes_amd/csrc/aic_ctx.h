@@ -1,7 +1,8 @@
 // aic_ctx.h -- what the translation units of the C ABI's host side share: the context behind the opaque `aic_ctx` of
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
-// (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace) and
-// aic_light_host.cpp only (all three are written inside `using namespace aic`, and so is this header). Whatever one of the
+// (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
+// aic_split_ops.cpp (reprojection, picking and presentation of a resident Split frame) and aic_light_host.cpp (the light updater)
+// only (all four are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
 #pragma once

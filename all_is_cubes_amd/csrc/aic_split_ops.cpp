@@ -1,0 +1,306 @@
+// aic_split_ops.cpp -- the operations of the C ABI declared in include/aic_hip.h that act on a resident Split frame: reproject it (aic_reproject_split),
+// pick the next pixels to trace (aic_pick_pixels), present it (aic_present_split) and present it with a line list drawn in (aic_present_split_lines),
+// with the size queries that go with them (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch).
+//
+// All four run on slot 0's stream, synchronously, and are written to one pattern: check the arguments, `begin`, size the context's scratch, fill the
+// launcher's parameters, then ev0, the launches, ev1, the copies back to the host and one synchronise, then the context's state and the caller's info.
+// Each rule they share is written once, in the anonymous namespace below. Of aic_abi.cpp it uses what aic_ctx.h declares; aic_cursor_wireframe,
+// which needs no context, is aic_cursor.cpp. tools/submit_record/split_ops_record.cpp drives every path of this file against a recording fake of the
+// HIP runtime.
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../../include/aic_hip.h"
+#include "aic_bloom.h"
+#include "aic_ctx.h"
+#include "aic_pick.h"
+#include "aic_present_lines.h"
+#include "aic_reproject.h"
+
+using namespace aic;
+
+namespace {
+
+// the kernels address a frame's pixels by 16-bit coordinates
+bool above_65535(uint32_t w, uint32_t h) { return w > 65535u || h > 65535u; }
+
+int reject(aic_ctx *c, const char *who, const char *why) { return fail(c, AIC_ERR_INVALID, (std::string(who) + ": " + why).c_str()); }
+
+// What every operation opens with once its arguments are checked: slot 0's stream is the one it queues on. `who` is the entry point the message names.
+int begin(aic_ctx *c, const char *who) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->slots[0].busy) return reject(c, who, "a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    return AIC_OK;
+}
+
+// the checks every size query and presentation shares; nullptr: the sizes are fine
+const char *present_sizes_invalid(uint32_t sw, uint32_t sh, uint32_t ow, uint32_t oh) {
+    if (above_65535(sw, sh) || above_65535(ow, oh)) return "dimensions above 65535 are not supported";
+    if ((uint64_t)ow * oh > AIC_PRESENT_MAX_PIXELS) return "an output of more than 2^31 pixels is not supported";
+    if (ow && oh && (!sw || !sh)) return "a source of zero size cannot fill an output";
+    return nullptr;
+}
+size_t present_scratch_texels(const BloomGeom &g, uint32_t sw, uint32_t sh) {
+    return (size_t)g.texels + ((sw != g.width || sh != g.height) ? (size_t)g.width * g.height : 0);
+}
+
+// a presentation's rejections of its arguments, in the order the header lists them, under the entry point's name; 0: none
+int present_args_invalid(aic_ctx *c, const aic_present_desc *d, const void *src, const void *out, int out_is_device, aic_present_info *info, const char *who) {
+    if (!c || !d || !src || !out) return reject(c, who, "bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (const char *why = present_sizes_invalid(d->src_width, d->src_height, d->out_width, d->out_height)) return reject(c, who, why);
+    if (d->flags & ~AIC_PRESENT_OUT_F16) return reject(c, who, "unknown flag bits");
+    if (!(d->bloom_intensity >= 0.f) || std::isinf(d->bloom_intensity)) return reject(c, who, "bloom_intensity is NaN, negative or infinite");
+    if (!(d->maximum_intensity >= 0.f)) return reject(c, who, "maximum_intensity is NaN or negative");
+    if (d->tone_mapping != 0 && d->tone_mapping != 1) return reject(c, who, "tone_mapping is neither 0 (Clamp) nor 1 (Reinhard)");
+    const size_t px_bytes = (d->flags & AIC_PRESENT_OUT_F16) ? 8 : 4;
+    const size_t src_bytes = (size_t)d->src_width * d->src_height * 12, out_bytes = (size_t)d->out_width * d->out_height * px_bytes;
+    if ((uintptr_t)src & 7u) return reject(c, who, "a Split frame starts at an 8-byte boundary");
+    if (out_is_device) {
+        const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
+        if (o0 & (px_bytes - 1)) return reject(c, who, "a device out starts at its element's boundary (4 bytes for RGBA8, 8 for f16)");
+        if (s0 < o0 + out_bytes && o0 < s0 + src_bytes) return reject(c, who, "out overlaps src");
+    }
+    return 0;
+}
+
+// A presentation, with the lines of `ld` drawn into the scene or (ld == nullptr) without: the body of aic_present_split and aic_present_split_lines.
+// Without lines the frame goes through launch_present as it is. With lines launch_present_scene stores the scene S in the line scratch, the line pass
+// draws into it, and launch_present shows that S' at its own size -- so the presentation scratch then holds the chain's mips alone.
+int present(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const void *src, void *out, int out_is_device, aic_present_info *info,
+            aic_lines_info *lines_info, const char *who) {
+    if (const int rc = present_args_invalid(c, d, src, out, out_is_device, info, who)) return rc;
+    const bool f16 = (d->flags & AIC_PRESENT_OUT_F16) != 0;
+    const size_t npix = (size_t)d->out_width * d->out_height, out_bytes = npix * (f16 ? 8 : 4);
+    if (const int rc = begin(c, who)) return rc;
+    if (!npix) return AIC_OK;
+    const BloomGeom g = bloom_geometry(d->out_width, d->out_height);
+    const bool bloomed = d->bloom_intensity > 0.f, staged = ld && !(ld->flags & AIC_LINES_DEVICE);
+    hipError_t e;
+    if (bloomed && (e = c->present_scratch.ensure(ld ? g.texels : present_scratch_texels(g, d->src_width, d->src_height))) != hipSuccess)
+        return hip_fail(c, "alloc presentation scratch", e);
+    LinesLayout lay;
+    if (ld) {
+        lay = lines_layout(d->out_width, d->out_height, staged ? ld->n_lines : 0u);
+        const unsigned char *scratch_before = c->lines_scratch.p;
+        if ((e = c->lines_scratch.ensure(lay.bytes)) != hipSuccess) return hip_fail(c, "alloc line scratch", e);
+        if (c->lines_scratch.p != scratch_before) c->lines_keys_clean = 0;
+    }
+    if (!out_is_device && (e = c->out.ensure(out_bytes / 4)) != hipSuccess) return hip_fail(c, "alloc output", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    unsigned char *const ls = c->lines_scratch.p;
+    PresentParams pp;
+    pp.src = (const uint2 *)src;
+    pp.src_width = d->src_width;
+    pp.src_height = d->src_height;
+    pp.mips = bloomed ? c->present_scratch.p : nullptr;
+    pp.scene = ld ? (uint2 *)(ls + lay.scene) : (bloomed ? c->present_scratch.p + g.texels : nullptr);
+    pp.out = out_is_device ? out : (void *)c->out.p;
+    pp.intensity = d->bloom_intensity;
+    pp.tone_mapping = d->tone_mapping;
+    pp.maximum_intensity = d->maximum_intensity;
+    pp.srgb_thr = c->srgb_thr.p;
+    pp.out_f16 = f16;
+    LinesParams lp = {};
+    if (ld) {
+        lp.vertices = staged ? (const float *)(ls + lay.vertices) : (const float *)ld->vertices;
+        lp.n_lines = ld->n_lines;
+        std::memcpy(lp.m, ld->view_projection, sizeof(lp.m));
+        lp.depth = (const uint32_t *)((const unsigned char *)src + (size_t)d->src_width * d->src_height * 8);
+        lp.src_width = d->src_width;
+        lp.src_height = d->src_height;
+        lp.width = d->out_width;
+        lp.height = d->out_height;
+        lp.keys = (unsigned long long *)(ls + lay.keys);
+        lp.scene = pp.scene;
+        lp.counts = (LinesCounts *)(ls + lay.counts);
+        lp.reset_keys = !c->sw.lines_clear_keys;
+        lp.clear_keys = !lp.reset_keys || c->lines_keys_clean < npix;
+        c->lines_keys_clean = 0;  // until the call has finished
+        if (staged) HIP_TRY(c, hipMemcpyAsync(ls + lay.vertices, ld->vertices, (size_t)ld->n_lines * sizeof(aic_line_vertex) * 2, hipMemcpyHostToDevice, fs.stream));
+    }
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if (ld) {
+        launch_present_scene(g, pp, fs.stream);
+        if ((e = launch_present_lines(lp, fs.stream)) != hipSuccess) return hip_fail(c, "launch line pass", e);
+        pp.src = pp.scene;  // S' shown at its own size
+        pp.src_width = d->out_width;
+        pp.src_height = d->out_height;
+    }
+    launch_present(g, pp, fs.stream);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(c, "launch presentation", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    LinesCounts counts;
+    if (ld) HIP_TRY(c, hipMemcpyAsync(&counts, lp.counts, sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
+    if (!out_is_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, out_bytes, hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    if (ld && lp.reset_keys) c->lines_keys_clean = npix;
+    if (ld && lines_info) {
+        lines_info->n_clipped_away = counts.n_clipped_away;
+        lines_info->n_fragments = counts.n_fragments;
+        lines_info->n_passed = counts.n_passed;
+        lines_info->n_pixels = counts.n_pixels;
+    }
+    if (info) {
+        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+        info->levels = g.levels;
+        info->t0[0] = g.mw[0];
+        info->t0[1] = g.mh[0];
+        info->bloomed = bloomed ? 1u : 0u;
+    }
+    return AIC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aic_reproject_geometry(uint32_t width, uint32_t height, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes) {
+    if (above_65535(width, height)) return AIC_ERR_INVALID;
+    const ReprojectGeom g = reproject_geometry(width, height);
+    if (levels) *levels = g.levels;
+    if (t0) { t0[0] = g.mw[0]; t0[1] = g.mh[0]; }
+    if (scratch_bytes) *scratch_bytes = g.scratch_bytes();
+    return AIC_OK;
+}
+
+int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src, void *dst, aic_reproject_info *info) {
+    if (!c || !d || !src || !dst) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (above_65535(d->width, d->height)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: frame dimensions above 65535 are not supported");
+    if (d->flags & ~AIC_REPROJECT_KEEP_SPLATS) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: unknown flag bits");
+    if (((uintptr_t)src & 7u) || ((uintptr_t)dst & 7u)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a Split frame starts at an 8-byte boundary");
+    for (float v : d->reprojection)
+        if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a component of the reprojection matrix is not finite");
+    for (float v : d->inverse_projection_zw)
+        if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a component of inverse_projection_zw is not finite");
+    const ReprojectGeom g = reproject_geometry(d->width, d->height);
+    const size_t npix = g.npix(), frame_bytes = npix * 12;
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    if (s0 == d0 || (s0 < d0 + frame_bytes && d0 < s0 + frame_bytes)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: src and dst overlap");
+    if (const int rc = begin(c, "aic_reproject_split")) return rc;
+    if (!npix) return AIC_OK;  // (nothing written: the splat image of an earlier call stays what aic_pick_pixels reads)
+    const unsigned char *scratch_before = c->reproject_scratch.p;
+    hipError_t e = c->reproject_scratch.ensure(g.scratch_bytes());
+    if (e != hipSuccess) return hip_fail(c, "alloc reprojection scratch", e);
+    // a new allocation has lost the splat image aic_pick_pixels reads: if this call then fails, there is none
+    if (c->reproject_scratch.p != scratch_before) c->reproject_valid_w = c->reproject_valid_h = 0u;
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    ReprojectParams rp;
+    rp.src_color = (const uint2 *)src;
+    rp.src_depth = (const float *)((const unsigned char *)src + npix * 8);
+    rp.dst_color = (uint2 *)dst;
+    rp.dst_depth = (float *)((unsigned char *)dst + npix * 8);
+    rp.scratch = c->reproject_scratch.p;
+    std::memcpy(rp.m, d->reprojection, sizeof(rp.m));
+    std::memcpy(rp.ipzw, d->inverse_projection_zw, sizeof(rp.ipzw));
+    rp.keep_splats = (d->flags & AIC_REPROJECT_KEEP_SPLATS) ? 1u : 0u;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_reproject(g, rp, fs.stream)) != hipSuccess) return hip_fail(c, "launch reprojection", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    ReprojectCounts counts;
+    HIP_TRY(c, hipMemcpyAsync(&counts, reproject_counts(g, c->reproject_scratch.p), sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    c->reproject_valid_w = d->width;
+    c->reproject_valid_h = d->height;
+    if (info) {
+        info->n_splats = counts.n_splats;
+        info->n_dropped = counts.n_dropped;
+        info->n_gaps = counts.n_gaps;
+        info->n_unfilled = counts.n_unfilled;
+        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+        info->levels = g.levels;
+        info->t0[0] = g.mw[0];
+        info->t0[1] = g.mh[0];
+    }
+    return AIC_OK;
+}
+
+int aic_pick_pixels(aic_ctx *c, const aic_pick_desc *d, const uint32_t *order, uint32_t *pixels_out, aic_pick_info *info) {
+    if (!c || !d || !info) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: bad argument");
+    std::memset(info, 0, sizeof(*info));
+    if (above_65535(d->width, d->height)) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: frame dimensions above 65535 are not supported");
+    if (d->flags) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: unknown flag bits");
+    if (d->n > 2048u * 65535u) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: more than 2048 x 65535 picks");
+    if (d->n && !pixels_out) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: no list to write the picks to");
+    if (((uintptr_t)pixels_out & 3u) || ((uintptr_t)order & 3u)) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: a list starts at a 4-byte boundary");
+    const uint64_t count = (uint64_t)d->width * d->height;
+    if (d->n && !count) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: an empty frame has no pixel to pick");
+    if (const int rc = begin(c, "aic_pick_pixels")) return rc;
+    if (!d->n) return AIC_OK;  // (and so count == 0)
+    if (d->max_unknown && (!c->reproject_scratch.p || c->reproject_valid_w != d->width || c->reproject_valid_h != d->height))
+        return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: max_unknown needs the context's last successful aic_reproject_split to be of this size");
+    hipError_t e;
+    if (d->max_unknown && (e = c->pick_scratch.ensure(pick_scratch_words(count))) != hipSuccess) return hip_fail(c, "alloc pick scratch", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    PickParams pp;
+    pp.R = d->max_unknown ? (const uint2 *)(c->reproject_scratch.p + reproject_geometry(d->width, d->height).keys_bytes()) : nullptr;
+    pp.order = order;
+    pp.out = pixels_out;
+    pp.scratch = d->max_unknown ? c->pick_scratch.p : nullptr;
+    pp.count = (uint32_t)count;  // at most 65535^2
+    pp.n = d->n;
+    pp.max_unknown = d->max_unknown;
+    pp.skip_unknown = d->skip_unknown;
+    pp.cursor = d->cursor;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_pick(pp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    PickRecord rec = {};
+    if (d->max_unknown) {
+        HIP_TRY(c, hipMemcpyAsync(&rec, c->pick_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
+    } else {  // nothing was looked at: the whole list is the picker's
+        rec.n_from_order = d->n;
+        rec.next_cursor = d->cursor + d->n;
+    }
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    info->n_unknown = rec.n_unknown;
+    info->next_cursor = rec.next_cursor;
+    info->n_from_unknown = rec.n_from_unknown;
+    info->n_from_order = rec.n_from_order;
+    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    return AIC_OK;
+}
+
+int aic_present_geometry(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t *levels, uint32_t t0[2], uint64_t *scratch_bytes) {
+    if (present_sizes_invalid(src_w, src_h, out_w, out_h)) return AIC_ERR_INVALID;
+    const bool empty = !out_w || !out_h;
+    const BloomGeom g = bloom_geometry(out_w, out_h);
+    if (levels) *levels = empty ? 0u : g.levels;
+    if (t0) { t0[0] = empty ? 0u : g.mw[0]; t0[1] = empty ? 0u : g.mh[0]; }
+    if (scratch_bytes) *scratch_bytes = empty ? 0u : (uint64_t)present_scratch_texels(g, src_w, src_h) * 8u;
+    return AIC_OK;
+}
+
+int aic_present_split(aic_ctx *c, const aic_present_desc *d, const void *src, void *out, int out_is_device, aic_present_info *info) {
+    return present(c, d, nullptr, src, out, out_is_device, info, nullptr, "aic_present_split");
+}
+
+int aic_present_lines_scratch(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t n_lines, uint64_t *bytes) {
+    if (present_sizes_invalid(src_w, src_h, out_w, out_h) || n_lines > AIC_LINES_MAX) return AIC_ERR_INVALID;
+    if (bytes) *bytes = (n_lines && out_w && out_h) ? (uint64_t)lines_layout(out_w, out_h, n_lines).bytes : 0u;
+    return AIC_OK;
+}
+
+int aic_present_split_lines(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const void *src, void *out, int out_is_device, aic_present_info *info,
+                            aic_lines_info *lines_info) {
+    if (lines_info) std::memset(lines_info, 0, sizeof(*lines_info));
+    if (c && ld) {  // (the rejections this call adds; a NULL ctx is the presentation's to report)
+        if (info) std::memset(info, 0, sizeof(*info));
+        if (ld->flags & ~AIC_LINES_DEVICE) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: unknown line flag bits");
+        if (ld->n_lines > AIC_LINES_MAX) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: more than AIC_LINES_MAX lines");
+        if (ld->n_lines && !ld->vertices) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: no vertices");
+        if (ld->n_lines && (ld->flags & AIC_LINES_DEVICE) && ((uintptr_t)ld->vertices & 3u))
+            return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: device vertices start at a 4-byte boundary");
+        for (float v : ld->view_projection)
+            if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: a component of view_projection is not finite");
+    }
+    if (!c || !ld || !ld->n_lines) return aic_present_split(c, d, src, out, out_is_device, info);  // (and reports under that name)
+    return present(c, d, ld, src, out, out_is_device, info, lines_info, "aic_present_split_lines");
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-"""aic_present_split_lines' host side without a GPU: tools/submit_record/present_lines_check.cpp drives csrc/aic_abi.cpp against the recording fake of the
+"""aic_present_split_lines' host side without a GPU: tools/submit_record/present_lines_check.cpp drives csrc/aic_split_ops.cpp against the recording fake of the
 HIP runtime and of the kernel launchers -- every rejection queues and allocates nothing, a call without lines makes exactly aic_present_split's calls, the
 line scratch grows and is released, failing runtime calls leave the context usable -- and exits 0 when all of it holds. The program has its own main and
 is built here with -fsanitize=address,undefined: host code only, nothing of it is loaded into Python."""
@@ -17,13 +17,13 @@ pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.ex
 
 def test_present_lines_check_passes_under_the_sanitizers():
     exe = os.path.join(tempfile.mkdtemp(prefix="aic_present_lines_check_"), "present_lines_check")
-    subprocess.run(["bash", str(ROOT / "tools" / "submit_record" / "build_present_lines_check.sh"), str(ROOT / "all_is_cubes_amd" / "csrc"), exe, "-Xarch_host",
+    subprocess.run(["bash", str(ROOT / "tools" / "submit_record" / "build.sh"), str(ROOT / "all_is_cubes_amd" / "csrc"), exe, "present_lines_check.cpp", "-Xarch_host",
                     "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"], check=True, capture_output=True)
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0, run.stderr
     assert " 0 of " in run.stderr and "LEAK" not in run.stdout
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr
-    lines = run.stdout.split("\n")
+    lines = [line for line in run.stdout.split("\n") if not line.startswith("  ")]  # (a launcher's arguments follow its name, indented)
     # a lines call: S stored, the line pass, then the presentation of S'
     at = [i for i, line in enumerate(lines) if line.startswith("launch_present_lines")]
     assert len(at) >= 10

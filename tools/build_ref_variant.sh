@@ -33,6 +33,12 @@ if [ -f $C/aic_reproject.hip ]; then  # (revisions from the reprojection post-pr
   /opt/rocm/bin/hipcc $F -c $C/aic_reproject.hip -o $D/reproject.o &
   OBJS="$OBJS $D/reproject.o"
 fi
+for part in present_lines.hip cursor.cpp pick.hip split_ops.cpp; do  # (the later post-processes, the cursor's host code; from the Split operations' own translation unit on, aic_split_ops.cpp)
+  if [ -f $C/aic_$part ]; then
+    /opt/rocm/bin/hipcc $F -x hip -c $C/aic_$part -o $D/${part%.*}.o &
+    OBJS="$OBJS $D/${part%.*}.o"
+  fi
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -Wl,--no-undefined -o variants/libaic_hip_$NAME.so $OBJS
 rm -f $D/*.o

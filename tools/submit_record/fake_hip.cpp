@@ -1,7 +1,8 @@
-// fake_hip.cpp -- a recording stand-in for the HIP runtime calls and kernel launchers the host side of the C ABI (aic_abi.cpp, aic_frame.cpp) uses.
+// fake_hip.cpp -- a recording stand-in for the HIP runtime calls and kernel launchers the host side of the C ABI (aic_abi.cpp, aic_frame.cpp,
+// aic_split_ops.cpp) uses.
 // Nothing of the real runtime is loaded: device memory is host memory, streams and events are ordinals, a launch is a line of text. Every call is logged
 // with its sizes; streams and events by creation ordinal, every device pointer as allocation ordinal + offset, so that two builds of the host code driven
-// through the same scenarios (driver.cpp) give byte-identical records exactly when they make the same calls in the same order.
+// through the same scenarios (driver.cpp, split_ops_record.cpp) give byte-identical records exactly when they make the same calls in the same order.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -92,6 +93,18 @@ void rec_frame(const aic::DevFrame &F) {
     }
 }
 
+void rec_bloom_geom(const aic::BloomGeom &g) {
+    rec("  geom %ux%u levels %u texels %u", g.width, g.height, g.levels, g.texels);
+    rec_words("  geom mw", g.mw, aic::kBloomMaxLevels);
+    rec_words("  geom mh", g.mh, aic::kBloomMaxLevels);
+    rec_words("  geom off", g.off, aic::kBloomMaxLevels);
+}
+void rec_present(const aic::BloomGeom &g, const aic::PresentParams &p, hipStream_t stream) {
+    rec_bloom_geom(g);
+    rec("  src %s %ux%u scene %s mips %s out %s intensity %a tone_mapping %d maximum_intensity %a srgb_thr %s out_f16 %d %s", P(p.src), p.src_width, p.src_height, P(p.scene), P(p.mips),
+        P(p.out), p.intensity, p.tone_mapping, p.maximum_intensity, P(p.srgb_thr), (int)p.out_f16, S(stream));
+}
+
 }  // namespace
 
 void rec(const char *fmt, ...) {
@@ -127,7 +140,7 @@ extern "C" {
 
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
-hipError_t hipSetDevice(int) { return hipSuccess; }  // (every entry point begins with it: not logged)
+hipError_t hipSetDevice(int) { return failing("hipSetDevice") ? hipErrorInvalidValue : hipSuccess; }  // (every entry point begins with it: logged only where it is made to fail)
 hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) {
     std::memset(p, 0, sizeof(*p));
     p->multiProcessorCount = 256;
@@ -135,7 +148,7 @@ hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) {
     std::snprintf(p->gcnArchName, sizeof(p->gcnArchName), "gfx950");
     return hipSuccess;
 }
-hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipGetLastError(void) { return failing("hipGetLastError") ? hipErrorInvalidValue : hipSuccess; }  // (the same)
 const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "invalid value"; }
 
 hipError_t hipMalloc(void **p, size_t bytes) {
@@ -236,14 +249,35 @@ void launch_open_cubes(uint16_t *grid, const int size[3], hipStream_t stream) { 
 // (what the scenarios never reach: scene updates, strip assembly, the probes)
 void launch_scatter_cubes(uint16_t *, uint32_t *, const int32_t *, const uint16_t *, const uint32_t *, uint32_t, const int[3], const int[3], const uint32_t *, hipStream_t) { rec("launch_scatter_cubes"); }
 void launch_open_changed_cubes(uint16_t *, const int32_t *, uint32_t, const int[3], const int[3], hipStream_t) { rec("launch_open_changed_cubes"); }
-hipError_t launch_reproject(const ReprojectGeom &, const ReprojectParams &, hipStream_t) { rec("launch_reproject"); return hipSuccess; }
-hipError_t launch_pick(const PickParams &, hipStream_t) { rec("launch_pick"); return hipSuccess; }
-void launch_present(const BloomGeom &, const PresentParams &, hipStream_t) { rec("launch_present"); }
-void launch_present_scene(const BloomGeom &, const PresentParams &, hipStream_t) { rec("launch_present_scene"); }
-hipError_t launch_present_lines(const LinesParams &p, hipStream_t) {
+// (the operations on a resident Split frame. The first line is the launcher's name alone, its arguments follow indented; each can be made to fail like a runtime call)
+hipError_t launch_reproject(const ReprojectGeom &g, const ReprojectParams &p, hipStream_t stream) {
+    rec("launch_reproject");
+    rec("  geom %ux%u levels %u texels %zu", g.width, g.height, g.levels, g.texels);
+    rec_words("  geom mw", g.mw, kReprojectMaxLevels);
+    rec_words("  geom mh", g.mh, kReprojectMaxLevels);
+    std::string off = "  geom off";
+    for (size_t o : g.off) off += " " + std::to_string(o);
+    rec("%s", off.c_str());
+    rec("  src_color %s src_depth %s dst_color %s dst_depth %s scratch %s keep_splats %u %s", P(p.src_color), P(p.src_depth), P(p.dst_color), P(p.dst_depth), P(p.scratch), p.keep_splats,
+        S(stream));
+    rec_words("  m", p.m, 16);
+    rec_words("  ipzw", p.ipzw, 4);
+    return failing("launch_reproject") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_pick(const PickParams &p, hipStream_t stream) {
+    rec("launch_pick");
+    rec("  R %s order %s out %s scratch %s count %u n %u max_unknown %u skip_unknown %llu cursor %llu %s", P(p.R), P(p.order), P(p.out), P(p.scratch), p.count, p.n, p.max_unknown,
+        p.skip_unknown, p.cursor, S(stream));
+    return failing("launch_pick") ? hipErrorInvalidValue : hipSuccess;
+}
+void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stream) { rec("launch_present"); rec_present(g, p, stream); }
+void launch_present_scene(const BloomGeom &g, const PresentParams &p, hipStream_t stream) { rec("launch_present_scene"); rec_present(g, p, stream); }
+hipError_t launch_present_lines(const LinesParams &p, hipStream_t stream) {
     rec("launch_present_lines vertices %s n_lines %u keys %s scene %s counts %s clear_keys %d reset_keys %d", P(p.vertices), p.n_lines, P(p.keys), P(p.scene), P(p.counts),
         (int)p.clear_keys, (int)p.reset_keys);
-    return hipSuccess;
+    rec("  depth %s src %ux%u out %ux%u %s", P(p.depth), p.src_width, p.src_height, p.width, p.height, S(stream));
+    rec_words("  m", p.m, 16);
+    return failing("launch_present_lines") ? hipErrorInvalidValue : hipSuccess;
 }
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }

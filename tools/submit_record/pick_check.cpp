@@ -1,6 +1,6 @@
-// pick_check.cpp -- the host side of aic_pick_pixels (csrc/aic_abi.cpp) against the recording fake (fake_hip.cpp), as a program of its own: every
+// pick_check.cpp -- the host side of aic_pick_pixels (csrc/aic_split_ops.cpp) against the recording fake (fake_hip.cpp), as a program of its own: every
 // rejection the header lists, the state aic_reproject_split keeps for it, and the calls a good pick makes. Exits 0 when every expectation holds.
-// Host code only, so it can be built with sanitizers (build_pick_check.sh ... -Xarch_host -fsanitize=address,undefined) and run anywhere.
+// Host code only, so it can be built with sanitizers (build.sh ... pick_check.cpp -Xarch_host -fsanitize=address,undefined) and run anywhere.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>

@@ -1,8 +1,8 @@
-// present_lines_check.cpp -- the host side of aic_present_split_lines (csrc/aic_abi.cpp) against the recording fake (fake_hip.cpp), as a program of its
+// present_lines_check.cpp -- the host side of aic_present_split_lines (csrc/aic_split_ops.cpp) against the recording fake (fake_hip.cpp), as a program of its
 // own: every rejection the header lists queues and allocates nothing, a call without lines records what aic_present_split records, the line scratch grows
 // and is released, a failing runtime call leaves the context usable; and aic_cursor_wireframe's line counts. Exits 0 when every expectation holds; where it
 // writes "# ... clear_keys V" into the record, the next launch_present_lines line must say the same (tests/test_present_lines_host_cpu.py compares).
-// Host code only, so it can be built with sanitizers (build_present_lines_check.sh ... -Xarch_host -fsanitize=address,undefined) and run anywhere.
+// Host code only, so it can be built with sanitizers (build.sh ... present_lines_check.cpp -Xarch_host -fsanitize=address,undefined) and run anywhere.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
