@@ -78,7 +78,7 @@ ABI_SYMBOLS = [
     "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
-    "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f",
+    "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
     "aic_create_multi", "aic_destroy_multi", "aic_multi_device_count", "aic_multi_context", "aic_multi_last_error", "aic_multi_upload_space",
     "aic_multi_clear_space", "aic_multi_update_cubes", "aic_multi_update_light_volume", "aic_multi_evaluate_light", "aic_multi_light_cubes_changed", "aic_multi_replace_blocks", "aic_multi_set_options", "aic_multi_set_depth_transform",
     "aic_multi_render", "aic_multi_render_submit", "aic_multi_render_wait",
@@ -354,6 +354,7 @@ def load() -> C.CDLL:
         lib.aic_light_cubes_changed.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
         lib.aic_probe_derived.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.aic_probe_log2f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.aic_probe_cube_grid.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         assert C.sizeof(BlockDesc) == 48
         _lib = lib
     return _lib
@@ -907,6 +908,16 @@ class Context:
         opq = np.zeros((n_blocks, 6), np.uint8)
         self._check(self._lib.aic_probe_derived(self._h, layer, out.ctypes.data, opq.ctypes.data))
         return out, opq
+
+    def probe_cube_grid(self, layer: int, shape, n_blocks: int):
+        """The layer's cube grid as it stands on the device (test hook): (grid u16 [sx, sy, sz] -- indices with their tags where the
+        grid carries them, csrc/aic_device.h --, class table u32 [ceil(n_blocks / 16)], 2 bits per block index, whether the grid is tagged)."""
+        grid = np.zeros(tuple(int(v) for v in shape), np.uint16)
+        cls = np.zeros((int(n_blocks) + 15) // 16, np.uint32)
+        tagged = C.c_uint32(0)
+        # (an array of no elements still has an address: the library rejects NULL, and writes nothing there)
+        self._check(self._lib.aic_probe_cube_grid(self._h, layer, grid.ctypes.data, _ptr(cls), C.byref(tagged)))
+        return grid, cls, bool(tagged.value)
 
     def probe_log2f(self, x) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

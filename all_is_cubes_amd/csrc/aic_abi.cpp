@@ -522,6 +522,20 @@ int aic_update_cubes(aic_ctx *c, int layer, uint32_t n, const int32_t *xyz, cons
     return AIC_OK;
 }
 
+// Test probe: the cube grid as it stands on the device -- indices, tags and OPEN marks (aic_device.h) -- and the class table behind the tags. Copies only.
+int aic_probe_cube_grid(aic_ctx *c, int layer, uint16_t *out_grid, uint32_t *out_cls, uint32_t *out_tagged) {
+    if (!c || !valid_layer(layer) || !out_grid) return fail(c, AIC_ERR_INVALID, "aic_probe_cube_grid: bad argument");
+    Layer &l = c->layers[layer];
+    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_probe_cube_grid: no space uploaded for this layer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    { int qrc = quiesce(c); if (qrc != AIC_OK) return qrc; }
+    const size_t n = l.n_cubes(), n_words = (l.host_blocks.size() + 15u) / 16u;
+    if (n) HIP_TRY(c, hipMemcpy(out_grid, l.pool.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (out_cls && n_words) HIP_TRY(c, hipMemcpy(out_cls, l.cls.p, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_tagged) *out_tagged = l.cls_in_code ? 1u : 0u;
+    return AIC_OK;
+}
+
 int aic_update_light_volume(aic_ctx *c, int layer, const uint8_t *light) {
     if (!c || !valid_layer(layer) || !light) return fail(c, AIC_ERR_INVALID, "aic_update_light_volume: bad argument");
     Layer &l = c->layers[layer];

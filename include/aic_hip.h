@@ -723,6 +723,12 @@ uint32_t aic_light_chart(float *weights, uint32_t *children, uint32_t *depth);
  * as PackedLight::scalar_in uses it (data.rs:214-218). */
 int aic_probe_derived(aic_ctx *ctx, int layer, float *out, uint8_t *out_opaque);
 int aic_probe_log2f(aic_ctx *ctx, const float *x, uint32_t n, float *out);
+/* test hook: the layer's cube grid as it stands on the device, after the frames in flight: out_grid[n cubes], Z-major, each entry the block
+ * index with -- for a block table of at most 16384 entries -- the cube's tag in bits 14-15 (block class plus one; 0 on an open cube: an
+ * invisible cube inside the outermost layer whose six face neighbours are invisible). out_cls, if not NULL: the device's class table,
+ * (n_blocks + 15) / 16 words of 2 bits per block index (0 invisible single voxel, 1 visible single voxel, 2 recursive). out_tagged, if not
+ * NULL: 1 if the grid carries tags, 0 if it holds plain indices. A grid of no cubes writes nothing to out_grid. */
+int aic_probe_cube_grid(aic_ctx *ctx, int layer, uint16_t *out_grid, uint32_t *out_cls, uint32_t *out_tagged);
 /* aic_evaluate_light on the first device; the resulting light volume is handed to the others (the updater does not shard) */
 int aic_multi_evaluate_light(aic_multi *m, int layer, const aic_light_params *params, aic_light_info *info);
 /* aic_light_cubes_changed on the device that runs the light updater (device 0). The texels it writes there (PackedLight::OPAQUE at
