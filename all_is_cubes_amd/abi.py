@@ -34,6 +34,7 @@ PRESENT_MAX_PIXELS = 1 << 31  # AIC_PRESENT_MAX_PIXELS
 LINES_DEVICE = 1  # AIC_LINES_DEVICE: the line vertices are a device pointer
 LINES_MAX = 1 << 20  # AIC_LINES_MAX
 CURSOR_MAX_LINES = 28  # AIC_CURSOR_MAX_LINES
+TEXT_DEVICE = 1  # AIC_TEXT_DEVICE: the character codes are a device pointer
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
@@ -75,7 +76,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -247,6 +248,10 @@ class LinesInfo(C.Structure):
     _fields_ = [("n_clipped_away", C.c_uint64), ("n_fragments", C.c_uint64), ("n_passed", C.c_uint64), ("n_pixels", C.c_uint64)]
 
 
+class TextDesc(C.Structure):
+    _fields_ = [("scale", C.c_float * 2), ("origin", C.c_float * 2), ("cols", C.c_uint32), ("rows", C.c_uint32), ("flags", C.c_uint32), ("codes", C.c_void_p)]
+
+
 class CursorDesc(C.Structure):
     _fields_ = [("cube", C.c_int32 * 3), ("face_entered", C.c_int32), ("face_selected", C.c_int32), ("point_entered", C.c_double * 3),
                 ("distance_to_point", C.c_double), ("voxel_lo", C.c_int32 * 3), ("voxel_size", C.c_int32 * 3), ("resolution", C.c_int32),
@@ -272,6 +277,37 @@ def cursor_wireframe(cube, face_entered: int, face_selected: int, point_entered,
     if rc != 0:
         raise AicError(rc, "aic_cursor_wireframe")
     return out[:2 * n.value].copy()
+
+
+def text_geometry(nominal_size, cell=(9, 18, 1), origin_px=(5.0, 5.0)):
+    """The info text's character grid and texture-coordinate transform for a viewport of `nominal_size` = (width, height) nominal pixels and a font
+    `cell` = (cell_width, cell_height, cell_margin) (aic_text_geometry; character_texture_size, text.rs:20-52, and PostprocessUniforms::new,
+    postprocess.rs:316-331): (cols, rows, scale [2] float32, origin [2] float32). Host-only: needs no device or context."""
+    lib = load()
+    lib.aic_text_geometry.restype = C.c_int
+    lib.aic_text_geometry.argtypes = [C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    cols, rows, scale, origin, px = C.c_uint32(0), C.c_uint32(0), (C.c_float * 2)(), (C.c_float * 2)(), (C.c_double * 2)(float(origin_px[0]), float(origin_px[1]))
+    rc = lib.aic_text_geometry(float(nominal_size[0]), float(nominal_size[1]), int(cell[0]), int(cell[1]), int(cell[2]), px, C.byref(cols), C.byref(rows), scale, origin)
+    if rc != 0:
+        raise AicError(rc, f"aic_text_geometry({tuple(nominal_size)}, {tuple(cell)})")
+    return cols.value, rows.value, np.array(scale[:], np.float32), np.array(origin[:], np.float32)
+
+
+def text_layout(text, cols: int, rows: int):
+    """`text` -- a str, or bytes taken as UTF-8, malformed or not -- laid out in a rows x cols grid of character codes (aic_text_layout;
+    render_text_to_character_texture, text.rs:56-73): (codes [rows][cols] uint8, (used columns, used rows)). Host-only."""
+    lib = load()
+    lib.aic_text_layout.restype = C.c_int
+    lib.aic_text_layout.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    ok = 0 < cols <= 65535 and 0 < rows <= 65535
+    codes = np.zeros((rows, cols) if ok else (1, 1), np.uint8)
+    used = (C.c_uint32 * 2)()
+    rc = lib.aic_text_layout(raw, len(raw), int(cols), int(rows), codes.ctypes.data_as(C.c_void_p), used)
+    if rc != 0:
+        raise AicError(rc, f"aic_text_layout(cols {cols}, rows {rows})")
+    return codes, (used[0], used[1])
 
 
 PIXEL_AUX_DTYPE = np.dtype(
@@ -331,6 +367,9 @@ def load() -> C.CDLL:
         lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
         lib.aic_present_split_lines.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo),
                                                 C.POINTER(LinesInfo)]
+        lib.aic_set_text_font.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.aic_present_split_text.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.POINTER(TextDesc), C.c_void_p, C.c_void_p, C.c_int,
+                                               C.POINTER(PresentInfo), C.POINTER(LinesInfo)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_read_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -757,6 +796,56 @@ class Context:
         image = np.zeros((d.out_height, d.out_width, 4), np.uint16 if flags & PRESENT_OUT_F16 else np.uint8)
         self._check(self._lib.aic_present_split_lines(self._h, C.byref(d), C.byref(ld), C.c_void_p(src_ptr or None), image.ctypes.data_as(C.c_void_p), 0,
                                                       C.byref(info), C.byref(lines_info)))
+        return image, info, lines_info
+
+    def set_text_font(self, atlas, cell_width: int = 0, cell_height: int = 0, cell_margin: int = 0) -> None:
+        """The font atlas of the info text (aic_set_text_font): `atlas` = [16 * cell_height][16 * cell_width][4] uint8, premultiplied RGBA8, the cell of
+        code k at column k % 16, row k / 16, with `cell_margin` texels on every side outside the logical cell; None drops the font. Copied to the
+        device, resident until replaced."""
+        if atlas is None:
+            self._check(self._lib.aic_set_text_font(self._h, None, 0, 0, 0))
+            return
+        keep = np.ascontiguousarray(atlas, np.uint8)
+        if keep.shape != (16 * int(cell_height), 16 * int(cell_width), 4):
+            raise ValueError(f"set_text_font: atlas of shape {keep.shape} for cells of {cell_width} x {cell_height}")
+        self._check(self._lib.aic_set_text_font(self._h, keep.ctypes.data_as(C.c_void_p), int(cell_width), int(cell_height), int(cell_margin)))
+
+    def present_split_text(self, src_ptr: int, src_size, out_size, bloom_intensity: float, tone_mapping: int, maximum_intensity: float, text=None,
+                           view_projection=None, vertices=None, n_lines: int | None = None, flags: int = 0, out_device: int | None = None):
+        """present_split_lines with the info text laid over the tone-mapped scene (aic_present_split_text). `text` = (codes, scale, origin): codes a
+        [rows][cols] uint8 array on the host, or (device pointer, cols, rows); scale and origin as text_geometry gives them; None: no text. Lines as in
+        present_split_lines, with view_projection None for none. Returns (image or None, info, lines_info)."""
+        d = PresentDesc()
+        d.src_width, d.src_height = int(src_size[0]), int(src_size[1])
+        d.out_width, d.out_height = int(out_size[0]), int(out_size[1])
+        d.bloom_intensity, d.tone_mapping, d.maximum_intensity, d.flags = float(bloom_intensity), int(tone_mapping), float(maximum_intensity), int(flags)
+        ld, keep = None, None
+        if view_projection is not None:
+            ld = LinesDesc()
+            ld.view_projection[:] = [float(v) for v in np.asarray(view_projection, np.float32).reshape(16)]
+            if isinstance(vertices, int):
+                ld.vertices, ld.n_lines, ld.flags = vertices, int(n_lines), LINES_DEVICE
+            elif vertices is not None:
+                keep = np.asarray(vertices)
+                keep = np.ascontiguousarray(keep.view(np.float32) if keep.dtype == LINE_VERTEX_DTYPE else keep, np.float32).reshape(-1, 2, 7)
+                ld.vertices, ld.n_lines = keep.ctypes.data, len(keep) if n_lines is None else int(n_lines)
+        td, keep_codes = None, None
+        if text is not None:
+            codes, scale, origin = text
+            td = TextDesc()
+            td.scale[:], td.origin[:] = [float(v) for v in scale], [float(v) for v in origin]
+            if isinstance(codes, tuple):
+                td.codes, td.cols, td.rows, td.flags = codes[0], int(codes[1]), int(codes[2]), TEXT_DEVICE
+            else:
+                keep_codes = np.ascontiguousarray(codes, np.uint8)
+                td.codes, td.rows, td.cols = keep_codes.ctypes.data, keep_codes.shape[0], keep_codes.shape[1]
+        info, lines_info = PresentInfo(), LinesInfo()
+        args = (C.byref(d), C.byref(ld) if ld is not None else None, C.byref(td) if td is not None else None, C.c_void_p(src_ptr or None))
+        if out_device is not None:
+            self._check(self._lib.aic_present_split_text(self._h, *args, C.c_void_p(out_device or None), 1, C.byref(info), C.byref(lines_info)))
+            return None, info, lines_info
+        image = np.zeros((d.out_height, d.out_width, 4), np.uint16 if flags & PRESENT_OUT_F16 else np.uint8)
+        self._check(self._lib.aic_present_split_text(self._h, *args, image.ctypes.data_as(C.c_void_p), 0, C.byref(info), C.byref(lines_info)))
         return image, info, lines_info
 
     def render_submit(self, frame: FrameDesc, device_ptr: int, slot: int) -> None:

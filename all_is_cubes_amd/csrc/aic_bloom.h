@@ -64,8 +64,20 @@ void launch_bloom_stages(const BloomGeom &g, uint2 *mips, hipStream_t stream);
 
 // Presentation of a resident Split frame (aic_present_split): the reference's per-frame draw of its resident textures, raytrace_to_texture.rs:546-568 with
 // shaders/rt-copy.wgsl:41-71 (the linear ClampToEdge stretch into the scene texture, alpha 1), then the same chain and postprocess.wgsl:140-158, 251-276.
+// The info text of a presentation (aic_present_split_text; postprocess.wgsl:160-246): a grid of character codes and the context's
+// resident font atlas, composited over the tone-mapped scene. codes == nullptr: no text, and the composite is the one without.
+struct PresentText {
+    const uint8_t *codes = nullptr;   // [rows][cols], device memory; 0 reads as 0x20
+    const uint32_t *atlas = nullptr;  // [16 * cell_h][16 * cell_w] RGBA8, premultiplied alpha, device memory
+    float scale[2] = {0.f, 0.f}, origin[2] = {0.f, 0.f};
+    uint32_t cols = 0, rows = 0;
+    uint32_t cell_w = 0, cell_h = 0, margin = 0;
+    // the output pixels [x0, x1) x [y0, y1) outside which no cell can contribute anything but zeros: the lanes there skip the four lookups
+    uint32_t x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+};
+
 struct PresentParams {
-    const uint2 *src;                 // the frame's colour plane [src_height][src_width] f16 x 4 (its depth plane is not read)
+    const uint2 *src;               // the frame's colour plane [src_height][src_width] f16 x 4 (its depth plane is not read)
     uint32_t src_width, src_height;
     uint2 *scene;                     // S, [geom.height][geom.width]: written and read only when bloomed AND the sizes differ
     uint2 *mips;                      // [geom.texels]: only when bloomed
@@ -75,9 +87,11 @@ struct PresentParams {
     float maximum_intensity;
     const float *srgb_thr;
     bool out_f16;                     // AIC_PRESENT_OUT_F16
+    PresentText text;                 // codes != nullptr: the composite's TEXT variant lays the info text over the tone-mapped scene
 };
 // Queues the presentation on `stream`; `g` = bloom_geometry of the OUTPUT size, at most 2^31 pixels (the kernels' texel indices are 32-bit). Launches:
-// the composite alone at intensity 0; else the chain's 6 L - 5 stages before it, and the stretch into S before those when the sizes differ.
+// the composite alone at intensity 0; else the chain's 6 L - 5 stages before it, and the stretch into S before those when the sizes differ. The text
+// adds no launch: it is a variant of the composite.
 void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stream);
 // Queues S alone, stored into p.scene whatever the sizes: the stretch when they differ, the source texels (saturated, alpha 1) when they do not. What a
 // pass that draws into the scene before the chain runs (aic_present_lines.h) starts from; launch_present then takes p.scene as a frame of the output's size.

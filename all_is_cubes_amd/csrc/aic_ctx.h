@@ -130,6 +130,12 @@ struct aic_ctx {
     // the first lines_keys_clean keys of lines_scratch are all ones (cleared once after an allocation; every finished call leaves them so). 0 after an
     // allocation and while a call that may have failed between its draw and its resolve is the last one: the next call clears first
     size_t lines_keys_clean = 0;
+    // aic_set_text_font: the resident font atlas, [16 * text_cell_h][16 * text_cell_w] RGBA8 (n == 0: no font set), and whether its cell 0x20 was all
+    // zero, which lets a presentation skip the pixels out of the text's reach; aic_present_split_text: the staged codes of a host list
+    DevBuf<uint32_t> text_atlas;
+    uint32_t text_cell_w = 0, text_cell_h = 0, text_margin = 0;
+    bool text_space_blank = false;
+    DevBuf<unsigned char> text_codes;
     uint64_t aux_records = 0;
     double depth_zw[4] = {1.0, 0.0, 0.0, 1.0};  // aic_set_depth_transform: the Split frames' depth transform
     bool streaming_submit = false;  // set around aic_render_submit: frames meant to overlap are sized for throughput, synchronous ones for latency

@@ -7,6 +7,9 @@
 //    x = s (1 - i) + B i needs no division: alpha is 1 everywhere (postprocess.wgsl:140-158).
 //  * S is stored only for a stretched AND bloomed frame (downsample 0 reads each of its texels five times over); otherwise the composite forms it
 //    where it reads it. The bits are the same either way.
+//  * The info text (aic_present_split_text; postprocess.wgsl:160-276, DESIGN.md "The info text in a presentation") is a variant of the composite: the
+//    four nearest cells of a grid of character codes are looked up in the resident font atlas and their maximum is laid over the tone-mapped scene.
+//    Codes are byte loads, atlas texels dword loads; lanes outside the rectangle the host found in the text's reach skip the lookups.
 //  * Everything else -- the f16 texel, the sampler, the chain's stages from mip 1 on, the tone map and the encoder -- is the bloom post-process's own
 //    (aic_bloom_device.h, launch_bloom_stages, aic_encode.h). A texel per lane, 256-thread workgroups, one 8-byte load or store per colour texel.
 
@@ -58,17 +61,40 @@ __global__ void __launch_bounds__(256) present_down0_kernel(const uint2 *__restr
     out[t] = downsample_texel(SrcSplit{scene}, sw, sh, ow, oh, (int)(t % (uint32_t)ow), (int)(t / (uint32_t)ow));
 }
 
-// postprocess_fragment (postprocess.wgsl:140-158, 251-276) on an opaque scene: mix(S, B, i), the tone map, then sRGB8 with alpha byte 255 or (F16) the
-// linear colour as four f16 with alpha 1.0. STRETCH: S is formed here from an sw x sh frame; otherwise `src` holds S's texels at the window's size.
-template <bool STRETCH, bool F16>
-__global__ void __launch_bounds__(256) present_composite_kernel(const uint2 *__restrict__ src, int sw, int sh, const uint2 *__restrict__ mip0, int w, int h, int t0x,
-                                                                int t0y, float intensity, int32_t tone_mapping, float m, const float *__restrict__ thr,
-                                                                void *__restrict__ out) {
-    __shared__ float s_thr[F16 ? 1u : kSrgbWindowWords];
-    if (!F16) {
-        srgb_window_to_lds(s_thr, thr, threadIdx.x, 256u);
-        __syncthreads();
-    }
+// render_character_cell (postprocess.wgsl:202-246): the atlas texel that the cell (cx, cy) -- whole numbers held in f32, tested against the grid before
+// any conversion -- shows at the position (px, py) measured in cells from its top left corner; 0 where the cell is outside the grid or the position
+// outside the atlas cell. DESIGN.md 4.14.
+AIC_DEV uint32_t text_cell(const PresentText &tx, float cx, float cy, float px, float py) {
+    if (!(cx >= 0.0f && cy >= 0.0f && cx < (float)tx.cols && cy < (float)tx.rows)) return 0u;
+    uint32_t k = tx.codes[(uint32_t)cy * tx.cols + (uint32_t)cx];
+    if (k == 0u) k = 0x20u;  // (the character texture is cleared to zero, not to spaces)
+    const float ftx = px * (float)(tx.cell_w - 2u * tx.margin) + (float)tx.margin;
+    const float fty = py * (float)(tx.cell_h - 2u * tx.margin) + (float)tx.margin;
+    if (!(ftx >= 0.0f && fty >= 0.0f && ftx < (float)tx.cell_w && fty < (float)tx.cell_h)) return 0u;
+    return tx.atlas[((k >> 4) * tx.cell_h + (uint32_t)fty) * (16u * tx.cell_w) + (k & 15u) * tx.cell_w + (uint32_t)ftx];
+}
+AIC_DEV uint32_t max_bytes(uint32_t a, uint32_t b) {
+    return max(a & 0xffu, b & 0xffu) | max(a & 0xff00u, b & 0xff00u) | max(a & 0xff0000u, b & 0xff0000u) | max(a & 0xff000000u, b & 0xff000000u);
+}
+// render_text (postprocess.wgsl:160-194) at the centre (u, v) of an output pixel: the component-wise maximum of the four nearest cells' texels. The
+// maximum is taken on the bytes: b / 255 is monotonic, so it is the maximum of the quotients.
+AIC_DEV float4 text_at(const PresentText &tx, float u, float v) {
+    const float tcx = (u - tx.origin[0]) * tx.scale[0] * (float)tx.cols, tcy = (v - tx.origin[1]) * tx.scale[1] * (float)tx.rows;
+    float fx = floorf(tcx), fy = floorf(tcy);
+    float px = tcx - fx, py = tcy - fy;
+    if (px < 0.5f) { fx -= 1.0f; px += 1.0f; }
+    if (py < 0.5f) { fy -= 1.0f; py += 1.0f; }
+    const uint32_t t = max_bytes(max_bytes(text_cell(tx, fx, fy, px, py), text_cell(tx, fx + 1.0f, fy, px - 1.0f, py)),
+                                 max_bytes(text_cell(tx, fx, fy + 1.0f, px, py - 1.0f), text_cell(tx, fx + 1.0f, fy + 1.0f, px - 1.0f, py - 1.0f)));
+    return make_float4((float)(t & 0xffu) / 255.0f, (float)((t >> 8) & 0xffu) / 255.0f, (float)((t >> 16) & 0xffu) / 255.0f, (float)(t >> 24) / 255.0f);
+}
+
+// postprocess_fragment (postprocess.wgsl:140-158, 251-276) on an opaque scene: mix(S, B, i), the tone map, (TEXT) the info text over it, then sRGB8 with
+// alpha byte 255 or (F16) the linear colour as four f16 with alpha 1.0. STRETCH: S is formed here from an sw x sh frame; otherwise `src` holds S's
+// texels at the window's size. The body of the composite kernels below: one output texel per lane, s_thr the workgroup's sRGB window in LDS.
+template <bool STRETCH, bool F16, bool TEXT>
+AIC_DEV void composite_texel(const float *s_thr, const uint2 *__restrict__ src, int sw, int sh, const uint2 *__restrict__ mip0, int w, int h, int t0x, int t0y,
+                             float intensity, int32_t tone_mapping, float m, const PresentText &tx, void *__restrict__ out) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     const uint32_t npix = (uint32_t)w * (uint32_t)h;
     const uint32_t pix = t < npix ? t : npix - 1u;  // (every lane of the wave runs srgb8_rgb's ballot; only the real pixels store)
@@ -94,6 +120,16 @@ __global__ void __launch_bounds__(256) present_composite_kernel(const uint2 *__r
             r = ps_mul(r, scale); g = ps_mul(g, scale); bl = ps_mul(bl, scale);
         }
     }
+    if (TEXT) {  // tone_mapped_scene * (1 - text.a) + text (postprocess.wgsl:268-273): the text is not tone-mapped
+        float4 text = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        // outside the rectangle every cell in reach holds a blank: the same zeros without the lookups
+        if ((uint32_t)x >= tx.x0 && (uint32_t)x < tx.x1 && (uint32_t)y >= tx.y0 && (uint32_t)y < tx.y1)
+            text = text_at(tx, ((float)x + 0.5f) / (float)w, ((float)y + 0.5f) / (float)h);
+        const float keep = 1.0f - text.w;
+        r = r * keep + text.x;
+        g = g * keep + text.y;
+        bl = bl * keep + text.z;
+    }
     if (F16) {
         if (t < npix) ((uint2 *)out)[t] = pack_texel(make_float4(r, g, bl, 1.0f));
     } else {
@@ -101,6 +137,29 @@ __global__ void __launch_bounds__(256) present_composite_kernel(const uint2 *__r
         srgb8_rgb(r, g, bl, s_thr, R, G, B);
         if (t < npix) ((uint32_t *)out)[t] = R | (G << 8) | (B << 16) | 0xff000000u;
     }
+}
+template <bool STRETCH, bool F16>
+__global__ void __launch_bounds__(256) present_composite_kernel(const uint2 *__restrict__ src, int sw, int sh, const uint2 *__restrict__ mip0, int w, int h, int t0x,
+                                                                int t0y, float intensity, int32_t tone_mapping, float m, const float *__restrict__ thr,
+                                                                void *__restrict__ out) {
+    __shared__ float s_thr[F16 ? 1u : kSrgbWindowWords];
+    if (!F16) {
+        srgb_window_to_lds(s_thr, thr, threadIdx.x, 256u);
+        __syncthreads();
+    }
+    composite_texel<STRETCH, F16, false>(s_thr, src, sw, sh, mip0, w, h, t0x, t0y, intensity, tone_mapping, m, PresentText{}, out);
+}
+// ... with the info text of `tx` laid over the tone-mapped scene (aic_present_split_text)
+template <bool STRETCH, bool F16>
+__global__ void __launch_bounds__(256) present_composite_text_kernel(const uint2 *__restrict__ src, int sw, int sh, const uint2 *__restrict__ mip0, int w, int h, int t0x,
+                                                                     int t0y, float intensity, int32_t tone_mapping, float m, const float *__restrict__ thr,
+                                                                     const PresentText tx, void *__restrict__ out) {
+    __shared__ float s_thr[F16 ? 1u : kSrgbWindowWords];
+    if (!F16) {
+        srgb_window_to_lds(s_thr, thr, threadIdx.x, 256u);
+        __syncthreads();
+    }
+    composite_texel<STRETCH, F16, true>(s_thr, src, sw, sh, mip0, w, h, t0x, t0y, intensity, tone_mapping, m, tx, out);
 }
 
 }  // namespace
@@ -133,7 +192,13 @@ void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stre
     const int cw = stretch ? sw : w, ch = stretch ? sh : h;
     auto composite = stretch ? (p.out_f16 ? present_composite_kernel<true, true> : present_composite_kernel<true, false>)
                              : (p.out_f16 ? present_composite_kernel<false, true> : present_composite_kernel<false, false>);
-    composite<<<blocks, 256, 0, stream>>>(scene, cw, ch, mip0, w, h, (int)g.mw[0], (int)g.mh[0], p.intensity, p.tone_mapping, p.maximum_intensity, p.srgb_thr, p.out);
+    if (!p.text.codes) {
+        composite<<<blocks, 256, 0, stream>>>(scene, cw, ch, mip0, w, h, (int)g.mw[0], (int)g.mh[0], p.intensity, p.tone_mapping, p.maximum_intensity, p.srgb_thr, p.out);
+        return;
+    }
+    auto with_text = stretch ? (p.out_f16 ? present_composite_text_kernel<true, true> : present_composite_text_kernel<true, false>)
+                             : (p.out_f16 ? present_composite_text_kernel<false, true> : present_composite_text_kernel<false, false>);
+    with_text<<<blocks, 256, 0, stream>>>(scene, cw, ch, mip0, w, h, (int)g.mw[0], (int)g.mh[0], p.intensity, p.tone_mapping, p.maximum_intensity, p.srgb_thr, p.text, p.out);
 }
 
 }  // namespace aic

@@ -1,8 +1,9 @@
 // aic_split_ops.cpp -- the operations of the C ABI declared in include/aic_hip.h that act on a resident Split frame: reproject it (aic_reproject_split),
-// pick the next pixels to trace (aic_pick_pixels), present it (aic_present_split) and present it with a line list drawn in (aic_present_split_lines),
-// with the size queries that go with them (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch).
+// pick the next pixels to trace (aic_pick_pixels), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
+// with the info text laid over it (aic_present_split_text, aic_set_text_font), with the size queries and host-only helpers that go with them
+// (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch, aic_text_geometry, aic_text_layout).
 //
-// All four run on slot 0's stream, synchronously, and are written to one pattern: check the arguments, `begin`, size the context's scratch, fill the
+// The operations run on slot 0's stream, synchronously, and are written to one pattern: check the arguments, `begin`, size the context's scratch, fill the
 // launcher's parameters, then ev0, the launches, ev1, the copies back to the host and one synchronise, then the context's state and the caller's info.
 // Each rule they share is written once, in the anonymous namespace below. Of aic_abi.cpp it uses what aic_ctx.h declares; aic_cursor_wireframe,
 // which needs no context, is aic_cursor.cpp. tools/submit_record/split_ops_record.cpp drives every path of this file against a recording fake of the
@@ -68,11 +69,56 @@ int present_args_invalid(aic_ctx *c, const aic_present_desc *d, const void *src,
     return 0;
 }
 
-// A presentation, with the lines of `ld` drawn into the scene or (ld == nullptr) without: the body of aic_present_split and aic_present_split_lines.
+// what aic_present_split_lines adds to a presentation's rejections, under the entry point's name; 0: none
+int lines_args_invalid(aic_ctx *c, const aic_lines_desc *ld, const char *who) {
+    if (ld->flags & ~AIC_LINES_DEVICE) return reject(c, who, "unknown line flag bits");
+    if (ld->n_lines > AIC_LINES_MAX) return reject(c, who, "more than AIC_LINES_MAX lines");
+    if (ld->n_lines && !ld->vertices) return reject(c, who, "no vertices");
+    if (ld->n_lines && (ld->flags & AIC_LINES_DEVICE) && ((uintptr_t)ld->vertices & 3u)) return reject(c, who, "device vertices start at a 4-byte boundary");
+    for (float v : ld->view_projection)
+        if (!std::isfinite(v)) return reject(c, who, "a component of view_projection is not finite");
+    return 0;
+}
+
+// a font cell's rejections, shared by aic_set_text_font and aic_text_geometry
+bool text_cell_invalid(uint32_t cw, uint32_t ch, uint32_t margin) {
+    return cw < 1u || cw > 1024u || ch < 1u || ch > 1024u || 2ull * margin >= (cw < ch ? cw : ch);
+}
+// what aic_present_split_text adds
+int text_args_invalid(aic_ctx *c, const aic_text_desc *td, const char *who) {
+    if (td->flags & ~AIC_TEXT_DEVICE) return reject(c, who, "unknown text flag bits");
+    if (!c->text_atlas.n) return reject(c, who, "no font set (aic_set_text_font)");
+    if (!td->codes) return reject(c, who, "no codes");
+    if (!td->cols || !td->rows || above_65535(td->cols, td->rows)) return reject(c, who, "cols or rows of 0 or above 65535");
+    for (float v : {td->scale[0], td->scale[1], td->origin[0], td->origin[1]})
+        if (!std::isfinite(v)) return reject(c, who, "a component of scale or origin is not finite");
+    return 0;
+}
+
+// [lo, hi) of the n output pixels along one axis outside which the cells [c_lo, c_hi) of `cells` cannot be among a pixel's four: a pixel centre at
+// tc (in cells) reaches the cells floor(tc - 0.5) and the next, so cell k is in reach of tc in [k - 0.5, k + 1.5), and the range is grown to whole
+// cells on both sides. tc = ((x + 0.5) / n - origin) * scale * cells is inverted in f64; the slack covers the kernel's f32 roundings, which are 2^-23
+// relative to 1 + |origin| + |a| in window units, eight times over, and two pixels. Anything that is not a plain increasing map gives the whole axis.
+void text_reach(uint32_t n, float scale, float origin, uint32_t cells, uint32_t c_lo, uint32_t c_hi, uint32_t *lo, uint32_t *hi) {
+    *lo = 0u;
+    *hi = n;
+    const double k = (double)scale * (double)cells;
+    if (!(k > 0.0)) return;
+    const double a_lo = ((double)c_lo - 1.0) / k, a_hi = ((double)c_hi + 1.0) / k;
+    const double slack = 2.0 + (double)n * (1.0 / 1048576.0) * (1.0 + std::fabs((double)origin) + std::fmax(std::fabs(a_lo), std::fabs(a_hi)));
+    const double x_lo = std::floor((a_lo + (double)origin) * (double)n - 0.5 - slack), x_hi = std::ceil((a_hi + (double)origin) * (double)n - 0.5 + slack) + 1.0;
+    if (!std::isfinite(x_lo) || !std::isfinite(x_hi)) return;
+    *lo = x_lo <= 0.0 ? 0u : (x_lo >= (double)n ? n : (uint32_t)x_lo);
+    *hi = x_hi <= 0.0 ? 0u : (x_hi >= (double)n ? n : (uint32_t)x_hi);
+    if (*hi < *lo) *hi = *lo;
+}
+
+// A presentation, with the lines of `ld` drawn into the scene or (ld == nullptr) without, and with the text of `td` laid over the tone-mapped scene or
+// (td == nullptr) without: the body of aic_present_split, aic_present_split_lines and aic_present_split_text.
 // Without lines the frame goes through launch_present as it is. With lines launch_present_scene stores the scene S in the line scratch, the line pass
 // draws into it, and launch_present shows that S' at its own size -- so the presentation scratch then holds the chain's mips alone.
-int present(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const void *src, void *out, int out_is_device, aic_present_info *info,
-            aic_lines_info *lines_info, const char *who) {
+int present(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const aic_text_desc *td, const void *src, void *out, int out_is_device,
+            aic_present_info *info, aic_lines_info *lines_info, const char *who) {
     if (const int rc = present_args_invalid(c, d, src, out, out_is_device, info, who)) return rc;
     const bool f16 = (d->flags & AIC_PRESENT_OUT_F16) != 0;
     const size_t npix = (size_t)d->out_width * d->out_height, out_bytes = npix * (f16 ? 8 : 4);
@@ -91,6 +137,9 @@ int present(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, con
         if (c->lines_scratch.p != scratch_before) c->lines_keys_clean = 0;
     }
     if (!out_is_device && (e = c->out.ensure(out_bytes / 4)) != hipSuccess) return hip_fail(c, "alloc output", e);
+    const bool text_staged = td && !(td->flags & AIC_TEXT_DEVICE);
+    const size_t n_codes = td ? (size_t)td->cols * td->rows : 0;
+    if (text_staged && (e = c->text_codes.ensure(n_codes)) != hipSuccess) return hip_fail(c, "alloc text staging", e);
     aic_ctx::FrameSlot &fs = c->slots[0];
     unsigned char *const ls = c->lines_scratch.p;
     PresentParams pp;
@@ -105,6 +154,37 @@ int present(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, con
     pp.maximum_intensity = d->maximum_intensity;
     pp.srgb_thr = c->srgb_thr.p;
     pp.out_f16 = f16;
+    if (td) {
+        PresentText &tx = pp.text;
+        tx.codes = text_staged ? c->text_codes.p : td->codes;
+        tx.atlas = c->text_atlas.p;
+        std::memcpy(tx.scale, td->scale, sizeof(tx.scale));
+        std::memcpy(tx.origin, td->origin, sizeof(tx.origin));
+        tx.cols = td->cols;
+        tx.rows = td->rows;
+        tx.cell_w = c->text_cell_w;
+        tx.cell_h = c->text_cell_h;
+        tx.margin = c->text_margin;
+        // the pixels in reach of a cell that can hold a non-zero code; every other cell shows the atlas's cell 0x20, which must then be blank
+        uint32_t used[2] = {td->cols, td->rows};
+        if (text_staged) {
+            used[0] = used[1] = 0u;
+            for (uint32_t y = 0; y < td->rows; y++)
+                for (uint32_t x = 0; x < td->cols; x++)
+                    if (td->codes[(size_t)y * td->cols + x]) { used[0] = used[0] > x + 1u ? used[0] : x + 1u; used[1] = y + 1u; }
+        }
+        tx.x0 = tx.y0 = 0u;
+        tx.x1 = d->out_width;
+        tx.y1 = d->out_height;
+        if (c->text_space_blank) {
+            if (!used[0]) tx.x1 = tx.y1 = 0u;
+            else {
+                text_reach(d->out_width, td->scale[0], td->origin[0], td->cols, 0u, used[0], &tx.x0, &tx.x1);
+                text_reach(d->out_height, td->scale[1], td->origin[1], td->rows, 0u, used[1], &tx.y0, &tx.y1);
+            }
+        }
+        if (text_staged) HIP_TRY(c, hipMemcpyAsync(c->text_codes.p, td->codes, n_codes, hipMemcpyHostToDevice, fs.stream));
+    }
     LinesParams lp = {};
     if (ld) {
         lp.vertices = staged ? (const float *)(ls + lay.vertices) : (const float *)ld->vertices;
@@ -277,7 +357,7 @@ int aic_present_geometry(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_
 }
 
 int aic_present_split(aic_ctx *c, const aic_present_desc *d, const void *src, void *out, int out_is_device, aic_present_info *info) {
-    return present(c, d, nullptr, src, out, out_is_device, info, nullptr, "aic_present_split");
+    return present(c, d, nullptr, nullptr, src, out, out_is_device, info, nullptr, "aic_present_split");
 }
 
 int aic_present_lines_scratch(uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, uint32_t n_lines, uint64_t *bytes) {
@@ -291,16 +371,103 @@ int aic_present_split_lines(aic_ctx *c, const aic_present_desc *d, const aic_lin
     if (lines_info) std::memset(lines_info, 0, sizeof(*lines_info));
     if (c && ld) {  // (the rejections this call adds; a NULL ctx is the presentation's to report)
         if (info) std::memset(info, 0, sizeof(*info));
-        if (ld->flags & ~AIC_LINES_DEVICE) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: unknown line flag bits");
-        if (ld->n_lines > AIC_LINES_MAX) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: more than AIC_LINES_MAX lines");
-        if (ld->n_lines && !ld->vertices) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: no vertices");
-        if (ld->n_lines && (ld->flags & AIC_LINES_DEVICE) && ((uintptr_t)ld->vertices & 3u))
-            return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: device vertices start at a 4-byte boundary");
-        for (float v : ld->view_projection)
-            if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_present_split_lines: a component of view_projection is not finite");
+        if (const int rc = lines_args_invalid(c, ld, "aic_present_split_lines")) return rc;
     }
     if (!c || !ld || !ld->n_lines) return aic_present_split(c, d, src, out, out_is_device, info);  // (and reports under that name)
-    return present(c, d, ld, src, out, out_is_device, info, lines_info, "aic_present_split_lines");
+    return present(c, d, ld, nullptr, src, out, out_is_device, info, lines_info, "aic_present_split_lines");
+}
+
+int aic_set_text_font(aic_ctx *c, const uint8_t *atlas, uint32_t cell_w, uint32_t cell_h, uint32_t margin) {
+    if (!c) return fail(c, AIC_ERR_INVALID, "aic_set_text_font: bad argument");
+    if (atlas && text_cell_invalid(cell_w, cell_h, margin))
+        return reject(c, "aic_set_text_font", "a cell dimension outside 1..1024, or 2 * cell_margin >= min(cell_width, cell_height)");
+    if (const int rc = begin(c, "aic_set_text_font")) return rc;
+    if (!atlas) {
+        c->text_atlas.release();
+        c->text_cell_w = c->text_cell_h = c->text_margin = 0u;
+        c->text_space_blank = false;
+        return AIC_OK;
+    }
+    // (slot 0's stream is idle: every operation of this file leaves it so, and no frame occupies the slot)
+    const size_t row = 16u * (size_t)cell_w, texels = row * 16u * cell_h;
+    const hipError_t e = c->text_atlas.ensure(texels);
+    if (e != hipSuccess) return hip_fail(c, "alloc font atlas", e);  // (the font set before stays)
+    c->text_atlas.n = 0;  // no font until the new atlas is whole
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    HIP_TRY(c, hipMemcpyAsync(c->text_atlas.p, atlas, texels * 4, hipMemcpyHostToDevice, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    c->text_atlas.n = texels;
+    c->text_cell_w = cell_w;
+    c->text_cell_h = cell_h;
+    c->text_margin = margin;
+    bool blank = true;  // cell 0x20: column 0, row 2
+    for (uint32_t y = 0; y < cell_h && blank; y++)
+        for (size_t b = 0; b < (size_t)cell_w * 4; b++)
+            if (atlas[((2u * (size_t)cell_h + y) * row) * 4 + b]) { blank = false; break; }
+    c->text_space_blank = blank;
+    return AIC_OK;
+}
+
+int aic_text_geometry(double nominal_w, double nominal_h, uint32_t cell_w, uint32_t cell_h, uint32_t margin, const double origin_px[2], uint32_t *cols, uint32_t *rows,
+                      float scale[2], float origin[2]) {
+    if (!origin_px || !std::isfinite(nominal_w) || !std::isfinite(nominal_h) || !(nominal_w > 0.0) || !(nominal_h > 0.0)) return AIC_ERR_INVALID;
+    if (text_cell_invalid(cell_w, cell_h, margin)) return AIC_ERR_INVALID;
+    const uint32_t logical[2] = {cell_w - 2u * margin, cell_h - 2u * margin};
+    const double nominal[2] = {nominal_w, nominal_h};
+    uint32_t n[2];
+    for (int a = 0; a < 2; a++) {
+        const double cells = std::ceil(nominal[a] / (double)logical[a]);
+        if (cells > 65535.0) return AIC_ERR_INVALID;
+        n[a] = cells < 1.0 ? 1u : (uint32_t)cells;
+    }
+    if (cols) *cols = n[0];
+    if (rows) *rows = n[1];
+    for (int a = 0; a < 2; a++) {
+        if (scale) scale[a] = (float)nominal[a] / (float)(n[a] * logical[a]);
+        if (origin) origin[a] = (float)(origin_px[a] / nominal[a]);
+    }
+    return AIC_OK;
+}
+
+int aic_text_layout(const char *utf8, uint64_t len, uint32_t cols, uint32_t rows, uint8_t *codes, uint32_t used[2]) {
+    if (!codes || (len && !utf8) || !cols || !rows || above_65535(cols, rows)) return AIC_ERR_INVALID;
+    std::memset(codes, 0, (size_t)cols * rows);
+    uint32_t x = 0, y = 0, ux = 0, uy = 0;
+    for (uint64_t i = 0; i < len;) {
+        // the next scalar value (`str::chars`); malformed input cannot occur in a Rust &str, here it decodes to U+FFFD
+        uint32_t ch = (unsigned char)utf8[i];
+        uint64_t n = 1;
+        if (ch >= 0xf0u) { n = 4; ch &= 0x07u; } else if (ch >= 0xe0u) { n = 3; ch &= 0x0fu; } else if (ch >= 0xc0u) { n = 2; ch &= 0x1fu; } else if (ch >= 0x80u) { ch = 0xfffdu; }
+        if (i + n > len) { ch = 0xfffdu; n = 1; }
+        else for (uint64_t k = 1; k < n; k++) ch = (ch << 6) | ((unsigned char)utf8[i + k] & 0x3fu);
+        i += n;
+        if (ch == '\n') {
+            x = 0;
+            if (y != UINT32_MAX) y++;
+            continue;
+        }
+        if (x < cols && y < rows) {
+            const uint8_t code = ch <= 0xffu ? (uint8_t)ch : (uint8_t)'?';
+            codes[(size_t)y * cols + x] = code;
+            if (code) { ux = ux > x + 1u ? ux : x + 1u; uy = uy > y + 1u ? uy : y + 1u; }
+        }
+        if (x != UINT32_MAX) x++;
+    }
+    if (used) { used[0] = ux; used[1] = uy; }
+    return AIC_OK;
+}
+
+int aic_present_split_text(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const aic_text_desc *td, const void *src, void *out, int out_is_device,
+                           aic_present_info *info, aic_lines_info *lines_info) {
+    if (!td) return aic_present_split_lines(c, d, ld, src, out, out_is_device, info, lines_info);  // (and reports under that name, or aic_present_split's)
+    if (lines_info) std::memset(lines_info, 0, sizeof(*lines_info));
+    if (c) {
+        if (info) std::memset(info, 0, sizeof(*info));
+        if (ld)
+            if (const int rc = lines_args_invalid(c, ld, "aic_present_split_text")) return rc;
+        if (const int rc = text_args_invalid(c, td, "aic_present_split_text")) return rc;
+    }
+    return present(c, d, (ld && ld->n_lines) ? ld : nullptr, td, src, out, out_is_device, info, lines_info, "aic_present_split_text");
 }
 
 }  // extern "C"

@@ -771,6 +771,54 @@ aic_present_info HipRtRenderer::present_split_to_device(const void *src_device, 
     return pi;
 }
 
+aic_text_desc HipRtRenderer::text_desc(const std::string &info_text) {
+    if (!text_font_set_) {
+        const std::vector<uint8_t> atlas = info_text_font_atlas();
+        check(aic_set_text_font(ctx_, atlas.data(), kInfoTextCell[0], kInfoTextCell[1], kInfoTextCell[2]), "aic_set_text_font");
+        text_font_set_ = true;
+    }
+    const Viewport vp = world_camera_.viewport();
+    const double origin_px[2] = {5.0, 5.0};  // postprocess.rs:324
+    aic_text_desc t{};
+    if (aic_text_geometry(vp.nominal_width, vp.nominal_height, kInfoTextCell[0], kInfoTextCell[1], kInfoTextCell[2], origin_px, &t.cols, &t.rows, t.scale, t.origin) != AIC_OK)
+        throw std::invalid_argument("present_split: the viewport's nominal size gives no character grid");
+    text_codes_.assign((size_t)t.cols * t.rows, 0);
+    const bool shown = world_camera_.options().debug_info_text;  // everything.rs:786-788: an empty text otherwise
+    if (aic_text_layout(info_text.data(), shown ? info_text.size() : 0, t.cols, t.rows, text_codes_.data(), nullptr) != AIC_OK)
+        throw std::invalid_argument("present_split: aic_text_layout");
+    t.codes = text_codes_.data();
+    return t;
+}
+
+Rendering HipRtRenderer::present_split(const void *src_device, uint32_t out_width, uint32_t out_height, const std::string &info_text, bool with_lines,
+                                       const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info) {
+    const aic_present_desc d = present_desc(out_width, out_height, 0);
+    const aic_lines_desc l = lines_desc(lines);
+    const aic_text_desc t = text_desc(info_text);
+    Rendering r;
+    r.width = out_width;
+    r.height = out_height;
+    r.data.assign((size_t)out_width * out_height * 4, 0);
+    uint8_t none = 0;
+    aic_present_info pi;
+    check(aic_present_split_text(ctx_, &d, with_lines ? &l : nullptr, &t, src_device, r.data.empty() ? &none : r.data.data(), 0, &pi, lines_info), "aic_present_split_text");
+    r.info.kernel_ms = pi.kernel_ms;
+    r.info.width = out_width;
+    r.info.height = out_height;
+    r.info.rows_rendered = out_height;
+    return r;
+}
+
+aic_present_info HipRtRenderer::present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags,
+                                                        const std::string &info_text, bool with_lines, const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info) {
+    const aic_present_desc d = present_desc(out_width, out_height, flags);
+    const aic_lines_desc l = lines_desc(lines);
+    const aic_text_desc t = text_desc(info_text);
+    aic_present_info pi;
+    check(aic_present_split_text(ctx_, &d, with_lines ? &l : nullptr, &t, src_device, out_device, 1, &pi, lines_info), "aic_present_split_text");
+    return pi;
+}
+
 SplitRendering HipRtRenderer::draw_split() {
     aic_frame_desc f = make_frame();
     f.flags |= AIC_FRAME_OUT_SPLIT;
@@ -855,6 +903,25 @@ void draw_info_text(uint8_t *rgba, uint32_t width, uint32_t height, const uint8_
                 std::memcpy(rgba + ((size_t)py * width + (size_t)px) * 4, paint, 4);
             }
     }
+}
+
+std::vector<uint8_t> info_text_font_atlas() {
+    constexpr uint32_t cw = kInfoTextCell[0], ch = kInfoTextCell[1];
+    std::vector<uint8_t> atlas((size_t)16 * ch * 16 * cw * 4, 0);
+    const uint8_t outline[4] = {0, 0, 0, 255}, foreground[4] = {255, 255, 255, 255};
+    std::vector<uint8_t> cell(32 * 32 * 4);
+    for (uint32_t code = 0; code < 256; code++) {
+        // the character alone, as draw_info_text places it: its glyph origin at (5, 5), so the cell -- origin less the margin -- starts at (4, 4)
+        std::string one;  // `char::encode_utf8`
+        if (code < 0x80u) one.push_back((char)code);
+        else { one.push_back((char)(0xc0u | (code >> 6))); one.push_back((char)(0x80u | (code & 0x3fu))); }
+        std::fill(cell.begin(), cell.end(), 0);
+        draw_info_text(cell.data(), 32, 32, outline, foreground, one);
+        const uint32_t ax = (code % 16u) * cw, ay = (code / 16u) * ch;
+        for (uint32_t y = 0; y < ch; y++)
+            std::memcpy(&atlas[(((size_t)ay + y) * 16 * cw + ax) * 4], &cell[((size_t)(4 + y) * 32 + 4) * 4], (size_t)cw * 4);
+    }
+    return atlas;
 }
 
 void encode_paint(const Camera &camera, float exposure, const float rgb_in[3], uint8_t out[4]) {

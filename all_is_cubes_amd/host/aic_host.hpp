@@ -285,6 +285,12 @@ struct Rendering {  // headless.rs:52-67
 // height, outline pixels in `outline`, glyph pixels in `foreground`, in the reference's call order (a later glyph's outline
 // may overwrite an earlier glyph's edge, as it does there). Pixels outside the image are dropped.
 void draw_info_text(uint8_t *rgba, uint32_t width, uint32_t height, const uint8_t outline[4], const uint8_t foreground[4], const std::string &text);
+// The font atlas of the interactive renderer's info text: generate_texture_atlas (all-is-cubes-gpu/src/text.rs:108-155) on Builtin::FontSystem16, what
+// aic_set_text_font takes with cells of kInfoTextCell. [16 * 18][16 * 9][4] RGBA8, premultiplied: each of the 256 codes drawn alone by the routine
+// above -- through char_to_glyph_index and its outline rule -- at (x * 9 + 1, y * 18 + 1) of its cell, outline (0, 0, 0, 255), foreground
+// (255, 255, 255, 255). A code that draws nothing (space, '\n') leaves its cell zero.
+constexpr uint32_t kInfoTextCell[3] = {9, 18, 1};  // cell width, height, margin: the 7 x 16 character cell and an outline of one
+std::vector<uint8_t> info_text_font_atlas();
 // Camera::post_process_color(color).to_srgb8() (camera_struct.rs:376-382, math/color.rs:669-676, 1038-1054) of an opaque
 // colour: what the reference's encoder makes of the overlay's black and white paints
 void encode_paint(const class Camera &camera, float exposure, const float rgb[3], uint8_t out[4]);
@@ -431,7 +437,7 @@ class HipRtRenderer : public HeadlessRenderer {
     // shaders/postprocess.wgsl:140-158 and 251-276; aic_present_split): the resident Split frame `src_device` -- of raytracer's viewport, i.e. the current
     // (size-policy-modified) viewport -- stretched with a linear filter to out_width x out_height, bloomed, tone-mapped and encoded, with bloom_intensity,
     // tone_mapping and maximum_intensity of the renderer's GraphicsOptions. The Rendering is the window's sRGB RGBA8 image (no flaws: nothing is left
-    // out; draw_info_text stays a separate host step, as it is for draw); the device form writes RGBA8 or, with AIC_PRESENT_OUT_F16, four linear f16
+    // out; the info text is the overloads' below that take it); the device form writes RGBA8 or, with AIC_PRESENT_OUT_F16, four linear f16
     // per pixel to `out_device`, which must not overlap the frame.
     Rendering present_split(const void *src_device, uint32_t out_width, uint32_t out_height);
     aic_present_info present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags = 0);
@@ -441,6 +447,14 @@ class HipRtRenderer : public HeadlessRenderer {
     Rendering present_split(const void *src_device, uint32_t out_width, uint32_t out_height, const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info = nullptr);
     aic_present_info present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags,
                                              const std::vector<aic_line_vertex> *lines, aic_lines_info *lines_info = nullptr);
+    // The same with the info text of the interactive renderer laid over the tone-mapped scene on the device (shaders/postprocess.wgsl:160-276,
+    // everything.rs:777-806; aic_present_split_text): the font atlas is set on first use, the character grid is character_texture_size of the world
+    // camera's viewport's nominal size with the text's origin at (5, 5) nominal pixels, and the text is empty when the options' debug_info_text is
+    // false (everything.rs:786-788). with_lines: the lines pass as above, `lines` == nullptr meaning the cursor's.
+    Rendering present_split(const void *src_device, uint32_t out_width, uint32_t out_height, const std::string &info_text, bool with_lines = false,
+                            const std::vector<aic_line_vertex> *lines = nullptr, aic_lines_info *lines_info = nullptr);
+    aic_present_info present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags, const std::string &info_text,
+                                             bool with_lines = false, const std::vector<aic_line_vertex> *lines = nullptr, aic_lines_info *lines_info = nullptr);
     // the world camera of the last update(): what to keep beside a resident frame as its `traced_with`
     const Camera &world_camera() const { return world_camera_; }
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)
@@ -504,6 +518,9 @@ class HipRtRenderer : public HeadlessRenderer {
     bool had_cursor_ = false;
     std::vector<aic_line_vertex> cursor_lines_;  // the wireframe of the cursor of the last update()
     aic_lines_desc lines_desc(const std::vector<aic_line_vertex> *lines) const;
+    bool text_font_set_ = false;
+    std::vector<uint8_t> text_codes_;  // the character grid of the last presentation with text
+    aic_text_desc text_desc(const std::string &info_text);
     bool bloom_ = false;  // set_bloom
     uint64_t pick_cursor_ = 0, pick_skip_unknown_ = 0;  // pick_pixels
     uint32_t pick_width_ = 0, pick_height_ = 0;         // ... and the viewport they belong to

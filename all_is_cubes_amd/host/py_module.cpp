@@ -85,6 +85,13 @@ PYBIND11_MODULE(_host, m) {
         if (image.ndim() != 3 || image.shape(2) != 4) throw std::invalid_argument("draw_info_text: image must be [h][w][4] uint8");
         draw_info_text(image.mutable_data(), (uint32_t)image.shape(1), (uint32_t)image.shape(0), outline.data(), foreground.data(), text);
     }, py::arg("image"), py::arg("text"), py::arg("outline") = std::array<uint8_t, 4>{0, 0, 0, 255}, py::arg("foreground") = std::array<uint8_t, 4>{255, 255, 255, 255});
+    m.def("info_text_font_atlas", [] {
+        const std::vector<uint8_t> a = info_text_font_atlas();
+        py::array_t<uint8_t> out({(py::ssize_t)(16 * kInfoTextCell[1]), (py::ssize_t)(16 * kInfoTextCell[0]), (py::ssize_t)4});
+        std::memcpy(out.mutable_data(), a.data(), a.size());
+        return out;
+    });
+    m.attr("INFO_TEXT_CELL") = py::make_tuple(kInfoTextCell[0], kInfoTextCell[1], kInfoTextCell[2]);
     m.def("rotation_around_y", [](double radians) { Quat q = rotation_around_y(radians); return std::array<double, 4>{q.i, q.j, q.k, q.r}; });
 
     py::class_<Camera>(m, "Camera")
@@ -374,6 +381,39 @@ PYBIND11_MODULE(_host, m) {
             l["n_clipped_away"] = li.n_clipped_away; l["n_fragments"] = li.n_fragments; l["n_passed"] = li.n_passed; l["n_pixels"] = li.n_pixels;
             return py::make_tuple(first, l);
         }, py::arg("src_ptr"), py::arg("out_width"), py::arg("out_height"), py::arg("lines") = py::none(), py::arg("flags") = 0u, py::arg("out_ptr") = (uintptr_t)0)
+        .def("present_split_text", [](HipRtRenderer &r, uintptr_t src_ptr, uint32_t out_width, uint32_t out_height, const std::string &info_text, bool with_lines,
+                                      py::object lines, uint32_t flags, uintptr_t out_ptr) {
+            // present_split_lines' arguments and result, with the info text; with_lines = false: no lines pass
+            std::vector<aic_line_vertex> v;
+            if (!lines.is_none()) {
+                const auto a = lines.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                if (a.size() % 14 != 0) throw std::invalid_argument("lines: [2 n, 7] floats");
+                v.resize((size_t)a.size() / 7);
+                if (!v.empty()) std::memcpy(v.data(), a.data(), v.size() * sizeof(aic_line_vertex));
+            }
+            const std::vector<aic_line_vertex> *given = lines.is_none() ? nullptr : &v;
+            aic_lines_info li{};
+            py::object first;
+            if (!out_ptr) {
+                if (flags) throw std::invalid_argument("present_split_text: a host Rendering is RGBA8; AIC_PRESENT_OUT_F16 needs out_ptr");
+                Rendering out;
+                { py::gil_scoped_release rel; out = r.present_split(reinterpret_cast<const void *>(src_ptr), out_width, out_height, info_text, with_lines, given, &li); }
+                first = py::cast(std::move(out));
+            } else {
+                aic_present_info i;
+                {
+                    py::gil_scoped_release rel;
+                    i = r.present_split_to_device(reinterpret_cast<const void *>(src_ptr), reinterpret_cast<void *>(out_ptr), out_width, out_height, flags, info_text, with_lines, given, &li);
+                }
+                py::dict d;
+                d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]); d["bloomed"] = i.bloomed;
+                first = std::move(d);
+            }
+            py::dict l;
+            l["n_clipped_away"] = li.n_clipped_away; l["n_fragments"] = li.n_fragments; l["n_passed"] = li.n_passed; l["n_pixels"] = li.n_pixels;
+            return py::make_tuple(first, l);
+        }, py::arg("src_ptr"), py::arg("out_width"), py::arg("out_height"), py::arg("info_text"), py::arg("with_lines") = false, py::arg("lines") = py::none(),
+           py::arg("flags") = 0u, py::arg("out_ptr") = (uintptr_t)0)
         .def("world_camera", [](const HipRtRenderer &r) { return Camera(r.world_camera()); })
         .def("set_world_camera_override", [](HipRtRenderer &r, py::object inv, float exposure) {
             if (inv.is_none()) { r.set_world_camera_override(nullptr, 1.0f); return; }

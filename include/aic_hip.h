@@ -543,6 +543,51 @@ typedef struct aic_cursor_desc {
 } aic_cursor_desc;
 #define AIC_CURSOR_MAX_LINES 28u
 int aic_cursor_wireframe(const aic_cursor_desc *cursor, aic_line_vertex *out /* [2 * 28] */, uint32_t *n_lines);
+/* The info text -- the frame-rate and statistics overlay, on by default (GraphicsOptions::debug_info_text) -- of the interactive renderer, which is
+ * part of its presentation's last shader: four entry points, DESIGN.md 4.14, tests/present_text_ref.py is that text in NumPy.
+ *
+ * aic_set_text_font replaces: the font atlas texture that generate_texture_atlas makes (all-is-cubes-gpu/src/text.rs:108-155) and
+ * EverythingRenderer::new binds with its metrics (everything.rs:305-311). atlas_rgba8: host memory, a grid of 16 x 16 cells of cell_width x cell_height
+ * RGBA8 texels with premultiplied alpha, [16 * cell_height][16 * cell_width][4], the cell of character code k at column k % 16, row k / 16;
+ * cell_margin texels on every side of a cell lie outside the logical cell (room for an outline that overlaps the neighbouring cells). The library
+ * knows no font, as the reference's shader knows none: the caller draws the atlas (the host mirror's info_text_font_atlas, the Rust shim's
+ * font_atlas). The atlas is copied into device memory the context owns, and is resident until it is replaced or the context destroyed; a NULL atlas
+ * drops it (the cell arguments are then not looked at). The call waits for nothing in flight, except that it is rejected while a frame occupies
+ * slot 0. AIC_ERR_INVALID: a cell dimension outside 1..1024; 2 * cell_margin >= min(cell_width, cell_height). */
+int aic_set_text_font(aic_ctx *ctx, const uint8_t *atlas_rgba8, uint32_t cell_width, uint32_t cell_height, uint32_t cell_margin);
+/* replaces: character_texture_size (all-is-cubes-gpu/src/text.rs:20-52) and the two text fields of PostprocessUniforms::new (postprocess.rs:316-331),
+ * host-only, in the reference's types and order: the logical cell is the cell less 2 * cell_margin; cols = max(1, (u32)ceil(nominal_width /
+ * logical_width)) in f64, rows likewise; scale = (f32)nominal / (f32)(cols * logical) as an f32 division; origin = (f32)(origin_px / nominal) with an
+ * f64 division (the reference passes (5, 5)). Any output may be NULL. AIC_ERR_INVALID: a nominal size that is not finite or <= 0; a cell or margin
+ * aic_set_text_font rejects; cols or rows above 65535. */
+int aic_text_geometry(double nominal_width, double nominal_height, uint32_t cell_width, uint32_t cell_height, uint32_t cell_margin, const double origin_px[2],
+                      uint32_t *cols, uint32_t *rows, float scale[2], float origin[2]);
+/* replaces: render_text_to_character_texture (all-is-cubes-gpu/src/text.rs:56-73), host-only: codes[rows][cols] is cleared to 0; '\n' starts a new
+ * row; every other scalar value of the `len` bytes of UTF-8 is its code if <= 0xFF, else '?'; the column advances with saturation; a character outside
+ * the grid is dropped (draw_to_texture.rs:69-81). Malformed UTF-8 decodes to U+FFFD, which becomes '?'. used, which may be NULL: the extent in columns
+ * and rows of the non-zero cells (the reference's `nonzero` rectangle from the grid's origin). AIC_ERR_INVALID: NULL codes, NULL utf8 with len > 0,
+ * cols or rows of 0 or above 65535. */
+int aic_text_layout(const char *utf8, uint64_t len, uint32_t cols, uint32_t rows, uint8_t *codes /* [rows][cols] */, uint32_t used[2]);
+/* replaces: render_text / render_character_cell and the text blend of postprocess_fragment (all-is-cubes-gpu/src/shaders/postprocess.wgsl:160-276),
+ * with the character texture of everything.rs:777-806: aic_present_split_lines with the info text laid over the tone-mapped scene on the device, before
+ * the output encoding. Per output pixel the four nearest cells of the code grid are looked up in the resident font atlas, the component-wise maximum
+ * of their texels is the text, and x = tone_mapped * (1 - text.a) + text: the text is neither tone-mapped nor bloomed, and lies over any lines. Output
+ * alpha stays 255 / 1.0. DESIGN.md 4.14 restates every operation (f32, one rounding each) and the device equals tests/present_text_ref.py bit for bit.
+ * text == NULL: the call is aic_present_split_lines itself -- the same launches, the same scratch.
+ * codes: [rows][cols] character codes (0 reads as a space), host memory staged into context scratch before the call returns, or with AIC_TEXT_DEVICE
+ * a device pointer. scale, origin: aic_text_geometry's. The staging belongs to the context, is allocated on first use and released in aic_destroy.
+ * Pixels that cannot show text pay next to nothing: when the atlas's cell 0x20 was all zero at aic_set_text_font, only the pixels within one cell of
+ * the non-zero codes of a host list (of the whole grid for a device list) look anything up. This changes no bit of the image.
+ * Rejected like aic_present_split_lines, and also: text given but no font set; NULL codes; cols or rows of 0 or above 65535; a non-finite component of
+ * scale or origin; unknown flag bits. All AIC_ERR_INVALID, before anything is queued, the context still usable. */
+#define AIC_TEXT_DEVICE 1u       /* `codes` is a device pointer on the context's device */
+typedef struct aic_text_desc {
+    float scale[2], origin[2];   /* info_text_coordinate_scale and info_text_origin (postprocess.rs:316-331): tc = (uv - origin) * scale */
+    uint32_t cols, rows, flags;  /* the character texture's size; AIC_TEXT_* */
+    const uint8_t *codes;
+} aic_text_desc;
+int aic_present_split_text(aic_ctx *ctx, const aic_present_desc *desc, const aic_lines_desc *lines /* may be NULL */, const aic_text_desc *text /* may be NULL */,
+                           const void *src_device, void *out, int out_is_device, aic_present_info *info, aic_lines_info *lines_info);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

@@ -34,6 +34,7 @@ pub const AIC_REPROJECT_MAX_LEVELS: u32 = 12;
 pub const AIC_PRESENT_OUT_F16: u32 = 1;
 pub const AIC_PRESENT_MAX_PIXELS: u64 = 2147483648;
 pub const AIC_LINES_DEVICE: u32 = 1;
+pub const AIC_TEXT_DEVICE: u32 = 1;
 pub const AIC_LINES_MAX: u32 = 1048576;
 pub const AIC_CURSOR_MAX_LINES: u32 = 28;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
@@ -237,6 +238,17 @@ pub struct aic_lines_info {
 }
 
 #[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct aic_text_desc {
+    pub scale: [f32; 2],
+    pub origin: [f32; 2],
+    pub cols: u32,
+    pub rows: u32,
+    pub flags: u32,
+    pub codes: *const u8,
+}
+
+#[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct aic_cursor_desc {
     pub cube: [i32; 3],
@@ -346,6 +358,10 @@ unsafe extern "C" {
     pub fn aic_present_split_lines(ctx: *mut aic_ctx, desc: *const aic_present_desc, lines: *const aic_lines_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info, lines_info: *mut aic_lines_info) -> c_int;
     pub fn aic_present_lines_scratch(src_w: u32, src_h: u32, out_w: u32, out_h: u32, n_lines: u32, bytes: *mut u64) -> c_int;
     pub fn aic_cursor_wireframe(cursor: *const aic_cursor_desc, out: *mut aic_line_vertex, n_lines: *mut u32) -> c_int;
+    pub fn aic_set_text_font(ctx: *mut aic_ctx, atlas_rgba8: *const u8, cell_width: u32, cell_height: u32, cell_margin: u32) -> c_int;
+    pub fn aic_text_geometry(nominal_width: f64, nominal_height: f64, cell_width: u32, cell_height: u32, cell_margin: u32, origin_px: *const f64, cols: *mut u32, rows: *mut u32, scale: *mut f32, origin: *mut f32) -> c_int;
+    pub fn aic_text_layout(utf8: *const c_char, len: u64, cols: u32, rows: u32, codes: *mut u8, used: *mut u32) -> c_int;
+    pub fn aic_present_split_text(ctx: *mut aic_ctx, desc: *const aic_present_desc, lines: *const aic_lines_desc, text: *const aic_text_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info, lines_info: *mut aic_lines_info) -> c_int;
     pub fn aic_pixel_order(width: u32, height: u32, order: *mut u32, central: *mut u32, cycle_length: *mut u64) -> c_int;
     pub fn aic_read_aux(ctx: *mut aic_ctx, out: *mut aic_pixel_aux, n_records: u64) -> c_int;
     pub fn aic_synchronize(ctx: *mut aic_ctx) -> c_int;

@@ -261,6 +261,8 @@ pub struct HipRtRenderer {
     device_light: Option<u8>,
     /// frames are bloomed on the device (`AIC_FRAME_BLOOM`, see `set_bloom`)
     bloom: bool,
+    /// the context holds [`font_atlas`] (`aic_set_text_font`, on the first [`HipRtRenderer::present_split_text`])
+    text_font_set: bool,
 }
 
 // SAFETY: the contexts are only used through `&mut self`; libaic_hip keeps no thread affinity besides hipSetDevice,
@@ -281,6 +283,38 @@ pub fn cursor_wireframe(cursor: &ffi::aic_cursor_desc) -> Option<Vec<[ffi::aic_l
     }
     out.truncate(n as usize);
     Some(out)
+}
+
+/// Cell width, height and margin of [`font_atlas`]: `FONT_SYSTEM_16`'s 7 x 16 character cell and an outline of one.
+const FONT_CELL: [u32; 3] = [9, 18, 1];
+
+/// The font atlas of the info text, as the reference makes it: `generate_texture_atlas` (all-is-cubes-gpu/src/text.rs:108-155) on
+/// `Builtin::FontSystem16`. 16 x 16 cells of the character cell grown by an outline of one texel, RGBA8 with premultiplied alpha; each of the first
+/// 256 scalar values drawn alone by `FontDef::draw_str_monospaced`, outline (0, 0, 0, 255), foreground (255, 255, 255, 255). Returns the texels,
+/// row-major, and the cell's width, height and margin: what `aic_set_text_font` takes.
+#[must_use]
+pub fn font_atlas() -> (Vec<[u8; 4]>, [u32; 3]) {
+    const OUTLINE_RADIUS: u32 = 1;
+    let font = universe::Builtin::FontSystem16.read::<text::FontDef>();
+    let logical = font.metrics().character_cell_size();
+    let cell = [logical.width as u32 + 2 * OUTLINE_RADIUS, logical.height as u32 + 2 * OUTLINE_RADIUS];
+    let row = 16 * cell[0] as usize;
+    let mut atlas = vec![[0u8; 4]; row * 16 * cell[1] as usize];
+    let mut buf = [0u8; 4];
+    for code in 0u32..256 {
+        let string = char::from_u32(code).expect("a scalar value below 256").encode_utf8(&mut buf);
+        let origin = [(code % 16 * cell[0] + OUTLINE_RADIUS) as i32, (code / 16 * cell[1] + OUTLINE_RADIUS) as i32];
+        font.draw_str_monospaced(string, |pixel, value| {
+            let (x, y) = (pixel.x + origin[0], pixel.y + origin[1]);
+            if x >= 0 && y >= 0 && (x as usize) < row && (y as usize) < 16 * cell[1] as usize {
+                atlas[y as usize * row + x as usize] = match value {
+                    text::Value::Outline => [0, 0, 0, 255],
+                    text::Value::Foreground => [255, 255, 255, 255],
+                };
+            }
+        });
+    }
+    (atlas, [cell[0], cell[1], OUTLINE_RADIUS])
 }
 
 fn options_of(o: &GraphicsOptions) -> ffi::aic_options {
@@ -361,7 +395,7 @@ impl HipRtRenderer {
                     .ok_or_else(|| format!("aic_create_multi failed with status {status}"))?,
             ),
         };
-        Ok(Self { device, cameras, size_policy, layers: Layers::default(), had_cursor: false, device_light: None, bloom: false })
+        Ok(Self { device, cameras, size_policy, layers: Layers::default(), had_cursor: false, device_light: None, bloom: false, text_font_set: false })
     }
 
     /// Blooms the frames drawn from now on as the reference's GPU renderer does (`AIC_FRAME_BLOOM`; all-is-cubes-gpu raytrace_to_texture.rs:644-661)
@@ -849,6 +883,102 @@ impl HipRtRenderer {
         // SAFETY: the context is live; the caller vouches for the frame and the target; `lines` is copied before the call returns, and the call
         // returns when the image is written
         self.device.check(unsafe { ffi::aic_present_split_lines(ctx.as_ptr(), &desc, &lines_desc, src_device, out_device, 1, &mut info, &mut lines_info) })?;
+        Ok((info, lines_info))
+    }
+
+    /// [`Self::present_split_lines`] with the info text of the interactive renderer laid over the tone-mapped scene on the device, as
+    /// `postprocess_fragment` does (all-is-cubes-gpu/src/shaders/postprocess.wgsl:160-276): the font atlas is [`font_atlas`], set on the first call;
+    /// the character grid is `character_texture_size` of the viewport's nominal size (text.rs:20-52) with the text's origin at (5, 5) nominal
+    /// pixels (postprocess.rs:316-331), filled as `render_text_to_character_texture` fills it (text.rs:56-73); the text is empty when the options'
+    /// `debug_info_text` is false (everything.rs:786-788). `lines`: `None` for no lines pass.
+    ///
+    /// # Safety
+    /// As [`Self::present_split`].
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer, with more than `ffi::AIC_LINES_MAX` lines, or with a viewport whose nominal size gives no character grid.
+    pub unsafe fn present_split_text(
+        &mut self,
+        src_device: *const core::ffi::c_void,
+        out_device: *mut core::ffi::c_void,
+        out_size: [u32; 2],
+        flags: u32,
+        lines: Option<&[[ffi::aic_line_vertex; 2]]>,
+        info_text: &str,
+    ) -> Result<(ffi::aic_present_info, ffi::aic_lines_info), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("present_split_text needs a single-device renderer") };
+        let cell = FONT_CELL;
+        if !self.text_font_set {
+            let (atlas, made_cell) = font_atlas();
+            assert_eq!(made_cell, cell, "FontSystem16's character cell is 7 x 16");
+            // SAFETY: the context is live; the atlas holds 16 x 16 cells of the size given and is copied before the call returns
+            self.device.check(unsafe { ffi::aic_set_text_font(ctx.as_ptr(), atlas.as_ptr().cast(), cell[0], cell[1], cell[2]) })?;
+            self.text_font_set = true;
+        }
+        let (viewport, _) = self.frame_desc();
+        let camera = &self.cameras.cameras().world;
+        let options = options_of(camera.options());
+        let desc = ffi::aic_present_desc {
+            src_width: viewport.framebuffer_size.width,
+            src_height: viewport.framebuffer_size.height,
+            out_width: out_size[0],
+            out_height: out_size[1],
+            bloom_intensity: options.bloom_intensity,
+            tone_mapping: options.tone_mapping,
+            maximum_intensity: options.maximum_intensity,
+            flags,
+        };
+        let view_projection = camera.view_matrix().then(&camera.projection_matrix()).to_array().map(|v| v as f32);
+        let lines_desc = lines.map(|lines| ffi::aic_lines_desc {
+            view_projection,
+            n_lines: u32::try_from(lines.len()).expect("too many lines"),
+            flags: 0,
+            vertices: lines.as_ptr().cast(),
+        });
+        let mut text_desc = ffi::aic_text_desc { scale: [0.0; 2], origin: [0.0; 2], cols: 0, rows: 0, flags: 0, codes: core::ptr::null() };
+        let origin_px = [5.0f64, 5.0];
+        // SAFETY: every pointer is to a local of the size the call writes
+        let rc = unsafe {
+            ffi::aic_text_geometry(
+                viewport.nominal_size.width.into_inner(),
+                viewport.nominal_size.height.into_inner(),
+                cell[0],
+                cell[1],
+                cell[2],
+                origin_px.as_ptr(),
+                &mut text_desc.cols,
+                &mut text_desc.rows,
+                text_desc.scale.as_mut_ptr(),
+                text_desc.origin.as_mut_ptr(),
+            )
+        };
+        assert_eq!(rc, 0, "the viewport's nominal size gives no character grid");
+        let shown = if camera.options().debug_info_text { info_text } else { "" };
+        let mut codes = vec![0u8; text_desc.cols as usize * text_desc.rows as usize];
+        // SAFETY: `codes` holds rows x cols bytes, which is what the call writes
+        let rc = unsafe { ffi::aic_text_layout(shown.as_ptr().cast(), shown.len() as u64, text_desc.cols, text_desc.rows, codes.as_mut_ptr(), core::ptr::null_mut()) };
+        assert_eq!(rc, 0, "aic_text_layout");
+        text_desc.codes = codes.as_ptr();
+        let mut info = ffi::aic_present_info::default();
+        let mut lines_info = ffi::aic_lines_info::default();
+        // SAFETY: the context is live; the caller vouches for the frame and the target; `lines` and `codes` are copied before the call returns, and
+        // the call returns when the image is written
+        self.device.check(unsafe {
+            ffi::aic_present_split_text(
+                ctx.as_ptr(),
+                &desc,
+                lines_desc.as_ref().map_or(core::ptr::null(), core::ptr::from_ref),
+                &text_desc,
+                src_device,
+                out_device,
+                1,
+                &mut info,
+                &mut lines_info,
+            )
+        })?;
         Ok((info, lines_info))
     }
 

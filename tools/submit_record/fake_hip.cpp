@@ -103,6 +103,10 @@ void rec_present(const aic::BloomGeom &g, const aic::PresentParams &p, hipStream
     rec_bloom_geom(g);
     rec("  src %s %ux%u scene %s mips %s out %s intensity %a tone_mapping %d maximum_intensity %a srgb_thr %s out_f16 %d %s", P(p.src), p.src_width, p.src_height, P(p.scene), P(p.mips),
         P(p.out), p.intensity, p.tone_mapping, p.maximum_intensity, P(p.srgb_thr), (int)p.out_f16, S(stream));
+    const aic::PresentText &t = p.text;
+    if (t.codes)  // (a presentation without text records what it did before there was any)
+        rec("  text codes %s atlas %s scale %a %a origin %a %a grid %ux%u cell %ux%u margin %u reach %u %u %u %u", P(t.codes), P(t.atlas), t.scale[0], t.scale[1], t.origin[0],
+            t.origin[1], t.cols, t.rows, t.cell_w, t.cell_h, t.margin, t.x0, t.y0, t.x1, t.y1);
 }
 
 }  // namespace

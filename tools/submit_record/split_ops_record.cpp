@@ -1,5 +1,5 @@
 // split_ops_record.cpp -- drives the operations on a resident Split frame (csrc/aic_split_ops.cpp: aic_reproject_split, aic_pick_pixels,
-// aic_present_split, aic_present_split_lines and their size queries) through a fixed list of scenarios against the recording fake (fake_hip.cpp) and
+// aic_present_split, aic_present_split_lines, aic_present_split_text with aic_set_text_font, and their size queries and host-only helpers) through a fixed list of scenarios against the recording fake (fake_hip.cpp) and
 // prints the record: every runtime call and launch with its arguments, each call's return code and message, every field of its info structs and what
 // the context keeps for these operations afterwards. Two builds of the host code make the same calls exactly when their records are byte-identical
 // (build.sh, tests/test_split_ops_record_cpu.py). A scenario named "reject: ..." is one refused call on a context an earlier scenario made; every
@@ -134,6 +134,48 @@ int present(aic_ctx *c, const aic_present_desc *d, bool through_lines, const aic
     return rc;
 }
 
+// aic_present_split_text with `ld` and `td` (either may be NULL); the text state is recorded on a line of its own, so that rec_state's stays what it was
+void rec_text_state(const aic_ctx *c) {
+    if (!c) return;
+    rec("  text state atlas %zu/%zu cell %ux%u margin %u space_blank %d codes %zu/%zu", c->text_atlas.n, c->text_atlas.cap, c->text_cell_w, c->text_cell_h, c->text_margin,
+        (int)c->text_space_blank, c->text_codes.n, c->text_codes.cap);
+}
+int present_text(aic_ctx *c, const aic_present_desc *d, const aic_lines_desc *ld, const aic_text_desc *td, const void *src, void *out, int out_is_device, bool want_info = true) {
+    aic_present_info i;
+    aic_lines_info li;
+    std::memset(&i, 0xff, sizeof(i));
+    std::memset(&li, 0xff, sizeof(li));
+    const int rc = aic_present_split_text(c, d, ld, td, src, out, out_is_device, want_info ? &i : nullptr, want_info ? &li : nullptr);
+    rec_rc(c, "aic_present_split_text", rc);
+    rec("  info kernel_ms %a levels %u t0 %u %u bloomed %u reserved %u %u %u", i.kernel_ms, i.levels, i.t0[0], i.t0[1], i.bloomed, i.reserved[0], i.reserved[1], i.reserved[2]);
+    rec("  lines_info clipped_away %llu fragments %llu passed %llu pixels %llu", (unsigned long long)li.n_clipped_away, (unsigned long long)li.n_fragments,
+        (unsigned long long)li.n_passed, (unsigned long long)li.n_pixels);
+    rec_state(c);
+    rec_text_state(c);
+    return rc;
+}
+int set_font(aic_ctx *c, const uint8_t *atlas, uint32_t cw, uint32_t ch, uint32_t margin) {
+    const int rc = aic_set_text_font(c, atlas, cw, ch, margin);
+    rec_rc(c, "aic_set_text_font", rc);
+    rec_text_state(c);
+    return rc;
+}
+// a (9, 18, 1) atlas with every cell but 0x20 (blank_space) or every cell filled; an 8 x 3 grid of codes with "ab" and "c" in its first two rows
+std::vector<uint8_t> atlas_9x18(bool blank_space) {
+    std::vector<uint8_t> a(16 * 18 * 16 * 9 * 4, 0x80);
+    if (blank_space)
+        for (int y = 0; y < 18; y++) std::memset(&a[((size_t)(2 * 18 + y) * 16 * 9) * 4], 0, 9 * 4);
+    return a;
+}
+aic_text_desc text_desc(const uint8_t *codes, uint32_t flags = 0) {
+    aic_text_desc t;
+    std::memset(&t, 0, sizeof(t));
+    t.scale[0] = 0.875f; t.scale[1] = 0.75f; t.origin[0] = 0.125f; t.origin[1] = 0.0625f;
+    t.cols = 8; t.rows = 3; t.flags = flags; t.codes = codes;
+    return t;
+}
+const uint8_t kCodes[24] = {'a', 'b', 0, 0, 0, 0, 0, 0, 'c', 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
 // one scenario: ordinals from zero, everything it allocates freed at its end -- or (not fresh) one that goes on with what the scenario before left
 void scenario(const std::string &name, const std::function<void()> &body, bool fresh = true) {
     if (fresh) fake_reset();
@@ -222,6 +264,98 @@ void lines() {
                                     if (to_device) (void)hipFree(out); else std::free(out);
                                     aic_destroy(c);
                                 });
+}
+
+// ---- text: a host list and a device list, with and without lines, a blank and a non-blank space cell; without text the call is aic_present_split_lines
+void text() {
+    static const std::vector<aic_line_vertex> host(2 * 28);
+    for (const auto &s : kPresentShapes)
+        for (int blank = 0; blank < 2; blank++)
+            for (uint32_t text_flags : {0u, (uint32_t)AIC_TEXT_DEVICE})
+                for (uint32_t n_lines : {0u, 28u})
+                    for (float bloom : {0.f, 0.125f})
+                        for (uint32_t flags : {0u, (uint32_t)AIC_PRESENT_OUT_F16})
+                            for (int to_device = 0; to_device < 2; to_device++)
+                                scenario("text" + str({s[0], s[1], s[2], s[3], blank, text_flags, n_lines, (long)(bloom * 1000), flags, to_device}), [&] {
+                                    aic_ctx *c = make_ctx();
+                                    const std::vector<uint8_t> atlas = atlas_9x18(blank != 0);
+                                    set_font(c, atlas.data(), 9, 18, 1);
+                                    const size_t out_bytes = (size_t)s[2] * s[3] * (flags ? 8 : 4);
+                                    void *src = dev((size_t)s[0] * s[1] * 12), *out = to_device ? dev(out_bytes) : std::malloc(out_bytes + 1);
+                                    uint8_t *on_device = (uint8_t *)dev(sizeof(kCodes));
+                                    const aic_present_desc d = present_desc(s[0], s[1], s[2], s[3], bloom, flags);
+                                    const aic_lines_desc l = lines_desc(host.data(), n_lines);
+                                    const aic_text_desc t = text_desc(text_flags ? on_device : kCodes, text_flags);
+                                    for (int n = 0; n < 2; n++) present_text(c, &d, n_lines ? &l : nullptr, &t, src, out, to_device);  // (the second finds its staging)
+                                    (void)hipFree(src); (void)hipFree(on_device);
+                                    if (to_device) (void)hipFree(out); else std::free(out);
+                                    aic_destroy(c);
+                                });
+    scenario("text: sequence on one context", [] {
+        aic_ctx *c = make_ctx();
+        const uint32_t W = 40, H = 24;
+        void *src = dev(W * H * 12), *out = dev(W * H * 8);
+        const aic_present_desc d = present_desc(W, H, W, H);
+        const aic_lines_desc l = lines_desc(host.data(), 28), none = lines_desc(nullptr, 0);
+        aic_text_desc t = text_desc(kCodes);
+        rec("-- no text: the call is aic_present_split_lines, with lines, with a list of none and with no list");
+        present_text(c, &d, &l, nullptr, src, out, 1);
+        present_text(c, &d, &none, nullptr, src, out, 1);
+        present_text(c, &d, nullptr, nullptr, src, out, 1);
+        rec("-- text before any font is refused; then a font, a text, an empty text, a larger grid");
+        present_text(c, &d, nullptr, &t, src, out, 1);
+        const std::vector<uint8_t> blank = atlas_9x18(true), full = atlas_9x18(false);
+        set_font(c, blank.data(), 9, 18, 1);
+        present_text(c, &d, nullptr, &t, src, out, 1);
+        static const uint8_t zeros[64 * 8] = {0};
+        t = text_desc(zeros);
+        present_text(c, &d, &none, &t, src, out, 1);
+        t.cols = 64; t.rows = 8;
+        present_text(c, &d, nullptr, &t, src, out, 1);
+        rec("-- the font replaced by a smaller one whose space is not blank, then by a larger one, then dropped");
+        set_font(c, full.data(), 3, 3, 1);
+        t = text_desc(kCodes);
+        present_text(c, &d, nullptr, &t, src, out, 1);
+        set_font(c, full.data(), 9, 18, 1);
+        set_font(c, nullptr, 0, 0, 0);
+        present_text(c, &d, nullptr, &t, src, out, 1);
+        rec("-- an empty output with text");
+        set_font(c, blank.data(), 9, 18, 1);
+        const aic_present_desc e = present_desc(W, H, 0, H);
+        present_text(c, &e, nullptr, &t, src, out, 1);
+        (void)hipFree(src); (void)hipFree(out);
+        aic_destroy(c);
+    });
+    scenario("text: host-only helpers", [] {
+        const double origin_px[2] = {5.0, 5.0};
+        const double sizes[][2] = {{1, 1}, {7, 16}, {8, 17}, {640.5, 480.25}, {1920, 1080}, {65535, 1}};
+        const uint32_t cells[][3] = {{9, 18, 1}, {5, 7, 0}, {3, 3, 1}};
+        for (const auto &n : sizes)
+            for (const auto &cell : cells) {
+                uint32_t cols = 99, rows = 99;
+                float scale[2] = {99.f, 99.f}, origin[2] = {99.f, 99.f};
+                const int rc = aic_text_geometry(n[0], n[1], cell[0], cell[1], cell[2], origin_px, &cols, &rows, scale, origin);
+                rec("aic_text_geometry %a x %a cell %u %u %u rc %d grid %ux%u scale %a %a origin %a %a", n[0], n[1], cell[0], cell[1], cell[2], rc, cols, rows, scale[0], scale[1], origin[0],
+                    origin[1]);
+            }
+        rec("aic_text_geometry invalid rc %d %d %d %d %d %d %d %d", aic_text_geometry(0, 1, 9, 18, 1, origin_px, nullptr, nullptr, nullptr, nullptr),
+            aic_text_geometry(1, -1, 9, 18, 1, origin_px, nullptr, nullptr, nullptr, nullptr), aic_text_geometry(kInf, 1, 9, 18, 1, origin_px, nullptr, nullptr, nullptr, nullptr),
+            aic_text_geometry(1, kNaN, 9, 18, 1, origin_px, nullptr, nullptr, nullptr, nullptr), aic_text_geometry(8, 8, 0, 18, 1, origin_px, nullptr, nullptr, nullptr, nullptr),
+            aic_text_geometry(8, 8, 9, 1025, 1, origin_px, nullptr, nullptr, nullptr, nullptr), aic_text_geometry(8, 8, 4, 18, 2, origin_px, nullptr, nullptr, nullptr, nullptr),
+            aic_text_geometry(65536, 8, 3, 3, 1, origin_px, nullptr, nullptr, nullptr, nullptr));
+        const char *texts[] = {"", "\n\n", "a b\nc d", "a line longer than the grid", "1\n2\n3\n4", "\xc3\xa9\xe2\x82\xac", "\xff\xc3"};
+        for (const char *text : texts) {
+            uint8_t codes[3 * 8];
+            uint32_t used[2] = {99, 99};
+            const int rc = aic_text_layout(text, std::strlen(text), 8, 3, codes, used);
+            std::string line;
+            for (uint8_t code : codes) { char b[4]; std::snprintf(b, sizeof(b), " %02x", code); line += b; }
+            rec("aic_text_layout rc %d used %u %u codes%s", rc, used[0], used[1], line.c_str());
+        }
+        uint8_t one;
+        rec("aic_text_layout invalid rc %d %d %d %d", aic_text_layout("a", 1, 1, 1, nullptr, nullptr), aic_text_layout(nullptr, 1, 1, 1, &one, nullptr),
+            aic_text_layout("a", 1, 0, 1, &one, nullptr), aic_text_layout("a", 1, 1, 65536, &one, nullptr));
+    });
 }
 
 // ---- sequences on one context
@@ -429,6 +563,8 @@ void rejections() {
     rejection("busy: present", [&] { present(c, &d, false, nullptr, src, out, 1); });
     rejection("busy: present with lines", [&] { present(c, &d, true, &l, src, out, 1); });
     rejection("busy: present through aic_present_split_lines, no lines", [&] { present(c, &d, true, &none, src, out, 1); });
+    const std::vector<uint8_t> busy_atlas = atlas_9x18(true);
+    rejection("busy: font", [&] { set_font(c, busy_atlas.data(), 9, 18, 1); });
     scenario("rejections: the frame is waited for, and every entry point runs", [&] {
         aic_frame_info fi;
         rec_rc(c, "aic_render_wait", aic_render_wait(c, 0, &fi));
@@ -437,6 +573,60 @@ void rejections() {
         present(c, &d, false, nullptr, src, out, 1);
         present(c, &d, true, &l, src, out, 1);
         for (void *p : {src, dst, out, lists}) (void)hipFree(p);
+        aic_destroy(c);
+    }, false);
+}
+
+// ---- what aic_set_text_font and aic_present_split_text refuse, each on its own, on a context of their own
+void text_rejections() {
+    const uint32_t W = 40, H = 24, N = 28;
+    aic_ctx *c = nullptr;
+    char *src = nullptr, *out = nullptr;
+    static const std::vector<aic_line_vertex> host(2 * N);
+    scenario("text rejections: the context they share", [&] {
+        c = make_ctx();
+        src = (char *)dev(W * H * 12); out = (char *)dev(W * H * 8);
+    });
+    // what aic_set_text_font and aic_present_split_text add; the font is set by a scenario of its own, then every refusal stands alone
+    const std::vector<uint8_t> atlas = atlas_9x18(true);
+    rejection("font: no context", [&] { set_font(nullptr, atlas.data(), 9, 18, 1); });
+    rejection("font: cell of no width", [&] { set_font(c, atlas.data(), 0, 18, 1); });
+    rejection("font: cell too high", [&] { set_font(c, atlas.data(), 9, 1025, 1); });
+    rejection("font: margin takes the whole cell", [&] { set_font(c, atlas.data(), 4, 18, 2); });
+    {
+        const aic_present_desc d = present_desc(W, H, W, H);
+        const aic_text_desc t = text_desc(kCodes);
+        rejection("text: no font set", [&] { present_text(c, &d, nullptr, &t, src, out, 1); });
+    }
+    scenario("text rejections: a font for the context they share", [&] { set_font(c, atlas.data(), 9, 18, 1); }, false);
+    {
+        const aic_present_desc d = present_desc(W, H, W, H);
+        const aic_lines_desc l = lines_desc(host.data(), N);
+        auto tr = [&](const char *what, const aic_text_desc &t, const aic_lines_desc *ld = nullptr) {
+            rejection(std::string("text: ") + what, [&] { present_text(c, &d, ld, &t, src, out, 1); });
+        };
+        auto with = [](aic_text_desc t, const std::function<void(aic_text_desc &)> &edit) { edit(t); return t; };
+        const aic_text_desc t = text_desc(kCodes);
+        tr("no codes", text_desc(nullptr));
+        tr("no device codes", text_desc(nullptr, AIC_TEXT_DEVICE));
+        tr("unknown flag", text_desc(kCodes, 2u));
+        tr("no columns", with(t, [](aic_text_desc &e) { e.cols = 0; }));
+        tr("no rows", with(t, [](aic_text_desc &e) { e.rows = 0; }));
+        tr("too many columns", with(t, [](aic_text_desc &e) { e.cols = 65536; }));
+        tr("too many rows", with(t, [](aic_text_desc &e) { e.rows = 65536; }));
+        tr("NaN scale", with(t, [](aic_text_desc &e) { e.scale[1] = kNaN; }));
+        tr("infinite origin", with(t, [](aic_text_desc &e) { e.origin[0] = -kInf; }));
+        tr("a bad line list", t, [&] { static aic_lines_desc bad; bad = lines_desc(host.data(), N, 2u); return &bad; }());
+        rejection("text: the presentation's own, no src", [&] { present_text(c, &d, &l, &t, nullptr, out, 1); });
+        rejection("text: the presentation's own, no context", [&] { present_text(nullptr, &d, &l, &t, src, out, 1); });
+        const aic_present_desc bad = present_desc(W, H, W, H, -0.125f);
+        rejection("text: the presentation's own, negative bloom", [&] { present_text(c, &bad, nullptr, &t, src, out, 1); });
+    }
+    scenario("text rejections: a good call, and the context is released", [&] {
+        const aic_present_desc d = present_desc(W, H, W, H);
+        const aic_text_desc t = text_desc(kCodes);
+        present_text(c, &d, nullptr, &t, src, out, 1);
+        for (void *p : {src, out}) (void)hipFree(p);
         aic_destroy(c);
     }, false);
 }
@@ -493,6 +683,16 @@ void all_runtime_failures() {
                 return present(c, &d, true, &l, b.src, to_device ? b.out : (void *)image.data(), to_device);
             });
     }
+    // with text: the font set before the counted call; a host list to the host, a device list (in the vertex list's buffer) to the device
+    static const std::vector<uint8_t> atlas = atlas_9x18(true);
+    for (int to_device = 0; to_device < 2; to_device++)
+        runtime_failures("text" + str({to_device}), false, [&](aic_ctx *c, const Buffers &b) {
+            const aic_present_desc d = present_desc(W, H, 2 * W, 2 * H, 0.125f, to_device ? AIC_PRESENT_OUT_F16 : 0u);
+            const aic_lines_desc l = lines_desc(host.data(), 28);
+            const aic_text_desc t = to_device ? text_desc((const uint8_t *)b.list, AIC_TEXT_DEVICE) : text_desc(kCodes);
+            return present_text(c, &d, &l, &t, b.src, to_device ? b.out : (void *)image.data(), to_device);
+        }, [](aic_ctx *c, const Buffers &) { set_font(c, atlas.data(), 9, 18, 1); });
+    runtime_failures("font", false, [](aic_ctx *c, const Buffers &) { return set_font(c, atlas.data(), 9, 18, 1); });
 }
 
 }  // namespace
@@ -500,8 +700,10 @@ void all_runtime_failures() {
 int main() {
     shapes();
     lines();
+    text();
     sequences();
     rejections();
+    text_rejections();
     all_runtime_failures();
     fake_reset();
     rec("total: %d scenarios", n_scenarios);
