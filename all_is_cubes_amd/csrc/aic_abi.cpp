@@ -27,6 +27,7 @@
 #include "aic_bloom.h"
 #include "aic_ctx.h"
 #include "aic_device.h"
+#include "aic_encode.h"
 #include "aic_launch.h"
 
 using namespace aic;
@@ -327,6 +328,10 @@ aic_ctx *aic_create(int device_id, int *status) {
             std::memcpy(&thr[k], &hi_b, 4);
         }
         ok = ok && c->srgb_thr.ensure(256) == hipSuccess && hipMemcpy(c->srgb_thr.p, thr, sizeof(thr), hipMemcpyHostToDevice) == hipSuccess;
+        // ... and as the bucket table the trace kernels read (aic_encode.h). Thresholds that did not fit it would be a libm whose powf is far off.
+        uint32_t buckets[kSrgbBucketWords];
+        ok = ok && srgb8_bucket_build(thr, buckets) && c->srgb_buckets.ensure(kSrgbBucketWords) == hipSuccess &&
+             hipMemcpy(c->srgb_buckets.p, buckets, sizeof(buckets), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) {
         *status = AIC_ERR_DEVICE;
@@ -360,7 +365,7 @@ void aic_destroy(aic_ctx *c) {
         if (i > 0 && fs.stream) (void)hipStreamDestroy(fs.stream);
     }
     for (auto &l : c->layers) l.release();
-    c->lut.release(); c->srgb_thr.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->pick_scratch.release(); c->present_scratch.release(); c->lines_scratch.release();
+    c->lut.release(); c->srgb_thr.release(); c->srgb_buckets.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->pick_scratch.release(); c->present_scratch.release(); c->lines_scratch.release();
     c->text_atlas.release(); c->text_codes.release();
     if (c->dump) std::fclose(c->dump);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);

@@ -52,7 +52,7 @@ struct BloomParams {
     float intensity;         // GraphicsOptions::bloom_intensity
     int32_t tone_mapping;
     float maximum_intensity;
-    const float *srgb_thr;   // the context's 256 sRGB8 thresholds (as DevFrame::srgb_thr)
+    const float *srgb_thr;   // the context's 256 sRGB8 thresholds: srgb_thr[k] = smallest linear value whose sRGB8 encoding is >= k
 };
 
 // Queues the whole post-process on `stream`: the chain (downsample 0 from the ColorBuf, then the stages of mip_ping.rs:301-420) and the composite into

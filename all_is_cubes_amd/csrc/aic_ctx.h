@@ -115,7 +115,8 @@ struct aic_ctx {
     hipStream_t upload_stream = nullptr;  // light-volume uploads run beside the frames in flight
     Layer layers[2];
     DevBuf<float> lut;
-    DevBuf<float> srgb_thr;
+    DevBuf<float> srgb_thr;         // the 256 sRGB8 thresholds (bloom and presentation kernels)
+    DevBuf<uint32_t> srgb_buckets;  // the same as a bucket table (aic_encode.h): what the trace kernels encode from
     DevBuf<uint32_t> out;      // internal RGBA8 target when the caller wants a host copy
     DevBuf<DevAux> aux;
     DevBuf<unsigned char> staging;  // scratch for scatter updates / probes

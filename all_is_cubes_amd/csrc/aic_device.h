@@ -195,7 +195,7 @@ struct DevFrame {
     uint32_t n_sub;          // frames this launch traces: 1, 2, 4 or 8 (DevSub)
     DevSub sub[kMaxSub];
     const float *light_lut;  // 256 floats
-    const float *srgb_thr;   // 256 floats: srgb_thr[k] = smallest linear value whose sRGB8 encoding is >= k
+    const uint32_t *srgb_buckets;  // kSrgbBucketWords entries: the sRGB8 encoding by the upper 16 bits of a value's pattern (aic_encode.h; made with the context)
     // Pixel-edge tables (host-made, per frame shape): edge_x[x] = x / width * 2 - 1 for x = 0..width, edge_y[y] = -(y / height * 2 - 1) for
     // y = 0..height -- Viewport's pixel edges (viewport.rs:104-113) evaluated once in the reference's own f64 operations, so that starting a
     // ray (and re-deriving its origin, below) costs two 16-byte loads instead of four f64 divisions. Null for patch batches and orthographic views.

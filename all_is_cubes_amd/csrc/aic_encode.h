@@ -1,10 +1,88 @@
 // aic_encode.h -- the colour encoder shared by the trace kernels (aic_trace.hip) and the bloom post-process (aic_bloom.hip):
 // Rgba::from(ColorBuf), the PositiveSign arithmetic it relies on, and Rgba::to_srgb8 through the window table of sRGB8 thresholds.
 // The bodies are the trace kernels' own, moved here unchanged so that a bloomed frame is encoded by the same instructions as a plain one.
+// The bucket table of sRGB8 (srgb8_bucket_*, the trace kernels' FINISH) is plain C++ that also compiles for the host without HIP: tests build it with g++ and
+// check it against the thresholds for every bit pattern (tests/test_srgb8_bucket_host.py).
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define AIC_ENC_HD __host__ __device__ __forceinline__
+#else
+#define AIC_ENC_HD static inline
+#endif
+
+namespace aic {
+
+// Rgba::to_srgb8 colour channels by BUCKET: the encoding of c is the number of thresholds thr[1..255] <= c (below), a step function of c's bit pattern. The
+// thresholds lie at least 100 925 bit patterns apart (k = 189 / 190, near 0.506), more than 2^16, so the patterns that share their upper 16 bits -- a bucket -- hold
+// at most one threshold. One 4-byte entry per bucket from thr[1]'s (0x391f) to 1.0's (0x3f80) then gives the exact code with one load, one compare and one add:
+//   bits 24-31  the code at the bucket's first pattern: the number of thresholds in the buckets below
+//   bits 0-16   the low 16 bits of the bucket's threshold, or 0x10000 (which no pattern's low half reaches) when it has none
+// A value below the first bucket encodes like the first bucket's first pattern (at or below thr[1]), one above 1.0 like 1.0: the caller clamps.
+constexpr uint32_t kSrgbBucketFirst = 0x391fu, kSrgbBucketLast = 0x3f80u;
+constexpr uint32_t kSrgbBucketWords = kSrgbBucketLast - kSrgbBucketFirst + 1u;  // 1634
+constexpr uint32_t kSrgbBucketNoThreshold = 0x10000u;
+
+AIC_ENC_HD uint32_t srgb8_float_bits(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float_as_uint(v);
+#else
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    return b;
+#endif
+}
+
+// Builds the table from thr[0..255] (thr[k], k >= 1: the smallest f32 whose encoding is >= k; thr[0] is not read). False -- and the table is not to be used -- if
+// the thresholds do not fit it: not ascending, outside the buckets, or two in one bucket.
+AIC_ENC_HD bool srgb8_bucket_build(const float *thr, uint32_t *table) {
+    for (uint32_t i = 0; i < kSrgbBucketWords; i++) table[i] = kSrgbBucketNoThreshold;
+    uint32_t below = kSrgbBucketFirst << 16;  // (what smaller values are clamped to has to encode to 0)
+    for (uint32_t k = 1; k < 256u; k++) {
+        const uint32_t bits = srgb8_float_bits(thr[k]);
+        if (bits <= below || (bits >> 16) < kSrgbBucketFirst || (bits >> 16) >= kSrgbBucketLast) return false;  // (the last bucket is 1.0's alone)
+        below = bits;
+        uint32_t &e = table[(bits >> 16) - kSrgbBucketFirst];
+        if (e != kSrgbBucketNoThreshold) return false;
+        e = bits & 0xffffu;
+    }
+    uint32_t code = 0u;
+    for (uint32_t i = 0; i < kSrgbBucketWords; i++) {
+        const bool has = table[i] != kSrgbBucketNoThreshold;
+        table[i] |= code << 24;
+        code += has ? 1u : 0u;
+    }
+    return code == 255u;
+}
+
+// The encoding of the float with bit pattern `bits`, which the caller has clamped to [kSrgbBucketFirst << 16, 1.0f]
+AIC_ENC_HD uint32_t srgb8_bucket_encode(uint32_t bits, const uint32_t *table) {
+    const uint32_t e = table[(bits >> 16) - kSrgbBucketFirst];
+    return (e >> 24) + ((bits & 0xffffu) >= (e & 0x1ffffu) ? 1u : 0u);
+}
+
+// One colour channel: clamped into the table's range (NaN goes to its lower end: fmaxf returns the operand that is a number) and looked up for every value, so
+// that nothing branches; 0, negatives (cannot occur) and NaN encode to 0.
+AIC_ENC_HD uint32_t srgb8_bucket_channel(float c, const uint32_t *table) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float lo = __uint_as_float(kSrgbBucketFirst << 16);
+#else
+    const uint32_t lo_bits = kSrgbBucketFirst << 16;
+    float lo;
+    memcpy(&lo, &lo_bits, 4);
+#endif
+    const uint32_t code = srgb8_bucket_encode(srgb8_float_bits(fminf(fmaxf(c, lo), 1.0f)), table);
+    return c > 0.f ? code : 0u;
+}
+
+}  // namespace aic
+
+#if defined(__HIPCC__)
 
 #ifndef AIC_DEV
 #define AIC_DEV __device__ __forceinline__
@@ -99,4 +177,13 @@ AIC_DEV void srgb8_rgb(float r, float g, float b, const float *__restrict__ w, u
         if (open_b) B = srgb8_search(b, kb, w);
     }
 }
+
+// The three channels from the bucket table in global memory (the trace kernels' FINISH): one load per channel, no LDS
+AIC_DEV void srgb8_rgb_bucket(float r, float g, float b, const uint32_t *__restrict__ table, uint32_t &R, uint32_t &G, uint32_t &B) {
+    R = srgb8_bucket_channel(r, table);
+    G = srgb8_bucket_channel(g, table);
+    B = srgb8_bucket_channel(b, table);
+}
 }  // namespace aic
+
+#endif  // __HIPCC__

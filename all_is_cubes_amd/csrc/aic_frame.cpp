@@ -250,7 +250,7 @@ void plan_geometry(const aic_ctx *c, uint32_t k, const aic_frame_desc *f, uint32
     F.n_cus = c->n_cus;
     F.tiles_per_wave = c->sw.tiles_per_wave ? c->sw.tiles_per_wave : (c->streaming_submit ? 4u : 1u);
     if (!c->sw.tiles_per_wave && c->streaming_submit && k == 1u) F.tiles_per_wave = part_grid_tiles_per_wave(c, slot, F);
-    F.srgb_thr = c->srgb_thr.p;
+    F.srgb_buckets = c->srgb_buckets.p;
 }
 
 // Step 2b: what the launch is to be -- recording or production (want_aux, diag), how its tiles are handed out (tile queues, super-blocks, cost feedback)

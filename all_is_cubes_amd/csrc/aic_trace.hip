@@ -192,11 +192,9 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
     uint32_t tile_x0 = 0, tile_y0 = 0;  // wave-uniform: pixel origin of the tile the refill is drawing from
     // small decode tables live in LDS for the life of the persistent workgroup
     __shared__ float s_lut[256];     // PackedLight scalar decode (light/data.rs:301-354)
-    __shared__ float s_thr[kSrgbWindowWords];  // sRGB8 encode thresholds, as a window table (srgb8_rgb)
     __shared__ double s_pow[64];     // powf tables (powf_table)
     pow_tables_to_lds(s_pow, threadIdx.x, WGT);
     for (uint32_t i = threadIdx.x; i < 256u; i += WGT) s_lut[i] = F.light_lut[i];
-    srgb_window_to_lds(s_thr, F.srgb_thr, threadIdx.x, WGT);
     __syncthreads();
     const float *lut = s_lut;
     // Kernel arguments and the persistent loop. The stepping phase needs three scalars of them (the pool pointer and the cube
@@ -1379,7 +1377,7 @@ __global__ __launch_bounds__((XC && !DIAG && LMODE != 3) ? AIC_XWG_THREADS : AIC
                             }
                         }
                         uint32_t R, G, B;
-                        srgb8_rgb(r, g, bl, s_thr, R, G, B);
+                        srgb8_rgb_bucket(r, g, bl, F.srgb_buckets, R, G, B);  // (the sRGB8 bucket table stays in global memory: 6.5 KB every workgroup reads)
                         const uint32_t A = round_sat_u8(c[3] * 255.0f);
                         S.out[opix] = R | (G << 8) | (B << 16) | (A << 24);
                         }

@@ -79,7 +79,7 @@ void rec_frame(const aic::DevFrame &F) {
         F.macro, F.macros_x, F.macros_y, F.n_cus, F.tiles_per_wave, F.pass, F.hit_layer, F.use_init, F.pixel_centers, F.out_mode);
     rec("  ortho %s ortho_n %d patches %s n_patches %u bare_trace %d rays %s aux %s n_queues %u n_sub %u", P(F.ortho), F.ortho_n, P(F.patches), F.n_patches, F.bare_trace, P(F.rays),
         P(F.aux), F.n_queues, F.n_sub);
-    rec("  light_lut %s srgb_thr %s edge_x %s edge_y %s ray_cold %s ray_cold_groups %u ray_mode %u exchange %u", P(F.light_lut), P(F.srgb_thr), P(F.edge_x), P(F.edge_y),
+    rec("  light_lut %s srgb_buckets %s edge_x %s edge_y %s ray_cold %s ray_cold_groups %u ray_mode %u exchange %u", P(F.light_lut), P(F.srgb_buckets), P(F.edge_x), P(F.edge_y),
         P(F.ray_cold), F.ray_cold_groups, F.ray_mode, F.exchange);
     rec_words("  depth_zw", F.depth_zw, 8);
     static const aic::DevSub none = {};
