@@ -76,7 +76,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -178,6 +178,17 @@ def present_lines_scratch(src_size, out_size, n_lines: int) -> int:
     return int(scratch.value)
 
 
+def export_size(size, max_area: float = 640.0 * 480.0):
+    """The size an exported image of a `size` = (width, height) frame is logged at (aic_export_size; logged_image_size_policy, rerun_image.rs:302-311): the
+    size itself when its area is at most `max_area`, else scaled by sqrt(max_area / area) and rounded up per axis. Host-only: needs no device or context."""
+    lib = load()
+    out = (C.c_uint32 * 2)(0, 0)
+    rc = lib.aic_export_size(int(size[0]), int(size[1]), float(max_area), out)
+    if rc != 0:
+        raise AicError(rc, f"aic_export_size({tuple(size)}, {max_area})")
+    return int(out[0]), int(out[1])
+
+
 class SpaceDesc(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("size", C.c_int32 * 3), ("block_index", C.c_void_p), ("light", C.c_void_p),
                 ("n_blocks", C.c_uint32), ("blocks", C.c_void_p), ("voxels", C.c_void_p), ("n_voxels", C.c_uint64),
@@ -238,6 +249,15 @@ class PresentDesc(C.Structure):
 
 class PresentInfo(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("levels", C.c_uint32), ("t0", C.c_uint32 * 2), ("bloomed", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class ExportDesc(C.Structure):
+    _fields_ = [("src_width", C.c_uint32), ("src_height", C.c_uint32), ("out_width", C.c_uint32), ("out_height", C.c_uint32),
+                ("inverse_projection_zw", C.c_float * 4), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class ExportInfo(C.Structure):
+    _fields_ = [("kernel_ms", C.c_float), ("n_surface", C.c_uint32), ("depth_min", C.c_float), ("depth_max", C.c_float), ("reserved", C.c_uint32 * 4)]
 
 
 class LinesDesc(C.Structure):
@@ -370,6 +390,9 @@ def load() -> C.CDLL:
         lib.aic_set_text_font.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_present_split_text.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.POINTER(TextDesc), C.c_void_p, C.c_void_p, C.c_int,
                                                C.POINTER(PresentInfo), C.POINTER(LinesInfo)]
+        lib.aic_export_split.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ExportInfo)]
+        lib.aic_export_size.restype = C.c_int
+        lib.aic_export_size.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_assemble_strips_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.aic_read_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -768,6 +791,29 @@ class Context:
         image = np.zeros((d.out_height, d.out_width, 4), np.uint16 if flags & PRESENT_OUT_F16 else np.uint8)
         self._check(self._lib.aic_present_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), image.ctypes.data_as(C.c_void_p), 0, C.byref(info)))
         return image, info
+
+    def export_split(self, src, src_size, out_size, inverse_projection_zw, color: bool = True, depth: bool = True, device_outs=None):
+        """A resident Split frame exported as sRGB8 colour and metric depth (aic_export_split): the colour is what present_split gives at `out_size`
+        without bloom or tone mapping; the depth is the nearest depth texel as a distance along the view axis, 0 where there is no surface (a UI pixel,
+        the sky, a marker of an unfilled reprojection). `src` is the whole frame of `src_size` = (width, height) in HBM on the context's device;
+        `inverse_projection_zw` = {ipz.z, ipw.z, ipz.w, ipw.w} of the camera's inverse projection, as reproject_split takes it. Returns (colour, depth,
+        info): [height][width][4] uint8 and [height][width] float32 read back to the host, None for a plane not asked for. With `device_outs` = (colour
+        pointer, depth pointer) -- either may be 0 or None -- the planes are written to that device memory instead and both returned planes are None.
+        info.n_surface, depth_min and depth_max cover the pixels with a finite depth > 0, whatever planes are asked for."""
+        d = ExportDesc()
+        d.src_width, d.src_height = int(src_size[0]), int(src_size[1])
+        d.out_width, d.out_height = int(out_size[0]), int(out_size[1])
+        d.inverse_projection_zw[:] = [float(v) for v in np.asarray(inverse_projection_zw, np.float32).reshape(4)]
+        info = ExportInfo()
+        if device_outs is not None:
+            self._check(self._lib.aic_export_split(self._h, C.byref(d), C.c_void_p(src or None), C.c_void_p(device_outs[0] or None), C.c_void_p(device_outs[1] or None), 1,
+                                                   C.byref(info)))
+            return None, None, info
+        rgba = np.zeros((d.out_height, d.out_width, 4), np.uint8) if color else None
+        dist = np.zeros((d.out_height, d.out_width), np.float32) if depth else None
+        self._check(self._lib.aic_export_split(self._h, C.byref(d), C.c_void_p(src or None), rgba.ctypes.data_as(C.c_void_p) if color else None,
+                                               dist.ctypes.data_as(C.c_void_p) if depth else None, 0, C.byref(info)))
+        return rgba, dist, info
 
     def present_split_lines(self, src_ptr: int, src_size, out_size, bloom_intensity: float, tone_mapping: int, maximum_intensity: float, view_projection,
                             vertices=None, n_lines: int | None = None, flags: int = 0, out_device: int | None = None):

@@ -97,4 +97,24 @@ void launch_present(const BloomGeom &g, const PresentParams &p, hipStream_t stre
 // pass that draws into the scene before the chain runs (aic_present_lines.h) starts from; launch_present then takes p.scene as a frame of the output's size.
 void launch_present_scene(const BloomGeom &g, const PresentParams &p, hipStream_t stream);
 
+// The RGB-D export of a resident Split frame (aic_export_split; all-is-cubes-gpu/src/rerun_image.rs:62-225, shaders/rerun-copy.wgsl): the
+// presentation's scene texel at the logged size encoded as sRGB8, and the nearest depth texel unprojected to a view-space distance, 0 where there is
+// no surface.
+// The statistics are kept in kExportSlots slots, each a 128-byte line of its own, and a wave adds to the slot its index selects: atomics of every wave on
+// one address ran one after the other and took 1.1 ms of a 1080p export that otherwise takes 0.01 (profiles/export_split.txt). The host sums the slots.
+constexpr uint32_t kExportSlots = 64;
+struct alignas(128) ExportCounts { uint32_t n_surface, min_bits, max_bits, pad[29]; };  // min_bits, max_bits: the bit patterns of the least and greatest exported depth
+struct ExportParams {
+    const uint2 *src;               // the whole Split frame: [src_height][src_width] f16 x 4, then [src_height][src_width] f32 depth
+    uint32_t src_width, src_height;
+    uint32_t out_width, out_height;  // at most 2^31 pixels
+    uint32_t *color;                // [out_height][out_width] RGBA8, or nullptr: not written
+    float *depth;                   // [out_height][out_width] f32, or nullptr: not written
+    float ipzw[4];                  // aic_export_desc.inverse_projection_zw
+    const float *srgb_thr;
+    ExportCounts *counts;           // [kExportSlots], device memory at a 128-byte boundary; cleared here, complete when the stream is
+};
+// Queues the clear of the counters and the one kernel on `stream`: a lane per output pixel. Returns the first failure of what it queued.
+hipError_t launch_export(const ExportParams &p, hipStream_t stream);
+
 }  // namespace aic

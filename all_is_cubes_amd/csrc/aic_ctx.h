@@ -1,7 +1,7 @@
 // aic_ctx.h -- what the translation units of the C ABI's host side share: the context behind the opaque `aic_ctx` of
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
-// aic_split_ops.cpp (reprojection, picking and presentation of a resident Split frame) and aic_light_host.cpp (the light updater)
+// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame) and aic_light_host.cpp (the light updater)
 // only (all four are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
@@ -137,6 +137,7 @@ struct aic_ctx {
     uint32_t text_cell_w = 0, text_cell_h = 0, text_margin = 0;
     bool text_space_blank = false;
     DevBuf<unsigned char> text_codes;
+    DevBuf<uint32_t> export_counts;  // aic_export_split: the slots of its statistics (kExportSlots ExportCounts, aic_bloom.h), cleared on the stream by every call
     uint64_t aux_records = 0;
     double depth_zw[4] = {1.0, 0.0, 0.0, 1.0};  // aic_set_depth_transform: the Split frames' depth transform
     bool streaming_submit = false;  // set around aic_render_submit: frames meant to overlap are sized for throughput, synchronous ones for latency

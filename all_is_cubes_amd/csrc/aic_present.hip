@@ -19,6 +19,7 @@
 #include "aic_bloom.h"
 #include "aic_bloom_device.h"
 #include "aic_encode.h"
+#include "aic_split_texel.h"
 
 namespace aic {
 
@@ -42,6 +43,11 @@ AIC_DEV uint2 stretch_texel(const SrcSplit &s, int sw, int sh, int ow, int oh, i
     float4 r = sample<false>(s, sw, sh, u, v);
     r.w = 1.0f;
     return pack_texel(r);
+}
+// the scene texel a composite or an export reads at (x, y) of a w x h window: formed from an sw x sh frame (STRETCH), or the frame's own texel
+template <bool STRETCH>
+AIC_DEV float4 scene_at(const SrcSplit &s, int sw, int sh, int w, int h, int x, int y) {
+    return STRETCH ? unpack_texel(stretch_texel(s, sw, sh, w, h, x, y)) : s.at(x, y, w);
 }
 __global__ void __launch_bounds__(256) present_stretch_kernel(const uint2 *__restrict__ src, int sw, int sh, uint2 *__restrict__ out, int ow, int oh) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -100,7 +106,7 @@ AIC_DEV void composite_texel(const float *s_thr, const uint2 *__restrict__ src, 
     const uint32_t pix = t < npix ? t : npix - 1u;  // (every lane of the wave runs srgb8_rgb's ballot; only the real pixels store)
     const int x = (int)(pix % (uint32_t)w), y = (int)(pix / (uint32_t)w);
     const SrcSplit s{src};
-    const float4 c = STRETCH ? unpack_texel(stretch_texel(s, sw, sh, w, h, x, y)) : s.at(x, y, w);
+    const float4 c = scene_at<STRETCH>(s, sw, sh, w, h, x, y);
     float r = c.x, g = c.y, bl = c.z;
     if (mip0) {  // (launch-uniform: bloom_intensity > 0)
         const float u = ((float)x + 0.5f) / (float)w, v = ((float)y + 0.5f) / (float)h;
@@ -162,7 +168,73 @@ __global__ void __launch_bounds__(256) present_composite_text_kernel(const uint2
     composite_texel<STRETCH, F16, true>(s_thr, src, sw, sh, mip0, w, h, t0x, t0y, intensity, tone_mapping, m, tx, out);
 }
 
+// rerun_frame_copy_color_fragment / rerun_frame_copy_depth_fragment (rerun-copy.wgsl:47-88) on a resident Split frame, DESIGN.md 4.15: one output pixel per
+// lane. COLOR: the scene texel of a presentation at the logged size through the same encoder, alpha byte 255. The depth is the NEAREST depth texel's
+// (never interpolated): 0 for a UI pixel or a pixel of no layer (sign bit), a NaN, a pixel whose colour texel is the "nothing known" marker, and the far
+// plane (1.0); else the distance lin_depth gives. The pixels whose exported depth is finite and > 0 are counted by ballot and their least and greatest
+// depth reduced across the wave: one atomic of each kind per wave that has any, on the bit patterns (positive floats order as unsigned integers), into
+// the slot of the counters that the wave's index selects.
+struct ExportZw { float z[4]; };
+template <bool STRETCH, bool COLOR>
+__global__ void __launch_bounds__(256) export_kernel(const uint2 *__restrict__ src, const float *__restrict__ src_depth, int sw, int sh, int w, int h,
+                                                     const ExportZw ipzw, const float *__restrict__ thr, uint32_t *__restrict__ color,
+                                                     float *__restrict__ depth, ExportCounts *__restrict__ counts) {
+    __shared__ float s_thr[COLOR ? kSrgbWindowWords : 1u];
+    if (COLOR) {
+        srgb_window_to_lds(s_thr, thr, threadIdx.x, 256u);
+        __syncthreads();
+    }
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;
+    const uint32_t pix = t < npix ? t : npix - 1u;  // (every lane of the wave runs the ballots and the reduction; only the real pixels store and count)
+    const int x = (int)(pix % (uint32_t)w), y = (int)(pix / (uint32_t)w);
+    if (COLOR) {
+        const float4 c = scene_at<STRETCH>(SrcSplit{src}, sw, sh, w, h, x, y);
+        uint32_t R, G, B;
+        srgb8_rgb(c.x, c.y, c.z, s_thr, R, G, B);
+        if (t < npix) color[t] = R | (G << 8) | (B << 16) | 0xff000000u;
+    }
+    const float u = ((float)x + 0.5f) / (float)w, v = ((float)y + 0.5f) / (float)h;
+    const uint32_t ix = min((uint32_t)(u * (float)sw), (uint32_t)sw - 1u), iy = min((uint32_t)(v * (float)sh), (uint32_t)sh - 1u);
+    const uint32_t at = iy * (uint32_t)sw + ix;
+    const float d = src_depth[at];
+    const uint2 c = src[at];
+    float z = 0.0f;
+    if ((__float_as_uint(d) >> 31) == 0u && d == d && texel_valid(c) && d != 1.0f) z = lin_depth(d, ipzw.z);
+    if (depth && t < npix) depth[t] = z;
+    const bool surface = t < npix && z > 0.0f && z <= 3.4028235e38f;  // finite and positive
+    const unsigned long long b = __ballot(surface);
+    if (b == 0ull) return;  // (wave-uniform)
+    uint32_t lo = surface ? __float_as_uint(z) : 0xffffffffu, hi = surface ? __float_as_uint(z) : 0u;
+    for (int m = 32; m >= 1; m >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, m, 64));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, m, 64));
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        ExportCounts *const slot = counts + ((blockIdx.x * 4u + (threadIdx.x >> 6)) & (kExportSlots - 1u));
+        atomicAdd(&slot->n_surface, (uint32_t)__popcll(b));
+        atomicMin(&slot->min_bits, lo);
+        atomicMax(&slot->max_bits, hi);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_export(const ExportParams &p, hipStream_t stream) {
+    const uint32_t npix = p.out_width * p.out_height;
+    if (!npix) return hipSuccess;
+    hipError_t e;
+    if ((e = hipMemsetAsync(p.counts, 0, sizeof(ExportCounts) * kExportSlots, stream)) != hipSuccess) return e;
+    if ((e = hipMemset2DAsync(&p.counts->min_bits, sizeof(ExportCounts), 0xff, 4, kExportSlots, stream)) != hipSuccess) return e;
+    const int w = (int)p.out_width, h = (int)p.out_height, sw = (int)p.src_width, sh = (int)p.src_height;
+    const bool stretch = sw != w || sh != h;
+    auto kernel = stretch ? (p.color ? export_kernel<true, true> : export_kernel<true, false>) : (p.color ? export_kernel<false, true> : export_kernel<false, false>);
+    const float *src_depth = reinterpret_cast<const float *>(p.src + (size_t)p.src_width * p.src_height);
+    ExportZw ipzw;
+    for (int i = 0; i < 4; i++) ipzw.z[i] = p.ipzw[i];
+    kernel<<<bloom_blocks_of(npix), 256, 0, stream>>>(p.src, src_depth, sw, sh, w, h, ipzw, p.srgb_thr, p.color, p.depth, p.counts);
+    return hipGetLastError();
+}
 
 void launch_present_scene(const BloomGeom &g, const PresentParams &p, hipStream_t stream) {
     if (!g.width || !g.height) return;

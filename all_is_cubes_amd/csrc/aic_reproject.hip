@@ -16,11 +16,8 @@
 #include <stdint.h>
 
 #include "aic_reproject.h"
+#include "aic_split_texel.h"
 #include "aic_tunables.h"
-
-#ifndef AIC_DEV
-#define AIC_DEV __device__ __forceinline__
-#endif
 
 namespace aic {
 
@@ -36,7 +33,6 @@ AIC_DEV float4 unpack_texel(uint2 v) {
 }
 AIC_DEV uint2 pack_texel(float4 c) { return make_uint2(f16_bits(c.x) | (f16_bits(c.y) << 16), f16_bits(c.z) | (f16_bits(c.w) << 16)); }
 AIC_DEV uint2 marker() { return make_uint2(kMarkerLo, kMarkerHi); }
-AIC_DEV bool texel_valid(uint2 v) { return f16_value(v.y >> 16) > -0.5f; }  // gf_valid (resampling.wgsl:121-125)
 
 AIC_DEV int wrap_mirror(int i, int n) {  // AddressMode::MirrorRepeat on texel indices: period 2n, reflected
     if ((uint32_t)i < (uint32_t)n) return i;
@@ -57,8 +53,6 @@ struct SplatArgs {
     float ipzw[4];
     uint32_t width, height;
 };
-
-AIC_DEV float lin_depth(float t, const float *z) { return -(t * z[0] + z[1]) / (t * z[2] + z[3]); }  // rt-copy.wgsl:210-223
 
 // rt_reproject_vertex + rt_reproject_fragment (rt-copy.wgsl:73-223) for source pixel s, against every output pixel its sprite can cover
 __global__ void __launch_bounds__(256) reproject_splat_kernel(const float *__restrict__ depth, SplatArgs a, unsigned long long *__restrict__ keys,

@@ -1,7 +1,8 @@
 // aic_split_ops.cpp -- the operations of the C ABI declared in include/aic_hip.h that act on a resident Split frame: reproject it (aic_reproject_split),
 // pick the next pixels to trace (aic_pick_pixels), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
-// with the info text laid over it (aic_present_split_text, aic_set_text_font), with the size queries and host-only helpers that go with them
-// (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch, aic_text_geometry, aic_text_layout).
+// with the info text laid over it (aic_present_split_text, aic_set_text_font), export it as sRGB8 colour and metric depth (aic_export_split), with the size
+// queries and host-only helpers that go with them (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch, aic_text_geometry,
+// aic_text_layout, aic_export_size).
 //
 // The operations run on slot 0's stream, synchronously, and are written to one pattern: check the arguments, `begin`, size the context's scratch, fill the
 // launcher's parameters, then ev0, the launches, ev1, the copies back to the host and one synchronise, then the context's state and the caller's info.
@@ -47,6 +48,12 @@ const char *present_sizes_invalid(uint32_t sw, uint32_t sh, uint32_t ow, uint32_
 }
 size_t present_scratch_texels(const BloomGeom &g, uint32_t sw, uint32_t sh) {
     return (size_t)g.texels + ((sw != g.width || sh != g.height) ? (size_t)g.width * g.height : 0);
+}
+
+// two ranges of device memory that share a byte (an empty range shares none)
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 // a presentation's rejections of its arguments, in the order the header lists them, under the entry point's name; 0: none
@@ -468,6 +475,79 @@ int aic_present_split_text(aic_ctx *c, const aic_present_desc *d, const aic_line
         if (const int rc = text_args_invalid(c, td, "aic_present_split_text")) return rc;
     }
     return present(c, d, (ld && ld->n_lines) ? ld : nullptr, td, src, out, out_is_device, info, lines_info, "aic_present_split_text");
+}
+
+int aic_export_size(uint32_t width, uint32_t height, double max_area, uint32_t out[2]) {
+    if (!out || !(max_area > 0.0)) return AIC_ERR_INVALID;  // (NaN is not > 0)
+    out[0] = width;
+    out[1] = height;
+    const double area = (double)width * (double)height;
+    if (area <= max_area) return AIC_OK;
+    const double r = std::sqrt(max_area / area);
+    out[0] = (uint32_t)std::ceil((double)width * r);
+    out[1] = (uint32_t)std::ceil((double)height * r);
+    return AIC_OK;
+}
+
+int aic_export_split(aic_ctx *c, const aic_export_desc *d, const void *src, void *color_out, float *depth_out, int out_is_device, aic_export_info *info) {
+    const char *who = "aic_export_split";
+    if (!c || !d || !src) return reject(c, who, "bad argument");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!color_out && !depth_out && !info) return reject(c, who, "neither a plane nor the info is asked for");
+    if (const char *why = present_sizes_invalid(d->src_width, d->src_height, d->out_width, d->out_height)) return reject(c, who, why);
+    if (d->flags) return reject(c, who, "unknown flag bits");
+    for (float v : d->inverse_projection_zw)
+        if (!std::isfinite(v)) return reject(c, who, "a component of inverse_projection_zw is not finite");
+    if ((uintptr_t)src & 7u) return reject(c, who, "a Split frame starts at an 8-byte boundary");
+    const size_t npix = (size_t)d->out_width * d->out_height, plane_bytes = npix * 4, src_bytes = (size_t)d->src_width * d->src_height * 12;
+    if (out_is_device) {
+        if (((uintptr_t)color_out | (uintptr_t)depth_out) & 3u) return reject(c, who, "a device plane starts at a 4-byte boundary");
+        if (ranges_overlap(color_out, color_out ? plane_bytes : 0, src, src_bytes)) return reject(c, who, "color_out overlaps src");
+        if (ranges_overlap(depth_out, depth_out ? plane_bytes : 0, src, src_bytes)) return reject(c, who, "depth_out overlaps src");
+        if (ranges_overlap(color_out, color_out ? plane_bytes : 0, depth_out, depth_out ? plane_bytes : 0)) return reject(c, who, "color_out and depth_out overlap");
+    }
+    if (const int rc = begin(c, who)) return rc;
+    if (!npix) return AIC_OK;
+    hipError_t e;
+    if ((e = c->export_counts.ensure(sizeof(ExportCounts) / 4 * kExportSlots)) != hipSuccess) return hip_fail(c, "alloc export counters", e);
+    // a host target's planes are staged in the output buffer: colour first, then depth
+    const size_t n_planes = (color_out ? 1u : 0u) + (depth_out ? 1u : 0u);
+    if (!out_is_device && n_planes && (e = c->out.ensure(npix * n_planes)) != hipSuccess) return hip_fail(c, "alloc output", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    uint32_t *const staged_color = c->out.p, *const staged_depth = (!out_is_device && color_out && depth_out) ? c->out.p + npix : c->out.p;
+    ExportParams ep;
+    ep.src = (const uint2 *)src;
+    ep.src_width = d->src_width;
+    ep.src_height = d->src_height;
+    ep.out_width = d->out_width;
+    ep.out_height = d->out_height;
+    ep.color = !color_out ? nullptr : (out_is_device ? (uint32_t *)color_out : staged_color);
+    ep.depth = !depth_out ? nullptr : (out_is_device ? depth_out : (float *)staged_depth);
+    std::memcpy(ep.ipzw, d->inverse_projection_zw, sizeof(ep.ipzw));
+    ep.srgb_thr = c->srgb_thr.p;
+    ep.counts = (ExportCounts *)c->export_counts.p;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_export(ep, fs.stream)) != hipSuccess) return hip_fail(c, "launch export", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    ExportCounts counts[kExportSlots];
+    HIP_TRY(c, hipMemcpyAsync(counts, ep.counts, sizeof(counts), hipMemcpyDeviceToHost, fs.stream));
+    if (!out_is_device && color_out) HIP_TRY(c, hipMemcpyAsync(color_out, staged_color, plane_bytes, hipMemcpyDeviceToHost, fs.stream));
+    if (!out_is_device && depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, staged_depth, plane_bytes, hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    if (info) {
+        HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+        uint32_t min_bits = 0xffffffffu, max_bits = 0u;
+        for (const ExportCounts &slot : counts) {
+            info->n_surface += slot.n_surface;
+            min_bits = slot.min_bits < min_bits ? slot.min_bits : min_bits;
+            max_bits = slot.max_bits > max_bits ? slot.max_bits : max_bits;
+        }
+        if (info->n_surface) {
+            std::memcpy(&info->depth_min, &min_bits, 4);
+            std::memcpy(&info->depth_max, &max_bits, 4);
+        }
+    }
+    return AIC_OK;
 }
 
 }  // extern "C"

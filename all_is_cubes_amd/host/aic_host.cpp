@@ -260,6 +260,23 @@ std::array<float, 4> Camera::inverse_projection_zw() const {
     if (!projection_.inverse(&ip)) ip = Mat4();
     return {(float)MM(ip, 3, 3), (float)MM(ip, 4, 3), (float)MM(ip, 3, 4), (float)MM(ip, 4, 4)};
 }
+Pinhole Camera::pinhole() const {
+    const float w = (float)viewport_.framebuffer_width, h = (float)viewport_.framebuffer_height;
+    const float half_w = w * 0.5f, half_h = h * 0.5f;
+    const float aspect = w / h;
+    const float tan_fov_y = (float)std::tan((fov_y() * 0.5) * (3.14159265358979323846 / 180.0));  // f64::to_radians, f64::tan, `as f32`
+    const float tan_fov_x = tan_fov_y * aspect;
+    Pinhole p;
+    p.image_from_camera = {half_w / tan_fov_x, 0.f, 0.f, 0.f, half_h / tan_fov_y, 0.f, half_w, half_h, 1.f};
+    p.resolution = {w, h};
+    p.transform = view_transform();
+    return p;
+}
+std::array<uint32_t, 2> logged_image_size_policy(uint32_t width, uint32_t height) {
+    uint32_t out[2] = {width, height};
+    (void)aic_export_size(width, height, 640.0 * 480.0, out);  // (cannot fail: the cap is positive)
+    return {out[0], out[1]};
+}
 Vec3 Camera::project_ndc3_into_world(const Vec3 &ndc) const {
     Vec3 out;
     if (!inverse_projection_view_.transform_point3d(ndc, &out)) {
@@ -716,6 +733,36 @@ aic_present_info HipRtRenderer::present_split_to_device(const void *src_device, 
     aic_present_info pi;
     check(aic_present_split(ctx_, &d, src_device, out_device, 1, &pi), "aic_present_split");
     return pi;
+}
+
+HipRtRenderer::SplitExport HipRtRenderer::export_split(const void *src_device, uint32_t out_width, uint32_t out_height) {
+    const Viewport vp = world_camera_.viewport();
+    SplitExport r;
+    r.width = out_width;
+    r.height = out_height;
+    if (!out_width && !out_height) {
+        const std::array<uint32_t, 2> logged = logged_image_size_policy(vp.framebuffer_width, vp.framebuffer_height);
+        r.width = logged[0];
+        r.height = logged[1];
+    }
+    aic_export_desc d{};
+    d.src_width = vp.framebuffer_width;
+    d.src_height = vp.framebuffer_height;
+    d.out_width = r.width;
+    d.out_height = r.height;
+    const std::array<float, 4> zw = world_camera_.inverse_projection_zw();
+    std::memcpy(d.inverse_projection_zw, zw.data(), sizeof(d.inverse_projection_zw));
+    const size_t npix = (size_t)r.width * r.height;
+    r.color.assign(npix * 4, 0);
+    r.depth.assign(npix, 0.f);
+    uint8_t no_color = 0;  // (an empty image: the library still wants a plane to be asked for)
+    float no_depth = 0.f;
+    check(aic_export_split(ctx_, &d, src_device, npix ? r.color.data() : &no_color, npix ? r.depth.data() : &no_depth, 0, &r.info), "aic_export_split");
+    Camera logged_camera = world_camera_;
+    logged_camera.set_viewport(Viewport::with_scale(1.0, r.width, r.height));
+    r.pinhole = logged_camera.pinhole();
+    r.depth_range = {world_camera_.near_plane_distance(), world_camera_.view_distance()};
+    return r;
 }
 
 std::vector<aic_line_vertex> Cursor::wireframe() const {

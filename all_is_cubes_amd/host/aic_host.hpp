@@ -121,6 +121,17 @@ Quat rotation_around_x(double radians);
 Quat rotation_around_y(double radians);
 Quat rotation_then(const Quat &first, const Quat &second);
 
+// convert_camera_to_pinhole (all-is-cubes-gpu/src/rerun_image.rs:314-338): what travels with an exported image. image_from_camera is the column-major
+// 3 x 3 pinhole matrix in f32 exactly as written there -- {w/2 / tan_x, 0, 0, 0, h/2 / tan_y, 0, w/2, h/2, 1} with tan_y = (f32)tan(fov_y / 2) and
+// tan_x = tan_y * (w / h) --, resolution the camera's framebuffer size in f32, transform its view transform (ParentFromChild).
+struct Pinhole {
+    std::array<float, 9> image_from_camera;
+    std::array<float, 2> resolution;
+    ViewTransform transform;
+};
+// logged_image_size_policy (rerun_image.rs:302-311; aic_export_size with the reference's cap of 640 * 480)
+std::array<uint32_t, 2> logged_image_size_policy(uint32_t width, uint32_t height);
+
 class Camera {
   public:
     Camera(const GraphicsOptions &options, const Viewport &viewport);
@@ -150,6 +161,7 @@ class Camera {
     // {ipz.z, ipw.z, ipz.w, ipw.w} of the inverse projection (rt-copy.wgsl:210-223): what linearize_depth_value reads; the identity's when the projection
     // is singular (raytrace_to_texture.rs:460-465)
     std::array<float, 4> inverse_projection_zw() const;
+    Pinhole pinhole() const;
     Vec3 view_position() const { return view_position_; }
     Ray project_ndc_into_world(double ndc_x, double ndc_y) const;
     Vec3 project_ndc3_into_world(const Vec3 &ndc) const;
@@ -455,6 +467,19 @@ class HipRtRenderer : public HeadlessRenderer {
                             const std::vector<aic_line_vertex> *lines = nullptr, aic_lines_info *lines_info = nullptr);
     aic_present_info present_split_to_device(const void *src_device, void *out_device, uint32_t out_width, uint32_t out_height, uint32_t flags, const std::string &info_text,
                                              bool with_lines = false, const std::vector<aic_line_vertex> *lines = nullptr, aic_lines_info *lines_info = nullptr);
+    // RerunImageExport::start_frame_copy (all-is-cubes-gpu/src/rerun_image.rs:62-225; aic_export_split): the resident Split frame `src_device` -- of the
+    // current viewport -- as sRGB8 colour and metric depth at out_width x out_height, or (both 0) at logged_image_size_policy of the frame's size, with
+    // what perform_image_copy attaches: the pinhole of the world camera with its viewport set to that size, and the depth range
+    // {near_plane_distance, view_distance}.
+    struct SplitExport {
+        uint32_t width = 0, height = 0;
+        std::vector<uint8_t> color;  // [height][width][4] sRGB RGBA8
+        std::vector<float> depth;    // [height][width] distance along the view axis; 0: no surface
+        Pinhole pinhole;
+        std::array<double, 2> depth_range = {0.0, 0.0};
+        aic_export_info info = {};
+    };
+    SplitExport export_split(const void *src_device, uint32_t out_width = 0, uint32_t out_height = 0);
     // the world camera of the last update(): what to keep beside a resident frame as its `traced_with`
     const Camera &world_camera() const { return world_camera_; }
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)

@@ -92,6 +92,10 @@ PYBIND11_MODULE(_host, m) {
         return out;
     });
     m.attr("INFO_TEXT_CELL") = py::make_tuple(kInfoTextCell[0], kInfoTextCell[1], kInfoTextCell[2]);
+    m.def("logged_image_size_policy", [](const std::array<uint32_t, 2> &size) {
+        const std::array<uint32_t, 2> out = logged_image_size_policy(size[0], size[1]);
+        return py::make_tuple(out[0], out[1]);
+    }, py::arg("size"));
     m.def("rotation_around_y", [](double radians) { Quat q = rotation_around_y(radians); return std::array<double, 4>{q.i, q.j, q.k, q.r}; });
 
     py::class_<Camera>(m, "Camera")
@@ -108,6 +112,14 @@ PYBIND11_MODULE(_host, m) {
         .def("inverse_projection_view", [](const Camera &c) { return mat(c.inverse_projection_view()); })
         .def_static("reprojection_matrix", &Camera::reprojection_matrix, py::arg("traced_with"), py::arg("current"))
         .def("inverse_projection_zw", &Camera::inverse_projection_zw)
+        .def("pinhole", [](const Camera &c) {  // -> (image_from_camera [9] f32 column-major, resolution (w, h) f32, ViewTransform)
+            const Pinhole p = c.pinhole();
+            py::array_t<float> m(9);
+            std::memcpy(m.mutable_data(), p.image_from_camera.data(), sizeof(float) * 9);
+            py::array_t<float> res(2);
+            std::memcpy(res.mutable_data(), p.resolution.data(), sizeof(float) * 2);
+            return py::make_tuple(m, res, p.transform);
+        })
         .def("view_position", [](const Camera &c) { return a3(c.view_position()); })
         .def("project_ndc_into_world", [](const Camera &c, double x, double y) { Ray r = c.project_ndc_into_world(x, y); return py::make_tuple(a3(r.origin), a3(r.direction)); })
         .def("project_ndc3_into_world", [](const Camera &c, const std::array<double, 3> &p) { return a3(c.project_ndc3_into_world(v3(p))); })
@@ -352,6 +364,33 @@ PYBIND11_MODULE(_host, m) {
             d["kernel_ms"] = i.kernel_ms; d["levels"] = i.levels; d["t0"] = py::make_tuple(i.t0[0], i.t0[1]); d["bloomed"] = i.bloomed;
             return std::move(d);
         }, py::arg("src_ptr"), py::arg("out_width"), py::arg("out_height"), py::arg("flags") = 0u, py::arg("out_ptr") = (uintptr_t)0)
+        .def("export_split", [](HipRtRenderer &r, uintptr_t src_ptr, py::object size) {
+            // size = None: logged_image_size_policy of the frame's size; else (width, height). -> dict(size, color [h][w][4] u8, depth [h][w] f32,
+            // pinhole (Camera.pinhole()'s tuple), depth_range (near, far), n_surface, depth_min, depth_max, kernel_ms)
+            uint32_t w = 0, h = 0;
+            if (!size.is_none()) {
+                const auto wh = size.cast<std::array<uint32_t, 2>>();
+                w = wh[0];
+                h = wh[1];
+                if (!w && !h) throw std::invalid_argument("export_split: a size of (0, 0) asks for the policy's: pass None");
+            }
+            HipRtRenderer::SplitExport e;
+            { py::gil_scoped_release rel; e = r.export_split(reinterpret_cast<const void *>(src_ptr), w, h); }
+            py::array_t<uint8_t> color({(py::ssize_t)e.height, (py::ssize_t)e.width, (py::ssize_t)4});
+            if (!e.color.empty()) std::memcpy(color.mutable_data(), e.color.data(), e.color.size());
+            py::array_t<float> depth({(py::ssize_t)e.height, (py::ssize_t)e.width});
+            if (!e.depth.empty()) std::memcpy(depth.mutable_data(), e.depth.data(), e.depth.size() * sizeof(float));
+            py::array_t<float> m(9);
+            std::memcpy(m.mutable_data(), e.pinhole.image_from_camera.data(), sizeof(float) * 9);
+            py::array_t<float> res(2);
+            std::memcpy(res.mutable_data(), e.pinhole.resolution.data(), sizeof(float) * 2);
+            py::dict d;
+            d["size"] = py::make_tuple(e.width, e.height); d["color"] = color; d["depth"] = depth;
+            d["pinhole"] = py::make_tuple(m, res, e.pinhole.transform);
+            d["depth_range"] = py::make_tuple(e.depth_range[0], e.depth_range[1]);
+            d["n_surface"] = e.info.n_surface; d["depth_min"] = e.info.depth_min; d["depth_max"] = e.info.depth_max; d["kernel_ms"] = e.info.kernel_ms;
+            return d;
+        }, py::arg("src_ptr"), py::arg("size") = py::none())
         .def("present_split_lines", [](HipRtRenderer &r, uintptr_t src_ptr, uint32_t out_width, uint32_t out_height, py::object lines, uint32_t flags, uintptr_t out_ptr) {
             // lines = None: the cursor of the last update(); else [2 n, 7] f32 (position, linear RGBA). -> (present_split's result, dict(n_clipped_away,
             // n_fragments, n_passed, n_pixels))

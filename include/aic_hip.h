@@ -588,6 +588,52 @@ typedef struct aic_text_desc {
 } aic_text_desc;
 int aic_present_split_text(aic_ctx *ctx, const aic_present_desc *desc, const aic_lines_desc *lines /* may be NULL */, const aic_text_desc *text /* may be NULL */,
                            const void *src_device, void *out, int out_is_device, aic_present_info *info, aic_lines_info *lines_info);
+/* replaces: RerunImageExport::start_frame_copy / perform_image_copy (all-is-cubes-gpu/src/rerun_image.rs:62-225) with rerun_frame_copy_color_fragment and
+ * rerun_frame_copy_depth_fragment (shaders/rerun-copy.wgsl:47-88): the RGB-D export of the resident textures -- the scene colour resampled to a logging
+ * size as sRGB8, and the depth buffer unprojected to a distance along the view axis, an f32 per pixel in the world's units, 0 where nothing was hit.
+ * The intrinsics and pose that travel with the two planes (convert_camera_to_pinhole, rerun_image.rs:314-338) are host arithmetic on the camera: the
+ * host mirror's Camera::pinhole and the Rust shim's caller have them. DESIGN.md 4.15 restates every operation in the order written here;
+ * tests/export_ref.py is that text in NumPy and the device equals it bit for bit.
+ * Colour: output pixel (x, y) holds exactly the bytes aic_present_split writes for the same src and sizes with bloom_intensity 0, tone_mapping 0,
+ * maximum_intensity +inf and flags 0. The scene texel S is the source texel itself at equal size, else the ClampToEdge bilinear read at the pixel's
+ * centre rounded to f16, colour saturated at 65504 either way; S is clamped and encoded by the exact sRGB8 encoder of aic_render, alpha byte 255 (what
+ * the Rgba8UnormSrgb target of rerun_frame_copy_color_fragment does to scene_for_postprocessing_input). Decision: the reference resamples twice, frame ->
+ * window -> logged size; this call resamples once, from the frame. The two agree when the window has the frame's size.
+ * Depth: the nearest texel, never interpolated (rerun-copy.wgsl:73-88). u = (x + 0.5f) / out_width, v = (y + 0.5f) / out_height in f32;
+ * ix = min((uint32)(u * (float)src_width), src_width - 1), iy likewise; d the depth texel at (ix, iy), c the colour texel there. The value is, in this
+ * order: 0 if d has its sign bit set (a UI pixel, a pixel of no layer, -0.0) or is NaN; 0 if c is the "nothing known" marker of an unfilled reprojection
+ * (its alpha half is not above -0.5); 0 if d == 1.0f (linearize_depth_value, rerun-copy.wgsl:47-51); else -(d * a + b) / (d * c + e) with {a, b, c, e} =
+ * inverse_projection_zw, f32 with one rounding per operation -- aic_reproject_split's own linearisation. The first two rules are this library's: the
+ * reference's depth attachment would clamp a negative texel to 0 and log a point on the near plane for every UI pixel.
+ * info: n_surface counts the output pixels whose exported depth is finite and > 0, depth_min and depth_max are taken over them (0, 0 when there are
+ * none); computed on the device whether or not depth_out is NULL.
+ * color_out, depth_out: either may be NULL and is then not written; as in aic_render device pointers when out_is_device != 0, host memory the call
+ * reads back into otherwise (staged through the context's output buffer, 4 bytes a pixel and plane). Nothing is written to src.
+ * The call blocks and runs on slot 0, like aic_present_split. Its 8 KiB of counters belong to the context and are released in aic_destroy.
+ * Rejected before anything is queued or allocated, with AIC_ERR_INVALID and the context still usable: a frame still occupying slot 0; a NULL desc or
+ * src; color_out, depth_out and info all NULL; src not at an 8-byte boundary; a device color_out or depth_out not at a 4-byte boundary; a device
+ * output overlapping the src_width * src_height * 12 bytes of src, or the other output; any dimension above 65535; an output of more than
+ * AIC_PRESENT_MAX_PIXELS pixels; src of zero size with a non-empty output; a non-finite component of inverse_projection_zw; unknown flag bits. An empty
+ * output (out_width or out_height 0) is AIC_OK, writes nothing and zeroes the info. */
+typedef struct aic_export_desc {
+    uint32_t src_width, src_height;   /* the resident Split frame (no partition; layout as AIC_FRAME_OUT_SPLIT) */
+    uint32_t out_width, out_height;   /* the logged size; may equal, exceed or fall below the source in either axis */
+    float inverse_projection_zw[4];   /* {ipz.z, ipw.z, ipz.w, ipw.w}, as aic_reproject_desc's */
+    uint32_t flags;                   /* none defined: must be 0 */
+    uint32_t reserved[3];
+} aic_export_desc;
+typedef struct aic_export_info {
+    float kernel_ms;                  /* HIP events around the launch */
+    uint32_t n_surface;               /* output pixels whose exported depth is finite and > 0 */
+    float depth_min, depth_max;       /* over those pixels; 0, 0 when there are none */
+    uint32_t reserved[4];
+} aic_export_info;
+int aic_export_split(aic_ctx *ctx, const aic_export_desc *desc, const void *src_device, void *color_out /* [h][w] RGBA8, may be NULL */,
+                     float *depth_out /* [h][w] f32, may be NULL */, int out_is_device, aic_export_info *info /* may be NULL */);
+/* replaces: logged_image_size_policy (all-is-cubes-gpu/src/rerun_image.rs:302-311) with the area cap as a parameter, host-only, in f64: area = w * h; if
+ * area <= max_area the size is returned as it is, else r = sqrt(max_area / area) and out = ceil(size * r) per axis. The reference's cap is 640 * 480:
+ * (640, 480) -> (640, 480), (1920, 1080) -> (740, 416). (0, h) and (w, 0) return themselves. AIC_ERR_INVALID: a NULL out; max_area NaN or not positive. */
+int aic_export_size(uint32_t width, uint32_t height, double max_area, uint32_t out[2]);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

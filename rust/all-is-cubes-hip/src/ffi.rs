@@ -213,6 +213,28 @@ pub struct aic_present_info {
 }
 
 #[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_export_desc {
+    pub src_width: u32,
+    pub src_height: u32,
+    pub out_width: u32,
+    pub out_height: u32,
+    pub inverse_projection_zw: [f32; 4],
+    pub flags: u32,
+    pub reserved: [u32; 3],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_export_info {
+    pub kernel_ms: f32,
+    pub n_surface: u32,
+    pub depth_min: f32,
+    pub depth_max: f32,
+    pub reserved: [u32; 4],
+}
+
+#[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct aic_line_vertex {
     pub position: [f32; 3],
@@ -354,6 +376,8 @@ unsafe extern "C" {
     pub fn aic_reproject_geometry(width: u32, height: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
     pub fn aic_pick_pixels(ctx: *mut aic_ctx, desc: *const aic_pick_desc, order_device: *const u32, pixels_out_device: *mut u32, info: *mut aic_pick_info) -> c_int;
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;
+    pub fn aic_export_split(ctx: *mut aic_ctx, desc: *const aic_export_desc, src_device: *const c_void, color_out: *mut c_void, depth_out: *mut f32, out_is_device: c_int, info: *mut aic_export_info) -> c_int;
+    pub fn aic_export_size(width: u32, height: u32, max_area: f64, out: *mut u32) -> c_int;
     pub fn aic_present_geometry(src_w: u32, src_h: u32, out_w: u32, out_h: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
     pub fn aic_present_split_lines(ctx: *mut aic_ctx, desc: *const aic_present_desc, lines: *const aic_lines_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info, lines_info: *mut aic_lines_info) -> c_int;
     pub fn aic_present_lines_scratch(src_w: u32, src_h: u32, out_w: u32, out_h: u32, n_lines: u32, bytes: *mut u64) -> c_int;

@@ -835,6 +835,55 @@ impl HipRtRenderer {
         Ok(info)
     }
 
+    /// The RGB-D export of the resident textures (`RerunImageExport::start_frame_copy`, all-is-cubes-gpu/src/rerun_image.rs:62-225,
+    /// shaders/rerun-copy.wgsl): the resident Split frame at `src_device`, of the renderer's own viewport, resampled to `out_size` as sRGB RGBA8 into
+    /// `color_device`, and its nearest depth texel unprojected to a distance along the view axis -- an `f32` per pixel, 0 where nothing was hit -- into
+    /// `depth_device`. Either target may be null and is then not written. `out_size` `None`: `logged_image_size_policy` of the viewport
+    /// (rerun_image.rs:302-311). Returns the size written and the report: how many pixels carry a surface, and their least and greatest distance. The
+    /// pinhole and pose that go with the planes are `convert_camera_to_pinhole` of the world camera with its viewport set to the returned size.
+    ///
+    /// # Safety
+    /// `src_device` is a whole Split frame of the current viewport in device memory on the renderer's device, 8-byte aligned; `color_device` and
+    /// `depth_device` are null or device memory there of 4 bytes per output pixel, 4-byte aligned, overlapping neither the frame nor each other.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub unsafe fn export_split(
+        &mut self,
+        src_device: *const core::ffi::c_void,
+        color_device: *mut core::ffi::c_void,
+        depth_device: *mut f32,
+        out_size: Option<[u32; 2]>,
+    ) -> Result<([u32; 2], ffi::aic_export_info), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("export_split needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let camera = &self.cameras.cameras().world;
+        let ip = camera.projection_matrix().inverse().unwrap_or_default();
+        let frame = viewport.framebuffer_size;
+        let size = out_size.unwrap_or_else(|| {
+            let mut logged = [frame.width, frame.height];
+            // SAFETY: host arithmetic on two words; the cap is positive, so the call cannot fail
+            let _ = unsafe { ffi::aic_export_size(frame.width, frame.height, 640.0 * 480.0, logged.as_mut_ptr()) };
+            logged
+        });
+        let desc = ffi::aic_export_desc {
+            src_width: frame.width,
+            src_height: frame.height,
+            out_width: size[0],
+            out_height: size[1],
+            inverse_projection_zw: [ip.m33 as f32, ip.m43 as f32, ip.m34 as f32, ip.m44 as f32],
+            flags: 0,
+            reserved: [0; 3],
+        };
+        let mut info = ffi::aic_export_info::default();
+        // SAFETY: the context is live; the caller vouches for the frame and the targets; the call returns when the planes are written
+        self.device.check(unsafe { ffi::aic_export_split(ctx.as_ptr(), &desc, src_device, color_device, depth_device, 1, &mut info) })?;
+        Ok((size, info))
+    }
+
     /// [`Self::present_split`] with the lines pass of `EverythingRenderer::draw_frame_linear` (all-is-cubes-gpu/src/everything.rs:616-658): `lines`,
     /// pairs of world-space vertices with a linear RGBA colour -- the cursor's wireframe from [`cursor_wireframe`], debug lines --, are drawn into the
     /// scene before bloom and tone mapping, depth-tested against the resident frame's depth plane, under the world camera's projection x view.

@@ -283,6 +283,12 @@ hipError_t launch_present_lines(const LinesParams &p, hipStream_t stream) {
     rec_words("  m", p.m, 16);
     return failing("launch_present_lines") ? hipErrorInvalidValue : hipSuccess;
 }
+hipError_t launch_export(const ExportParams &p, hipStream_t stream) {
+    rec("launch_export src %s %ux%u out %ux%u color %s depth %s srgb_thr %s counts %s %s", P(p.src), p.src_width, p.src_height, p.out_width, p.out_height, P(p.color), P(p.depth),
+        P(p.srgb_thr), P(p.counts), S(stream));
+    rec_words("  ipzw", p.ipzw, 4);
+    return failing("launch_export") ? hipErrorInvalidValue : hipSuccess;
+}
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
 void launch_assemble_strips(const uint32_t *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t) { rec("launch_assemble_strips"); }

@@ -1,5 +1,5 @@
 // split_ops_record.cpp -- drives the operations on a resident Split frame (csrc/aic_split_ops.cpp: aic_reproject_split, aic_pick_pixels,
-// aic_present_split, aic_present_split_lines, aic_present_split_text with aic_set_text_font, and their size queries and host-only helpers) through a fixed list of scenarios against the recording fake (fake_hip.cpp) and
+// aic_present_split, aic_present_split_lines, aic_present_split_text with aic_set_text_font, aic_export_split, and their size queries and host-only helpers) through a fixed list of scenarios against the recording fake (fake_hip.cpp) and
 // prints the record: every runtime call and launch with its arguments, each call's return code and message, every field of its info structs and what
 // the context keeps for these operations afterwards. Two builds of the host code make the same calls exactly when their records are byte-identical
 // (build.sh, tests/test_split_ops_record_cpu.py). A scenario named "reject: ..." is one refused call on a context an earlier scenario made; every
@@ -87,6 +87,14 @@ aic_lines_desc lines_desc(const aic_line_vertex *v, uint32_t n, uint32_t flags =
     return l;
 }
 
+aic_export_desc export_desc(uint32_t sw, uint32_t sh, uint32_t ow, uint32_t oh, uint32_t flags = 0) {
+    aic_export_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.src_width = sw; d.src_height = sh; d.out_width = ow; d.out_height = oh; d.flags = flags;
+    d.inverse_projection_zw[0] = 0.25f; d.inverse_projection_zw[1] = -1.f; d.inverse_projection_zw[2] = 1.f; d.inverse_projection_zw[3] = 0.5f;
+    return d;
+}
+
 // ---- what is recorded after every call
 void rec_state(const aic_ctx *c) {
     if (!c) return;
@@ -131,6 +139,19 @@ int present(aic_ctx *c, const aic_present_desc *d, bool through_lines, const aic
         rec("  lines_info clipped_away %llu fragments %llu passed %llu pixels %llu", (unsigned long long)li.n_clipped_away, (unsigned long long)li.n_fragments,
             (unsigned long long)li.n_passed, (unsigned long long)li.n_pixels);
     rec_state(c);
+    return rc;
+}
+
+// aic_export_split; the counters' state is recorded on a line of its own, so that rec_state's stays what it was
+int export_split(aic_ctx *c, const aic_export_desc *d, const void *src, void *color, float *depth, int out_is_device, bool want_info = true) {
+    aic_export_info i;
+    std::memset(&i, 0xff, sizeof(i));
+    const int rc = aic_export_split(c, d, src, color, depth, out_is_device, want_info ? &i : nullptr);
+    rec_rc(c, "aic_export_split", rc);
+    rec("  info kernel_ms %a n_surface %u depth_min %a depth_max %a reserved %u %u %u %u", i.kernel_ms, i.n_surface, i.depth_min, i.depth_max, i.reserved[0], i.reserved[1], i.reserved[2],
+        i.reserved[3]);
+    rec_state(c);
+    if (c) rec("  export state counts %zu/%zu", c->export_counts.n, c->export_counts.cap);
     return rc;
 }
 
@@ -240,6 +261,40 @@ void shapes() {
                             if (to_device) (void)hipFree(out); else std::free(out);
                             aic_destroy(c);
                         });
+}
+
+// ---- export: equal, larger, smaller and empty outputs; both planes, one, none (the info alone); to the host and to the device; with and without info
+const uint32_t kExportShapes[][4] = {{0, 0, 0, 0}, {8, 8, 0, 8}, {1, 1, 1, 1}, {1, 7, 1, 7}, {33, 17, 33, 17}, {640, 360, 640, 360}, {20, 12, 40, 24}, {33, 17, 16, 8}, {1, 1, 5, 3}};
+void exports() {
+    for (const auto &s : kExportShapes)
+        for (int planes = 0; planes < 4; planes++)  // bit 0: colour, bit 1: depth
+            for (int to_device = 0; to_device < 2; to_device++)
+                scenario("export" + str({s[0], s[1], s[2], s[3], planes, to_device}), [&] {
+                    aic_ctx *c = make_ctx();
+                    const size_t plane_bytes = (size_t)s[2] * s[3] * 4;
+                    void *src = dev((size_t)s[0] * s[1] * 12);
+                    void *color = !(planes & 1) ? nullptr : (to_device ? dev(plane_bytes) : std::malloc(plane_bytes + 1));
+                    void *depth = !(planes & 2) ? nullptr : (to_device ? dev(plane_bytes) : std::malloc(plane_bytes + 1));
+                    const aic_export_desc d = export_desc(s[0], s[1], s[2], s[3]);
+                    for (int n = 0; n < 2; n++) export_split(c, &d, src, color, (float *)depth, to_device);  // (the second finds its counters and staging)
+                    if (planes) export_split(c, &d, src, color, (float *)depth, to_device, false);         // (no info)
+                    (void)hipFree(src);
+                    for (void *p : {color, depth})
+                        if (p) { if (to_device) (void)hipFree(p); else std::free(p); }
+                    aic_destroy(c);
+                });
+    scenario("export: size policy", [] {
+        const uint32_t sizes[][2] = {{640, 480}, {1920, 1080}, {641, 480}, {65535, 65535}, {0, 7}, {7, 0}, {1, 1}};
+        for (const auto &wh : sizes)
+            for (double cap : {640.0 * 480.0, 1.0, 0.5, (double)kInf}) {
+                uint32_t out[2] = {99, 99};
+                const int rc = aic_export_size(wh[0], wh[1], cap, out);
+                rec("aic_export_size %ux%u cap %a rc %d -> %ux%u", wh[0], wh[1], cap, rc, out[0], out[1]);
+            }
+        uint32_t out[2];
+        rec("aic_export_size invalid rc %d %d %d %d", aic_export_size(8, 8, 64.0, nullptr), aic_export_size(8, 8, 0.0, out), aic_export_size(8, 8, -1.0, out),
+            aic_export_size(8, 8, (double)kNaN, out));
+    });
 }
 
 // ---- lines: a host list and a device list, on a context that resets the keys it touched and on one that clears them all
@@ -542,6 +597,34 @@ void rejections() {
         ln("device vertices off by 2", lines_desc((const aic_line_vertex *)(lists + 2), N, AIC_LINES_DEVICE));
         ln("line rejections come before the presentation's", lines_desc(host.data(), N, 2u));
         rejection("lines: line rejections come before the presentation's, no desc", [&] { const aic_lines_desc l = lines_desc(host.data(), N, 2u); present(c, nullptr, true, &l, src, out, 1); });
+        // aic_export_split: colour in `out`, depth in `dst`
+        auto ex = [&](const char *what, const aic_export_desc &e, const void *s, void *color, void *depth, int is_device = 1, bool want_info = true) {
+            rejection(std::string("export: ") + what, [&] { export_split(c, &e, s, color, (float *)depth, is_device, want_info); });
+        };
+        auto with_zw = [](aic_export_desc e, int at, float v) { e.inverse_projection_zw[at] = v; return e; };
+        const aic_export_desc ed = export_desc(W, H, W, H);
+        rejection("export: no context", [&] { export_split(nullptr, &ed, src, out, (float *)dst, 1); });
+        rejection("export: no desc", [&] { export_split(c, nullptr, src, out, (float *)dst, 1); });
+        ex("no src", ed, nullptr, out, dst);
+        ex("nothing asked for", ed, src, nullptr, nullptr, 1, false);
+        ex("nothing asked for of the host", ed, src, nullptr, nullptr, 0, false);
+        ex("src off by 4", ed, src + 4, out, dst);
+        ex("color_out off by 2", ed, src, out + 2, dst);
+        ex("depth_out off by 1", ed, src, out, dst + 1);
+        ex("color_out is src", ed, src, src, dst);
+        ex("depth_out inside src", ed, src, out, src + W * H * 12 - 4);
+        ex("depth_out is color_out", ed, src, out, out);
+        ex("color_out inside depth_out", ed, src, dst + W * H * 4 - 4, dst);
+        ex("src too wide", export_desc(65536, 1, W, H), src, out, dst);
+        ex("src too high", export_desc(1, 65536, W, H), src, out, dst);
+        ex("out too wide", export_desc(W, H, 65536, 1), src, out, dst);
+        ex("out too high", export_desc(W, H, 1, 65536), src, out, dst);
+        ex("more than 2^31 pixels", export_desc(W, H, 65535, 32769), src, out, dst);
+        ex("src of no width", export_desc(0, H, W, H), src, out, dst);
+        ex("src of no height", export_desc(W, 0, W, H), src, out, dst);
+        ex("NaN in ipzw", with_zw(ed, 2, kNaN), src, out, dst);
+        ex("infinity in ipzw", with_zw(ed, 0, -kInf), src, out, dst);
+        ex("unknown flag", export_desc(W, H, W, H, 1u), src, out, dst);
     };
     arguments();
     scenario("rejections: the context they shared is released", [&] {
@@ -565,6 +648,8 @@ void rejections() {
     rejection("busy: present through aic_present_split_lines, no lines", [&] { present(c, &d, true, &none, src, out, 1); });
     const std::vector<uint8_t> busy_atlas = atlas_9x18(true);
     rejection("busy: font", [&] { set_font(c, busy_atlas.data(), 9, 18, 1); });
+    const aic_export_desc ed = export_desc(W, H, W, H);
+    rejection("busy: export", [&] { export_split(c, &ed, src, out, (float *)dst, 1); });
     scenario("rejections: the frame is waited for, and every entry point runs", [&] {
         aic_frame_info fi;
         rec_rc(c, "aic_render_wait", aic_render_wait(c, 0, &fi));
@@ -575,6 +660,16 @@ void rejections() {
         for (void *p : {src, dst, out, lists}) (void)hipFree(p);
         aic_destroy(c);
     }, false);
+    scenario("export: after a frame was waited for", [&] {
+        c = make_ctx();
+        src = (char *)dev(W * H * 12); dst = (char *)dev(W * H * 4); out = (char *)dev(W * H * 4); lists = (char *)dev(8 * 8 * 4);
+        submit_to_slot0(c, lists);
+        aic_frame_info fi;
+        rec_rc(c, "aic_render_wait", aic_render_wait(c, 0, &fi));
+        export_split(c, &ed, src, out, (float *)dst, 1);
+        for (void *p : {src, dst, out, lists}) (void)hipFree(p);
+        aic_destroy(c);
+    });
 }
 
 // ---- what aic_set_text_font and aic_present_split_text refuse, each on its own, on a context of their own
@@ -637,7 +732,7 @@ struct Buffers { void *src, *dst, *out, *list; };  // the caller's device memory
 void runtime_failures(const std::string &name, bool lines_clear_keys, const std::function<int(aic_ctx *, const Buffers &)> &call,
                       const std::function<void(aic_ctx *, const Buffers &)> &before = nullptr) {
     static const char *fns[] = {"hipSetDevice", "hipMalloc", "hipMemcpyAsync", "hipEventRecord", "hipGetLastError", "hipStreamSynchronize", "hipEventElapsedTime",
-                                "launch_reproject", "launch_pick", "launch_present_lines"};
+                                "launch_reproject", "launch_pick", "launch_present_lines", "launch_export"};
     const size_t n_fns = sizeof(fns) / sizeof(fns[0]);
     // fail < 0: the good call alone, which counts what there is to fail
     auto run = [&](int fn, int nth, int *counts) {
@@ -693,12 +788,20 @@ void all_runtime_failures() {
             return present_text(c, &d, &l, &t, b.src, to_device ? b.out : (void *)image.data(), to_device);
         }, [](aic_ctx *c, const Buffers &) { set_font(c, atlas.data(), 9, 18, 1); });
     runtime_failures("font", false, [](aic_ctx *c, const Buffers &) { return set_font(c, atlas.data(), 9, 18, 1); });
+    // stretched, both planes: colour in the output buffer, depth in the second frame's; to the host and to the device
+    for (int to_device = 0; to_device < 2; to_device++)
+        runtime_failures("export" + str({to_device}), false, [&](aic_ctx *c, const Buffers &b) {
+            const aic_export_desc d = export_desc(W, H, 2 * W, 2 * H);
+            return export_split(c, &d, b.src, to_device ? b.out : (void *)image.data(), to_device ? (float *)((char *)b.out + 2 * W * 2 * H * 4) : (float *)(image.data() + 2 * W * 2 * H * 4),
+                                to_device);
+        });
 }
 
 }  // namespace
 
 int main() {
     shapes();
+    exports();
     lines();
     text();
     sequences();
