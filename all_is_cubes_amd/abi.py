@@ -76,7 +76,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -272,6 +272,72 @@ class TextDesc(C.Structure):
     _fields_ = [("scale", C.c_float * 2), ("origin", C.c_float * 2), ("cols", C.c_uint32), ("rows", C.c_uint32), ("flags", C.c_uint32), ("codes", C.c_void_p)]
 
 
+EXPOSURE_SAMPLES, EXPOSURE_RAYS = 100, 10  # State::luminance_samples; rays per step (exposure.rs)
+
+
+class ExposureStateC(C.Structure):  # aic_exposure_state
+    _fields_ = [("luminance_samples", C.c_float * 100), ("luminance_sample_index", C.c_uint32), ("exposure_log", C.c_float)]
+
+
+def exposure_rays(rotation_ijkr, translation, first_index: int, n: int = EXPOSURE_RAYS) -> np.ndarray:
+    """The rays of one step of character::exposure::State::step (aic_exposure_rays; exposure.rs:85-105): [n,6] f64 = (origin xyz, direction xyz), ray k
+    for sample index (first_index + k) % 100, under the view transform (rotation quaternion i, j, k, r; translation). Host-only."""
+    lib = load()
+    lib.aic_exposure_rays.restype = C.c_int
+    lib.aic_exposure_rays.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_void_p]
+    q = (C.c_double * 4)(*[float(v) for v in rotation_ijkr])
+    t = (C.c_double * 3)(*[float(v) for v in translation])
+    rays = np.zeros((int(n), 6), np.float64)
+    rc = lib.aic_exposure_rays(q, t, int(first_index), int(n), rays.ctypes.data if rays.size else None)
+    if rc != 0:
+        raise AicError(rc, "aic_exposure_rays")
+    return rays
+
+
+class ExposureState:
+    """character::exposure::State (exposure.rs:37-151) over aic_exposure_state: the ring of 100 luminance samples, the index last written and the log of
+    the exposure. `advance` takes the samples of one step (Context.sample_luminance of `rays()`); everything here is host-only."""
+
+    def __init__(self):
+        self.c = ExposureStateC()
+        lib = load()
+        lib.aic_exposure_init.restype = C.c_int
+        lib.aic_exposure_init.argtypes = [C.POINTER(ExposureStateC)]
+        lib.aic_exposure_advance.restype = C.c_int
+        lib.aic_exposure_advance.argtypes = [C.POINTER(ExposureStateC), C.c_uint32, C.c_void_p, C.c_double, C.POINTER(C.c_float)]
+        rc = lib.aic_exposure_init(C.byref(self.c))
+        if rc != 0:
+            raise AicError(rc, "aic_exposure_init")
+
+    @property
+    def samples(self) -> np.ndarray:
+        return np.array(self.c.luminance_samples[:], np.float32)
+
+    @property
+    def index(self) -> int:
+        return int(self.c.luminance_sample_index)
+
+    @property
+    def exposure_log(self) -> np.float32:
+        return np.float32(self.c.exposure_log)
+
+    def rays(self, rotation_ijkr, translation, n: int = EXPOSURE_RAYS) -> np.ndarray:
+        """The next `n` rays of the ring: those of the sample indices the next advance() writes."""
+        return exposure_rays(rotation_ijkr, translation, (self.index + 1) % EXPOSURE_SAMPLES, n)
+
+    def advance(self, samples, dt: float) -> np.float32:
+        """Stores the samples, eases the exposure towards its target by `dt` seconds (dt == 0: nothing) and returns the exposure (aic_exposure_advance)."""
+        smp = np.ascontiguousarray(samples, np.float32).reshape(-1)
+        out = C.c_float(0)
+        rc = load().aic_exposure_advance(C.byref(self.c), len(smp), smp.ctypes.data if smp.size else None, float(dt), C.byref(out))
+        if rc != 0:
+            raise AicError(rc, "aic_exposure_advance")
+        return np.float32(out.value)
+
+    def exposure(self) -> np.float32:
+        return self.advance([], 0.0)
+
+
 class CursorDesc(C.Structure):
     _fields_ = [("cube", C.c_int32 * 3), ("face_entered", C.c_int32), ("face_selected", C.c_int32), ("point_entered", C.c_double * 3),
                 ("distance_to_point", C.c_double), ("voxel_lo", C.c_int32 * 3), ("voxel_size", C.c_int32 * 3), ("resolution", C.c_int32),
@@ -391,6 +457,7 @@ def load() -> C.CDLL:
         lib.aic_present_split_text.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.POINTER(TextDesc), C.c_void_p, C.c_void_p, C.c_int,
                                                C.POINTER(PresentInfo), C.POINTER(LinesInfo)]
         lib.aic_export_split.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ExportInfo)]
+        lib.aic_sample_luminance.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.aic_export_size.restype = C.c_int
         lib.aic_export_size.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -716,6 +783,21 @@ class Context:
         self._check(self._lib.aic_trace_rays(self._h, int(layer), int(n), C.c_void_p(rays_ptr), flags, float(exposure), C.c_void_p(out_ptr),
                                              C.c_void_p(aux_ptr or None), C.byref(info)))
         return info
+
+    def sample_luminance(self, layer: int, rays, max_steps: int) -> np.ndarray:
+        """The luminance each of the rays [n,6] = (origin xyz, direction xyz) sees in the layer's space (aic_sample_luminance; the sampling loop of
+        character::exposure::State::step, exposure.rs:91-128): float32 [n]. max_steps = 2 * maximum_distance, 0 for LightPhysics::None. Legal with
+        frames in flight."""
+        r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        out = np.zeros(len(r), np.float32)
+        self._check(self._lib.aic_sample_luminance(self._h, int(layer), len(r), _ptr(r), int(max_steps), 0, _ptr(out)))
+        return out
+
+    def sample_luminance_device(self, layer: int, n: int, rays_ptr: int, max_steps: int, out_ptr: int) -> None:
+        """The same with the rays ([n,6] f64) and the samples ([n] f32) in HBM on the context's device (AIC_RAYS_DEVICE): no staging, no read-back.
+        Returns once the samples are there."""
+        self._check(self._lib.aic_sample_luminance(self._h, int(layer), int(n), C.c_void_p(rays_ptr or None), int(max_steps), RAYS_DEVICE,
+                                                   C.c_void_p(out_ptr or None)))
 
     def trace_pixels(self, frame: FrameDesc, pixels, want_aux: bool = False):
         """The listed pixels of `frame` (indices y * width + x, host memory), each traced exactly as render() traces it, results in list order

@@ -1,8 +1,8 @@
 // aic_ctx.h -- what the translation units of the C ABI's host side share: the context behind the opaque `aic_ctx` of
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
-// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame) and aic_light_host.cpp (the light updater)
-// only (all four are written inside `using namespace aic`, and so is this header). Whatever one of the
+// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater) and
+// aic_exposure_host.cpp (the luminance sampler's call) only (all five are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
 #pragma once
@@ -92,9 +92,13 @@ struct Layer {
     uint64_t version = 0;      // bumped by every scene mutation; the light updater's host mirrors follow it
     uint64_t upload_serial = 0;  // bumped by aic_upload_space only: the light update queue lives as long as one upload
     LightState *lstate = nullptr;
+    // aic_sample_luminance: one bit per block index, EvaluatedBlock::visible() (light_visible_bits), made by the first sample after `version` moved
+    DevBuf<uint32_t> visible_bits;
+    uint64_t visible_version = ~0ull;  // the `version` visible_bits describes
     size_t n_cubes() const { return (size_t)size[0] * (size_t)size[1] * (size_t)size[2]; }
     void release() {
-        pool.release(); cls.release(); light.release(); blocks.release(); palette.release();
+        pool.release(); cls.release(); light.release(); blocks.release(); palette.release(); visible_bits.release();
+        visible_version = ~0ull;
         for (auto &sp : light_spare) sp.release();
         host_blocks.clear(); host_cls.clear(); vox_cap.clear(); pal_cap.clear(); vox_base.clear(); pal_base.clear();
         garbage_vox = garbage_pal = 0;
@@ -137,6 +141,7 @@ struct aic_ctx {
     uint32_t text_cell_w = 0, text_cell_h = 0, text_margin = 0;
     bool text_space_blank = false;
     DevBuf<unsigned char> text_codes;
+    DevBuf<unsigned char> exposure_scratch;  // aic_sample_luminance with host pointers: the staged rays, then the samples
     DevBuf<uint32_t> export_counts;  // aic_export_split: the slots of its statistics (kExportSlots ExportCounts, aic_bloom.h), cleared on the stream by every call
     uint64_t aux_records = 0;
     double depth_zw[4] = {1.0, 0.0, 0.0, 1.0};  // aic_set_depth_transform: the Split frames' depth transform
@@ -248,5 +253,7 @@ int take_light_spare(aic_ctx *c, Layer &l, int layer, size_t n, int *index);
 int quiesce(aic_ctx *c);
 // aic_light_host.cpp
 int light_job_finish(aic_ctx *c);
+constexpr uint32_t kVisibleBitsWords = 2048;  // 65536 block indices x 1 bit
+int light_visible_bits(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<uint32_t> *bits);
 
 }  // namespace aic

@@ -353,6 +353,26 @@ struct HVoxSum {
     }
 };
 
+// EvaluatedBlock::visible() as compute_derived decides it (derived.rs:78-240): a single voxel that is not fully transparent or emits, a voxel volume with
+// one such voxel. The one copy of the property: compute_derived_h's kDerivedVisible and the luminance sampler's bitmap (light_visible_bits) both ask here.
+bool derived_visible_h(const HostBlocks &hb, const DevBlock &b) {
+    if ((b.kind & 255u) == 0u) {
+        const bool emits = !(b.emission[0] == 0.f && b.emission[1] == 0.f && b.emission[2] == 0.f);
+        return !(b.color[3] <= 0.0f) || emits;
+    }
+    const int lo[3] = {(int)(b.vlo_packed & 255u), (int)((b.vlo_packed >> 8) & 255u), (int)((b.vlo_packed >> 16) & 255u)};
+    const int sz[3] = {(int)(b.vsize_packed & 255u), (int)((b.vsize_packed >> 8) & 255u), (int)((b.vsize_packed >> 16) & 255u)};
+    for (int x = lo[0]; x < lo[0] + sz[0]; x++)
+        for (int y = lo[1]; y < lo[1] + sz[1]; y++)
+            for (int z = lo[2]; z < lo[2] + sz[2]; z++) {
+                HostVoxel v;
+                std::memset(&v, 0, sizeof(v));
+                hb.get(b, I3h{x, y, z}, &v);
+                if (!(v.color[3] == 0.f && v.emission[0] == 0.f && v.emission[1] == 0.f && v.emission[2] == 0.f)) return true;
+            }
+    return false;
+}
+
 // derived.rs:78-240 compute_derived, on the flattened block
 DevDerived compute_derived_h(const HostBlocks &hb, const DevBlock &b) {
     DevDerived d;
@@ -363,8 +383,7 @@ DevDerived compute_derived_h(const HostBlocks &hb, const DevBlock &b) {
         for (int f = 0; f < 6; f++) for (int k = 0; k < 4; k++) d.face[f][k] = b.color[k];
         for (int k = 0; k < 3; k++) d.emission[k] = b.emission[k];
         if (b.color[3] >= 1.0f) d.flags |= 63u;
-        const bool emits = !(b.emission[0] == 0.f && b.emission[1] == 0.f && b.emission[2] == 0.f);
-        if (!(b.color[3] <= 0.0f) || emits) d.flags |= kDerivedVisible;
+        if (derived_visible_h(hb, b)) d.flags |= kDerivedVisible;
         return d;
     }
     const int lo[3] = {(int)(b.vlo_packed & 255u), (int)((b.vlo_packed >> 8) & 255u), (int)((b.vlo_packed >> 16) & 255u)};
@@ -394,16 +413,7 @@ DevDerived compute_derived_h(const HostBlocks &hb, const DevBlock &b) {
     const float surface_area = (float)(6.0 * (double)res * (double)res);
     all.color(surface_area, d.color);
     all.emission(surface_area, d.emission);
-    bool any_visible = false;
-    for (int x = lo[0]; x < hi[0] && !any_visible; x++)
-        for (int y = lo[1]; y < hi[1] && !any_visible; y++)
-            for (int z = lo[2]; z < hi[2]; z++) {
-                HostVoxel v;
-                std::memset(&v, 0, sizeof(v));
-                hb.get(b, I3h{x, y, z}, &v);
-                if (!(v.color[3] == 0.f && v.emission[0] == 0.f && v.emission[1] == 0.f && v.emission[2] == 0.f)) { any_visible = true; break; }
-            }
-    if (any_visible) d.flags |= kDerivedVisible;
+    if (derived_visible_h(hb, b)) d.flags |= kDerivedVisible;
     for (int f = 0; f < 6; f++) {
         const int axis = f % 3;
         const bool positive = f >= 3;
@@ -1556,6 +1566,29 @@ int light_job_finish(aic_ctx *c) {
     Layer &l = c->layers[J.layer];
     if (J.rc == AIC_OK && J.spare >= 0) std::swap(l.light, l.light_spare[J.spare]);  // (a failed update leaves the layer's volume as it was; its mirrors were marked stale)
     J.spare = -1;
+    return AIC_OK;
+}
+
+// The luminance sampler's bitmap (aic_exposure.h): bit i of `bits` = derived_visible_h of block i, kVisibleBitsWords words whatever the table's size. The
+// voxel and palette pools are read back only if a block has voxels, and on `stream` -- the caller's, which runs beside the frames in flight: nothing
+// here waits for a frame or goes through the null stream.
+int light_visible_bits(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<uint32_t> *bits) {
+    const size_t n = l.n_cubes();
+    HostBlocks hb;
+    hb.blocks = &l.host_blocks;
+    hb.n_cubes = n;
+    bool any_voxels = false;
+    for (const DevBlock &b : l.host_blocks) any_voxels = any_voxels || (b.kind & 255u) != 0u;
+    if (any_voxels) {
+        hb.vox.resize(l.pool.n > n ? l.pool.n - n : 0);
+        hb.pal.resize(l.palette.n);
+        if (!hb.vox.empty()) HIP_TRY(c, hipMemcpyAsync(hb.vox.data(), l.pool.p + n, hb.vox.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, stream));
+        if (!hb.pal.empty()) HIP_TRY(c, hipMemcpyAsync(hb.pal.data(), l.palette.p, hb.pal.size() * sizeof(DevPaletteEntry), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(c, hipStreamSynchronize(stream));
+    }
+    bits->assign(kVisibleBitsWords, 0u);
+    for (size_t i = 0; i < l.host_blocks.size() && i < 32u * kVisibleBitsWords; i++)
+        if (derived_visible_h(hb, l.host_blocks[i])) (*bits)[i >> 5] |= 1u << (i & 31u);
     return AIC_OK;
 }
 }  // namespace aic

@@ -1116,6 +1116,51 @@ HipRtRenderer::LightUpdateInfo HipRtRenderer::evaluate_light_wait() {
     return LightUpdateInfo{info.updates, info.batches, info.cost, info.device_ms, info.total_ms, info.queue_left, info.bundles_visited};
 }
 
+std::vector<float> HipRtRenderer::sample_luminance(int layer, const std::vector<Ray> &rays, uint32_t max_steps) {
+    static_assert(sizeof(Ray) == 6 * sizeof(double), "a Ray is the ABI's six doubles: origin, then direction");
+    if (rays.size() > (1u << 20)) throw RenderError(AIC_ERR_INVALID, "sample_luminance: more than 1 << 20 rays in one call");
+    std::vector<float> out(rays.size());
+    check(aic_sample_luminance(ctx_, layer, (uint32_t)rays.size(), rays.empty() ? nullptr : &rays[0].origin.x, max_steps, 0u, out.data()), "aic_sample_luminance");
+    return out;
+}
+
+// ---- ExposureState ------------------------------------------------------------------------------
+ExposureState::ExposureState() { (void)aic_exposure_init(&s_); }
+void ExposureState::step(HipRtRenderer &renderer, const ViewTransform &vt, int maximum_distance_or_minus_one, double dt) {
+    if (dt == 0.) return;  // (before anything is sampled: exposure.rs:70-72)
+    // usize::from(maximum_distance).saturating_mul(2); LightPhysics::None: 0
+    const uint32_t max_steps = maximum_distance_or_minus_one < 0 ? 0u : 2u * (uint32_t)maximum_distance_or_minus_one;
+    const double q[4] = {vt.rotation.i, vt.rotation.j, vt.rotation.k, vt.rotation.r};
+    const double t[3] = {vt.translation.x, vt.translation.y, vt.translation.z};
+    std::vector<Ray> rays(AIC_EXPOSURE_RAYS);
+    int rc = aic_exposure_rays(q, t, (s_.luminance_sample_index + 1u) % AIC_EXPOSURE_SAMPLES, AIC_EXPOSURE_RAYS, &rays[0].origin.x);
+    if (rc != AIC_OK) throw RenderError(rc, "aic_exposure_rays");
+    const std::vector<float> samples = renderer.sample_luminance(AIC_LAYER_WORLD, rays, max_steps);
+    rc = aic_exposure_advance(&s_, (uint32_t)samples.size(), samples.data(), dt, nullptr);
+    if (rc != AIC_OK) throw RenderError(rc, "aic_exposure_advance");
+}
+float ExposureState::exposure() const {
+    aic_exposure_state copy = s_;
+    float e = 1.0f;
+    (void)aic_exposure_advance(&copy, 0, nullptr, 0., &e);  // (dt == 0: reads the state)
+    return e;
+}
+float ExposureState::luminance_average() const {  // exposure.rs:139-142: the f32 sum in index order, from `Sum for f32`'s -0.0, times 100f32.recip()
+    float sum = -0.0f;
+    for (float v : s_.luminance_samples) sum += v;
+    return sum * (1.0f / (float)AIC_EXPOSURE_SAMPLES);
+}
+std::array<float, AIC_EXPOSURE_SAMPLES> ExposureState::samples() const {
+    std::array<float, AIC_EXPOSURE_SAMPLES> out;
+    std::memcpy(out.data(), s_.luminance_samples, sizeof(s_.luminance_samples));
+    return out;
+}
+float ExposureState::compute_target_exposure(float luminance) {
+    const float q = 0.9f / luminance;
+    const float derived_exposure = q < 0.1f ? 0.1f : (q > 4.f ? 4.f : q);  // f32::clamp: NaN stays NaN
+    return derived_exposure * 0.375f + 1.f * (1.f - 0.375f);
+}
+
 void HipRtRenderer::wait_event(void *hip_event) { check(aic_wait_event(ctx_, hip_event), "aic_wait_event"); }
 void HipRtRenderer::stream_wait_rows(uint32_t slot, void *hip_stream) { check(aic_stream_wait_frame(ctx_, slot, hip_stream), "aic_stream_wait_frame"); }
 

@@ -515,6 +515,10 @@ class HipRtRenderer : public HeadlessRenderer {
     // drained); `max_updates`: stop after that many cube updates (a per-frame light budget), 0 = run to the end.
     LightUpdateInfo evaluate_light(int maximum_distance, bool fast = true, int epsilon = 1, int batch = 32, int queue_order = 16, int lanes_per_cube = 0,
                                    bool continue_queue = false, uint64_t max_updates = 0);
+    // The sampling loop of character::exposure::State::step (exposure.rs:91-128; aic_sample_luminance) for a batch of world-space rays against one
+    // layer's space as last updated, light included wherever it was made: per ray the luminance of the light behind the first visible block that has
+    // a valid one, or of the sky. max_steps: 2 * maximum_distance, 0 for LightPhysics::None. Legal with frames in flight (submit_rows_to_device).
+    std::vector<float> sample_luminance(int layer, const std::vector<Ray> &rays, uint32_t max_steps);
     // true: the WORLD space's light lives on the device (evaluate_light): update() forwards block changes only, never the
     // host Space's light texels, and queues the changed cubes for relighting (aic_light_cubes_changed)
     bool device_light = false;
@@ -553,6 +557,28 @@ class HipRtRenderer : public HeadlessRenderer {
     Camera world_camera_, ui_camera_;
     float backdrop_[4] = {0, 0, 0, 0};
     bool show_ui_ = true;
+};
+
+// character::exposure::State (all-is-cubes/src/character/exposure.rs:37-151) over aic_exposure_state: what a host keeps per character when its
+// GraphicsOptions::exposure is Automatic. Once per simulation step:
+//     state.step(renderer, cams->world_view_transform, maximum_distance, dt);
+//     cams->measured_exposure = state.exposure();        // update() hands it to Camera::set_measured_exposure
+class ExposureState {
+  public:
+    ExposureState();  // Default: every sample 1.0, exposure 1.0
+    // State::step: dt == 0 does nothing; otherwise AIC_EXPOSURE_RAYS rays from the view transform's origin sample the renderer's WORLD space
+    // (sample_luminance) and the exposure eases towards compute_target_exposure of the ring's average. maximum_distance_or_minus_one: the space's
+    // LightPhysics::Rays { maximum_distance }, or -1 for LightPhysics::None (no steps: every sample is the sky).
+    void step(HipRtRenderer &renderer, const ViewTransform &view_transform, int maximum_distance_or_minus_one, double dt);
+    float exposure() const;           // State::exposure
+    float luminance_average() const;  // State::luminance_average
+    std::array<float, AIC_EXPOSURE_SAMPLES> samples() const;
+    uint32_t sample_index() const { return s_.luminance_sample_index; }
+    float exposure_log() const { return s_.exposure_log; }
+    static float compute_target_exposure(float luminance);  // exposure.rs:145-151
+
+  private:
+    aic_exposure_state s_;
 };
 
 // (inline, in the header: aic_host.cpp names no ray tracing call but aic_render and its kin -- tests/test_product_boundaries.py keeps a CPU renderer out of it by that word)

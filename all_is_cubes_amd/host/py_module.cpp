@@ -308,6 +308,17 @@ PYBIND11_MODULE(_host, m) {
             d["colorbuf"] = colors; d["hits"] = hits; d["info"] = res.info;
             return d;
         }, py::arg("layer"), py::arg("rays"), py::arg("include_sky") = true)
+        .def("sample_luminance", [](HipRtRenderer &r, int layer, py::array_t<double, py::array::c_style | py::array::forcecast> rays, uint32_t max_steps) {
+            // rays [n, 6] = origin xyz, direction xyz -> [n] f32
+            if (rays.size() % 6 != 0) throw std::invalid_argument("rays: [n, 6] doubles");
+            std::vector<Ray> v((size_t)rays.size() / 6);
+            if (!v.empty()) std::memcpy(&v[0].origin.x, rays.data(), v.size() * sizeof(Ray));
+            std::vector<float> res;
+            { py::gil_scoped_release rel; res = r.sample_luminance(layer, v, max_steps); }
+            py::array_t<float> out((py::ssize_t)res.size());
+            if (!res.empty()) std::memcpy(out.mutable_data(), res.data(), res.size() * sizeof(float));
+            return out;
+        }, py::arg("layer"), py::arg("rays"), py::arg("max_steps"))
         .def("trace_pixels", [](HipRtRenderer &r, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> pixels) {
             // pixels [n] = y * width + x -> dict(color_f16_bits [n, 4] u16 -- view it as numpy float16 --, depth [n] f32, hits [n, sizeof(aic_pixel_aux)] u8, info)
             std::vector<uint32_t> v((size_t)pixels.size());
@@ -514,4 +525,22 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("device_light", &HipRtRenderer::device_light)
         .def_readwrite("device_light_queue_order", &HipRtRenderer::device_light_queue_order)
         .def_readwrite("enable_counters", &HipRtRenderer::enable_counters);
+
+    py::class_<ExposureState>(m, "ExposureState")
+        .def(py::init<>())
+        .def("step", [](ExposureState &s, HipRtRenderer &r, const ViewTransform &vt, int maximum_distance_or_minus_one, double dt) {
+            py::gil_scoped_release rel;
+            s.step(r, vt, maximum_distance_or_minus_one, dt);
+        }, py::arg("renderer"), py::arg("view_transform"), py::arg("maximum_distance_or_minus_one"), py::arg("dt"))
+        .def("exposure", &ExposureState::exposure)
+        .def("luminance_average", &ExposureState::luminance_average)
+        .def("samples", [](const ExposureState &s) {
+            const std::array<float, AIC_EXPOSURE_SAMPLES> v = s.samples();
+            py::array_t<float> out((py::ssize_t)v.size());
+            std::memcpy(out.mutable_data(), v.data(), sizeof(float) * v.size());
+            return out;
+        })
+        .def_property_readonly("sample_index", &ExposureState::sample_index)
+        .def_property_readonly("exposure_log", &ExposureState::exposure_log)
+        .def_static("compute_target_exposure", &ExposureState::compute_target_exposure);
 }

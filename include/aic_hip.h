@@ -634,6 +634,54 @@ int aic_export_split(aic_ctx *ctx, const aic_export_desc *desc, const void *src_
  * area <= max_area the size is returned as it is, else r = sqrt(max_area / area) and out = ceil(size * r) per axis. The reference's cap is 640 * 480:
  * (640, 480) -> (640, 480), (1920, 1080) -> (740, 416). (0, h) and (w, 0) return themselves. AIC_ERR_INVALID: a NULL out; max_area NaN or not positive. */
 int aic_export_size(uint32_t width, uint32_t height, double max_area, uint32_t out[2]);
+
+/* --- automatic exposure ---------------------------------------------------------------------- */
+/* ExposureOption::Automatic: the camera's exposure follows the luminance the character sees, measured by character::exposure::State::step
+ * (all-is-cubes/src/character/exposure.rs:60-151) once per simulation step. Four entry points: three restate the state and its arithmetic on the host,
+ * one samples the scene on the device, next to the light volume it reads (which, once the light updater runs on the device, is nowhere else). One step
+ * of the reference with view transform `vt` and time step `dt` (nothing at all when dt == 0) is
+ *     aic_exposure_rays(vt.rotation, vt.translation, (s.luminance_sample_index + 1) % 100, 10, rays);
+ *     aic_sample_luminance(ctx, AIC_LAYER_WORLD, 10, rays, max_steps, 0, samples);
+ *     aic_exposure_advance(&s, 10, samples, dt, &exposure);        -> Camera::set_measured_exposure(exposure)
+ * DESIGN.md 4.16 has the arithmetic; tests/exposure_ref.py is that text in NumPy. An aic_multi replicates the scene on every device: a host of one
+ * samples through aic_multi_context(m, 0), and there is no aic_multi_* form of these calls. */
+#define AIC_EXPOSURE_SAMPLES 100 /* State::luminance_samples */
+#define AIC_EXPOSURE_RAYS 10     /* rays per step */
+/* replaces: character::exposure::State (exposure.rs:37-48) */
+typedef struct aic_exposure_state {
+    float luminance_samples[100];
+    uint32_t luminance_sample_index; /* the last element written */
+    float exposure_log;              /* ln of the exposure */
+} aic_exposure_state;
+/* replaces: impl Default for State (exposure.rs:50-58): every sample 1.0, index 0, exposure_log 0. Host-only. AIC_ERR_INVALID: NULL. */
+int aic_exposure_init(aic_exposure_state *s);
+/* replaces: the rays of State::step (exposure.rs:85-105), host-only and in f64 in the reference's order of operations. Ray k, k < n, belongs to
+ * sample index j = (first_index + k) % 100: rays[k] = {origin xyz, direction xyz} with origin = vt.transform_point3d(0, 0, 0) and direction =
+ * vt.transform_vector3d((j rem 10) / 10 * 2 - 1, (j div 10) / 10 * 2 - 1, -1) -- a fixed 90 degree field of view, directions not normalised --
+ * where vt = RigidTransform3D { rotation, translation }.to_transform(). AIC_ERR_INVALID: a NULL pointer (rays may be NULL when n == 0). */
+int aic_exposure_rays(const double rotation_ijkr[4], const double translation[3], uint32_t first_index, uint32_t n, double *rays /* [n][6] */);
+/* replaces: the sampling loop of State::step (exposure.rs:91-128) for n rays against the layer's space as last updated. Ray i = {origin, direction},
+ * taken as given and not normalised, steps through Raycaster(origin, direction).within(bounds, false).take(max_steps); at each step: the cube ahead
+ * outside the bounds -> the sky; a block ahead that is visible() (EvaluatedBlock::visible: a block with a voxel that is not fully transparent or emits
+ * -- a voxel block whose voxels are all invisible is NOT) and Space::get_light(cube behind) -- the layer's current light volume, BlockSky::light_outside
+ * for a cube outside it -- with status Visible -> out[i] = that texel's value().luminance(); the steps exhausted or the ray ended -> the sky:
+ * out[i] = sky.sample(direction).luminance() (sky.rs:32-41: the octant by >= 0.0, so -0.0 is positive and NaN negative). Rgb::luminance
+ * (color.rs:288-297) is g * 0.7152f + (r * 0.2126f + b * 0.0722f) in f32. max_steps: 2 * maximum_distance of LightPhysics::Rays, 0 for
+ * LightPhysics::None (every sample is then the sky). Zero, NaN and infinite components are legal and sample what the reference samples.
+ * flags: AIC_RAYS_DEVICE or 0 -- as for aic_trace_rays, `rays` (at a 16-byte boundary) and `out` are device pointers, nothing is staged or read back.
+ * The call returns when the samples are there. It is legal while frames are in flight on any slot and disturbs none of them (it reads what they read,
+ * on a stream that is none of theirs); it finishes a pending aic_evaluate_light_submit first, like every call that needs the scene, and sees every
+ * scene and light write issued before it. The first call after a change of the scene makes a bitmap of the visible blocks (a read-back of the voxel
+ * and palette pools if a block has voxels). AIC_ERR_INVALID: a NULL pointer with n > 0, a layer without a space, n above 1 << 20, unknown flag bits,
+ * misaligned device pointers; the context stays usable. n == 0 is AIC_OK. */
+int aic_sample_luminance(aic_ctx *ctx, int layer, uint32_t n, const double *rays, uint32_t max_steps, uint32_t flags, float *out /* [n] */);
+/* replaces: what State::step does with its samples (exposure.rs:67-73, 94-95, 113-135) and State::exposure (exposure.rs:63-65). Host-only. dt == 0
+ * changes nothing. Otherwise sample k is stored at (luminance_sample_index + 1 + k) % 100 and the index ends on the last one written; then
+ * luminance_average = (the f32 sum of the 100 samples in index order) * (1.0f / 100.0f); target = compute_target_exposure(luminance_average) =
+ * clamp(0.9f / l, 0.1f, 4.f) * 0.375f + 1.f * (1.f - 0.375f) (f32::clamp: NaN stays NaN); and if target is finite,
+ * exposure_log += (ln(target) - exposure_log) * (float)dt * 2.0f, in that order. *exposure (may be NULL) = exp(exposure_log). ln and exp are the f64
+ * functions rounded once to f32. AIC_ERR_INVALID: a NULL state, n above 100, NULL samples with n > 0, a state whose index is not below 100. */
+int aic_exposure_advance(aic_exposure_state *s, uint32_t n, const float *samples, double dt, float *exposure /* may be NULL */);
 /* number of rows / first rows a partition selects (host-side helper for buffer sizing) */
 uint32_t aic_partition_rows(uint32_t height, const aic_partition *partition);
 /* scatter compacted strips gathered from n_parts contexts back into a full frame, on device:

@@ -37,6 +37,8 @@ pub const AIC_LINES_DEVICE: u32 = 1;
 pub const AIC_TEXT_DEVICE: u32 = 1;
 pub const AIC_LINES_MAX: u32 = 1048576;
 pub const AIC_CURSOR_MAX_LINES: u32 = 28;
+pub const AIC_EXPOSURE_SAMPLES: u32 = 100;
+pub const AIC_EXPOSURE_RAYS: u32 = 10;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
 pub const AIC_MULTI_MAX_IN_FLIGHT: u32 = 8;
 pub const AIC_TUNE_QUEUES_SHIFT: u32 = 0;
@@ -234,6 +236,15 @@ pub struct aic_export_info {
     pub reserved: [u32; 4],
 }
 
+/// `character::exposure::State` (exposure.rs:37-48)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct aic_exposure_state {
+    pub luminance_samples: [f32; 100],
+    pub luminance_sample_index: u32,
+    pub exposure_log: f32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct aic_line_vertex {
@@ -378,6 +389,10 @@ unsafe extern "C" {
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;
     pub fn aic_export_split(ctx: *mut aic_ctx, desc: *const aic_export_desc, src_device: *const c_void, color_out: *mut c_void, depth_out: *mut f32, out_is_device: c_int, info: *mut aic_export_info) -> c_int;
     pub fn aic_export_size(width: u32, height: u32, max_area: f64, out: *mut u32) -> c_int;
+    pub fn aic_exposure_init(s: *mut aic_exposure_state) -> c_int;
+    pub fn aic_exposure_rays(rotation_ijkr: *const f64, translation: *const f64, first_index: u32, n: u32, rays: *mut f64) -> c_int;
+    pub fn aic_sample_luminance(ctx: *mut aic_ctx, layer: c_int, n: u32, rays: *const f64, max_steps: u32, flags: u32, out: *mut f32) -> c_int;
+    pub fn aic_exposure_advance(s: *mut aic_exposure_state, n: u32, samples: *const f32, dt: f64, exposure: *mut f32) -> c_int;
     pub fn aic_present_geometry(src_w: u32, src_h: u32, out_w: u32, out_h: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
     pub fn aic_present_split_lines(ctx: *mut aic_ctx, desc: *const aic_present_desc, lines: *const aic_lines_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info, lines_info: *mut aic_lines_info) -> c_int;
     pub fn aic_present_lines_scratch(src_w: u32, src_h: u32, out_w: u32, out_h: u32, n_lines: u32, bytes: *mut u64) -> c_int;

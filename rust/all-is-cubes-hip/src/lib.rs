@@ -43,7 +43,7 @@ use all_is_cubes::universe;
 use all_is_cubes::universe::{Handle, ReadTicket};
 use all_is_cubes_render::camera::{
     AntialiasingOption, Camera, FogOption, GraphicsOptions, Layers, LightingOption, StandardCameras, ToneMappingOperator,
-    TransparencyOption, Viewport,
+    TransparencyOption, ViewTransform, Viewport,
 };
 use all_is_cubes_render::{Flaws, HeadlessRenderer, RenderError, Rendering};
 use futures_core::future::BoxFuture;
@@ -670,6 +670,24 @@ impl HipRtRenderer {
         Ok((colors, hits))
     }
 
+    /// The sampling loop of `character::exposure::State::step` (exposure.rs:91-128) for a batch of world-space rays against the space of `layer` as
+    /// last uploaded by `update`, with its light wherever it was made: per ray the luminance of the light behind the first visible block that has a
+    /// valid one, or of the sky. `max_steps` is `2 * maximum_distance`, 0 for `LightPhysics::None`. Legal while frames are in flight. A multi-device
+    /// renderer samples on its first device: the scene is replicated.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a layer without a space, or more than `1 << 20` rays.
+    pub fn sample_luminance(&mut self, layer: core::ffi::c_int, rays: &[[f64; 6]], max_steps: u32) -> Result<Vec<f32>, RenderError> {
+        let n = u32::try_from(rays.len()).expect("more than u32::MAX rays");
+        let mut out = vec![0.0f32; rays.len()];
+        // SAFETY: the context is live; both buffers hold `n` elements and outlive the call, which returns when the samples are there
+        self.device.check(unsafe { ffi::aic_sample_luminance(self.device.first_ctx(), layer, n, rays.as_ptr().cast(), max_steps, 0, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
     /// One round of `raytrace_to_texture`'s `do_some_tracing` (raytrace_to_texture.rs:591-751): the listed pixels (`y * width + x`) of the frame
     /// `draw_split` renders, each traced exactly as there (`RtScene::trace_patch` on the pixel's own rectangle). Returns the two texels per pixel in list
     /// order -- the f16 colour bits and the signed depth -- for the caller to write at those pixels of its resident textures. A pixel may be listed more
@@ -1209,6 +1227,60 @@ impl HeadlessRenderer for HipRtRenderer {
     fn draw<'a>(&'a mut self, info_text: &'a str) -> BoxFuture<'a, Result<Rendering, RenderError>> {
         // `draw` must not touch the universe (headless.rs:36-38): everything it needs was forwarded by `update`
         Box::pin(async move { self.draw_rgba(info_text) })
+    }
+}
+
+/// `character::exposure::State` (all-is-cubes/src/character/exposure.rs:37-151) over the library's `aic_exposure_state`: what a host that steps no
+/// `Character` keeps to drive `GraphicsOptions::exposure = Automatic`. Once per simulation step, `step`, then hand `exposure()` to
+/// `Camera::set_measured_exposure`.
+#[derive(Clone, Debug)]
+pub struct ExposureState(ffi::aic_exposure_state);
+
+impl Default for ExposureState {
+    fn default() -> Self {
+        let mut s = ffi::aic_exposure_state { luminance_samples: [1.0; 100], luminance_sample_index: 0, exposure_log: 0.0 };
+        // SAFETY: a valid pointer to a state
+        let _ = unsafe { ffi::aic_exposure_init(&mut s) };
+        Self(s)
+    }
+}
+
+impl ExposureState {
+    /// `State::exposure`
+    pub fn exposure(&self) -> f32 {
+        let (mut copy, mut e) = (self.0, 1.0f32);
+        // SAFETY: valid pointers; `dt == 0` only reads the state
+        let _ = unsafe { ffi::aic_exposure_advance(&mut copy, 0, core::ptr::null(), 0.0, &mut e) };
+        e
+    }
+
+    /// The ring of luminance samples.
+    pub fn samples(&self) -> &[f32; 100] {
+        &self.0.luminance_samples
+    }
+
+    /// `State::step`: samples the renderer's world space from `view_transform` and eases the exposure towards its target. `maximum_distance` is that of
+    /// the space's `LightPhysics::Rays`, `None` for `LightPhysics::None`. `dt == 0` does nothing.
+    ///
+    /// # Errors
+    /// As [`HipRtRenderer::sample_luminance`].
+    pub fn step(&mut self, renderer: &mut HipRtRenderer, view_transform: ViewTransform, maximum_distance: Option<u8>, dt: f64) -> Result<(), RenderError> {
+        if dt == 0. {
+            return Ok(());
+        }
+        let max_steps = maximum_distance.map_or(0, |d| u32::from(d) * 2);
+        let r = view_transform.rotation;
+        let t = view_transform.translation;
+        let mut rays = [[0.0f64; 6]; ffi::AIC_EXPOSURE_RAYS as usize];
+        let first = (self.0.luminance_sample_index + 1) % ffi::AIC_EXPOSURE_SAMPLES;
+        // SAFETY: four and three doubles in, AIC_EXPOSURE_RAYS x 6 doubles out
+        let rc = unsafe { ffi::aic_exposure_rays([r.i, r.j, r.k, r.r].as_ptr(), [t.x, t.y, t.z].as_ptr(), first, ffi::AIC_EXPOSURE_RAYS, rays.as_mut_ptr().cast()) };
+        assert_eq!(rc, ffi::AIC_OK);
+        let samples = renderer.sample_luminance(ffi::AIC_LAYER_WORLD, &rays, max_steps)?;
+        // SAFETY: the samples hold AIC_EXPOSURE_RAYS floats
+        let rc = unsafe { ffi::aic_exposure_advance(&mut self.0, ffi::AIC_EXPOSURE_RAYS, samples.as_ptr(), dt, core::ptr::null_mut()) };
+        assert_eq!(rc, ffi::AIC_OK);
+        Ok(())
     }
 }
 
