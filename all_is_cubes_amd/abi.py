@@ -31,6 +31,8 @@ REPROJECT_KEEP_SPLATS = 1  # AIC_REPROJECT_KEEP_SPLATS: reprojected texels stay 
 REPROJECT_MAX_LEVELS = 12  # AIC_REPROJECT_MAX_LEVELS
 PRESENT_OUT_F16 = 1  # AIC_PRESENT_OUT_F16: the presented image as four f16 per pixel, linear, alpha 1.0, instead of sRGB RGBA8
 PRESENT_MAX_PIXELS = 1 << 31  # AIC_PRESENT_MAX_PIXELS
+STALE_DEPTH_TEST = 1  # AIC_STALE_DEPTH_TEST: a rectangle keeps out an opaque world pixel whose depth lies in front of it
+STALE_MAX_RECTS = 4096  # AIC_STALE_MAX_RECTS
 LINES_DEVICE = 1  # AIC_LINES_DEVICE: the line vertices are a device pointer
 LINES_MAX = 1 << 20  # AIC_LINES_MAX
 CURSOR_MAX_LINES = 28  # AIC_CURSOR_MAX_LINES
@@ -76,7 +78,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -137,6 +139,23 @@ def pixel_order(width: int, height: int):
     if rc != 0:
         raise AicError(rc, f"aic_pixel_order({width}, {height})")
     return order, int(central.value), int(cycle.value)
+
+
+def stale_rects(view_projection, width: int, height: int, boxes, expand: int = 1) -> np.ndarray:
+    """Boxes of changed cubes as the screen rectangles of the pixels they can have changed (aic_stale_rects): [n] STALE_RECT_DTYPE records for
+    pick_stale. `view_projection`: camera.projection * camera.view_matrix, column-major, 16 doubles; `boxes`: [n, 6] int32 (lower, upper exclusive cube
+    bounds); `expand`: cubes the box is grown by on every side -- 1 covers the light stencil and ambient occlusion at a surface beside a changed cube.
+    Host-only: needs no device or context."""
+    lib = load()
+    lib.aic_stale_rects.restype = C.c_int
+    lib.aic_stale_rects.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]
+    m = (C.c_double * 16)(*[float(v) for v in np.asarray(view_projection, np.float64).reshape(16)])
+    b = np.ascontiguousarray(np.asarray(boxes, np.int32).reshape(-1, 6))
+    out = np.zeros(len(b), STALE_RECT_DTYPE)
+    rc = lib.aic_stale_rects(m, int(width), int(height), len(b), b.ctypes.data if len(b) else None, int(expand), out.ctypes.data if len(b) else None)
+    if rc != 0:
+        raise AicError(rc, "aic_stale_rects")
+    return out
 
 
 def reproject_geometry(width: int, height: int):
@@ -239,6 +258,23 @@ class PickDesc(C.Structure):
 
 class PickInfo(C.Structure):
     _fields_ = [("n_unknown", C.c_uint64), ("next_cursor", C.c_uint64), ("n_from_unknown", C.c_uint32), ("n_from_order", C.c_uint32),
+                ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+class StaleRect(C.Structure):
+    _fields_ = [("x0", C.c_uint16), ("y0", C.c_uint16), ("x1", C.c_uint16), ("y1", C.c_uint16), ("dmin", C.c_float), ("reserved", C.c_uint32)]
+
+
+STALE_RECT_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2"), ("dmin", "<f4"), ("reserved", "<u4")])
+
+
+class StaleDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n", C.c_uint32), ("max_stale", C.c_uint32), ("skip_stale", C.c_uint64),
+                ("cursor", C.c_uint64), ("n_rects", C.c_uint32), ("flags", C.c_uint32), ("rects", C.c_void_p)]
+
+
+class StaleInfo(C.Structure):
+    _fields_ = [("n_stale", C.c_uint64), ("next_cursor", C.c_uint64), ("n_from_stale", C.c_uint32), ("n_from_order", C.c_uint32),
                 ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
 
 
@@ -450,6 +486,7 @@ def load() -> C.CDLL:
         lib.aic_trace_pixels.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(FrameInfo)]
         lib.aic_reproject_split.argtypes = [C.c_void_p, C.POINTER(ReprojectDesc), C.c_void_p, C.c_void_p, C.POINTER(ReprojectInfo)]
         lib.aic_pick_pixels.argtypes = [C.c_void_p, C.POINTER(PickDesc), C.c_void_p, C.c_void_p, C.POINTER(PickInfo)]
+        lib.aic_pick_stale.argtypes = [C.c_void_p, C.POINTER(StaleDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StaleInfo)]
         lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
         lib.aic_present_split_lines.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo),
                                                 C.POINTER(LinesInfo)]
@@ -853,6 +890,23 @@ class Context:
         d.skip_unknown, d.cursor, d.flags = int(skip_unknown), int(cursor), int(flags)
         info = PickInfo()
         self._check(self._lib.aic_pick_pixels(self._h, C.byref(d), C.c_void_p(order_ptr or None), C.c_void_p(out_ptr or None), C.byref(info)))
+        return info
+
+    def pick_stale(self, width: int, height: int, n: int, rects, src_ptr: int, order_ptr: int, out_ptr: int, cursor: int = 0, max_stale: int = 0,
+                   skip_stale: int = 0, flags: int = 0) -> StaleInfo:
+        """pick_pixels with the stale pixels of the resident Split frame `src_ptr` first (aic_pick_stale): the pixels inside at least one of `rects`
+        (stale_rects()'s records, at most STALE_MAX_RECTS) that does not keep them out -- with STALE_DEPTH_TEST a rectangle keeps out an opaque world
+        pixel whose depth is below its dmin; without it none does and the frame is not read. Up to `max_stale` of them, in the order's ranks, past the
+        first `skip_stale`; then the picker's picks `cursor`, `cursor` + 1, ... Returns once the list is written; the info's next_cursor and
+        n_from_stale are what the next call's cursor and skip_stale advance by."""
+        r = np.ascontiguousarray(np.asarray(rects, STALE_RECT_DTYPE).reshape(-1))
+        d = StaleDesc()
+        d.width, d.height, d.n, d.max_stale = int(width), int(height), int(n), int(max_stale)
+        d.skip_stale, d.cursor, d.n_rects, d.flags = int(skip_stale), int(cursor), len(r), int(flags)
+        d.rects = r.ctypes.data if len(r) else None
+        info = StaleInfo()
+        self._check(self._lib.aic_pick_stale(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(order_ptr or None), C.c_void_p(out_ptr or None),
+                                             C.byref(info)))
         return info
 
     def present_split(self, src_ptr: int, src_size, out_size, bloom_intensity: float, tone_mapping: int, maximum_intensity: float, flags: int = 0,

@@ -1,8 +1,8 @@
 // aic_ctx.h -- what the translation units of the C ABI's host side share: the context behind the opaque `aic_ctx` of
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
-// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater) and
-// aic_exposure_host.cpp (the luminance sampler's call) only (all five are written inside `using namespace aic`, and so is this header). Whatever one of the
+// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater),
+// aic_exposure_host.cpp (the luminance sampler's call) and aic_stale_host.cpp (the stale-pixel picker's) only (all six are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
 #pragma once
@@ -227,6 +227,8 @@ struct aic_ctx {
         std::string wave_prof;           // AIC_WAVE_PROF (-DAIC_PROFILE builds): file for the per-wave clocks
         bool lines_clear_keys = false;   // AIC_LINES_CLEAR_KEYS=1: every aic_present_split_lines clears its whole key image first instead of resetting the keys it touched
     } sw;
+    // (appended: no member the frame path reads moves)
+    DevBuf<unsigned char> stale_scratch;  // aic_pick_stale: the record, the scan blocks' counts and offsets, the bitmap, the rectangles (aic_stale.h)
 };
 
 namespace aic {

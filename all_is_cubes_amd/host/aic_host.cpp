@@ -536,6 +536,13 @@ bool HipRtRenderer::sync_space(int layer, const std::shared_ptr<Space> &space, c
         changed = true;
     }
     SpaceRendererTodo &todo = *ls.todo;
+    if (layer == AIC_LAYER_WORLD) {  // changed_boxes(): the whole space where the cubes are not known one by one
+        const GridAab &b = space->bounds();
+        if (todo.everything || !todo.blocks.empty()) changed_boxes_.push_back({b.lo[0], b.lo[1], b.lo[2], b.hi[0], b.hi[1], b.hi[2]});
+        else
+            for (const auto &c : todo.cubes) changed_boxes_.push_back({c[0], c[1], c[2], c[0] + 1, c[1] + 1, c[2] + 1});
+        if (!changed_boxes_.empty()) pick_skip_stale_ = 0;
+    }
     if (todo.everything) {
         upload_full(layer, *space);
         todo.clear();
@@ -597,6 +604,7 @@ bool HipRtRenderer::update_scene(const Cursor *cursor) {  // renderer.rs:96-161
     ui_camera_.set_view_transform(sc.ui.view_transform);
     std::memcpy(backdrop_, sc.ui.backdrop, sizeof(backdrop_));
     show_ui_ = sc.graphics_options.show_ui;
+    changed_boxes_.clear();
     bool changed = sync_space(AIC_LAYER_WORLD, sc.world_space, world_camera_.options());
     changed |= sync_space(AIC_LAYER_UI, show_ui_ ? sc.ui.space : nullptr, ui_camera_.options());
     return changed;
@@ -673,6 +681,7 @@ aic_reproject_info HipRtRenderer::reproject_split(const void *src, void *dst, co
     aic_reproject_info info;
     check(aic_reproject_split(ctx_, &d, src, dst, &info), "aic_reproject_split");
     pick_skip_unknown_ = 0;  // the unknown pixels are those of this reprojection now
+    pick_skip_stale_ = 0;    // ... and the stale ones lie elsewhere on the screen: the caller makes the rectangles again
     return info;
 }
 
@@ -681,7 +690,7 @@ aic_pick_info HipRtRenderer::pick_pixels(const uint32_t *device_order, uint32_t 
     if (vp.framebuffer_width != pick_width_ || vp.framebuffer_height != pick_height_) {
         pick_width_ = vp.framebuffer_width;
         pick_height_ = vp.framebuffer_height;
-        pick_cursor_ = pick_skip_unknown_ = 0;
+        pick_cursor_ = pick_skip_unknown_ = pick_skip_stale_ = 0;
     }
     aic_pick_desc d{};
     d.width = pick_width_;
@@ -694,6 +703,41 @@ aic_pick_info HipRtRenderer::pick_pixels(const uint32_t *device_order, uint32_t 
     check(aic_pick_pixels(ctx_, &d, device_order, device_pixels_out, &info), "aic_pick_pixels");
     pick_cursor_ = info.next_cursor;
     pick_skip_unknown_ += info.n_from_unknown;
+    return info;
+}
+
+std::vector<aic_stale_rect> HipRtRenderer::stale_rects(const std::vector<std::array<int32_t, 6>> &boxes, int32_t expand) const {
+    const Viewport vp = world_camera_.viewport();
+    const Mat4 m = world_camera_.view_matrix().then(world_camera_.projection_matrix());  // row-vector order: read column-major it is projection x view
+    std::vector<aic_stale_rect> out(boxes.size());
+    const int rc = aic_stale_rects(m.m, vp.framebuffer_width, vp.framebuffer_height, (uint32_t)boxes.size(), boxes.empty() ? nullptr : boxes[0].data(), expand,
+                                   out.data());
+    if (rc != AIC_OK) throw std::invalid_argument("stale_rects: a negative expand, a viewport edge above 65535 or a camera matrix that is not finite");
+    return out;
+}
+
+aic_stale_info HipRtRenderer::pick_stale(const std::vector<aic_stale_rect> &rects, const void *device_frame, const uint32_t *device_order,
+                                         uint32_t *device_pixels_out, uint32_t n, uint32_t max_stale, uint32_t flags) {
+    const Viewport vp = world_camera_.viewport();
+    if (vp.framebuffer_width != pick_width_ || vp.framebuffer_height != pick_height_) {
+        pick_width_ = vp.framebuffer_width;
+        pick_height_ = vp.framebuffer_height;
+        pick_cursor_ = pick_skip_unknown_ = pick_skip_stale_ = 0;
+    }
+    aic_stale_desc d{};
+    d.width = pick_width_;
+    d.height = pick_height_;
+    d.n = n;
+    d.max_stale = max_stale;
+    d.skip_stale = pick_skip_stale_;
+    d.cursor = pick_cursor_;
+    d.n_rects = (uint32_t)rects.size();
+    d.flags = flags;
+    d.rects = rects.data();
+    aic_stale_info info;
+    check(aic_pick_stale(ctx_, &d, device_frame, device_order, device_pixels_out, &info), "aic_pick_stale");
+    pick_cursor_ = info.next_cursor;
+    pick_skip_stale_ += info.n_from_stale;
     return info;
 }
 

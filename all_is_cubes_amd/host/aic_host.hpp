@@ -445,6 +445,21 @@ class HipRtRenderer : public HeadlessRenderer {
     aic_pick_info pick_pixels(const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n, uint32_t max_unknown = 0);
     uint64_t pick_cursor() const { return pick_cursor_; }
     uint64_t pick_skip_unknown() const { return pick_skip_unknown_; }
+    // The pixels a scene change made stale first (aic_stale_rects, aic_pick_stale; not in the reference, which re-arms a whole picker cycle,
+    // raytrace_to_texture.rs:587-589). stale_rects: boxes {lo x, y, z, hi x, y, z} (upper bounds exclusive) of changed cubes as the screen rectangles of
+    // the pixels they can have changed under the current world camera's projection x view; expand = 1 covers the light stencil and ambient occlusion
+    // beside a changed cube. changed_boxes: what the last update() sent to the device for the world layer, so that the loop needs no bookkeeping of its
+    // own: one box per cube of the space's dirty set (its block or its light texel changed), or the space's bounds as one box when the space was
+    // uploaded whole or a block definition was replaced (the cubes that use it are not tracked); empty when nothing changed.
+    // pick_stale: pick_pixels with, first, up to max_stale of the pixels of the resident Split frame `device_frame` inside a rectangle that does not keep
+    // them out (flags: AIC_STALE_DEPTH_TEST), past those handed out already. The renderer keeps that count beside the picker's cursor, which the two
+    // calls share: an update() that changed cubes, reproject_split, restart_stale() (new rectangles) and a change of the viewport's size set it to 0.
+    std::vector<aic_stale_rect> stale_rects(const std::vector<std::array<int32_t, 6>> &boxes, int32_t expand = 1) const;
+    const std::vector<std::array<int32_t, 6>> &changed_boxes() const { return changed_boxes_; }
+    aic_stale_info pick_stale(const std::vector<aic_stale_rect> &rects, const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out,
+                              uint32_t n, uint32_t max_stale, uint32_t flags = 0);
+    void restart_stale() { pick_skip_stale_ = 0; }
+    uint64_t pick_skip_stale() const { return pick_skip_stale_; }
     // raytrace_to_texture's per-frame presentation of its resident textures (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71, bloom.rs:41-60,
     // shaders/postprocess.wgsl:140-158 and 251-276; aic_present_split): the resident Split frame `src_device` -- of raytracer's viewport, i.e. the current
     // (size-policy-modified) viewport -- stretched with a linear filter to out_width x out_height, bloomed, tone-mapped and encoded, with bloom_intensity,
@@ -552,6 +567,8 @@ class HipRtRenderer : public HeadlessRenderer {
     aic_text_desc text_desc(const std::string &info_text);
     bool bloom_ = false;  // set_bloom
     uint64_t pick_cursor_ = 0, pick_skip_unknown_ = 0;  // pick_pixels
+    uint64_t pick_skip_stale_ = 0;  // pick_stale
+    std::vector<std::array<int32_t, 6>> changed_boxes_;  // of the last update(), world layer
     uint32_t pick_width_ = 0, pick_height_ = 0;         // ... and the viewport they belong to
     // snapshot taken by update(): draw() must not touch the scene objects (headless.rs:33-39)
     Camera world_camera_, ui_camera_;

@@ -359,6 +359,31 @@ PYBIND11_MODULE(_host, m) {
             d["kernel_ms"] = i.kernel_ms;
             return d;
         }, py::arg("order_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("max_unknown") = 0u)
+        .def("stale_rects", [](const HipRtRenderer &r, const std::vector<std::array<int32_t, 6>> &boxes, int32_t expand) {
+            // -> [(x0, y0, x1, y1, dmin, 0)]: the records of abi.STALE_RECT_DTYPE
+            py::list out;
+            for (const aic_stale_rect &q : r.stale_rects(boxes, expand)) out.append(py::make_tuple(q.x0, q.y0, q.x1, q.y1, q.dmin, q.reserved));
+            return out;
+        }, py::arg("boxes"), py::arg("expand") = 1)
+        .def("changed_boxes", [](const HipRtRenderer &r) { return r.changed_boxes(); })
+        .def("pick_stale", [](HipRtRenderer &r, const std::vector<std::tuple<uint16_t, uint16_t, uint16_t, uint16_t, float, uint32_t>> &rects, uintptr_t frame_ptr,
+                              uintptr_t order_ptr, uintptr_t out_ptr, uint32_t n, uint32_t max_stale, uint32_t flags) {
+            // -> dict(n_stale, next_cursor, n_from_stale, n_from_order, kernel_ms)
+            std::vector<aic_stale_rect> v;
+            for (const auto &t : rects) v.push_back(aic_stale_rect{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t)});
+            aic_stale_info i;
+            {
+                py::gil_scoped_release rel;
+                i = r.pick_stale(v, reinterpret_cast<const void *>(frame_ptr), reinterpret_cast<const uint32_t *>(order_ptr), reinterpret_cast<uint32_t *>(out_ptr), n,
+                                 max_stale, flags);
+            }
+            py::dict d;
+            d["n_stale"] = i.n_stale; d["next_cursor"] = i.next_cursor; d["n_from_stale"] = i.n_from_stale; d["n_from_order"] = i.n_from_order;
+            d["kernel_ms"] = i.kernel_ms;
+            return d;
+        }, py::arg("rects"), py::arg("frame_ptr"), py::arg("order_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("max_stale"), py::arg("flags") = 0u)
+        .def("restart_stale", &HipRtRenderer::restart_stale)
+        .def_property_readonly("pick_skip_stale", &HipRtRenderer::pick_skip_stale)
         .def_property_readonly("pick_cursor", &HipRtRenderer::pick_cursor)
         .def_property_readonly("pick_skip_unknown", &HipRtRenderer::pick_skip_unknown)
         .def("present_split", [](HipRtRenderer &r, uintptr_t src_ptr, uint32_t out_width, uint32_t out_height, uint32_t flags, uintptr_t out_ptr) -> py::object {

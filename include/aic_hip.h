@@ -437,6 +437,80 @@ typedef struct aic_pick_info {
     uint32_t reserved;
 } aic_pick_info;
 int aic_pick_pixels(aic_ctx *ctx, const aic_pick_desc *desc, const uint32_t *order_device, uint32_t *pixels_out_device, aic_pick_info *info);
+/* Adds what the reference does not have: after a scene change (aic_update_cubes, aic_replace_blocks) under a resident Split frame, the next picks are
+ * first the resident pixels the changed cubes can have changed, instead of a whole picker cycle re-armed by Inner::dirty()
+ * (all-is-cubes-gpu/src/raytrace_to_texture.rs:587-589). Two entry points; DESIGN.md 4.17 states the rule, tests/stale_ref.py is that text in NumPy.
+ *
+ * aic_stale_rects (host-only, f64, like aic_exposure_rays and aic_cursor_wireframe) turns boxes of changed cubes into screen rectangles. A pixel's value
+ * depends only on the cubes its sample rays pass through and, at a lit surface, on the cubes within one cube of the hit cube (the interpolated light
+ * stencil, the light-leak fix, ambient occlusion), and every sample ray of pixel (x, y) passes through an NDC point inside that pixel's square; so under
+ * an unchanged light volume a changed box [lo, hi) can only change a pixel whose square meets the bounding rectangle of the projected box grown by one
+ * cube: expand = 1. view_projection: camera.projection * camera.view_matrix as aic_lines_desc holds it (column-major [c*4+r], clip = M (x, y, z, 1)),
+ * in double. boxes = [n_boxes][6] {lo x, y, z, hi x, y, z}, upper bounds exclusive. Per box, in this order:
+ *   - hi <= lo on some axis (no volume): the empty rectangle, all fields 0.
+ *   - the eight corners of [lo - expand, hi + expand] (64-bit integers, then doubles) are projected, clip_r = ((M[r] x + M[4+r] y) + M[8+r] z) + M[12+r],
+ *     one rounding each. If a corner's w is not > 0 or a clip coordinate is not finite: the whole frame {0, 0, width, height} and dmin = -inf (the camera
+ *     inside or beside the box).
+ *   - otherwise, with [ax, bx] x [ay, by] the bounds of the eight x / w, y / w: columns floor((ax + 1) / 2 * width) - 1 up to and including
+ *     floor((bx + 1) / 2 * width) + 1, rows floor((1 - by) / 2 * height) - 1 up to and including floor((1 - ay) / 2 * height) + 1 (row 0 at NDC
+ *     y = +1: Viewport::normalize_fb_x_edge / _y_edge inverted; the pixel on every side is there against rounding), clamped to the frame; if no column
+ *     or no row is left, the empty rectangle, all fields 0.
+ *   - dmin = the least z / w of the eight, less 2^-24, rounded DOWN to f32 (DESIGN.md 4.17 on the margin).
+ * AIC_ERR_INVALID: a NULL pointer with n_boxes > 0, a negative expand, width or height above 65535, a matrix component that is not finite.
+ *
+ * aic_pick_stale is aic_pick_pixels with the unknown set U replaced by the stale set S of the resident frame `src_device` (a whole Split frame of
+ * width x height as aic_render with no partition lays it out): the pixels inside at least one rectangle that does not keep them out. Without
+ * AIC_STALE_DEPTH_TEST no rectangle keeps a pixel out: always conservative, and the frame is not read. With it rectangle b keeps pixel p out iff p's depth
+ * texel has a clear sign bit, p's alpha half is >= 1 (so not NaN, not the marker) and depth < b.dmin in f32: UI pixels, pixels of no layer, -0.0,
+ * translucent pixels, marker texels and NaN depths are always stale inside a rectangle. The flag needs a frame traced under the camera's own depth
+ * transform (Camera::depth_transform_zw(), as aic_present_split_lines' depth test does) and is the caller's knowledge and opt-in, as
+ * AIC_REPROJECT_KEEP_SPLATS is: it is exact only where no translucent surface lies in front of the changed cubes (a glass pane in front of an opaque
+ * wall stores the PANE's depth, and the alpha of what lies behind it), and, in an antialiased frame, only for pixels whose four samples all end in front
+ * of the box (the depth texel is the NEAREST sample's: a pixel on an occluder's silhouette is kept out although a sample passes the occluder).
+ * Rank list s_0, s_1, ...: the pixels order[r], r ascending, that are in S (an entry >= count is never stale); n_stale = |S|.
+ * g = min(n, max_stale, max(n_stale - skip_stale, 0)); pixels_out[i] = s_(skip_stale + i) for i < g; pixels_out[g + j] = pick(cursor + j) for
+ * j < n - g, pick exactly as under aic_pick_pixels; all 64-bit. With n_rects = 0 or max_stale = 0 nothing is looked at, n_stale is 0 and the list is the
+ * picker's. A pixel may appear both in the stale part and in the picker part: harmless, as with unknown pixels. Nothing beyond pixels_out[n) is written;
+ * src is only read. The call blocks and runs on slot 0, like its siblings. rects is host memory, copied into context scratch before the call returns
+ * (empty rectangles are left out of the copy). Scratch (40 bytes per 256 pixels, 16 a rectangle and a 32-byte record) belongs to the context, is allocated
+ * on first use, again when a call needs more, and released in aic_destroy.
+ * Rejected before anything is queued, with AIC_ERR_INVALID and the context still usable: everything aic_pick_pixels rejects for the arguments the two
+ * share (a NULL desc or info; a NULL pixels_out_device with n > 0; pixels_out_device or order_device off a 4-byte boundary; n > 0 with count = 0; width
+ * or height above 65535; n above 2048 x 65535; a frame still occupying slot 0); src_device off an 8-byte boundary, or NULL when it would be read (n > 0,
+ * n_rects > 0, max_stale > 0 and the depth test); NULL rects with n_rects > 0; n_rects above AIC_STALE_MAX_RECTS (a caller with more boxes merges them
+ * or passes one whole-frame rectangle); a rectangle with x0 > x1, y0 > y1, x1 > width or y1 > height; a NaN dmin; unknown flag bits. n = 0 is AIC_OK,
+ * writes nothing and zeroes the info.
+ * Limits: LightingOption::Bounce rays go anywhere. A light update changes cubes the caller did not edit: expand = the light's maximum_distance is the
+ * conservative answer, letting the light dissolve in over the picker's cycle is what happens without it. */
+#define AIC_STALE_DEPTH_TEST 1u
+#define AIC_STALE_MAX_RECTS 4096u
+typedef struct aic_stale_rect {
+    uint16_t x0, y0, x1, y1;  /* columns [x0, x1), rows [y0, y1) */
+    float dmin;               /* nothing of the box is nearer than this depth; -inf: unknown */
+    uint32_t reserved;
+} aic_stale_rect;
+typedef struct aic_stale_desc {
+    uint32_t width, height;  /* the resident frame */
+    uint32_t n;              /* picks to write */
+    uint32_t max_stale;      /* at most this many of them from the stale pixels; 0: none */
+    uint64_t skip_stale;     /* stale pixels (in rank order) already handed out under these rectangles */
+    uint64_t cursor;         /* pick index k of the first picker pick */
+    uint32_t n_rects;
+    uint32_t flags;          /* AIC_STALE_* */
+    const aic_stale_rect *rects;  /* host memory */
+} aic_stale_desc;
+typedef struct aic_stale_info {
+    uint64_t n_stale;        /* |S| (0 when n_rects == 0 or max_stale == 0: not looked at) */
+    uint64_t next_cursor;    /* cursor + n_from_order */
+    uint32_t n_from_stale;   /* g */
+    uint32_t n_from_order;   /* n - g */
+    float kernel_ms;         /* HIP events around the launches */
+    uint32_t reserved;
+} aic_stale_info;
+int aic_stale_rects(const double view_projection[16], uint32_t width, uint32_t height, uint32_t n_boxes, const int32_t *boxes /* [n][6] */, int32_t expand,
+                    aic_stale_rect *out /* [n] */);
+int aic_pick_stale(aic_ctx *ctx, const aic_stale_desc *desc, const void *src_device, const uint32_t *order_device, uint32_t *pixels_out_device,
+                   aic_stale_info *info);
 /* replaces: what raytrace_to_texture does with its resident textures every displayed frame: RaytraceToTexture::draw
  * (all-is-cubes-gpu/src/raytrace_to_texture.rs:546-568) draws rt_frame_copy_vertex / rt_frame_copy_fragment (shaders/rt-copy.wgsl:41-71) into the linear
  * scene texture -- the pipeline's linear ClampToEdge sampler stretches the frame to the viewport (the reference traces at half the nominal size,

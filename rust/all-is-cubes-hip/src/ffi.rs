@@ -36,6 +36,8 @@ pub const AIC_PRESENT_MAX_PIXELS: u64 = 2147483648;
 pub const AIC_LINES_DEVICE: u32 = 1;
 pub const AIC_TEXT_DEVICE: u32 = 1;
 pub const AIC_LINES_MAX: u32 = 1048576;
+pub const AIC_STALE_DEPTH_TEST: u32 = 1;
+pub const AIC_STALE_MAX_RECTS: u32 = 4096;
 pub const AIC_CURSOR_MAX_LINES: u32 = 28;
 pub const AIC_EXPOSURE_SAMPLES: u32 = 100;
 pub const AIC_EXPOSURE_RAYS: u32 = 10;
@@ -186,6 +188,42 @@ pub struct aic_pick_info {
     pub n_unknown: u64,
     pub next_cursor: u64,
     pub n_from_unknown: u32,
+    pub n_from_order: u32,
+    pub kernel_ms: f32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct aic_stale_rect {
+    pub x0: u16,
+    pub y0: u16,
+    pub x1: u16,
+    pub y1: u16,
+    pub dmin: f32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct aic_stale_desc {
+    pub width: u32,
+    pub height: u32,
+    pub n: u32,
+    pub max_stale: u32,
+    pub skip_stale: u64,
+    pub cursor: u64,
+    pub n_rects: u32,
+    pub flags: u32,
+    pub rects: *const aic_stale_rect,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_stale_info {
+    pub n_stale: u64,
+    pub next_cursor: u64,
+    pub n_from_stale: u32,
     pub n_from_order: u32,
     pub kernel_ms: f32,
     pub reserved: u32,
@@ -386,6 +424,15 @@ unsafe extern "C" {
     pub fn aic_reproject_split(ctx: *mut aic_ctx, desc: *const aic_reproject_desc, src_device: *const c_void, dst_device: *mut c_void, info: *mut aic_reproject_info) -> c_int;
     pub fn aic_reproject_geometry(width: u32, height: u32, levels: *mut u32, t0: *mut u32, scratch_bytes: *mut u64) -> c_int;
     pub fn aic_pick_pixels(ctx: *mut aic_ctx, desc: *const aic_pick_desc, order_device: *const u32, pixels_out_device: *mut u32, info: *mut aic_pick_info) -> c_int;
+    pub fn aic_stale_rects(view_projection: *const f64, width: u32, height: u32, n_boxes: u32, boxes: *const i32, expand: i32, out: *mut aic_stale_rect) -> c_int;
+    pub fn aic_pick_stale(
+        ctx: *mut aic_ctx,
+        desc: *const aic_stale_desc,
+        src_device: *const c_void,
+        order_device: *const u32,
+        pixels_out_device: *mut u32,
+        info: *mut aic_stale_info,
+    ) -> c_int;
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;
     pub fn aic_export_split(ctx: *mut aic_ctx, desc: *const aic_export_desc, src_device: *const c_void, color_out: *mut c_void, depth_out: *mut f32, out_is_device: c_int, info: *mut aic_export_info) -> c_int;
     pub fn aic_export_size(width: u32, height: u32, max_area: f64, out: *mut u32) -> c_int;

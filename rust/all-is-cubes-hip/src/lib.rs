@@ -813,6 +813,77 @@ impl HipRtRenderer {
         Ok(info)
     }
 
+    /// The screen rectangles of the pixels that boxes of changed cubes can have changed under the renderer's current world camera (`aic_stale_rects`):
+    /// one rectangle per box `[lower, upper)` grown by `expand` cubes -- 1 covers the light stencil and ambient occlusion beside a changed cube.
+    /// Host-only. `None`: a negative `expand` or a viewport edge above 65535.
+    pub fn stale_rects(&self, boxes: &[[i32; 6]], expand: i32) -> Option<Vec<ffi::aic_stale_rect>> {
+        let (viewport, _) = self.frame_desc();
+        let camera = &self.cameras.cameras().world;
+        let view_projection: [f64; 16] = camera.view_matrix().then(&camera.projection_matrix()).to_array();
+        let mut out = vec![ffi::aic_stale_rect::default(); boxes.len()];
+        let n = u32::try_from(boxes.len()).ok()?;
+        // SAFETY: both lists hold `n` records; the matrix is 16 doubles
+        let rc = unsafe {
+            ffi::aic_stale_rects(
+                view_projection.as_ptr(),
+                viewport.framebuffer_size.width,
+                viewport.framebuffer_size.height,
+                n,
+                boxes.as_ptr().cast(),
+                expand,
+                out.as_mut_ptr(),
+            )
+        };
+        (rc == 0).then_some(out)
+    }
+
+    /// [`Self::pick_pixels`] with the pixels a scene change made stale first (`aic_pick_stale`; not in the reference, which re-arms a whole picker
+    /// cycle, raytrace_to_texture.rs:587-589): the list begins with up to `max_stale` of the pixels of the resident Split frame at `src_device` that lie
+    /// inside one of `rects` ([`Self::stale_rects`]) which does not keep them out, in picker order, skipping the first `skip_stale`; the rest is the
+    /// reference's pick sequence from `cursor`. With `ffi::AIC_STALE_DEPTH_TEST` in `flags` a rectangle keeps out an opaque world pixel in front of
+    /// its box; without it the frame is not read. The caller keeps `cursor` and `skip_stale` (add `n_from_stale`; zero with new rectangles).
+    ///
+    /// # Safety
+    /// As [`Self::pick_pixels`]; `src_device` is a whole Split frame of the current viewport on the renderer's device, 8-byte aligned (it may be null
+    /// without the depth test).
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures; more than `ffi::AIC_STALE_MAX_RECTS` rectangles are rejected.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn pick_stale(
+        &mut self,
+        rects: &[ffi::aic_stale_rect],
+        flags: u32,
+        src_device: *const core::ffi::c_void,
+        order_device: *const u32,
+        pixels_out_device: *mut u32,
+        n: u32,
+        max_stale: u32,
+        skip_stale: u64,
+        cursor: u64,
+    ) -> Result<ffi::aic_stale_info, RenderError> {
+        let Device::One(ctx) = self.device else { panic!("pick_stale needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let desc = ffi::aic_stale_desc {
+            width: viewport.framebuffer_size.width,
+            height: viewport.framebuffer_size.height,
+            n,
+            max_stale,
+            skip_stale,
+            cursor,
+            n_rects: u32::try_from(rects.len()).unwrap_or(u32::MAX),
+            flags,
+            rects: rects.as_ptr(),
+        };
+        let mut info = ffi::aic_stale_info::default();
+        // SAFETY: the context is live; the caller vouches for the frame and the two lists; `rects` is copied before the call returns
+        self.device.check(unsafe { ffi::aic_pick_stale(ctx.as_ptr(), &desc, src_device, order_device, pixels_out_device, &mut info) })?;
+        Ok(info)
+    }
+
     /// What `raytrace_to_texture` does with its resident textures every displayed frame (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71,
     /// bloom.rs:41-60, shaders/postprocess.wgsl:140-158 and 251-276): the resident Split frame at `src_device`, of the renderer's own viewport, is
     /// stretched with a linear filter to `out_size`, bloomed with the world options' `bloom_intensity`, tone-mapped and written to `out_device` as sRGB
