@@ -55,10 +55,12 @@ def space_from_flat(flat_space):
 def evoxels_from_blockdef(b):
     from . import _host as H
 
+    carried = None if b.voxel_selectable is None else [bool(v) for v in b.voxel_selectable]
     if b.is_one:
-        e = H.Evoxels.from_one(tuple(float(v) for v in b.palette[0, 0:4]), tuple(float(v) for v in b.palette[0, 4:7]))
+        e = H.Evoxels.from_one(tuple(float(v) for v in b.palette[0, 0:4]), tuple(float(v) for v in b.palette[0, 4:7]), None if carried is None else carried[0])
     else:
-        e = H.Evoxels.paletted(b.resolution, tuple(int(v) for v in b.vlo), b.voxels, b.palette)
+        e = H.Evoxels.paletted(b.resolution, tuple(int(v) for v in b.vlo), b.voxels, b.palette, carried)
     e.is_air = bool(b.is_air)
+    e.selectable = bool(b.selectable) and not b.is_air
     e.display_name = "" if b.name == "#" else b.name
     return e

@@ -78,7 +78,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -380,6 +380,16 @@ class CursorDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+# aic_cursor_hit: 144 bytes, the first 88 an aic_cursor_desc (CursorDesc)
+CURSOR_HIT_DTYPE = np.dtype({
+    "names": ["cube", "face_entered", "face_selected", "point_entered", "distance_to_point", "voxel_lo", "voxel_size", "resolution", "reserved", "hit",
+              "block_index", "voxel", "has_preceding", "preceding_cube", "preceding_block_index", "light_hit", "light_preceding", "steps", "reserved_hit"],
+    "formats": [("<i4", (3,)), "<i4", "<i4", ("<f8", (3,)), "<f8", ("<i4", (3,)), ("<i4", (3,)), "<i4", "<i4", "<i4",
+                "<u4", ("<i4", (3,)), "<i4", ("<i4", (3,)), "<u4", ("u1", (4,)), ("u1", (4,)), "<u4", "<u4"],
+    "offsets": [0, 12, 16, 24, 48, 56, 68, 80, 84, 88, 92, 96, 108, 112, 124, 128, 132, 136, 140],
+    "itemsize": 144})
+CURSOR_NO_BLOCK = 0xFFFFFFFF  # AIC_CURSOR_NO_BLOCK: preceding_block_index of a cube outside the bounds
+
 LINE_VERTEX_DTYPE = np.dtype([("position", "<f4", (3,)), ("color", "<f4", (4,))])  # aic_line_vertex: 28 bytes
 
 
@@ -495,6 +505,7 @@ def load() -> C.CDLL:
                                                C.POINTER(PresentInfo), C.POINTER(LinesInfo)]
         lib.aic_export_split.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ExportInfo)]
         lib.aic_sample_luminance.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.aic_cursor_raycast.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_double, C.c_uint32, C.c_void_p]
         lib.aic_export_size.restype = C.c_int
         lib.aic_export_size.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -688,9 +699,9 @@ class Context:
         d.vlo[:] = list(block.vlo)
         d.vsize[:] = list(block.voxels.shape)
         d.pal_len = len(block.palette)
-        d.flags = (flat.FLAG_ONE if block.is_one else 0) | (flat.FLAG_AIR if block.is_air else 0)
+        d.flags = flat.block_flags(block)
         vox = np.ascontiguousarray(block.voxels, np.uint16)
-        pal = np.ascontiguousarray(block.palette, np.float32)
+        pal = flat.block_palette(block)
         self._check(self._lib.aic_replace_block(self._h, layer, index, C.byref(d), _ptr(vox), _ptr(pal)))
 
     def render_orthographic(self, layer: int = LAYER_WORLD, resolution: int = 32):
@@ -721,9 +732,9 @@ class Context:
             d.vlo[:] = list(block.vlo)
             d.vsize[:] = list(block.voxels.shape)
             d.pal_len = len(block.palette)
-            d.flags = (flat.FLAG_ONE if block.is_one else 0) | (flat.FLAG_AIR if block.is_air else 0)
+            d.flags = flat.block_flags(block)
             vox = np.ascontiguousarray(block.voxels, np.uint16)
-            pal = np.ascontiguousarray(block.palette, np.float32)
+            pal = flat.block_palette(block)
             keep += [vox, pal]
             vp[k], pp[k] = vox.ctypes.data, pal.ctypes.data
         self._check(self._lib.aic_replace_blocks(self._h, layer, n, _ptr(idx), C.cast(descs, C.c_void_p), C.cast(vp, C.c_void_p), C.cast(pp, C.c_void_p)))
@@ -835,6 +846,21 @@ class Context:
         Returns once the samples are there."""
         self._check(self._lib.aic_sample_luminance(self._h, int(layer), int(n), C.c_void_p(rays_ptr or None), int(max_steps), RAYS_DEVICE,
                                                    C.c_void_p(out_ptr or None)))
+
+    def cursor_raycast(self, layer: int, rays, maximum_distance: float) -> np.ndarray:
+        """cursor_raycast (cursor.rs:26-107) of each of the rays [n,6] = (origin xyz, direction xyz) against the layer's space, no further than
+        maximum_distance (inf is legal): [n] CURSOR_HIT_DTYPE records (aic_cursor_raycast), all zero where the reference returns None. Legal with
+        frames in flight."""
+        r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        out = np.zeros(len(r), CURSOR_HIT_DTYPE)
+        self._check(self._lib.aic_cursor_raycast(self._h, int(layer), len(r), _ptr(r), float(maximum_distance), 0, _ptr(out)))
+        return out
+
+    def cursor_raycast_device(self, layer: int, n: int, rays_ptr: int, maximum_distance: float, out_ptr: int) -> None:
+        """The same with the rays ([n,6] f64) and the records ([n] of 144 bytes) in HBM on the context's device (AIC_RAYS_DEVICE), both at 8-byte
+        boundaries: no staging, no read-back. Returns once the records are there."""
+        self._check(self._lib.aic_cursor_raycast(self._h, int(layer), int(n), C.c_void_p(rays_ptr or None), float(maximum_distance), RAYS_DEVICE,
+                                                 C.c_void_p(out_ptr or None)))
 
     def trace_pixels(self, frame: FrameDesc, pixels, want_aux: bool = False):
         """The listed pixels of `frame` (indices y * width + x, host memory), each traced exactly as render() traces it, results in list order

@@ -143,6 +143,11 @@ inline void set_class(std::vector<uint32_t> &cls, uint32_t index, uint32_t c2) {
 }
 
 inline bool invisible(const float *e) { return e[3] == 0.f && e[4] == 0.f && e[5] == 0.f && e[6] == 0.f; }
+inline bool selectable_float_ok(float v) {
+    uint32_t bits;
+    std::memcpy(&bits, &v, sizeof(bits));
+    return bits == 0u || bits == 0x3f800000u;
+}
 
 // Builds the device form of one block: palette reordered "invisible entries first", voxel
 // codes remapped accordingly (aic_device.h). Appends to vox/pal pools at the given offsets.
@@ -151,6 +156,7 @@ int convert_block(aic_ctx *c, const aic_block_desc &d, const uint16_t *voxels, c
     std::memset(out, 0, sizeof(*out));
     if (!valid_resolution(d.resolution)) return fail(c, AIC_ERR_INVALID, "block resolution must be a power of two in 1..128");
     const bool one = (d.flags & AIC_BLOCK_ONE) != 0;
+    const bool voxel_flag = (d.flags & AIC_BLOCK_VOXEL_SELECTABLE) != 0;
     size_t nvox = one ? 1 : (size_t)d.vsize[0] * (size_t)d.vsize[1] * (size_t)d.vsize[2];
     for (int a = 0; a < 3 && !one; a++) {
         if (d.vsize[a] < 0 || d.vlo[a] < 0 || d.vlo[a] + d.vsize[a] > d.resolution)
@@ -166,7 +172,12 @@ int convert_block(aic_ctx *c, const aic_block_desc &d, const uint16_t *voxels, c
         for (int k = 0; k < 7; k++)
             if (!(e[k] >= 0.f)) return fail(c, AIC_ERR_INVALID, "palette entry has a negative or NaN component");
         if (!(e[3] <= 1.f)) return fail(c, AIC_ERR_INVALID, "palette entry has alpha above 1");
+        // Evoxel::selectable of a block that carries it: the pattern of 1.0f or of +0.0f
+        if (voxel_flag && !selectable_float_ok(e[7])) return fail(c, AIC_ERR_INVALID, "palette entry of an AIC_BLOCK_VOXEL_SELECTABLE block: the eighth float is neither 1.0f nor 0.0f");
     }
+    // what aic_cursor_raycast reads (no other kernel does): the block's own attribute -- AIR's says unselectable -- and each voxel's
+    const bool block_selectable = !(d.flags & (AIC_BLOCK_UNSELECTABLE | AIC_BLOCK_AIR));
+    auto voxel_selectable = [&](const float *e) { return voxel_flag ? e[7] == 1.f : !invisible(e); };
     if (one || d.resolution == 1) {
         // Evoxels::single_voxel() (voxel_storage.rs:364-385)
         const float *e = nullptr;
@@ -187,6 +198,8 @@ int convert_block(aic_ctx *c, const aic_block_desc &d, const uint16_t *voxels, c
         // (+ 0.0f: a PositiveSign never holds -0.0 -- restricted_number.rs:283 -- and the kernel's ps_mul relies on the sign bit)
         for (int k = 0; k < 4; k++) out->color[k] = e[k] + 0.0f;
         for (int k = 0; k < 3; k++) out->emission[k] = e[4 + k] + 0.0f;
+        // (a single voxel: the block's attribute ANDed with the voxel's; the AIR read outside the stored volume is Evoxel::AIR, unselectable either way)
+        out->pad[0] = block_selectable && voxel_selectable(e) ? kBlockSelectable : 0u;
         return AIC_OK;
     }
     // recursive block
@@ -204,7 +217,7 @@ int convert_block(aic_ctx *c, const aic_block_desc &d, const uint16_t *voxels, c
         DevPaletteEntry &pe = (*pal_out)[pal_base + dst];
         for (int k = 0; k < 4; k++) pe.color[k] = e[k] + 0.0f;
         for (int k = 0; k < 3; k++) pe.emission[k] = e[4 + k] + 0.0f;
-        pe.pad = 0.f;
+        pe.pad = voxel_selectable(e) ? 1.f : 0.f;
     }
     size_t vox_base = vox_out->size();
     vox_out->resize(vox_base + nvox);
@@ -219,6 +232,7 @@ int convert_block(aic_ctx *c, const aic_block_desc &d, const uint16_t *voxels, c
     out->vox_off = vox_off;
     out->pal_off = pal_off;
     out->n_invisible = n_inv;
+    out->pad[0] = block_selectable ? kBlockSelectable : 0u;
     return AIC_OK;
 }
 
@@ -366,7 +380,7 @@ void aic_destroy(aic_ctx *c) {
     }
     for (auto &l : c->layers) l.release();
     c->lut.release(); c->srgb_thr.release(); c->srgb_buckets.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->pick_scratch.release(); c->stale_scratch.release(); c->present_scratch.release(); c->lines_scratch.release();
-    c->text_atlas.release(); c->text_codes.release(); c->export_counts.release(); c->exposure_scratch.release();
+    c->text_atlas.release(); c->text_codes.release(); c->export_counts.release(); c->exposure_scratch.release(); c->cursor_scratch.release();
     if (c->dump) std::fclose(c->dump);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -2,7 +2,7 @@
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
 // aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater),
-// aic_exposure_host.cpp (the luminance sampler's call) and aic_stale_host.cpp (the stale-pixel picker's) only (all six are written inside `using namespace aic`, and so is this header). Whatever one of the
+// aic_exposure_host.cpp (the luminance sampler's call), aic_stale_host.cpp (the stale-pixel picker's) and aic_cursor_raycast_host.cpp (the cursor raycast's) only (all seven are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
 #pragma once
@@ -229,6 +229,7 @@ struct aic_ctx {
     } sw;
     // (appended: no member the frame path reads moves)
     DevBuf<unsigned char> stale_scratch;  // aic_pick_stale: the record, the scan blocks' counts and offsets, the bitmap, the rectangles (aic_stale.h)
+    DevBuf<unsigned char> cursor_scratch;  // aic_cursor_raycast with host pointers: the staged rays, then the records
 };
 
 namespace aic {

@@ -14,7 +14,7 @@
 //             palette is reordered at upload so invisible entries (alpha == 0 && emission == 0,
 //             surface.rs:395) come first; code < DevBlock.n_invisible means "invisible voxel"
 //             and needs no palette fetch.
-//   palette : DevPaletteEntry pool, 32 B each (rgba f32x4, emission f32x3, pad)
+//   palette : DevPaletteEntry pool, 32 B each (rgba f32x4, emission f32x3, selectable as a float)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,14 +32,17 @@ struct DevBlock {
     uint32_t vox_off;     // u16 units into DevLayer.pool (already past the cube grid)
     uint32_t pal_off;     // entries into the palette pool
     uint32_t n_invisible; // device voxel codes below this are invisible
-    uint32_t pad[3];
+    uint32_t pad[3];      // pad[0]: kBlockSelectable (read by the cursor raycast alone, aic_cursor_raycast.hip); the rest zero
 };
+// DevBlock::pad[0] bit 0: EvaluatedBlock::attributes().selectable and the block is not AIR -- for a single-voxel block ANDed with its voxel's
+// Evoxel::selectable, so that the one bit decides such a block. No trace, light or exposure kernel reads DevBlock::pad or DevPaletteEntry::pad.
+static constexpr uint32_t kBlockSelectable = 1u;
 static_assert(sizeof(DevBlock) == 64, "DevBlock is one 64-byte line");
 
 struct DevPaletteEntry {
     float color[4];
     float emission[3];
-    float pad;
+    float pad;            // Evoxel::selectable as 1.0f / 0.0f (the cursor raycast alone reads it)
 };
 static_assert(sizeof(DevPaletteEntry) == 32, "palette entry is 32 B");
 

@@ -232,6 +232,15 @@ AIC_DEV LvlLim lvl_init(double ox, double oy, double oz, const RayDir rd, bool b
     return out;
 }
 
+// RaycastStep::recursive_raycast (raycast.rs:458-476) for a step whose cube_ahead is (cx, cy, cz): the sub-ray starts at
+// (origin - cube.lower_bounds) * resolution, keeps the direction (so `rd` and `half_over_len` are the outer ray's) and is cast within the block's voxel
+// bounds WITH the exit step. The arithmetic of the Bounce rays' EnterBlock (aic_light_bounce.h, which keeps its own three lines: calling this from there
+// moved 256 bytes of the trace kernels' code object, which stays as it is) as a function, for the cursor raycast (aic_cursor_raycast.hip).
+AIC_DEV LvlLim lvl_init_recursive(double ox, double oy, double oz, int cx, int cy, int cz, double kd /* the resolution */, const RayDir rd, int lox, int loy, int loz,
+                                  int hix, int hiy, int hiz, double half_over_len) {
+    return lvl_init((ox - (double)cx) * kd, (oy - (double)cy) * kd, (oz - (double)cz) * kd, rd, true, lox, loy, loz, hix, hiy, hiz, true, half_over_len);
+}
+
 // The deferred State::step (raycast.rs:577-626) along the axis recorded in `pick`.
 AIC_DEV Lvl lvl_do_step(Lvl s, const RayDir rd) {
     const uint32_t axis = (s.st >> 5) & 3u;

@@ -31,7 +31,7 @@ BLOCK_DTYPE = np.dtype(
         ("vox_off", "<u4"),
         ("pal_off", "<u4"),
         ("pal_len", "<u4"),
-        ("flags", "<u4"),  # bit0: Evoxels::One, bit1: block == AIR
+        ("flags", "<u4"),  # bit0: Evoxels::One, bit1: block == AIR, bit2: not selectable, bit3: the palette's eighth floats are Evoxel::selectable
         ("name_char", "<i4"),
     ],
     align=False,
@@ -40,6 +40,8 @@ assert BLOCK_DTYPE.itemsize == 48
 
 FLAG_ONE = 1
 FLAG_AIR = 2
+FLAG_UNSELECTABLE = 4  # AIC_BLOCK_UNSELECTABLE: EvaluatedBlock::attributes().selectable == false
+FLAG_VOXEL_SELECTABLE = 8  # AIC_BLOCK_VOXEL_SELECTABLE: palette[i][7] is Evoxel::selectable (1.0 / 0.0); without it a voxel is selectable iff visible
 
 # LightStatus discriminants (light/data.rs:36-47)
 STATUS_UNINITIALIZED = 0
@@ -64,12 +66,18 @@ class BlockDef:
     is_one: bool = False
     is_air: bool = False
     name: str = "#"
+    selectable: bool = True  # EvaluatedBlock::attributes().selectable
+    voxel_selectable: Optional[Sequence[bool]] = None  # per palette entry: Evoxel::selectable (None: selectable iff not invisible, the default rule)
 
     def __post_init__(self) -> None:
         if self.resolution not in VALID_RESOLUTIONS:
             raise ValueError(f"invalid resolution {self.resolution}")
         self.voxels = np.ascontiguousarray(self.voxels, dtype=np.uint16)
         self.palette = np.ascontiguousarray(self.palette, dtype=np.float32).reshape(-1, 8)
+        if self.voxel_selectable is not None:
+            self.voxel_selectable = np.ascontiguousarray(self.voxel_selectable, dtype=bool).reshape(-1)
+            if len(self.voxel_selectable) != len(self.palette):
+                raise ValueError("voxel_selectable needs one entry per palette entry")
         if self.voxels.ndim != 3:
             raise ValueError("voxels must be 3-D")
         if self.voxels.size and int(self.voxels.max()) >= len(self.palette):
@@ -94,6 +102,21 @@ def air() -> BlockDef:
     b = atom((0.0, 0.0, 0.0, 0.0), name=" ")
     b.is_air = True
     return b
+
+
+def block_flags(b: BlockDef) -> int:
+    """aic_block_desc.flags of a block"""
+    return ((FLAG_ONE if b.is_one else 0) | (FLAG_AIR if b.is_air else 0) | (0 if b.selectable else FLAG_UNSELECTABLE)
+            | (FLAG_VOXEL_SELECTABLE if b.voxel_selectable is not None else 0))
+
+
+def block_palette(b: BlockDef) -> np.ndarray:
+    """The block's palette as it is uploaded: as given, with Evoxel::selectable in the eighth float of each entry if the block carries it"""
+    pal = np.ascontiguousarray(b.palette, np.float32)
+    if b.voxel_selectable is not None:
+        pal = pal.copy()
+        pal[:, 7] = np.where(b.voxel_selectable, np.float32(1.0), np.float32(0.0))
+    return pal
 
 
 @dataclass
@@ -167,10 +190,10 @@ class FlatSpace:
             table[i]["vox_off"] = vox_off
             table[i]["pal_off"] = pal_off
             table[i]["pal_len"] = len(b.palette)
-            table[i]["flags"] = (FLAG_ONE if b.is_one else 0) | (FLAG_AIR if b.is_air else 0)
+            table[i]["flags"] = block_flags(b)
             table[i]["name_char"] = ord(b.name[0]) if b.name else ord("#")
             vox_parts.append(b.voxels.reshape(-1))
-            pal_parts.append(b.palette)
+            pal_parts.append(block_palette(b))
             vox_off += b.voxels.size
             pal_off += len(b.palette)
         voxels = np.concatenate(vox_parts) if vox_parts else np.zeros(0, np.uint16)
@@ -199,9 +222,9 @@ def pack_block(b: BlockDef):
     d = np.zeros(1, BLOCK_DTYPE)
     d["resolution"], d["vlo"], d["vsize"] = b.resolution, b.vlo, b.voxels.shape
     d["pal_len"] = len(b.palette)
-    d["flags"] = (FLAG_ONE if b.is_one else 0) | (FLAG_AIR if b.is_air else 0)
+    d["flags"] = block_flags(b)
     d["name_char"] = ord(b.name[0]) if b.name else ord("#")
-    return d, np.ascontiguousarray(b.voxels, np.uint16).reshape(-1), np.ascontiguousarray(b.palette, np.float32)
+    return d, np.ascontiguousarray(b.voxels, np.uint16).reshape(-1), block_palette(b)
 
 
 def voxel_block(

@@ -359,10 +359,28 @@ Evoxels Evoxels::from_one(const Evoxel &v) {
     e.palette = {v};
     return e;
 }
-Evoxels Evoxels::air() {
-    Evoxels e = from_one(Evoxel{});
+Evoxels Evoxels::air() {  // Evoxel::AIR and AIR's attributes: neither is selectable
+    Evoxel v;
+    v.selectable = false;
+    Evoxels e = from_one(v);
     e.is_air = true;
+    e.selectable = false;
     return e;
+}
+static bool evoxel_invisible(const Evoxel &v) { return v.color[3] == 0.f && v.emission[0] == 0.f && v.emission[1] == 0.f && v.emission[2] == 0.f; }
+uint32_t Evoxels::abi_flags() const {
+    uint32_t flags = (is_one ? AIC_BLOCK_ONE : 0u) | (is_air ? AIC_BLOCK_AIR : 0u) | (!selectable && !is_air ? AIC_BLOCK_UNSELECTABLE : 0u);
+    for (const Evoxel &v : palette)
+        if (v.selectable == evoxel_invisible(v)) flags |= AIC_BLOCK_VOXEL_SELECTABLE;  // the default rule would take this voxel for the opposite
+    return flags;
+}
+void Evoxels::palette_floats(std::vector<float> *out) const {
+    const bool carried = (abi_flags() & AIC_BLOCK_VOXEL_SELECTABLE) != 0;
+    for (const Evoxel &v : palette) {
+        out->insert(out->end(), v.color, v.color + 4);
+        out->insert(out->end(), v.emission, v.emission + 3);
+        out->push_back(carried && v.selectable ? 1.f : 0.f);
+    }
 }
 
 // ---- Space ------------------------------------------------------------------------------------
@@ -489,13 +507,9 @@ void HipRtRenderer::upload_full(int layer, const Space &space) {  // SpaceRaytra
         bd.vox_off = (uint32_t)vox.size();
         bd.pal_off = (uint32_t)(pal.size() / 8);
         bd.pal_len = (uint32_t)e.palette.size();
-        bd.flags = (e.is_one ? AIC_BLOCK_ONE : 0) | (e.is_air ? AIC_BLOCK_AIR : 0);
+        bd.flags = e.abi_flags();
         vox.insert(vox.end(), e.indices.begin(), e.indices.end());
-        for (const Evoxel &v : e.palette) {
-            pal.insert(pal.end(), v.color, v.color + 4);
-            pal.insert(pal.end(), v.emission, v.emission + 3);
-            pal.push_back(0.f);
-        }
+        e.palette_floats(&pal);
     }
     d.n_blocks = (uint32_t)blocks.size();
     d.blocks = blocks.data();
@@ -556,13 +570,9 @@ bool HipRtRenderer::sync_space(int layer, const std::shared_ptr<Space> &space, c
             bd.resolution = e.resolution;
             for (int a = 0; a < 3; a++) { bd.vlo[a] = e.vlo[a]; bd.vsize[a] = e.vsize[a]; }
             bd.pal_len = (uint32_t)e.palette.size();
-            bd.flags = (e.is_one ? AIC_BLOCK_ONE : 0) | (e.is_air ? AIC_BLOCK_AIR : 0);
+            bd.flags = e.abi_flags();
             std::vector<float> pal;
-            for (const Evoxel &v : e.palette) {
-                pal.insert(pal.end(), v.color, v.color + 4);
-                pal.insert(pal.end(), v.emission, v.emission + 3);
-                pal.push_back(0.f);
-            }
+            e.palette_floats(&pal);
             check(aic_replace_block(ctx_, layer, bi, &bd, e.indices.data(), pal.data()), "aic_replace_block");
         }
         changed = true;
@@ -1166,6 +1176,50 @@ std::vector<float> HipRtRenderer::sample_luminance(int layer, const std::vector<
     std::vector<float> out(rays.size());
     check(aic_sample_luminance(ctx_, layer, (uint32_t)rays.size(), rays.empty() ? nullptr : &rays[0].origin.x, max_steps, 0u, out.data()), "aic_sample_luminance");
     return out;
+}
+
+// ---- the cursor ------------------------------------------------------------------------------------
+std::vector<std::optional<Cursor>> HipRtRenderer::cursor_raycast(int layer, const std::vector<Ray> &rays, double maximum_distance) {
+    static_assert(sizeof(Ray) == 6 * sizeof(double), "a Ray is the ABI's six doubles: origin, then direction");
+    if (rays.size() > (1u << 20)) throw RenderError(AIC_ERR_INVALID, "cursor_raycast: more than 1 << 20 rays in one call");
+    std::vector<aic_cursor_hit> hits(rays.size());
+    check(aic_cursor_raycast(ctx_, layer, (uint32_t)rays.size(), rays.empty() ? nullptr : &rays[0].origin.x, maximum_distance, 0u, hits.data()), "aic_cursor_raycast");
+    std::vector<std::optional<Cursor>> out(rays.size());
+    for (size_t i = 0; i < hits.size(); i++) {
+        const aic_cursor_hit &h = hits[i];
+        if (!h.hit) continue;
+        Cursor c;
+        for (int a = 0; a < 3; a++) {
+            c.cube[a] = h.cursor.cube[a]; c.point_entered[a] = h.cursor.point_entered[a];
+            c.voxel_lo[a] = h.cursor.voxel_lo[a]; c.voxel_size[a] = h.cursor.voxel_size[a]; c.voxel[a] = h.voxel[a];
+        }
+        c.face_entered = h.cursor.face_entered; c.face_selected = h.cursor.face_selected;
+        c.distance_to_point = h.cursor.distance_to_point;
+        c.resolution = h.cursor.resolution;
+        c.block_index = h.block_index;
+        c.light = PackedLight{h.light_hit[0], h.light_hit[1], h.light_hit[2], h.light_hit[3]};
+        if (h.has_preceding) {
+            c.preceding_cube = std::array<int32_t, 3>{h.preceding_cube[0], h.preceding_cube[1], h.preceding_cube[2]};
+            c.preceding_light = PackedLight{h.light_preceding[0], h.light_preceding[1], h.light_preceding[2], h.light_preceding[3]};
+        }
+        out[i] = c;
+    }
+    return out;
+}
+std::optional<Cursor> HipRtRenderer::cursor_raycast(int layer, const Ray &ray, double maximum_distance) {
+    return cursor_raycast(layer, std::vector<Ray>{ray}, maximum_distance)[0];
+}
+std::optional<Cursor> HipRtRenderer::project_cursor(double ndc_x, double ndc_y) {  // stdcam.rs:357-389
+    if (layers_[AIC_LAYER_UI].space) {
+        const Ray ray = ui_camera_.project_ndc_into_world(ndc_x, ndc_y);
+        if (std::optional<Cursor> c = cursor_raycast(AIC_LAYER_UI, ray, std::numeric_limits<double>::infinity())) return c;
+    }
+    if (layers_[AIC_LAYER_WORLD].space) {
+        const Ray ray = world_camera_.project_ndc_into_world(ndc_x, ndc_y);
+        // TODO: maximum distance should be determined by character/universe parameters instead of hardcoded
+        if (std::optional<Cursor> c = cursor_raycast(AIC_LAYER_WORLD, ray, 6.0)) return c;
+    }
+    return std::nullopt;
 }
 
 // ---- ExposureState ------------------------------------------------------------------------------

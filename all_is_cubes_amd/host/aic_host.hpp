@@ -26,6 +26,7 @@
 #include <functional>
 #include <limits>
 #include <memory>
+#include <optional>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -195,6 +196,7 @@ struct Sky {
 struct Evoxel {
     float color[4] = {0, 0, 0, 0};
     float emission[3] = {0, 0, 0};
+    bool selectable = true;  // Evoxel::selectable (Evoxel::AIR: false -- Evoxels::air())
 };
 struct Evoxels {
     int32_t resolution = 1;
@@ -203,9 +205,15 @@ struct Evoxels {
     std::vector<Evoxel> palette;
     bool is_one = true;
     bool is_air = false;
+    bool selectable = true;  // EvaluatedBlock::attributes().selectable (AIR: false)
     std::string display_name;  // BlockAttributes::display_name: its first character is what text renderings show (text.rs:27-38)
     static Evoxels from_one(const Evoxel &v);
     static Evoxels air();
+    // How the block goes to the device (aic_block_desc.flags, and each palette entry's eighth float through palette_floats): AIC_BLOCK_UNSELECTABLE for
+    // a block that is not selectable (AIR says so itself); AIC_BLOCK_VOXEL_SELECTABLE, the exact form, exactly when some voxel's `selectable` is not
+    // what the ABI's default rule would take it for (selectable iff not invisible) -- a block that needs neither is uploaded as it always was.
+    uint32_t abi_flags() const;
+    void palette_floats(std::vector<float> *out) const;  // appends [n][8]
 };
 
 // EveryLight is this mirror's coalesced form of a burst of CubeLight notifications: what a light-propagation
@@ -321,8 +329,8 @@ struct StandardCameras {  // stdcam.rs:90-180, reduced to values the caller sets
     float measured_exposure = 1.0f;
     UiViewState ui;
 };
-// Cursor (all-is-cubes/src/character/cursor.rs): what of it the renderer draws. The application makes it (cursor_raycast needs the `selectable`
-// attribute, which the scene handed to the device does not carry); wireframe() is impl Wireframe for Cursor (cursor.rs:219-278) through
+// Cursor (all-is-cubes/src/character/cursor.rs): what of it the renderer draws and what cursor_raycast reports of the two cubes.
+// HipRtRenderer::cursor_raycast / project_cursor make it on the device; wireframe() is impl Wireframe for Cursor (cursor.rs:219-278) through
 // aic_cursor_wireframe: 12, 16, 24 or 28 lines in palette::CURSOR_OUTLINE. update(cursor) takes the wireframe before it touches the scene, so a Cursor
 // that has none (a face outside 0..6, resolution < 1, a negative voxel_size) makes update throw std::invalid_argument with nothing changed.
 struct Cursor {
@@ -332,6 +340,13 @@ struct Cursor {
     double distance_to_point = 0.0;
     int32_t voxel_lo[3] = {0, 0, 0}, voxel_size[3] = {1, 1, 1};  // the hit block's EvaluatedBlock::voxels_bounds()
     int32_t resolution = 1;
+    // Cursor::hit(): the block index of the cube (the application has the table), the selectable voxel found in block coordinates, the cube's light
+    uint32_t block_index = 0;
+    int32_t voxel[3] = {0, 0, 0};
+    PackedLight light = {0, 0, 0, 0};
+    // Cursor::preceding: the cube the ray was in before, unless it started in the hit cube (face_entered Within), and Space::get_light there
+    std::optional<std::array<int32_t, 3>> preceding_cube;
+    std::optional<PackedLight> preceding_light;
     std::vector<aic_line_vertex> wireframe() const;
 };
 
@@ -497,6 +512,7 @@ class HipRtRenderer : public HeadlessRenderer {
     SplitExport export_split(const void *src_device, uint32_t out_width = 0, uint32_t out_height = 0);
     // the world camera of the last update(): what to keep beside a resident frame as its `traced_with`
     const Camera &world_camera() const { return world_camera_; }
+    const Camera &ui_camera() const { return ui_camera_; }
     // multi-GPU extension: render the rows of one partition into a device buffer (no read-back)
     ImageInfo draw_rows_to_device(void *device_out, uint32_t strip_rows, uint32_t n_parts, uint32_t part, bool counters = false,
                                   bool no_feedback = false);
@@ -534,6 +550,13 @@ class HipRtRenderer : public HeadlessRenderer {
     // layer's space as last updated, light included wherever it was made: per ray the luminance of the light behind the first visible block that has
     // a valid one, or of the sky. max_steps: 2 * maximum_distance, 0 for LightPhysics::None. Legal with frames in flight (submit_rows_to_device).
     std::vector<float> sample_luminance(int layer, const std::vector<Ray> &rays, uint32_t max_steps);
+    // cursor_raycast (all-is-cubes/src/character/cursor.rs:26-107; aic_cursor_raycast) against one layer's space as last updated: the first selectable
+    // block the ray strikes within maximum_distance (infinity is legal), or nothing. Legal with frames in flight. The batch form is one launch.
+    std::optional<Cursor> cursor_raycast(int layer, const Ray &ray, double maximum_distance);
+    std::vector<std::optional<Cursor>> cursor_raycast(int layer, const std::vector<Ray> &rays, double maximum_distance);
+    // StandardCameras::project_cursor (all-is-cubes-render/src/camera/stdcam.rs:357-389) through the cameras of the last update(): the UI space, if
+    // there is one, at any distance; else, or if nothing is struck there, the world at 6.0. The result goes straight into update(cursor).
+    std::optional<Cursor> project_cursor(double ndc_x, double ndc_y);
     // true: the WORLD space's light lives on the device (evaluate_light): update() forwards block changes only, never the
     // host Space's light texels, and queues the changed cubes for relighting (aic_light_cubes_changed)
     bool device_light = false;

@@ -149,17 +149,21 @@ PYBIND11_MODULE(_host, m) {
         });
 
     py::class_<Evoxels>(m, "Evoxels")
-        .def_static("from_one", [](const std::array<float, 4> &rgba, const std::array<float, 3> &em) {
+        // voxel_selectable: Evoxel::selectable; None: what the ABI's default rule says of the voxel (selectable iff not invisible), so that a block made
+        // without it is uploaded as it always was
+        .def_static("from_one", [](const std::array<float, 4> &rgba, const std::array<float, 3> &em, std::optional<bool> voxel_selectable) {
             Evoxel v;
             for (int i = 0; i < 4; i++) v.color[i] = rgba[i];
             for (int i = 0; i < 3; i++) v.emission[i] = em[i];
+            v.selectable = voxel_selectable ? *voxel_selectable : !(rgba[3] == 0.f && em[0] == 0.f && em[1] == 0.f && em[2] == 0.f);
             return Evoxels::from_one(v);
-        }, py::arg("rgba"), py::arg("emission") = std::array<float, 3>{0, 0, 0})
+        }, py::arg("rgba"), py::arg("emission") = std::array<float, 3>{0, 0, 0}, py::arg("voxel_selectable") = py::none())
         .def_static("air", &Evoxels::air)
         .def_static("paletted", [](int resolution, const std::array<int32_t, 3> &vlo, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> idx,
-                                   py::array_t<float, py::array::c_style | py::array::forcecast> pal) {
+                                   py::array_t<float, py::array::c_style | py::array::forcecast> pal, std::optional<std::vector<bool>> voxel_selectable) {
             if (idx.ndim() != 3) throw std::invalid_argument("indices must be 3-D");
             if (pal.ndim() != 2 || pal.shape(1) != 8) throw std::invalid_argument("palette must be [n][8]");
+            if (voxel_selectable && voxel_selectable->size() != (size_t)pal.shape(0)) throw std::invalid_argument("voxel_selectable needs one entry per palette entry");
             Evoxels e;
             e.resolution = resolution;
             e.is_one = false;
@@ -170,8 +174,17 @@ PYBIND11_MODULE(_host, m) {
                 const float *p = pal.data() + 8 * i;
                 std::memcpy(e.palette[i].color, p, 16);
                 std::memcpy(e.palette[i].emission, p + 4, 12);
+                e.palette[i].selectable = voxel_selectable ? (bool)(*voxel_selectable)[i] : !(p[3] == 0.f && p[4] == 0.f && p[5] == 0.f && p[6] == 0.f);
             }
             return e;
+        }, py::arg("resolution"), py::arg("vlo"), py::arg("indices"), py::arg("palette"), py::arg("voxel_selectable") = py::none())
+        .def_readwrite("selectable", &Evoxels::selectable).def("abi_flags", &Evoxels::abi_flags)
+        .def("palette_floats", [](const Evoxels &e) {
+            std::vector<float> v;
+            e.palette_floats(&v);
+            py::array_t<float> a({(py::ssize_t)(v.size() / 8), (py::ssize_t)8});
+            if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * 4);
+            return a;
         })
         .def_readwrite("resolution", &Evoxels::resolution).def_readwrite("is_air", &Evoxels::is_air).def_readwrite("is_one", &Evoxels::is_one)
         .def_readwrite("display_name", &Evoxels::display_name);
@@ -259,6 +272,19 @@ PYBIND11_MODULE(_host, m) {
         .def_property("voxel_size", [](const Cursor &c) { return std::array<int32_t, 3>{c.voxel_size[0], c.voxel_size[1], c.voxel_size[2]}; },
                       [](Cursor &c, std::array<int32_t, 3> v) { std::copy(v.begin(), v.end(), c.voxel_size); })
         .def_readwrite("resolution", &Cursor::resolution)
+        .def_readwrite("block_index", &Cursor::block_index)
+        .def_property("voxel", [](const Cursor &c) { return std::array<int32_t, 3>{c.voxel[0], c.voxel[1], c.voxel[2]}; },
+                      [](Cursor &c, std::array<int32_t, 3> v) { std::copy(v.begin(), v.end(), c.voxel); })
+        .def_property("light", [](const Cursor &c) { return std::array<uint8_t, 4>{c.light.r, c.light.g, c.light.b, c.light.status}; },
+                      [](Cursor &c, std::array<uint8_t, 4> v) { c.light = PackedLight{v[0], v[1], v[2], v[3]}; })
+        .def_readwrite("preceding_cube", &Cursor::preceding_cube)
+        .def_property("preceding_light", [](const Cursor &c) -> std::optional<std::array<uint8_t, 4>> {
+                          if (!c.preceding_light) return std::nullopt;
+                          return std::array<uint8_t, 4>{c.preceding_light->r, c.preceding_light->g, c.preceding_light->b, c.preceding_light->status};
+                      },
+                      [](Cursor &c, std::optional<std::array<uint8_t, 4>> v) {
+                          if (v) c.preceding_light = PackedLight{(*v)[0], (*v)[1], (*v)[2], (*v)[3]}; else c.preceding_light.reset();
+                      })
         .def("wireframe", [](const Cursor &c) {  // [2 n, 7] f32: position, linear RGBA
             const std::vector<aic_line_vertex> v = c.wireframe();
             py::array_t<float> a({(py::ssize_t)v.size(), (py::ssize_t)7});
@@ -308,6 +334,21 @@ PYBIND11_MODULE(_host, m) {
             d["colorbuf"] = colors; d["hits"] = hits; d["info"] = res.info;
             return d;
         }, py::arg("layer"), py::arg("rays"), py::arg("include_sky") = true)
+        .def("cursor_raycast", [](HipRtRenderer &r, int layer, py::array_t<double, py::array::c_style | py::array::forcecast> rays, double maximum_distance) -> py::object {
+            // rays [6] -> a Cursor or None; rays [n, 6] -> a list of them (one launch)
+            if (!((rays.ndim() == 1 && rays.shape(0) == 6) || (rays.ndim() == 2 && rays.shape(1) == 6))) throw std::invalid_argument("rays must be [6] or [n][6]: origin xyz, direction xyz");
+            std::vector<Ray> v((size_t)(rays.size() / 6));
+            if (!v.empty()) std::memcpy((void *)v.data(), rays.data(), v.size() * sizeof(Ray));
+            std::vector<std::optional<Cursor>> res;
+            { py::gil_scoped_release rel; res = r.cursor_raycast(layer, v, maximum_distance); }
+            if (rays.ndim() == 1) return py::cast(res[0]);
+            return py::cast(res);
+        }, py::arg("layer"), py::arg("rays"), py::arg("maximum_distance"))
+        .def("project_cursor", [](HipRtRenderer &r, double ndc_x, double ndc_y) {
+            std::optional<Cursor> c;
+            { py::gil_scoped_release rel; c = r.project_cursor(ndc_x, ndc_y); }
+            return c;
+        }, py::arg("ndc_x"), py::arg("ndc_y"))
         .def("sample_luminance", [](HipRtRenderer &r, int layer, py::array_t<double, py::array::c_style | py::array::forcecast> rays, uint32_t max_steps) {
             // rays [n, 6] = origin xyz, direction xyz -> [n] f32
             if (rays.size() % 6 != 0) throw std::invalid_argument("rays: [n, 6] doubles");
@@ -490,6 +531,7 @@ PYBIND11_MODULE(_host, m) {
         }, py::arg("src_ptr"), py::arg("out_width"), py::arg("out_height"), py::arg("info_text"), py::arg("with_lines") = false, py::arg("lines") = py::none(),
            py::arg("flags") = 0u, py::arg("out_ptr") = (uintptr_t)0)
         .def("world_camera", [](const HipRtRenderer &r) { return Camera(r.world_camera()); })
+        .def("ui_camera", [](const HipRtRenderer &r) { return Camera(r.ui_camera()); })
         .def("set_world_camera_override", [](HipRtRenderer &r, py::object inv, float exposure) {
             if (inv.is_none()) { r.set_world_camera_override(nullptr, 1.0f); return; }
             const auto m = inv.cast<std::array<double, 16>>();

@@ -155,11 +155,14 @@ def _block_from_desc(desc, voxels: np.ndarray, palette: np.ndarray) -> flat.Bloc
     air = bool(int(desc["flags"]) & flat.FLAG_AIR)
     pal = np.ascontiguousarray(palette, np.float32).reshape(-1, 8)
     name = chr(int(desc["name_char"])) if 32 <= int(desc["name_char"]) < 127 else "#"
+    selectable = not int(desc["flags"]) & flat.FLAG_UNSELECTABLE
+    carries = bool(int(desc["flags"]) & flat.FLAG_VOXEL_SELECTABLE)  # the recorded palette's eighth floats are Evoxel::selectable
     if one:
-        return flat.BlockDef(1, (0, 0, 0), np.zeros((1, 1, 1), np.uint16), pal[:1].copy(), is_one=True, is_air=air, name=name)
+        return flat.BlockDef(1, (0, 0, 0), np.zeros((1, 1, 1), np.uint16), pal[:1].copy(), is_one=True, is_air=air, name=name, selectable=selectable,
+                             voxel_selectable=pal[:1, 7] != 0 if carries else None)
     vs = tuple(int(v) for v in desc["vsize"])
     return flat.BlockDef(int(desc["resolution"]), tuple(int(v) for v in desc["vlo"]), np.ascontiguousarray(voxels, np.uint16).reshape(vs),
-                         pal.copy(), is_air=air, name=name)
+                         pal.copy(), is_air=air, name=name, selectable=selectable, voxel_selectable=pal[:, 7] != 0 if carries else None)
 
 
 def space_from_upload(data) -> flat.FlatSpace:

@@ -50,6 +50,15 @@ extern "C" {
 /* block descriptor flags */
 #define AIC_BLOCK_ONE 1u  /* EvoxelsInner::One(voxel): resolution 1, palette[pal_off] is the voxel */
 #define AIC_BLOCK_AIR 2u  /* block == AIR (TracingCubeData.always_invisible, sr.rs:543-564) */
+/* What aic_cursor_raycast needs of a block beyond its picture (no trace, light or exposure kernel reads either; a caller that sets neither bit uploads
+ * what it always did):
+ * AIC_BLOCK_UNSELECTABLE: EvaluatedBlock::attributes().selectable == false. A block with AIC_BLOCK_AIR is unselectable with or without this bit.
+ * AIC_BLOCK_VOXEL_SELECTABLE: the eighth float of each of this block's palette entries is Evoxel::selectable, exactly 1.0f (selectable) or +0.0f (not);
+ * any other pattern is rejected with AIC_ERR_INVALID by aic_upload_space / aic_replace_block(s). This is the EXACT form. Without the bit the eighth float
+ * stays an ignored pad and a voxel counts as selectable iff it is not invisible (alpha != 0 or emission != 0): an APPROXIMATION whose one sure case is
+ * the commonest unselectable voxel, Evoxel::AIR -- an invisible voxel that is selectable, or a visible one that is not, needs the bit. */
+#define AIC_BLOCK_UNSELECTABLE 4u
+#define AIC_BLOCK_VOXEL_SELECTABLE 8u
 
 /* One Space block-palette entry = `TracingBlock.voxels: Evoxels`
  * (sr.rs:568-587; all-is-cubes/src/block/eval/voxel_storage.rs:199-227). 48 bytes. */
@@ -74,7 +83,8 @@ typedef struct aic_space_desc {
     const aic_block_desc *blocks;
     const uint16_t *voxels;      /* pool of palette indices, Z-major per block */
     uint64_t n_voxels;
-    const float *palette;        /* pool [n_palette][8]: Evoxel color rgba, emission rgb, pad. Every component must be what the
+    const float *palette;        /* pool [n_palette][8]: Evoxel color rgba, emission rgb, pad (Evoxel::selectable for the entries of a block flagged
+                                  * AIC_BLOCK_VOXEL_SELECTABLE). Every component of colour and emission must be what the
                                   * reference's Rgba / Rgb can hold (PositiveSign<f32> x 3 + ZeroOne<f32>, math/color.rs:288-314): not NaN,
                                   * not negative, alpha <= 1 -- anything else is rejected with AIC_ERR_INVALID by aic_upload_space /
                                   * aic_replace_block(s) (since round 3; the kernel's compositing and its table powf rely on it). A block
@@ -604,8 +614,8 @@ int aic_present_lines_scratch(uint32_t src_w, uint32_t src_h, uint32_t out_w, ui
  * the hit block's voxel bounds (scaled by 1 / resolution, translated to the cube, expanded by 0.001 * distance_to_point) in Aab::wireframe_points' order
  * (all-is-cubes-base/src/math/aab.rs:569-588); if face_selected is a real face, the 12 edges of that box shrunk by 1/128 and flattened onto the face;
  * if face_entered is a real face, the 4-line diamond with tips at 1/32 around point_entered + face * offset. 12, 16, 24 or 28 lines; positions as f32,
- * colour palette::CURSOR_OUTLINE = linear (0, 0, 0, 1). Making the Cursor (cursor_raycast) stays the application's: it needs the `selectable`
- * attribute, which the scene of this ABI does not carry. AIC_ERR_INVALID: a NULL pointer, a face outside 0..6, resolution < 1, a negative voxel_size. */
+ * colour palette::CURSOR_OUTLINE = linear (0, 0, 0, 1). aic_cursor_raycast (below) makes the Cursor: its record begins with this struct.
+ * AIC_ERR_INVALID: a NULL pointer, a face outside 0..6, resolution < 1, a negative voxel_size. */
 typedef struct aic_cursor_desc {
     int32_t cube[3];
     int32_t face_entered, face_selected;   /* Face7 discriminants, as aic_pixel_aux.face */
@@ -617,6 +627,47 @@ typedef struct aic_cursor_desc {
 } aic_cursor_desc;
 #define AIC_CURSOR_MAX_LINES 28u
 int aic_cursor_wireframe(const aic_cursor_desc *cursor, aic_line_vertex *out /* [2 * 28] */, uint32_t *n_lines);
+/* replaces: cursor_raycast (all-is-cubes/src/character/cursor.rs:26-107) for n rays against the layer's space as last updated; DESIGN.md 4.18,
+ * tests/cursor_ref.py is this text in Python. Ray i = {origin, direction}; the direction is normalised first, d / sqrt(dx * dx + dy * dy + dz * dz) in
+ * f64 with one rounding per operation. Then, for each step of Raycaster(origin, d).within(space bounds, false): a step whose t_distance is greater
+ * than maximum_distance ends the ray with no Cursor; a block that is unselectable (AIC_BLOCK_UNSELECTABLE, AIC_BLOCK_AIR) is passed over; a
+ * single-voxel block (AIC_BLOCK_ONE or resolution 1) is hit if its voxel is selectable, with face_selected = the step's face; in any other block the
+ * sub-ray of RaycastStep::recursive_raycast (raycast.rs:458-476: origin (origin - cube) * resolution, the same direction, within the block's voxel
+ * bounds with the exit step) is walked: face_selected is the face of its first step, whatever lies there (Within for a ray that starts inside the voxel
+ * bounds), and the first selectable voxel is the hit; a block without one, or one whose voxel bounds the sub-ray misses, is passed over. Voxel
+ * selectability: see AIC_BLOCK_VOXEL_SELECTABLE. A ray takes at most size_x + size_y + size_z + 3 steps, which no ray within the bounds exceeds.
+ * One record per ray, 144 bytes. A miss (the reference's None) is all zero. A hit has hit = 1 and
+ *   cursor: cube, face_entered = the step's face, face_selected, point_entered = step.intersection_point(ray), distance_to_point = t_distance if it is
+ *       greater than 0, else 0 (PositiveSign::new_clamped), and the hit block's voxel bounds and resolution (0,0,0 / 1,1,1 / 1 for a single-voxel block):
+ *       aic_cursor_wireframe takes it as it stands;
+ *   block_index of the hit cube; voxel = the selectable voxel found, in block coordinates (0,0,0 for a single-voxel block);
+ *   has_preceding = face_entered is not Within, and then preceding_cube = cube + the face's normal with preceding_block_index = its block index, or
+ *       0xFFFFFFFF for a cube outside the bounds, where the reference reads AIR;
+ *   light_hit, light_preceding: Space::get_light of the two cubes as texels r, g, b, status from the layer's current light volume; for a cube outside
+ *       the bounds BlockSky::light_outside (sky.rs:113-147);
+ *   steps: the steps of the outer Raycaster examined, the hit's included.
+ * Zero, NaN and infinite components are legal and give what the reference's arithmetic gives up to where it would panic: no hit has a NaN distance.
+ * flags: AIC_RAYS_DEVICE or 0 -- `rays` and `out` are device pointers at 8-byte boundaries, nothing is staged or read back. The call returns when the
+ * records are there. Like aic_sample_luminance it is legal while frames are in flight and disturbs none of them, finishes a pending
+ * aic_evaluate_light_submit first and sees every scene and light write issued before it. AIC_ERR_INVALID, the context still usable: a NULL pointer with
+ * n > 0, a layer without a space, n above 1 << 20, unknown flag bits, a NaN or negative maximum_distance (+infinity is legal), misaligned device
+ * pointers. n == 0 is AIC_OK. An aic_multi replicates the scene: a host of one raycasts through the context of its first device. */
+typedef struct aic_cursor_hit {
+    aic_cursor_desc cursor;
+    int32_t hit;
+    uint32_t block_index;
+    int32_t voxel[3];
+    int32_t has_preceding;
+    int32_t preceding_cube[3];
+    uint32_t preceding_block_index;
+    uint8_t light_hit[4];
+    uint8_t light_preceding[4];
+    uint32_t steps;
+    uint32_t reserved_hit;
+} aic_cursor_hit;
+#define AIC_CURSOR_NO_BLOCK 0xFFFFFFFFu /* preceding_block_index of a cube outside the bounds */
+int aic_cursor_raycast(aic_ctx *ctx, int layer, uint32_t n, const double *rays /* [n][6] origin, direction */, double maximum_distance,
+                       uint32_t flags /* 0 or AIC_RAYS_DEVICE */, aic_cursor_hit *out /* [n] */);
 /* The info text -- the frame-rate and statistics overlay, on by default (GraphicsOptions::debug_info_text) -- of the interactive renderer, which is
  * part of its presentation's last shader: four entry points, DESIGN.md 4.14, tests/present_text_ref.py is that text in NumPy.
  *

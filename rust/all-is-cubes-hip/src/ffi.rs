@@ -15,6 +15,8 @@ pub const AIC_LAYER_WORLD: c_int = 0;
 pub const AIC_LAYER_UI: c_int = 1;
 pub const AIC_BLOCK_ONE: u32 = 1;
 pub const AIC_BLOCK_AIR: u32 = 2;
+pub const AIC_BLOCK_UNSELECTABLE: u32 = 4;
+pub const AIC_BLOCK_VOXEL_SELECTABLE: u32 = 8;
 pub const AIC_FLAW_UNSUPPORTED: u32 = 1;
 pub const AIC_FLAW_NO_BLOOM: u32 = 2;
 pub const AIC_FRAME_COUNTERS: u32 = 1;
@@ -39,6 +41,7 @@ pub const AIC_LINES_MAX: u32 = 1048576;
 pub const AIC_STALE_DEPTH_TEST: u32 = 1;
 pub const AIC_STALE_MAX_RECTS: u32 = 4096;
 pub const AIC_CURSOR_MAX_LINES: u32 = 28;
+pub const AIC_CURSOR_NO_BLOCK: u32 = 0xFFFF_FFFF;
 pub const AIC_EXPOSURE_SAMPLES: u32 = 100;
 pub const AIC_EXPOSURE_RAYS: u32 = 10;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
@@ -333,6 +336,23 @@ pub struct aic_cursor_desc {
     pub reserved: i32,
 }
 
+/// One record of `aic_cursor_raycast`: 144 bytes, all zero for the reference's `None`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_cursor_hit {
+    pub cursor: aic_cursor_desc,
+    pub hit: i32,
+    pub block_index: u32,
+    pub voxel: [i32; 3],
+    pub has_preceding: i32,
+    pub preceding_cube: [i32; 3],
+    pub preceding_block_index: u32,
+    pub light_hit: [u8; 4],
+    pub light_preceding: [u8; 4],
+    pub steps: u32,
+    pub reserved_hit: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct aic_pixel_aux {
@@ -444,6 +464,7 @@ unsafe extern "C" {
     pub fn aic_present_split_lines(ctx: *mut aic_ctx, desc: *const aic_present_desc, lines: *const aic_lines_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info, lines_info: *mut aic_lines_info) -> c_int;
     pub fn aic_present_lines_scratch(src_w: u32, src_h: u32, out_w: u32, out_h: u32, n_lines: u32, bytes: *mut u64) -> c_int;
     pub fn aic_cursor_wireframe(cursor: *const aic_cursor_desc, out: *mut aic_line_vertex, n_lines: *mut u32) -> c_int;
+    pub fn aic_cursor_raycast(ctx: *mut aic_ctx, layer: c_int, n: u32, rays: *const f64, maximum_distance: f64, flags: u32, out: *mut aic_cursor_hit) -> c_int;
     pub fn aic_set_text_font(ctx: *mut aic_ctx, atlas_rgba8: *const u8, cell_width: u32, cell_height: u32, cell_margin: u32) -> c_int;
     pub fn aic_text_geometry(nominal_width: f64, nominal_height: f64, cell_width: u32, cell_height: u32, cell_margin: u32, origin_px: *const f64, cols: *mut u32, rows: *mut u32, scale: *mut f32, origin: *mut f32) -> c_int;
     pub fn aic_text_layout(utf8: *const c_char, len: u64, cols: u32, rows: u32, codes: *mut u8, used: *mut u32) -> c_int;

@@ -39,7 +39,8 @@ fn push_evoxel(out: &mut Vec<f32>, v: &Evoxel) {
         v.emission.red().into_inner(),
         v.emission.green().into_inner(),
         v.emission.blue().into_inner(),
-        0.0,
+        // Evoxel::selectable, exactly (every block is flagged AIC_BLOCK_VOXEL_SELECTABLE): what aic_cursor_raycast reads
+        if v.selectable { 1.0 } else { 0.0 },
     ]);
 }
 
@@ -47,7 +48,10 @@ fn push_evoxel(out: &mut Vec<f32>, v: &Evoxel) {
 pub(crate) fn flatten_block(sbd: &SpaceBlockData) -> FlatBlock {
     let voxels: &Evoxels = sbd.evaluated().voxels();
     let is_air = sbd.block() == &AIR; // TracingCubeData.always_invisible (sr.rs:547)
-    let mut flags = if is_air { ffi::AIC_BLOCK_AIR } else { 0 };
+    let mut flags = if is_air { ffi::AIC_BLOCK_AIR } else { 0 } | ffi::AIC_BLOCK_VOXEL_SELECTABLE;
+    if !sbd.evaluated().attributes().selectable {
+        flags |= ffi::AIC_BLOCK_UNSELECTABLE; // cursor.rs:43
+    }
     if let Some(single) = voxels.single_voxel().filter(|_| voxels.resolution() == all_is_cubes::block::Resolution::R1) {
         // Evoxels::One, or a resolution-1 volume (voxel_storage.rs:364-385)
         flags |= ffi::AIC_BLOCK_ONE;

@@ -688,6 +688,48 @@ impl HipRtRenderer {
         Ok(out)
     }
 
+    /// `cursor_raycast` (all-is-cubes/src/character/cursor.rs:26-107) for a batch of rays against the space of `layer` as last uploaded by `update`,
+    /// on the device: per ray the first selectable block struck within `maximum_distance` (infinity is legal), or `None`. The record is what a
+    /// `Cursor` holds that the device knows -- `Cursor`'s own fields are private to its crate and its `hit().block` / `evaluated` are objects of the
+    /// application's, found through `block_index` -- and its `cursor` member is what [`cursor_wireframe`] takes. Legal while frames are in flight.
+    /// A multi-device renderer raycasts on its first device: the scene is replicated.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a layer without a space, a NaN or negative `maximum_distance`, or more than `1 << 20` rays.
+    pub fn cursor_raycast(&mut self, layer: core::ffi::c_int, rays: &[[f64; 6]], maximum_distance: f64) -> Result<Vec<Option<ffi::aic_cursor_hit>>, RenderError> {
+        let n = u32::try_from(rays.len()).expect("more than u32::MAX rays");
+        let mut out = vec![ffi::aic_cursor_hit::default(); rays.len()];
+        // SAFETY: the context is live; both buffers hold `n` elements and outlive the call, which returns when the records are there
+        self.device.check(unsafe { ffi::aic_cursor_raycast(self.device.first_ctx(), layer, n, rays.as_ptr().cast(), maximum_distance, 0, out.as_mut_ptr()) })?;
+        Ok(out.into_iter().map(|h| (h.hit != 0).then_some(h)).collect())
+    }
+
+    /// `StandardCameras::project_cursor` (all-is-cubes-render/src/camera/stdcam.rs:357-389) through the cameras of the last `update`: the UI space,
+    /// if there is one, at any distance; else, or if nothing is struck there, the character's space at 6.0.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    pub fn project_cursor(&mut self, ndc_pos: all_is_cubes_render::camera::NdcPoint2) -> Result<Option<ffi::aic_cursor_hit>, RenderError> {
+        let ray_of = |ray: all_is_cubes::raycast::Ray| [ray.origin.x, ray.origin.y, ray.origin.z, ray.direction.x, ray.direction.y, ray.direction.z];
+        if self.cameras.ui_space().is_some() {
+            let ray = ray_of(self.cameras.cameras().ui.project_ndc_into_world(ndc_pos));
+            if let Some(hit) = self.cursor_raycast(ffi::AIC_LAYER_UI, &[ray], f64::INFINITY)?.pop().flatten() {
+                return Ok(Some(hit));
+            }
+        }
+        if self.cameras.character().is_some() && self.cameras.world_space().get().is_some() {
+            let ray = ray_of(self.cameras.cameras().world.project_ndc_into_world(ndc_pos));
+            // TODO: maximum distance should be determined by character/universe parameters instead of hardcoded
+            if let Some(hit) = self.cursor_raycast(ffi::AIC_LAYER_WORLD, &[ray], 6.0)?.pop().flatten() {
+                return Ok(Some(hit));
+            }
+        }
+        Ok(None)
+    }
+
     /// One round of `raytrace_to_texture`'s `do_some_tracing` (raytrace_to_texture.rs:591-751): the listed pixels (`y * width + x`) of the frame
     /// `draw_split` renders, each traced exactly as there (`RtScene::trace_patch` on the pixel's own rectangle). Returns the two texels per pixel in list
     /// order -- the f16 colour bits and the signed depth -- for the caller to write at those pixels of its resident textures. A pixel may be listed more

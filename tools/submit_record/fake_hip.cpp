@@ -1,5 +1,5 @@
 // fake_hip.cpp -- a recording stand-in for the HIP runtime calls and kernel launchers the host side of the C ABI (aic_abi.cpp, aic_frame.cpp,
-// aic_split_ops.cpp) uses.
+// aic_split_ops.cpp, aic_cursor_raycast_host.cpp) uses.
 // Nothing of the real runtime is loaded: device memory is host memory, streams and events are ordinals, a launch is a line of text. Every call is logged
 // with its sizes; streams and events by creation ordinal, every device pointer as allocation ordinal + offset, so that two builds of the host code driven
 // through the same scenarios (driver.cpp, split_ops_record.cpp) give byte-identical records exactly when they make the same calls in the same order.
@@ -13,6 +13,7 @@
 #include <string>
 
 #include "aic_bloom.h"
+#include "aic_cursor_raycast.h"
 #include "aic_device.h"
 #include "aic_launch.h"
 #include "aic_pick.h"
@@ -288,6 +289,14 @@ hipError_t launch_export(const ExportParams &p, hipStream_t stream) {
         P(p.srgb_thr), P(p.counts), S(stream));
     rec_words("  ipzw", p.ipzw, 4);
     return failing("launch_export") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_cursor_raycast(const CursorRaycastParams &p, hipStream_t stream) {
+    rec("launch_cursor_raycast groups %u n %u rays %s out %s maximum_distance %a index_mask %u %s", cursor_raycast_groups(p.n), p.n, P(p.rays), P(p.out), p.maximum_distance, p.index_mask,
+        S(stream));
+    rec("  pool %s light %s blocks %s palette %s", P(p.pool), P(p.light), P(p.blocks), P(p.palette));
+    rec_words("  lo size", p.lo, 6);
+    rec_words("  block_sky", p.block_sky, 7);
+    return failing("launch_cursor_raycast") ? hipErrorInvalidValue : hipSuccess;
 }
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
