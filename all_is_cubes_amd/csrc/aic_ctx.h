@@ -1,8 +1,8 @@
 // aic_ctx.h -- what the translation units of the C ABI's host side share: the context behind the opaque `aic_ctx` of
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
-// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater),
-// aic_exposure_host.cpp (the luminance sampler's call), aic_stale_host.cpp (the stale-pixel picker's) and aic_cursor_raycast_host.cpp (the cursor raycast's) only (all seven are written inside `using namespace aic`, and so is this header). Whatever one of the
+// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater) and
+// aic_ray_queries.cpp (the luminance sampler's call and the cursor raycast's) only (all five are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
 #pragma once
@@ -238,6 +238,8 @@ namespace aic {
 extern thread_local std::string *tl_err_sink;
 int fail(aic_ctx *c, int code, const char *what, hipError_t e = hipSuccess);
 int hip_fail(aic_ctx *c, const char *what, hipError_t e);
+// an AIC_ERR_INVALID refusal under the entry point's name: "<who>: <why>"
+inline int reject(aic_ctx *c, const char *who, const char *why) { return fail(c, AIC_ERR_INVALID, (std::string(who) + ": " + why).c_str()); }
 #define HIP_TRY(ctx, expr)                                    \
     do {                                                      \
         hipError_t e_ = (expr);                               \

@@ -22,16 +22,13 @@
 #include <stdint.h>
 
 #include "aic_cursor_raycast.h"
-#include "aic_lightmath.h"
-#include "aic_raycast.h"
+#include "aic_ray_query.h"
 
 namespace aic {
 
 __global__ void __launch_bounds__(64) cursor_raycast_kernel(const CursorRaycastParams p) {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    // (the lanes past the end walk the last ray again and store nothing: the Raycaster's set-up asks the whole wave questions)
-    const uint32_t k = i < p.n ? i : p.n - 1u;
-    const double *ray = p.rays + 6u * (size_t)k;
+    const double *ray = query_ray(p.rays, p.n, i);
     const double ox = ray[0], oy = ray[1], oz = ray[2];
     // Vector3D::normalize: self / self.length(), length = sqrt(x * x + y * y + z * z)
     const double len = sqrt(ray[3] * ray[3] + ray[4] * ray[4] + ray[5] * ray[5]);
@@ -40,12 +37,7 @@ __global__ void __launch_bounds__(64) cursor_raycast_kernel(const CursorRaycastP
     const int lox = p.lo[0], loy = p.lo[1], loz = p.lo[2];
     const uint32_t sx = (uint32_t)p.size[0], sy = (uint32_t)p.size[1], sz = (uint32_t)p.size[2];
     const int hix = lox + (int)sx, hiy = loy + (int)sy, hiz = loz + (int)sz;  // (fits: aic_upload_space checks lo + size)
-    LightGridView G;
-    G.light = p.light;
-    G.lo_x = lox; G.lo_y = loy; G.lo_z = loz;
-    G.size_x = (int)sx; G.size_y = (int)sy; G.size_z = (int)sz;
-    G.sky_nx = p.block_sky[0]; G.sky_ny = p.block_sky[1]; G.sky_nz = p.block_sky[2];
-    G.sky_px = p.block_sky[3]; G.sky_py = p.block_sky[4]; G.sky_pz = p.block_sky[5]; G.sky_mean = p.block_sky[6];
+    const LightGridView G = query_light_grid(p);
 
     aic_cursor_hit rec = {};  // None: all zero
 
@@ -115,20 +107,11 @@ __global__ void __launch_bounds__(64) cursor_raycast_kernel(const CursorRaycastP
         const uint32_t th = p.light[cube_index];
         rec.light_hit[0] = (uint8_t)th; rec.light_hit[1] = (uint8_t)(th >> 8); rec.light_hit[2] = (uint8_t)(th >> 16); rec.light_hit[3] = (uint8_t)(th >> 24);
         if (face != FACE_WITHIN) {
-            // cube_behind = cube_ahead + the normal of the face crossed; faces NX NY NZ PX PY PZ = 1..6
-            const int sign = face > 3 ? 1 : -1;
-            const int face_axis = face > 3 ? face - 4 : face - 1;
-            const int bx = (int)((uint32_t)s.cx + (uint32_t)(face_axis == 0 ? sign : 0));
-            const int by = (int)((uint32_t)s.cy + (uint32_t)(face_axis == 1 ? sign : 0));
-            const int bz = (int)((uint32_t)s.cz + (uint32_t)(face_axis == 2 ? sign : 0));
-            const uint32_t ex = (uint32_t)bx - (uint32_t)lox, ey = (uint32_t)by - (uint32_t)loy, ez = (uint32_t)bz - (uint32_t)loz;
-            const bool inside = (ex < sx) & (ey < sy) & (ez < sz);
-            const size_t behind_index = inside ? ((size_t)ex * sy + ey) * sz + ez : 0u;
-            uint32_t tp = p.light[behind_index];
-            if (!inside) tp = lm_light_outside(G, bx, by, bz);
+            const CubeBehind b = cube_behind(s, G);
+            const uint32_t tp = b.texel;
             rec.has_preceding = 1;
-            rec.preceding_cube[0] = bx; rec.preceding_cube[1] = by; rec.preceding_cube[2] = bz;
-            rec.preceding_block_index = inside ? ((uint32_t)p.pool[behind_index] & p.index_mask) : AIC_CURSOR_NO_BLOCK;
+            rec.preceding_cube[0] = b.x; rec.preceding_cube[1] = b.y; rec.preceding_cube[2] = b.z;
+            rec.preceding_block_index = b.inside ? ((uint32_t)p.pool[b.index] & p.index_mask) : AIC_CURSOR_NO_BLOCK;
             rec.light_preceding[0] = (uint8_t)tp; rec.light_preceding[1] = (uint8_t)(tp >> 8); rec.light_preceding[2] = (uint8_t)(tp >> 16);
             rec.light_preceding[3] = (uint8_t)(tp >> 24);
         }

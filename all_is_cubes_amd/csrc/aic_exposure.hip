@@ -18,8 +18,7 @@
 #include <stdint.h>
 
 #include "aic_exposure.h"
-#include "aic_lightmath.h"
-#include "aic_raycast.h"
+#include "aic_ray_query.h"
 
 namespace aic {
 
@@ -28,9 +27,7 @@ AIC_DEV float rgb_luminance(float r, float g, float b) { return g * 0.7152f + (r
 
 __global__ void __launch_bounds__(64) sample_luminance_kernel(const ExposureParams p) {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    // (the lanes past the end trace the last ray again and store nothing: the Raycaster's set-up asks the whole wave questions)
-    const uint32_t k = i < p.n ? i : p.n - 1u;
-    const double *ray = p.rays + 6u * (size_t)k;
+    const double *ray = query_ray(p.rays, p.n, i);
     const double ox = ray[0], oy = ray[1], oz = ray[2], dx = ray[3], dy = ray[4], dz = ray[5];
 
     // Sky::sample (sky.rs:32-41) on the direction as given: -0.0 counts as positive, NaN as negative
@@ -40,12 +37,7 @@ __global__ void __launch_bounds__(64) sample_luminance_kernel(const ExposurePara
     const int lox = p.lo[0], loy = p.lo[1], loz = p.lo[2];
     const uint32_t sx = (uint32_t)p.size[0], sy = (uint32_t)p.size[1], sz = (uint32_t)p.size[2];
     const int hix = lox + (int)sx, hiy = loy + (int)sy, hiz = loz + (int)sz;  // (fits: aic_upload_space checks lo + size)
-    LightGridView G;
-    G.light = p.light;
-    G.lo_x = lox; G.lo_y = loy; G.lo_z = loz;
-    G.size_x = (int)sx; G.size_y = (int)sy; G.size_z = (int)sz;
-    G.sky_nx = p.block_sky[0]; G.sky_ny = p.block_sky[1]; G.sky_nz = p.block_sky[2];
-    G.sky_px = p.block_sky[3]; G.sky_py = p.block_sky[4]; G.sky_pz = p.block_sky[5]; G.sky_mean = p.block_sky[6];
+    const LightGridView G = query_light_grid(p);
 
     const RayDir rd = raydir_init(dx, dy, dz);
     const LvlLim ll = lvl_init(ox, oy, oz, rd, true, lox, loy, loz, hix, hiy, hiz, false, 0.5 / sqrt(rd.dx * rd.dx + rd.dy * rd.dy + rd.dz * rd.dz));
@@ -58,17 +50,7 @@ __global__ void __launch_bounds__(64) sample_luminance_kernel(const ExposurePara
         if (!((ax < sx) & (ay < sy) & (az < sz))) break;  // the cube ahead is outside the bounds: the sky
         const uint32_t block = (uint32_t)p.grid[(ax * sy + ay) * sz + az] & p.index_mask;
         if (!((p.visible[block >> 5] >> (block & 31u)) & 1u)) continue;
-        // cube_behind = cube_ahead + the normal of the face crossed (Within: the cube itself); faces NX NY NZ PX PY PZ = 1..6
-        const int face = lvl_face(s);
-        const int sign = face == FACE_WITHIN ? 0 : (face > 3 ? 1 : -1);
-        const int face_axis = face > 3 ? face - 4 : face - 1;
-        const int bx = (int)((uint32_t)s.cx + (uint32_t)(face_axis == 0 ? sign : 0));
-        const int by = (int)((uint32_t)s.cy + (uint32_t)(face_axis == 1 ? sign : 0));
-        const int bz = (int)((uint32_t)s.cz + (uint32_t)(face_axis == 2 ? sign : 0));
-        const uint32_t ex = (uint32_t)bx - (uint32_t)lox, ey = (uint32_t)by - (uint32_t)loy, ez = (uint32_t)bz - (uint32_t)loz;
-        const bool inside = (ex < sx) & (ey < sy) & (ez < sz);
-        uint32_t t = p.light[inside ? (ex * sy + ey) * sz + ez : 0u];
-        if (!inside) t = lm_light_outside(G, bx, by, bz);
+        const uint32_t t = cube_behind(s, G).texel;
         if ((t >> 24) == 255u) {  // LightStatus::Visible: PackedLight::valid (light/data.rs:127-135)
             result = rgb_luminance(p.lut[t & 255u], p.lut[(t >> 8) & 255u], p.lut[(t >> 16) & 255u]);
             break;

@@ -3,6 +3,9 @@
 // submit_frames queues the frames of one launch on a slot's stream as a sequence of named steps (DESIGN.md 4.3 "One frame, step by step"); wait_frame
 // collects them. The entry points -- aic_render, aic_render_orthographic, aic_trace_patches, aic_trace_rays, aic_trace_pixels, aic_render_submit(_batch),
 // aic_render_wait(_batch) -- say what is traced (Traced) and where the result goes. Of aic_abi.cpp it uses what aic_ctx.h declares.
+// What the listed traces (aic_trace_patches, aic_trace_rays, aic_trace_pixels) share is written once, ahead of the entry points (batch_image to
+// finish_listed). Each keeps its own order of checks; the copies of its list in and of its results out stay with it too, because a failed one is reported
+// by the expression that made it.
 // Built with -ffp-contract=off, like the kernels: the pixel-edge table is the reference's own f64 operations (bind_pixel_edges).
 
 #include <hip/hip_runtime.h>
@@ -723,6 +726,44 @@ void multi_ortho(int resolution, const int32_t lo[3], const int32_t size[3], Dev
 }
 bool valid_ortho_resolution(int r) { return r >= 1 && r <= 128 && (r & (r - 1)) == 0; }
 
+// A listed trace's batch is laid out as an image of up to 2048 columns: pixel i of that image traces item i of the list. `what`: the items, for the refusal.
+int batch_image(aic_ctx *c, const char *who, const char *what, uint32_t n, aic_frame_desc *g) {
+    g->width = n < 2048u ? n : 2048u;
+    g->height = (n + g->width - 1u) / g->width;
+    g->partition = aic_partition{0, 1, 0, 0};
+    return g->height > 65535u ? reject(c, who, ("more than 2048 x 65535 " + std::string(what) + " in one call").c_str()) : AIC_OK;
+}
+// slot 0's stream is the one a synchronous trace queues on
+int begin_on_slot0(aic_ctx *c, const char *who) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    return c->slots[0].busy ? reject(c, who, "a submitted frame still occupies slot 0 (aic_render_wait it first)") : AIC_OK;
+}
+// a host list's staging and the results' buffer, which the launch is then aimed at
+int size_staging(aic_ctx *c, size_t out_words, size_t list_bytes) {
+    hipError_t e;
+    if ((e = c->out.ensure(out_words)) != hipSuccess) return hip_fail(c, "alloc output", e);
+    if ((e = c->staging.ensure(list_bytes)) != hipSuccess) return hip_fail(c, "alloc staging", e);
+    return AIC_OK;
+}
+// behind the results' copy back: the frame is collected, a host caller's hit records are read back, and the info counts the items
+int finish_listed(aic_ctx *c, uint32_t n, bool to_host, aic_pixel_aux *aux, aic_frame_info *info) {
+    const int rc = wait_frame(c, 0, info, to_host);
+    if (rc != AIC_OK) return rc;
+    if (aux && to_host) HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
+    if (info) info->rows_rendered = n;
+    return AIC_OK;
+}
+
+// Rays and orthographic views are traced as the WORLD layer of the launch, whatever layer holds the space: submit_frame with `layer` in that seat. (One
+// way in and one way out: nothing between the two swaps can return.)
+int submit_in_world_seat(aic_ctx *c, int layer, const aic_frame_desc *f, uint32_t *target, bool allow_aux, const Traced &what) {
+    const bool swap_layers = layer != AIC_LAYER_WORLD;
+    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
+    const int rc = submit_frame(c, f, target, 0, allow_aux, what);
+    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -730,8 +771,7 @@ extern "C" {
 int aic_render(aic_ctx *c, const aic_frame_desc *f, void *out_rgba8, int out_is_device, aic_frame_info *info) {
     if (!c || !f) return fail(c, AIC_ERR_INVALID, "aic_render: bad argument");
     if (info) std::memset(info, 0, sizeof(*info));
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_render: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (const int rc = begin_on_slot0(c, "aic_render")) return rc;
     uint32_t *target = (uint32_t *)out_rgba8;
     const size_t px_words = (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) ? 4 : ((f->flags & AIC_FRAME_OUT_SPLIT) ? 3 : 1);  // 16, 12 or 4 bytes per pixel
     if (!out_is_device && out_rgba8) {
@@ -789,11 +829,7 @@ int aic_render_orthographic(aic_ctx *c, int layer, int resolution, void *out_rgb
     Traced views;
     views.ortho = c->ortho_views.p;
     views.ortho_n = 5;
-    // the views are traced as the WORLD layer of the launch, whatever layer holds the space
-    const bool swap_layers = layer != AIC_LAYER_WORLD;
-    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
-    int rc = submit_frame(c, &f, target, 0, false, views);
-    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
+    const int rc = submit_in_world_seat(c, layer, &f, target, false, views);
     if (rc != AIC_OK) return rc;
     if (!out_is_device) HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->out.p, npix * 4, hipMemcpyDeviceToHost, c->slots[0].stream));
     return wait_frame(c, 0, info, !out_is_device);
@@ -804,36 +840,22 @@ int aic_trace_patches(aic_ctx *c, const aic_frame_desc *f, uint32_t n, const dou
     if (!c || !f || (n && (!rects || !out_rgba8))) return fail(c, AIC_ERR_INVALID, "aic_trace_patches: bad argument");
     if (info) std::memset(info, 0, sizeof(*info));
     if (!n) return AIC_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_trace_patches: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (const int rc = begin_on_slot0(c, "aic_trace_patches")) return rc;
     if (f->flags & AIC_FRAME_BLOOM) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_patches: AIC_FRAME_BLOOM needs a whole frame");
     if (f->flags & AIC_FRAME_OUT_SPLIT) return fail(c, AIC_ERR_UNSUPPORTED, "aic_trace_patches: AIC_FRAME_OUT_SPLIT is for whole frames");
-    // the batch is laid out as an image of up to 2048 columns; pixel i of that image traces rects[i]
     aic_frame_desc g = *f;
-    g.width = n < 2048u ? n : 2048u;
-    g.height = (n + g.width - 1u) / g.width;
-    if (g.height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_trace_patches: more than 2048 x 65535 rectangles in one call");
-    g.partition = aic_partition{0, 1, 0, 0};
+    if (const int rc = batch_image(c, "aic_trace_patches", "rectangles", n, &g)) return rc;
     g.flags = (f->flags & (AIC_FRAME_COUNTERS | AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) | (aux ? AIC_FRAME_AUX : 0u);
-    const size_t npix = (size_t)g.width * g.height;
-    hipError_t e;
     const size_t px_words = (f->flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) ? 4 : 1;
-    if ((e = c->out.ensure(npix * px_words)) != hipSuccess) return hip_fail(c, "alloc output", e);
-    if ((e = c->staging.ensure((size_t)n * 32)) != hipSuccess) return hip_fail(c, "alloc staging", e);
+    if (const int rc = size_staging(c, (size_t)g.width * g.height * px_words, (size_t)n * 32)) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->staging.p, rects, (size_t)n * 32, hipMemcpyHostToDevice, c->slots[0].stream));
     Traced batch;
     batch.patches = (const double *)c->staging.p;
     batch.n_patches = n;
-    int rc = submit_frame(c, &g, c->out.p, 0, true, batch);
+    const int rc = submit_frame(c, &g, c->out.p, 0, true, batch);
     if (rc != AIC_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->out.p, (size_t)n * px_words * 4, hipMemcpyDeviceToHost, c->slots[0].stream));
-    rc = wait_frame(c, 0, info, true);
-    if (rc != AIC_OK) return rc;
-    if (aux) {
-        HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
-    }
-    if (info) info->rows_rendered = n;
-    return AIC_OK;
+    return finish_listed(c, n, true, aux, info);
 }
 
 int aic_trace_rays(aic_ctx *c, int layer, uint32_t n, const double *rays, uint32_t flags, float exposure, void *out, aic_pixel_aux *aux,
@@ -844,50 +866,34 @@ int aic_trace_rays(aic_ctx *c, int layer, uint32_t n, const double *rays, uint32
     if ((flags & AIC_FRAME_OUT_LINEAR) && (flags & AIC_FRAME_OUT_COLORBUF)) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: AIC_FRAME_OUT_LINEAR and AIC_FRAME_OUT_COLORBUF exclude each other");
     if (!(exposure >= 0.f)) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: exposure is negative or NaN");
     if (!n) return AIC_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (const int rc = begin_on_slot0(c, "aic_trace_rays")) return rc;
     if (!c->layers[layer].present) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: no space uploaded for this layer");
     const bool on_device = (flags & AIC_RAYS_DEVICE) != 0;
     const size_t px_words = (flags & (AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) ? 4 : 1;
     // (the kernel fetches a ray with 16-byte loads and stores a float result as one: an allocation's start, or any whole number of rays / results into it)
     if (on_device && (((uintptr_t)rays & 15u) || ((uintptr_t)out & (px_words * 4u - 1u)) || ((uintptr_t)aux & 7u)))
         return fail(c, AIC_ERR_INVALID, "aic_trace_rays: AIC_RAYS_DEVICE wants rays at a 16-byte boundary, out and aux at their element's");
-    // the batch is laid out as an image of up to 2048 columns, like a patch batch; pixel i of that image traces rays[i]
     aic_frame_desc g;
     std::memset(&g, 0, sizeof(g));
-    g.width = n < 2048u ? n : 2048u;
-    g.height = (n + g.width - 1u) / g.width;
-    if (g.height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_trace_rays: more than 2048 x 65535 rays in one call");
-    g.partition = aic_partition{0, 1, 0, 0};
+    if (const int rc = batch_image(c, "aic_trace_rays", "rays", n, &g)) return rc;
     g.flags = (flags & (AIC_FRAME_COUNTERS | AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF)) | (aux ? AIC_FRAME_AUX : 0u);
     g.tuning = flags & (3u << AIC_TUNE_VARIANT_SHIFT);  // (the variant bits sit above every flag: measurement and tests ask for a production variant here)
     g.world.exposure = exposure;
     g.ui.exposure = 1.0f;
-    hipError_t e;
     RayBatch rb{rays, n, (flags & AIC_RAYS_NO_SKY) != 0, (uint32_t)layer, on_device ? reinterpret_cast<DevAux *>(aux) : nullptr};
-    uint32_t *target = (uint32_t *)out;
     hipStream_t stream = c->slots[0].stream;
     if (!on_device) {
-        if ((e = c->out.ensure((size_t)n * px_words)) != hipSuccess) return hip_fail(c, "alloc output", e);
-        if ((e = c->staging.ensure((size_t)n * 48)) != hipSuccess) return hip_fail(c, "alloc staging", e);
+        if (const int rc = size_staging(c, (size_t)n * px_words, (size_t)n * 48)) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->staging.p, rays, (size_t)n * 48, hipMemcpyHostToDevice, stream));
         rb.rays = (const double *)c->staging.p;
-        target = c->out.p;
     }
-    // the rays are traced as the WORLD layer of the launch, whatever layer holds the space (aic_render_orthographic does the same)
-    const bool swap_layers = layer != AIC_LAYER_WORLD;
-    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
+    uint32_t *const target = on_device ? (uint32_t *)out : c->out.p;
     Traced batch;
     batch.rb = &rb;
-    int rc = submit_frame(c, &g, target, 0, true, batch);
-    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
+    const int rc = submit_in_world_seat(c, layer, &g, target, true, batch);
     if (rc != AIC_OK) return rc;
     if (!on_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, (size_t)n * px_words * 4, hipMemcpyDeviceToHost, stream));
-    rc = wait_frame(c, 0, info, !on_device);
-    if (rc != AIC_OK) return rc;
-    if (aux && !on_device) HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
-    if (info) info->rows_rendered = n;
-    return AIC_OK;
+    return finish_listed(c, n, !on_device, aux, info);
 }
 
 int aic_trace_pixels(aic_ctx *c, const aic_frame_desc *f, uint32_t n, const uint32_t *pixels, uint32_t mode, void *out, aic_pixel_aux *aux,
@@ -910,39 +916,27 @@ int aic_trace_pixels(aic_ctx *c, const aic_frame_desc *f, uint32_t n, const uint
     if (!on_device)
         for (uint32_t i = 0; i < n; i++)
             if (pixels[i] >= count) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: a listed pixel is outside the frame");
-    // the batch is laid out as an image of up to 2048 columns, like a patch batch; pixel i of that image traces pixel pixels[i] of the frame
     aic_frame_desc g = *f;
-    g.width = n < 2048u ? n : 2048u;
-    g.height = (n + g.width - 1u) / g.width;
-    if (g.height > 65535u) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: more than 2048 x 65535 pixels in one call");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->slots[0].busy) return fail(c, AIC_ERR_INVALID, "aic_trace_pixels: a submitted frame still occupies slot 0 (aic_render_wait it first)");
+    if (const int rc = batch_image(c, "aic_trace_pixels", "pixels", n, &g)) return rc;
+    if (const int rc = begin_on_slot0(c, "aic_trace_pixels")) return rc;
     if (!count) return AIC_OK;  // (a device list over an empty viewport: every entry is outside it)
-    g.partition = aic_partition{0, 1, 0, 0};
     g.flags = (f->flags & (AIC_FRAME_COUNTERS | AIC_FRAME_OUT_LINEAR | AIC_FRAME_OUT_COLORBUF | AIC_FRAME_OUT_SPLIT | AIC_FRAME_PIXEL_CENTERS)) | (aux ? AIC_FRAME_AUX : 0u);
     g.tuning = 0;
     PixelList px{pixels, n, f->width, f->height, in_place, on_device ? reinterpret_cast<DevAux *>(aux) : nullptr};
-    uint32_t *target = (uint32_t *)out;
     hipStream_t stream = c->slots[0].stream;
     const size_t px_words = floats ? 4 : (split ? 3 : 1);  // (compact Split: [n] colour texels, then [n] depths -- contiguous, one copy)
-    hipError_t e;
     if (!on_device) {
-        if ((e = c->out.ensure((size_t)n * px_words)) != hipSuccess) return hip_fail(c, "alloc output", e);
-        if ((e = c->staging.ensure((size_t)n * 4)) != hipSuccess) return hip_fail(c, "alloc staging", e);
+        if (const int rc = size_staging(c, (size_t)n * px_words, (size_t)n * 4)) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->staging.p, pixels, (size_t)n * 4, hipMemcpyHostToDevice, stream));
         px.pixels = (const uint32_t *)c->staging.p;
-        target = c->out.p;
     }
+    uint32_t *const target = on_device ? (uint32_t *)out : c->out.p;
     Traced batch;
     batch.px = &px;
-    int rc = submit_frame(c, &g, target, 0, true, batch);
+    const int rc = submit_frame(c, &g, target, 0, true, batch);
     if (rc != AIC_OK) return rc;
     if (!on_device) HIP_TRY(c, hipMemcpyAsync(out, c->out.p, (size_t)n * px_words * 4, hipMemcpyDeviceToHost, stream));
-    rc = wait_frame(c, 0, info, !on_device);
-    if (rc != AIC_OK) return rc;
-    if (aux && !on_device) HIP_TRY(c, hipMemcpy(aux, c->aux.p, (size_t)n * sizeof(aic_pixel_aux), hipMemcpyDeviceToHost));
-    if (info) info->rows_rendered = n;
-    return AIC_OK;
+    return finish_listed(c, n, !on_device, aux, info);
 }
 
 // PixelPicker::new (raytrace_to_texture.rs:856-891). sort_by_key is stable; the keys are small non-negative integers, so a counting sort gives the same order.

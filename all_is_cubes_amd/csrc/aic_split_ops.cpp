@@ -1,5 +1,5 @@
 // aic_split_ops.cpp -- the operations of the C ABI declared in include/aic_hip.h that act on a resident Split frame: reproject it (aic_reproject_split),
-// pick the next pixels to trace (aic_pick_pixels), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
+// pick the next pixels to trace (aic_pick_pixels; aic_pick_stale: the pixels a scene change made stale first), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
 // with the info text laid over it (aic_present_split_text, aic_set_text_font), export it as sRGB8 colour and metric depth (aic_export_split), with the size
 // queries and host-only helpers that go with them (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch, aic_text_geometry,
 // aic_text_layout, aic_export_size).
@@ -7,14 +7,15 @@
 // The operations run on slot 0's stream, synchronously, and are written to one pattern: check the arguments, `begin`, size the context's scratch, fill the
 // launcher's parameters, then ev0, the launches, ev1, the copies back to the host and one synchronise, then the context's state and the caller's info.
 // Each rule they share is written once, in the anonymous namespace below. Of aic_abi.cpp it uses what aic_ctx.h declares; aic_cursor_wireframe,
-// which needs no context, is aic_cursor.cpp. tools/submit_record/split_ops_record.cpp drives every path of this file against a recording fake of the
-// HIP runtime.
+// which needs no context, is aic_cursor.cpp, and aic_stale_rects aic_stale_host.cpp. tools/submit_record/split_ops_record.cpp (aic_pick_stale:
+// listed_ops_record.cpp) drives every path of this file against a recording fake of the HIP runtime.
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/aic_hip.h"
 #include "aic_bloom.h"
@@ -22,15 +23,28 @@
 #include "aic_pick.h"
 #include "aic_present_lines.h"
 #include "aic_reproject.h"
+#include "aic_stale.h"
 
 using namespace aic;
+
+static_assert(sizeof(aic_stale_rect) == sizeof(StaleRect) && sizeof(aic_stale_rect) == 16, "the device reads aic_stale_rect as it is");
 
 namespace {
 
 // the kernels address a frame's pixels by 16-bit coordinates
 bool above_65535(uint32_t w, uint32_t h) { return w > 65535u || h > 65535u; }
 
-int reject(aic_ctx *c, const char *who, const char *why) { return fail(c, AIC_ERR_INVALID, (std::string(who) + ": " + why).c_str()); }
+// where a resident Split frame may start: its colour texels are read as 8-byte words; 0: the pointers are fine
+int split_frame_rule(aic_ctx *c, const char *who, const void *a, const void *b = nullptr) { return (((uintptr_t)a | (uintptr_t)b) & 7u) ? reject(c, who, "a Split frame starts at an 8-byte boundary") : 0; }
+
+// what the two pickers reject of the arguments they share, up to where a list of pixels may start; unknown_flags: the flag bits the entry point does not know
+int pick_args_invalid(aic_ctx *c, const char *who, uint32_t w, uint32_t h, uint32_t unknown_flags, uint32_t n, const uint32_t *pixels_out, const uint32_t *order) {
+    if (above_65535(w, h)) return reject(c, who, "frame dimensions above 65535 are not supported");
+    if (unknown_flags) return reject(c, who, "unknown flag bits");
+    if (n > 2048u * 65535u) return reject(c, who, "more than 2048 x 65535 picks");
+    if (n && !pixels_out) return reject(c, who, "no list to write the picks to");
+    return (((uintptr_t)pixels_out | (uintptr_t)order) & 3u) ? reject(c, who, "a list starts at a 4-byte boundary") : 0;
+}
 
 // What every operation opens with once its arguments are checked: slot 0's stream is the one it queues on. `who` is the entry point the message names.
 int begin(aic_ctx *c, const char *who) {
@@ -67,7 +81,7 @@ int present_args_invalid(aic_ctx *c, const aic_present_desc *d, const void *src,
     if (d->tone_mapping != 0 && d->tone_mapping != 1) return reject(c, who, "tone_mapping is neither 0 (Clamp) nor 1 (Reinhard)");
     const size_t px_bytes = (d->flags & AIC_PRESENT_OUT_F16) ? 8 : 4;
     const size_t src_bytes = (size_t)d->src_width * d->src_height * 12, out_bytes = (size_t)d->out_width * d->out_height * px_bytes;
-    if ((uintptr_t)src & 7u) return reject(c, who, "a Split frame starts at an 8-byte boundary");
+    if (const int rc = split_frame_rule(c, who, src)) return rc;
     if (out_is_device) {
         const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
         if (o0 & (px_bytes - 1)) return reject(c, who, "a device out starts at its element's boundary (4 bytes for RGBA8, 8 for f16)");
@@ -260,7 +274,7 @@ int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src
     if (info) std::memset(info, 0, sizeof(*info));
     if (above_65535(d->width, d->height)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: frame dimensions above 65535 are not supported");
     if (d->flags & ~AIC_REPROJECT_KEEP_SPLATS) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: unknown flag bits");
-    if (((uintptr_t)src & 7u) || ((uintptr_t)dst & 7u)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a Split frame starts at an 8-byte boundary");
+    if (const int rc = split_frame_rule(c, "aic_reproject_split", src, dst)) return rc;
     for (float v : d->reprojection)
         if (!std::isfinite(v)) return fail(c, AIC_ERR_INVALID, "aic_reproject_split: a component of the reprojection matrix is not finite");
     for (float v : d->inverse_projection_zw)
@@ -310,11 +324,7 @@ int aic_reproject_split(aic_ctx *c, const aic_reproject_desc *d, const void *src
 int aic_pick_pixels(aic_ctx *c, const aic_pick_desc *d, const uint32_t *order, uint32_t *pixels_out, aic_pick_info *info) {
     if (!c || !d || !info) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: bad argument");
     std::memset(info, 0, sizeof(*info));
-    if (above_65535(d->width, d->height)) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: frame dimensions above 65535 are not supported");
-    if (d->flags) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: unknown flag bits");
-    if (d->n > 2048u * 65535u) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: more than 2048 x 65535 picks");
-    if (d->n && !pixels_out) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: no list to write the picks to");
-    if (((uintptr_t)pixels_out & 3u) || ((uintptr_t)order & 3u)) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: a list starts at a 4-byte boundary");
+    if (const int rc = pick_args_invalid(c, "aic_pick_pixels", d->width, d->height, d->flags, d->n, pixels_out, order)) return rc;
     const uint64_t count = (uint64_t)d->width * d->height;
     if (d->n && !count) return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: an empty frame has no pixel to pick");
     if (const int rc = begin(c, "aic_pick_pixels")) return rc;
@@ -348,6 +358,68 @@ int aic_pick_pixels(aic_ctx *c, const aic_pick_desc *d, const uint32_t *order, u
     info->n_unknown = rec.n_unknown;
     info->next_cursor = rec.next_cursor;
     info->n_from_unknown = rec.n_from_unknown;
+    info->n_from_order = rec.n_from_order;
+    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    return AIC_OK;
+}
+
+int aic_pick_stale(aic_ctx *c, const aic_stale_desc *d, const void *src, const uint32_t *order, uint32_t *pixels_out, aic_stale_info *info) {
+    const char *who = "aic_pick_stale";
+    if (!c || !d || !info) return reject(c, who, "bad argument");
+    std::memset(info, 0, sizeof(*info));
+    if (const int rc = pick_args_invalid(c, who, d->width, d->height, d->flags & ~AIC_STALE_DEPTH_TEST, d->n, pixels_out, order)) return rc;
+    if (const int rc = split_frame_rule(c, who, src)) return rc;
+    const uint64_t count = (uint64_t)d->width * d->height;
+    if (d->n && !count) return reject(c, who, "an empty frame has no pixel to pick");
+    if (d->n_rects > AIC_STALE_MAX_RECTS) return reject(c, who, "more than AIC_STALE_MAX_RECTS rectangles");
+    if (d->n_rects && !d->rects) return reject(c, who, "no rectangles");
+    std::vector<aic_stale_rect> rects;  // the ones that hold a pixel
+    for (uint32_t i = 0; i < d->n_rects; i++) {
+        const aic_stale_rect &r = d->rects[i];
+        if (r.x0 > r.x1 || r.y0 > r.y1 || r.x1 > d->width || r.y1 > d->height) return reject(c, who, "a rectangle is inside out or leaves the frame");
+        if (std::isnan(r.dmin)) return reject(c, who, "a rectangle's dmin is NaN");
+        if (r.x0 < r.x1 && r.y0 < r.y1) rects.push_back(r);
+    }
+    const bool depth_test = (d->flags & AIC_STALE_DEPTH_TEST) != 0;
+    const uint32_t n_rects = (uint32_t)rects.size();
+    // whether anything is looked at (no rectangle that holds a pixel: the kernels would count nothing, the answer is known)
+    const bool look = d->n && n_rects && d->max_stale;
+    if (d->n && d->n_rects && d->max_stale && depth_test && !src) return reject(c, who, "no frame to test the depths of");
+    if (const int rc = begin(c, who)) return rc;
+    if (!d->n) return AIC_OK;  // (and so count == 0)
+    hipError_t e;
+    if (look && (e = c->stale_scratch.ensure(stale_scratch_bytes(count, n_rects))) != hipSuccess) return hip_fail(c, "alloc stale scratch", e);
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    StaleParams sp;
+    sp.color = look && depth_test ? (const uint2 *)src : nullptr;
+    sp.depth = look && depth_test ? (const float *)((const unsigned char *)src + count * 8u) : nullptr;
+    sp.order = order;
+    sp.out = pixels_out;
+    sp.scratch = look ? c->stale_scratch.p : nullptr;
+    sp.rects = look ? (const StaleRect *)(c->stale_scratch.p + stale_rects_offset(count)) : nullptr;
+    sp.width = d->width;
+    sp.count = (uint32_t)count;  // at most 65535^2
+    sp.n = d->n;
+    sp.max_stale = look ? d->max_stale : 0u;
+    sp.n_rects = look ? n_rects : 0u;
+    sp.depth_test = depth_test ? 1u : 0u;
+    sp.skip_stale = d->skip_stale;
+    sp.cursor = d->cursor;
+    if (look) HIP_TRY(c, hipMemcpyAsync(c->stale_scratch.p + stale_rects_offset(count), rects.data(), sizeof(aic_stale_rect) * (size_t)n_rects, hipMemcpyHostToDevice, fs.stream));
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_pick_stale(sp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick stale", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    StaleRecord rec = {};
+    if (look) {
+        HIP_TRY(c, hipMemcpyAsync(&rec, c->stale_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
+    } else {  // nothing was looked at: the whole list is the picker's
+        rec.n_from_order = d->n;
+        rec.next_cursor = d->cursor + d->n;
+    }
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));  // (`rects` goes out of scope)
+    info->n_stale = rec.n_stale;
+    info->next_cursor = rec.next_cursor;
+    info->n_from_stale = rec.n_from_stale;
     info->n_from_order = rec.n_from_order;
     HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
     return AIC_OK;
@@ -498,7 +570,7 @@ int aic_export_split(aic_ctx *c, const aic_export_desc *d, const void *src, void
     if (d->flags) return reject(c, who, "unknown flag bits");
     for (float v : d->inverse_projection_zw)
         if (!std::isfinite(v)) return reject(c, who, "a component of inverse_projection_zw is not finite");
-    if ((uintptr_t)src & 7u) return reject(c, who, "a Split frame starts at an 8-byte boundary");
+    if (const int rc = split_frame_rule(c, who, src)) return rc;
     const size_t npix = (size_t)d->out_width * d->out_height, plane_bytes = npix * 4, src_bytes = (size_t)d->src_width * d->src_height * 12;
     if (out_is_device) {
         if (((uintptr_t)color_out | (uintptr_t)depth_out) & 3u) return reject(c, who, "a device plane starts at a 4-byte boundary");

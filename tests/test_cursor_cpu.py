@@ -1,5 +1,5 @@
 """aic_cursor_raycast without a GPU: the restatement (tests/cursor_ref.py) against the reference's own seven tests (cursor.rs:310-436), the coverage of
-the case list the GPU test runs, what flat.pack / pack_block make of `selectable`, the library's export, and the host side -- aic_cursor_raycast_host.cpp
+the case list the GPU test runs, what flat.pack / pack_block make of `selectable`, the library's export, and the host side -- aic_cursor_raycast in aic_ray_queries.cpp
 and convert_block -- driven by tools/submit_record/cursor_raycast_record.cpp against the recording fake of the HIP runtime. That program has its own main
 and is built here with -fsanitize=address,undefined: host code only, nothing of it is loaded into Python."""
 import ctypes

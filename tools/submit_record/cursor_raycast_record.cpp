@@ -1,4 +1,4 @@
-// cursor_raycast_record.cpp -- drives aic_cursor_raycast (csrc/aic_cursor_raycast_host.cpp) and what convert_block (csrc/aic_abi.cpp) leaves of
+// cursor_raycast_record.cpp -- drives aic_cursor_raycast (csrc/aic_ray_queries.cpp) and what convert_block (csrc/aic_abi.cpp) leaves of
 // "selectable" in the block table and the palette pool, against the recording fake (fake_hip.cpp), and prints the record: every runtime call and launch
 // with its arguments, each call's return code and message, and after every scene write the bits the cursor raycast will read. The fake's device memory
 // is host memory, so the tables are read where the context keeps them. tests/test_cursor_cpu.py builds this with -fsanitize=address,undefined and reads

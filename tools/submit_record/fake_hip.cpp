@@ -1,8 +1,8 @@
 // fake_hip.cpp -- a recording stand-in for the HIP runtime calls and kernel launchers the host side of the C ABI (aic_abi.cpp, aic_frame.cpp,
-// aic_split_ops.cpp, aic_cursor_raycast_host.cpp) uses.
+// aic_split_ops.cpp, aic_ray_queries.cpp) uses.
 // Nothing of the real runtime is loaded: device memory is host memory, streams and events are ordinals, a launch is a line of text. Every call is logged
 // with its sizes; streams and events by creation ordinal, every device pointer as allocation ordinal + offset, so that two builds of the host code driven
-// through the same scenarios (driver.cpp, split_ops_record.cpp) give byte-identical records exactly when they make the same calls in the same order.
+// through the same scenarios (driver.cpp, split_ops_record.cpp, listed_ops_record.cpp) give byte-identical records exactly when they make the same calls in the same order.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -11,14 +11,17 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <vector>
 
 #include "aic_bloom.h"
 #include "aic_cursor_raycast.h"
 #include "aic_device.h"
+#include "aic_exposure.h"
 #include "aic_launch.h"
 #include "aic_pick.h"
 #include "aic_present_lines.h"
 #include "aic_reproject.h"
+#include "aic_stale.h"
 #include "record.h"
 
 namespace {
@@ -217,9 +220,17 @@ struct aic_ctx;
 namespace aic {
 
 struct LightState;
+struct Layer;
 void light_state_free(LightState *) {}
 void light_state_cubes_updated(LightState *, uint64_t, uint64_t, uint32_t, const int32_t *, const uint16_t *, const uint8_t *) {}
 int light_job_finish(aic_ctx *) { return 0; }
+// (the luminance sampler's bitmap, kVisibleBitsWords words: a fixed pattern; can be made to fail like a runtime call)
+int light_visible_bits(aic_ctx *, Layer &, hipStream_t stream, std::vector<uint32_t> *bits) {
+    rec("light_visible_bits %s", S(stream));
+    if (failing("light_visible_bits")) return AIC_ERR_DEVICE;
+    bits->assign(2048, 0xa5a5a5a5u);
+    return AIC_OK;
+}
 
 size_t trace_ray_cold_bytes(uint32_t n_cus, uint32_t *groups) {  // (a pure question, not a launch: not logged. The numbers are arbitrary, not the library's: any non-zero size serves)
     *groups = n_cus * 4u;
@@ -297,6 +308,25 @@ hipError_t launch_cursor_raycast(const CursorRaycastParams &p, hipStream_t strea
     rec_words("  lo size", p.lo, 6);
     rec_words("  block_sky", p.block_sky, 7);
     return failing("launch_cursor_raycast") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_sample_luminance(const ExposureParams &p, hipStream_t stream) {
+    rec("launch_sample_luminance");
+    rec("  grid %s light %s visible %s lut %s rays %s out %s index_mask %u n %u max_steps %u sky_kind %d %s", P(p.grid), P(p.light), P(p.visible), P(p.lut), P(p.rays), P(p.out), p.index_mask,
+        p.n, p.max_steps, p.sky_kind, S(stream));
+    rec_words("  lo size", p.lo, 6);
+    std::string sky = "  sky";
+    for (int o = 0; o < 8; o++)
+        for (int k = 0; k < 3; k++) { char b[32]; std::snprintf(b, sizeof(b), " %a", p.sky[o][k]); sky += b; }
+    rec("%s", sky.c_str());
+    rec_words("  block_sky", p.block_sky, 7);
+    return failing("launch_sample_luminance") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_pick_stale(const StaleParams &p, hipStream_t stream) {
+    rec("launch_pick_stale");
+    rec("  color %s depth %s order %s out %s scratch %s rects %s width %u count %u n %u max_stale %u n_rects %u depth_test %u skip_stale %llu cursor %llu %s", P(p.color), P(p.depth),
+        P(p.order), P(p.out), P(p.scratch), P(p.rects), p.width, p.count, p.n, p.max_stale, p.n_rects, p.depth_test, p.skip_stale, p.cursor, S(stream));
+    for (uint32_t i = 0; i < p.n_rects; i++) rec("  rect %u x0y0 %08x x1y1 %08x dmin %a reserved %u", i, p.rects[i].x0y0, p.rects[i].x1y1, p.rects[i].dmin, p.rects[i].reserved);
+    return failing("launch_pick_stale") ? hipErrorInvalidValue : hipSuccess;
 }
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }

@@ -1,4 +1,4 @@
-// record.h -- what the recording fake (fake_hip.cpp) offers the programs that drive it (driver.cpp, split_ops_record.cpp and the two check programs).
+// record.h -- what the recording fake (fake_hip.cpp) offers the programs that drive it (driver.cpp, split_ops_record.cpp, cursor_raycast_record.cpp, listed_ops_record.cpp and the two check programs).
 #pragma once
 #include <string>
 
