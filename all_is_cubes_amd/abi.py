@@ -33,6 +33,7 @@ PRESENT_OUT_F16 = 1  # AIC_PRESENT_OUT_F16: the presented image as four f16 per 
 PRESENT_MAX_PIXELS = 1 << 31  # AIC_PRESENT_MAX_PIXELS
 STALE_DEPTH_TEST = 1  # AIC_STALE_DEPTH_TEST: a rectangle keeps out an opaque world pixel whose depth lies in front of it
 STALE_MAX_RECTS = 4096  # AIC_STALE_MAX_RECTS
+STALE_DEPTH_BEHIND = 2  # AIC_STALE_DEPTH_BEHIND (aic_pick_stale_cubes): a light cube's rectangle keeps out a world pixel whose nearest surface lies behind it
 LINES_DEVICE = 1  # AIC_LINES_DEVICE: the line vertices are a device pointer
 LINES_MAX = 1 << 20  # AIC_LINES_MAX
 CURSOR_MAX_LINES = 28  # AIC_CURSOR_MAX_LINES
@@ -78,10 +79,10 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
-    "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
+    "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_light_changed_count", "aic_light_changed_take", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
     "aic_create_multi", "aic_destroy_multi", "aic_multi_device_count", "aic_multi_context", "aic_multi_last_error", "aic_multi_upload_space",
     "aic_multi_clear_space", "aic_multi_update_cubes", "aic_multi_update_light_volume", "aic_multi_evaluate_light", "aic_multi_light_cubes_changed", "aic_multi_replace_blocks", "aic_multi_set_options", "aic_multi_set_depth_transform",
     "aic_multi_render", "aic_multi_render_submit", "aic_multi_render_wait",
@@ -276,6 +277,20 @@ class StaleDesc(C.Structure):
 class StaleInfo(C.Structure):
     _fields_ = [("n_stale", C.c_uint64), ("next_cursor", C.c_uint64), ("n_from_stale", C.c_uint32), ("n_from_order", C.c_uint32),
                 ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+class StaleCubesDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n", C.c_uint32), ("max_stale", C.c_uint32), ("skip_stale", C.c_uint64),
+                ("cursor", C.c_uint64), ("view_projection", C.c_double * 16), ("n_boxes", C.c_uint32), ("expand", C.c_int32),
+                ("n_light_cubes", C.c_uint32), ("flags", C.c_uint32), ("boxes", C.c_void_p), ("light_cubes", C.c_void_p)]
+
+
+class StaleCubesInfo(C.Structure):
+    _fields_ = [("n_stale", C.c_uint64), ("next_cursor", C.c_uint64), ("n_from_stale", C.c_uint32), ("n_from_order", C.c_uint32),
+                ("kernel_ms", C.c_float), ("reserved", C.c_uint32), ("n_rects", C.c_uint32), ("whole_frame", C.c_uint32)]
+
+
+STALE_CUBE_RECT_DTYPE = np.dtype([("x0", "<u4"), ("y0", "<u4"), ("x1", "<u4"), ("y1", "<u4"), ("dmin", "<f4"), ("dmax", "<f4")])
 
 
 class PresentDesc(C.Structure):
@@ -497,6 +512,10 @@ def load() -> C.CDLL:
         lib.aic_reproject_split.argtypes = [C.c_void_p, C.POINTER(ReprojectDesc), C.c_void_p, C.c_void_p, C.POINTER(ReprojectInfo)]
         lib.aic_pick_pixels.argtypes = [C.c_void_p, C.POINTER(PickDesc), C.c_void_p, C.c_void_p, C.POINTER(PickInfo)]
         lib.aic_pick_stale.argtypes = [C.c_void_p, C.POINTER(StaleDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StaleInfo)]
+        lib.aic_light_changed_count.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_void_p]
+        lib.aic_light_changed_take.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.aic_pick_stale_cubes.argtypes = [C.c_void_p, C.POINTER(StaleCubesDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StaleCubesInfo)]
+        lib.aic_probe_stale_cube_rects.argtypes = [C.c_void_p, C.POINTER(StaleCubesDesc), C.c_void_p]
         lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
         lib.aic_present_split_lines.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo),
                                                 C.POINTER(LinesInfo)]
@@ -934,6 +953,63 @@ class Context:
         self._check(self._lib.aic_pick_stale(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(order_ptr or None), C.c_void_p(out_ptr or None),
                                              C.byref(info)))
         return info
+
+    def light_changed(self, layer: int, take: bool = True):
+        """The cubes of `layer` whose light texel the updater changed since the baseline (aic_light_changed_count / _take): (xyz [n, 3] int32 ascending
+        in the volume's cube index, bounds [6] int32 {lo, hi exclusive}; all 0 when n = 0). With `take` the baseline becomes the current volume -- and a
+        submitted update is ended and published first; without it nothing is consumed, no update is waited for, and the answer is (n, bounds)."""
+        n = C.c_uint64(0)
+        bounds = np.zeros(6, np.int32)
+        if take:
+            written = C.c_uint32(0)
+            # a take of no capacity ends a submitted update, whose changes then join, and succeeds only when there is nothing to report
+            rc = self._lib.aic_light_changed_take(self._h, int(layer), 0, None, C.byref(written))
+            if rc == 0:
+                return np.zeros((0, 3), np.int32), bounds
+            if rc != 1:  # not AIC_ERR_INVALID
+                self._check(rc)
+            self._check(self._lib.aic_light_changed_count(self._h, int(layer), C.byref(n), C.c_void_p(bounds.ctypes.data)))
+            xyz = np.zeros((max(int(n.value), 1), 3), np.int32)
+            self._check(self._lib.aic_light_changed_take(self._h, int(layer), int(n.value), C.c_void_p(xyz.ctypes.data), C.byref(written)))
+            return xyz[:written.value], bounds
+        self._check(self._lib.aic_light_changed_count(self._h, int(layer), C.byref(n), C.c_void_p(bounds.ctypes.data)))
+        return int(n.value), bounds
+
+    @staticmethod
+    def _stale_cubes_desc(view_projection, width, height, boxes, light_cubes, expand):
+        """(desc, the arrays it points to) of the arguments pick_stale_cubes and probe_stale_cube_rects share"""
+        b = np.ascontiguousarray(np.asarray(boxes if boxes is not None else [], np.int32).reshape(-1, 6))
+        q = np.ascontiguousarray(np.asarray(light_cubes if light_cubes is not None else [], np.int32).reshape(-1, 3))
+        d = StaleCubesDesc()
+        d.width, d.height, d.n_boxes, d.n_light_cubes, d.expand = int(width), int(height), len(b), len(q), int(expand)
+        d.view_projection = (C.c_double * 16)(*np.asarray(view_projection, np.float64).reshape(16))
+        d.boxes = b.ctypes.data if len(b) else None
+        d.light_cubes = q.ctypes.data if len(q) else None
+        return d, (b, q)
+
+    def pick_stale_cubes(self, view_projection, width: int, height: int, n: int, boxes, light_cubes, src_ptr: int, order_ptr: int, out_ptr: int,
+                         cursor: int = 0, max_stale: int = 0, skip_stale: int = 0, flags: int = 0, expand: int = 1) -> StaleCubesInfo:
+        """pick_stale from the changed cubes themselves, any number of them (aic_pick_stale_cubes): `boxes` [n, 6] int32 are changed blocks, grown by
+        `expand` as under stale_rects(); `light_cubes` [n, 3] int32 are cubes whose light texel changed (Context.light_changed), each the box [q, q + 1)
+        grown by one. The device projects them under `view_projection` and marks their rectangles. STALE_DEPTH_TEST is pick_stale's front test;
+        STALE_DEPTH_BEHIND lets a light cube's rectangle keep out a world pixel whose depth lies beyond the cube's greatest depth -- exact under
+        translucency and antialiasing. The info adds n_rects (rectangles that hold a pixel) and whole_frame."""
+        d, keep = self._stale_cubes_desc(view_projection, width, height, boxes, light_cubes, expand)
+        d.n, d.max_stale, d.skip_stale, d.cursor, d.flags = int(n), int(max_stale), int(skip_stale), int(cursor), int(flags)
+        info = StaleCubesInfo()
+        self._check(self._lib.aic_pick_stale_cubes(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(order_ptr or None),
+                                                   C.c_void_p(out_ptr or None), C.byref(info)))
+        del keep
+        return info
+
+    def probe_stale_cube_rects(self, view_projection, width: int, height: int, boxes, light_cubes, expand: int = 1) -> np.ndarray:
+        """The rectangles pick_stale_cubes projects on the device (aic_probe_stale_cube_rects): [n_boxes + n_light_cubes] STALE_CUBE_RECT_DTYPE records,
+        the boxes' first, all zero for a dropped one."""
+        d, keep = self._stale_cubes_desc(view_projection, width, height, boxes, light_cubes, expand)
+        out = np.zeros(d.n_boxes + d.n_light_cubes, STALE_CUBE_RECT_DTYPE)
+        self._check(self._lib.aic_probe_stale_cube_rects(self._h, C.byref(d), C.c_void_p(out.ctypes.data if len(out) else None)))
+        del keep
+        return out
 
     def present_split(self, src_ptr: int, src_size, out_size, bloom_intensity: float, tone_mapping: int, maximum_intensity: float, flags: int = 0,
                       out_device: int | None = None):

@@ -230,6 +230,7 @@ struct aic_ctx {
     // (appended: no member the frame path reads moves)
     DevBuf<unsigned char> stale_scratch;  // aic_pick_stale: the record, the scan blocks' counts and offsets, the bitmap, the rectangles (aic_stale.h)
     DevBuf<unsigned char> cursor_scratch;  // aic_cursor_raycast with host pointers: the staged rays, then the records
+    DevBuf<unsigned char> stale_cubes_scratch;  // aic_pick_stale_cubes: the record, the pixel bitmap, the scan blocks' counts, offsets and ballots, the rectangles, the staged boxes and cubes (aic_stale_cubes.h)
 };
 
 namespace aic {

@@ -755,6 +755,64 @@ struct LightState {
     double wall_clock_khz = 0.0;
     int queue_width = -1;
     uint64_t upload_serial = ~0ull;  // Layer::upload_serial the queue belongs to
+    // What aic_light_changed_count / _take answer from (include/aic_hip.h): `baseline` is the volume the report is measured against -- the mirror as
+    // first read, then following the caller's own texels and every take --, `cand` the cubes the updater wrote since (each once: `cand_bits`, a bit
+    // per cube; `cand_all`: fast = 1 wrote them all). A cube is reported iff it is a candidate and light[i] != baseline[i]: exact, and the apply loop
+    // gets no work per update -- deliver_changed() hands over what a batch changed, which it has sorted already.
+    std::vector<uint32_t> baseline, cand;
+    std::vector<uint64_t> cand_bits;
+    bool cand_all = false;
+    bool reread_own = false;          // the mirrors were marked stale by a failed update, not by the caller: the next re-read keeps every candidate
+    uint64_t report_serial = ~0ull;   // Layer::upload_serial the baseline belongs to
+    std::vector<uint32_t> published;  // while a submitted update runs: the answer for the published volume, taken at the submit (the worker owns the rest)
+    void cand_add(uint32_t i) {
+        if (cand_all) return;
+        uint64_t &w = cand_bits[i >> 6];
+        const uint64_t b = 1ull << (i & 63u);
+        if (w & b) return;
+        w |= b;
+        cand.push_back(i);
+    }
+    void cand_clear() {
+        for (uint32_t i : cand) cand_bits[i >> 6] = 0;
+        if (cand_all) std::fill(cand_bits.begin(), cand_bits.end(), 0);
+        cand.clear();
+        cand_all = false;
+    }
+    // the reported cubes, ascending
+    void changed_list(std::vector<uint32_t> *out) const {
+        out->clear();
+        if (cand_all) {
+            for (size_t i = 0; i < light.size(); i++)
+                if (light[i] != baseline[i]) out->push_back((uint32_t)i);
+        } else {
+            for (uint32_t i : cand)
+                if (light[i] != baseline[i]) out->push_back(i);
+            std::sort(out->begin(), out->end());
+        }
+    }
+    // The mirror `light` has just been read again from the device, `before` is what it held (empty: nothing was pending). A new space starts the
+    // report afresh. Otherwise whoever replaced texels owns them -- the baseline follows, their candidates go --, and a candidate whose texel the
+    // re-read did not move keeps its pending report.
+    void report_reread(uint64_t serial, const std::vector<uint32_t> &before) {
+        const size_t n = light.size();
+        const bool keep = report_serial == serial && baseline.size() == n && before.size() == n;
+        std::vector<std::pair<uint32_t, uint32_t>> kept;  // (cube, its baseline)
+        if (keep) {
+            auto consider = [&](uint32_t i) {
+                if (before[i] != baseline[i] && (reread_own ? light[i] != baseline[i] : light[i] == before[i])) kept.emplace_back(i, baseline[i]);
+            };
+            if (cand_all) for (size_t i = 0; i < n; i++) consider((uint32_t)i);
+            else for (uint32_t i : cand) consider(i);
+        }
+        baseline = light;
+        cand_bits.assign((n + 63) / 64, 0);
+        cand.clear();
+        cand_all = false;
+        for (const auto &k : kept) { baseline[k.first] = k.second; cand_add(k.first); }
+        reread_own = false;
+        report_serial = serial;
+    }
     void release() {
         delete queue;
         queue = nullptr;
@@ -778,7 +836,10 @@ void light_state_cubes_updated(LightState *s, uint64_t version_before, uint64_t 
         size_t idx;
         if (!s->geom.index(I3h{xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]}, &idx)) continue;  // the scatter kernel skips these too
         if (block_index) s->grid[idx] = block_index[k];
-        if (light) s->light[idx] = (uint32_t)light[4 * k] | ((uint32_t)light[4 * k + 1] << 8) | ((uint32_t)light[4 * k + 2] << 16) | ((uint32_t)light[4 * k + 3] << 24);
+        if (light) {
+            s->light[idx] = (uint32_t)light[4 * k] | ((uint32_t)light[4 * k + 1] << 8) | ((uint32_t)light[4 * k + 2] << 16) | ((uint32_t)light[4 * k + 3] << 24);
+            if (s->baseline.size() == s->light.size()) s->baseline[idx] = s->light[idx];  // the caller's own texel is never reported (aic_light_changed_count)
+        }
     }
     s->version = version_after;
 }
@@ -886,6 +947,8 @@ int light_prepare(aic_ctx *c, Layer &l, LightState &S, const uint32_t *vol = nul
     if (S.version == l.version) return AIC_OK;
     for (int a = 0; a < 3; a++) { S.geom.lo[a] = l.lo[a]; S.geom.size[a] = l.size[a]; }
     S.grid.resize(n);
+    std::vector<uint32_t> before;  // the mirror as it was, if the light report has something pending (LightState::report_reread)
+    if (S.report_serial == l.upload_serial && S.light.size() == n && (S.cand_all || !S.cand.empty())) before = S.light;
     S.light.resize(n);
     if (n) {
         HIP_TRY(c, hipMemcpy(S.grid.data(), l.pool.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
@@ -904,6 +967,7 @@ int light_prepare(aic_ctx *c, Layer &l, LightState &S, const uint32_t *vol = nul
     for (size_t i = 0; i < l.host_blocks.size(); i++) S.derived[i] = compute_derived_h(hb, l.host_blocks[i]);
     if ((e = S.d_derived.ensure(std::max<size_t>(S.derived.size(), 1))) != hipSuccess) return hip_fail(c, "alloc derived", e);
     if (!S.derived.empty()) HIP_TRY(c, hipMemcpy(S.d_derived.p, S.derived.data(), S.derived.size() * sizeof(DevDerived), hipMemcpyHostToDevice));
+    S.report_reread(l.upload_serial, before);
     S.version = l.version;
     return AIC_OK;
 }
@@ -1071,6 +1135,7 @@ struct LightCall {
         //  from their own streams, which do not wait for `ls` -- ADVICE r04)
         (void)hipStreamSynchronize(ls);
         S.version = ~0ull;
+        S.reread_own = true;
         const int kRequeue = 250;  // Priority::NEWLY_VISIBLE (all of them: after a failure the order of these updates is no longer the reference's)
         for (uint32_t idx : cubes) R.queue.insert(idx, kRequeue);
         for (uint32_t idx : changed) R.queue.insert(idx, kRequeue);
@@ -1082,6 +1147,8 @@ struct LightCall {
         const size_t n = l.n_cubes();
         if (p->fast) {
             fast_evaluate_light_h(R, l.block_sky);
+            S.cand_clear();  // every texel was written: a full relight is measured against the whole baseline
+            S.cand_all = true;
             if (n) HIP_TRY(c, hipMemcpyAsync(vol, S.light.data(), n * 4, hipMemcpyHostToDevice, ls));
         } else {
             if (p->n_queue < 0)
@@ -1469,6 +1536,7 @@ struct LightCall {
             std::sort(changed.begin(), changed.end());
             changed.erase(std::unique(changed.begin(), changed.end()), changed.end());
             const size_t m = changed.size();
+            for (uint32_t idx : changed) S.cand_add(idx);  // what aic_light_changed_count may report
             if (m <= kLightPrepMax) {
                 prep.n_scatter = (uint32_t)m;
                 for (size_t k = 0; k < m; k++) { prep.scatter_index[k] = changed[k]; prep.scatter_texel[k] = S.light[changed[k]]; }
@@ -1656,6 +1724,10 @@ int aic_evaluate_light_submit(aic_ctx *c, int layer, const aic_light_params *p) 
     { const int rc = take_light_spare(c, l, layer, nc, &spare); if (rc != AIC_OK) return rc; }
     if (nc) HIP_TRY(c, hipMemcpyAsync(l.light_spare[spare].p, l.light.p, nc * 4, hipMemcpyDeviceToDevice, c->upload_stream));
     HIP_TRY(c, hipStreamSynchronize(c->upload_stream));
+    // aic_light_changed_count answers for the PUBLISHED volume while the worker owns the mirrors: its answer is taken now
+    if (!l.lstate) l.lstate = new LightState();
+    { const int rc = light_prepare(c, l, *l.lstate); if (rc != AIC_OK) return rc; }
+    l.lstate->changed_list(&l.lstate->published);
     J.params = *p;
     J.queue_cubes.assign(p->n_queue > 0 ? p->queue_cubes : nullptr, p->n_queue > 0 ? p->queue_cubes + 3 * (size_t)p->n_queue : nullptr);
     J.queue_priorities.assign(p->n_queue > 0 ? p->queue_priorities : nullptr, p->n_queue > 0 ? p->queue_priorities + (size_t)p->n_queue : nullptr);
@@ -1758,6 +1830,7 @@ int aic_light_cubes_changed(aic_ctx *c, int layer, uint32_t n_cubes, const int32
         ~Unwind() {
             if (ok) return;
             S.version = ~0ull;
+            S.reread_own = true;
             for (uint32_t idx : owed) R.queue.insert(idx, 250);
         }
     } unwind{S, R, scatter_idx};
@@ -1768,6 +1841,7 @@ int aic_light_cubes_changed(aic_ctx *c, int layer, uint32_t n_cubes, const int32
         const DevDerived &ev = S.derived[S.grid[idx]];
         if (d_opaque_for_light(ev)) {
             S.light[idx] = kTexelOpaque;
+            S.cand_add((uint32_t)idx);  // the updater's write: aic_light_changed_count may report it
             scatter_idx.push_back((uint32_t)idx);
             R.queue.remove((uint32_t)idx);
         } else {
@@ -1794,6 +1868,62 @@ int aic_light_cubes_changed(aic_ctx *c, int layer, uint32_t n_cubes, const int32
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     unwind.ok = true;
+    return AIC_OK;
+}
+
+// The cubes whose light texel the updater changed (include/aic_hip.h). While a submitted update runs the worker thread owns the layer's mirrors, and its
+// changes are not published: the count answers from LightState::published, the take ends the update first, as every call that changes light state does.
+int aic_light_changed_count(aic_ctx *c, int layer, uint64_t *n, int32_t bounds[6]) {
+    if (!c || !valid_layer(layer) || !n) return fail(c, AIC_ERR_INVALID, "aic_light_changed_count: bad argument");
+    Layer &l = c->layers[layer];
+    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_light_changed_count: no space uploaded for this layer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!l.lstate) l.lstate = new LightState();
+    LightState &S = *l.lstate;
+    std::vector<uint32_t> fresh;
+    const std::vector<uint32_t> *list = &S.published;
+    if (!(c->ljob.pending && c->ljob.layer == layer)) {
+        { int rc = light_prepare(c, l, S); if (rc != AIC_OK) return rc; }
+        S.changed_list(&fresh);
+        list = &fresh;
+    }
+    *n = list->size();
+    if (bounds) {
+        for (int a = 0; a < 6; a++) bounds[a] = 0;
+        bool first = true;
+        for (uint32_t idx : *list) {
+            const I3h q = S.geom.cube_of(idx);
+            for (int a = 0; a < 3; a++) {
+                if (first || q[a] < bounds[a]) bounds[a] = q[a];
+                if (first || q[a] + 1 > bounds[3 + a]) bounds[3 + a] = q[a] + 1;
+            }
+            first = false;
+        }
+    }
+    return AIC_OK;
+}
+
+int aic_light_changed_take(aic_ctx *c, int layer, uint32_t capacity, int32_t *xyz, uint32_t *n_written) {
+    if (!c || !valid_layer(layer) || !n_written || (capacity && !xyz)) return fail(c, AIC_ERR_INVALID, "aic_light_changed_take: bad argument");
+    Layer &l = c->layers[layer];
+    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_light_changed_take: no space uploaded for this layer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int rc = light_job_finish(c); if (rc != AIC_OK) return rc; }
+    if (!l.lstate) l.lstate = new LightState();
+    LightState &S = *l.lstate;
+    { int rc = light_prepare(c, l, S); if (rc != AIC_OK) return rc; }
+    std::vector<uint32_t> list;
+    S.changed_list(&list);
+    if (list.size() > capacity) return fail(c, AIC_ERR_INVALID, "aic_light_changed_take: capacity is below the count (aic_light_changed_count)");
+    for (size_t k = 0; k < list.size(); k++) {
+        const I3h q = S.geom.cube_of(list[k]);
+        xyz[3 * k] = q[0]; xyz[3 * k + 1] = q[1]; xyz[3 * k + 2] = q[2];
+    }
+    *n_written = (uint32_t)list.size();
+    // the baseline becomes the current volume
+    if (S.cand_all) S.baseline = S.light;
+    else for (uint32_t i : S.cand) S.baseline[i] = S.light[i];
+    S.cand_clear();
     return AIC_OK;
 }
 

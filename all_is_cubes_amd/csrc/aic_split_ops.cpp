@@ -1,5 +1,5 @@
 // aic_split_ops.cpp -- the operations of the C ABI declared in include/aic_hip.h that act on a resident Split frame: reproject it (aic_reproject_split),
-// pick the next pixels to trace (aic_pick_pixels; aic_pick_stale: the pixels a scene change made stale first), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
+// pick the next pixels to trace (aic_pick_pixels; aic_pick_stale: the pixels a scene change made stale first; aic_pick_stale_cubes: the same from any number of changed boxes and light cubes), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
 // with the info text laid over it (aic_present_split_text, aic_set_text_font), export it as sRGB8 colour and metric depth (aic_export_split), with the size
 // queries and host-only helpers that go with them (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch, aic_text_geometry,
 // aic_text_layout, aic_export_size).
@@ -24,10 +24,12 @@
 #include "aic_present_lines.h"
 #include "aic_reproject.h"
 #include "aic_stale.h"
+#include "aic_stale_cubes.h"
 
 using namespace aic;
 
 static_assert(sizeof(aic_stale_rect) == sizeof(StaleRect) && sizeof(aic_stale_rect) == 16, "the device reads aic_stale_rect as it is");
+static_assert(sizeof(aic_stale_cube_rect) == sizeof(StaleCubeRect) && sizeof(aic_stale_cube_rect) == 24, "the probe copies the device's rectangles back as they are");
 
 namespace {
 
@@ -422,6 +424,115 @@ int aic_pick_stale(aic_ctx *c, const aic_stale_desc *d, const void *src, const u
     info->n_from_stale = rec.n_from_stale;
     info->n_from_order = rec.n_from_order;
     HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    return AIC_OK;
+}
+
+namespace {
+
+// what aic_pick_stale_cubes and its probe reject of the boxes, the light cubes and the camera; 0: none
+int stale_cubes_args_invalid(aic_ctx *c, const char *who, const aic_stale_cubes_desc *d) {
+    if (above_65535(d->width, d->height)) return reject(c, who, "frame dimensions above 65535 are not supported");
+    if (d->n_boxes && !d->boxes) return reject(c, who, "no boxes");
+    if (d->n_light_cubes && !d->light_cubes) return reject(c, who, "no light cubes");
+    if ((uint64_t)d->n_boxes + d->n_light_cubes > 0xFFFFFFFFull) return reject(c, who, "more than 2^32 - 1 boxes and light cubes");
+    if (d->expand < 0) return reject(c, who, "a negative expand");
+    for (double v : d->view_projection)
+        if (!std::isfinite(v)) return reject(c, who, "a component of view_projection is not finite");
+    return 0;
+}
+
+// sizes the scratch for the desc's boxes and cubes, fills the launcher's parameters that describe them and queues their copy to the device
+int stale_cubes_stage(aic_ctx *c, const aic_stale_cubes_desc *d, StaleCubesParams &sp, hipStream_t stream) {
+    hipError_t e = c->stale_cubes_scratch.ensure(stale_cubes_scratch_bytes(d->width, d->height, d->n_boxes, d->n_light_cubes));
+    if (e != hipSuccess) return hip_fail(c, "alloc stale cubes scratch", e);
+    unsigned char *s = c->stale_cubes_scratch.p;
+    const size_t in0 = stale_cubes_input_offset(d->width, d->height, (uint64_t)d->n_boxes + d->n_light_cubes), box_bytes = 24u * (size_t)d->n_boxes;
+    sp.scratch = s;
+    sp.rects = (StaleCubeRect *)(s + stale_cubes_rects_offset(d->width, d->height));
+    sp.boxes = (const int32_t *)(s + in0);
+    sp.light_cubes = (const int32_t *)(s + in0 + box_bytes);
+    std::memcpy(sp.m, d->view_projection, sizeof(sp.m));
+    sp.width = d->width;
+    sp.height = d->height;
+    sp.n_boxes = d->n_boxes;
+    sp.n_light_cubes = d->n_light_cubes;
+    sp.expand = d->expand;
+    if (d->n_boxes) HIP_TRY(c, hipMemcpyAsync(s + in0, d->boxes, box_bytes, hipMemcpyHostToDevice, stream));
+    if (d->n_light_cubes) HIP_TRY(c, hipMemcpyAsync(s + in0 + box_bytes, d->light_cubes, 12u * (size_t)d->n_light_cubes, hipMemcpyHostToDevice, stream));
+    return AIC_OK;
+}
+
+}  // namespace
+
+int aic_pick_stale_cubes(aic_ctx *c, const aic_stale_cubes_desc *d, const void *src, const uint32_t *order, uint32_t *pixels_out, aic_stale_cubes_info *info) {
+    const char *who = "aic_pick_stale_cubes";
+    if (!c || !d || !info) return reject(c, who, "bad argument");
+    std::memset(info, 0, sizeof(*info));
+    if (const int rc = pick_args_invalid(c, who, d->width, d->height, d->flags & ~(AIC_STALE_DEPTH_TEST | AIC_STALE_DEPTH_BEHIND), d->n, pixels_out, order)) return rc;
+    if (const int rc = split_frame_rule(c, who, src)) return rc;
+    const uint64_t count = (uint64_t)d->width * d->height;
+    if (d->n && !count) return reject(c, who, "an empty frame has no pixel to pick");
+    if (const int rc = stale_cubes_args_invalid(c, who, d)) return rc;
+    const bool front = (d->flags & AIC_STALE_DEPTH_TEST) != 0, behind = (d->flags & AIC_STALE_DEPTH_BEHIND) != 0;
+    const uint32_t n_total = d->n_boxes + d->n_light_cubes;
+    const bool look = d->n && n_total && d->max_stale;  // whether anything is looked at
+    const bool reads_frame = look && (front || (behind && d->n_light_cubes));
+    if (reads_frame && !src) return reject(c, who, "no frame to test the depths of");
+    if (const int rc = begin(c, who)) return rc;
+    if (!d->n) return AIC_OK;  // (and so count == 0)
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    StaleCubesParams sp = {};
+    if (look)
+        if (const int rc = stale_cubes_stage(c, d, sp, fs.stream)) return rc;
+    sp.color = reads_frame ? (const uint2 *)src : nullptr;
+    sp.depth = reads_frame ? (const float *)((const unsigned char *)src + count * 8u) : nullptr;
+    sp.order = order;
+    sp.out = pixels_out;
+    sp.width = d->width;
+    sp.height = d->height;
+    sp.n = d->n;
+    sp.max_stale = look ? d->max_stale : 0u;
+    sp.depth_front = front ? 1u : 0u;
+    sp.depth_behind = behind ? 1u : 0u;
+    sp.skip_stale = d->skip_stale;
+    sp.cursor = d->cursor;
+    hipError_t e;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_pick_stale_cubes(sp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick stale cubes", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    StaleCubesRecord rec = {};
+    if (look) {
+        HIP_TRY(c, hipMemcpyAsync(&rec, c->stale_cubes_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
+    } else {  // nothing was looked at: the whole list is the picker's
+        rec.n_from_order = d->n;
+        rec.next_cursor = d->cursor + d->n;
+    }
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    info->n_stale = rec.n_stale;
+    info->next_cursor = rec.next_cursor;
+    info->n_from_stale = rec.n_from_stale;
+    info->n_from_order = rec.n_from_order;
+    info->n_rects = rec.n_rects;
+    info->whole_frame = rec.whole_frame ? 1u : 0u;
+    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    return AIC_OK;
+}
+
+int aic_probe_stale_cube_rects(aic_ctx *c, const aic_stale_cubes_desc *d, aic_stale_cube_rect *out) {
+    const char *who = "aic_probe_stale_cube_rects";
+    if (!c || !d) return reject(c, who, "bad argument");
+    if (const int rc = stale_cubes_args_invalid(c, who, d)) return rc;
+    const uint32_t n_total = d->n_boxes + d->n_light_cubes;
+    if (n_total && !out) return reject(c, who, "no rectangles to write to");
+    if (const int rc = begin(c, who)) return rc;
+    if (!n_total) return AIC_OK;
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    StaleCubesParams sp = {};
+    if (const int rc = stale_cubes_stage(c, d, sp, fs.stream)) return rc;
+    hipError_t e;
+    if ((e = launch_project_stale_cubes(sp, fs.stream)) != hipSuccess) return hip_fail(c, "launch project stale cubes", e);
+    HIP_TRY(c, hipMemcpyAsync(out, sp.rects, sizeof(StaleCubeRect) * (size_t)n_total, hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
     return AIC_OK;
 }
 

@@ -751,6 +751,50 @@ aic_stale_info HipRtRenderer::pick_stale(const std::vector<aic_stale_rect> &rect
     return info;
 }
 
+aic_stale_cubes_info HipRtRenderer::pick_stale_cubes(const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n,
+                                                     uint32_t max_stale, uint32_t flags, int32_t expand) {
+    const Viewport vp = world_camera_.viewport();
+    if (vp.framebuffer_width != pick_width_ || vp.framebuffer_height != pick_height_) {
+        pick_width_ = vp.framebuffer_width;
+        pick_height_ = vp.framebuffer_height;
+        pick_cursor_ = pick_skip_unknown_ = pick_skip_stale_ = 0;
+    }
+    const Mat4 m = world_camera_.view_matrix().then(world_camera_.projection_matrix());  // row-vector order: read column-major it is projection x view
+    aic_stale_cubes_desc d{};
+    d.width = pick_width_;
+    d.height = pick_height_;
+    d.n = n;
+    d.max_stale = max_stale;
+    d.skip_stale = pick_skip_stale_;
+    d.cursor = pick_cursor_;
+    std::memcpy(d.view_projection, m.m, sizeof(d.view_projection));
+    d.n_boxes = (uint32_t)changed_boxes_.size();
+    d.expand = expand;
+    d.n_light_cubes = (uint32_t)changed_light_cubes_.size();
+    d.flags = flags;
+    d.boxes = changed_boxes_.empty() ? nullptr : changed_boxes_[0].data();
+    d.light_cubes = changed_light_cubes_.empty() ? nullptr : changed_light_cubes_[0].data();
+    aic_stale_cubes_info info;
+    check(aic_pick_stale_cubes(ctx_, &d, device_frame, device_order, device_pixels_out, &info), "aic_pick_stale_cubes");
+    pick_cursor_ = info.next_cursor;
+    pick_skip_stale_ += info.n_from_stale;
+    return info;
+}
+
+void HipRtRenderer::take_changed_light() {
+    if (!track_light_changes || !layers_[AIC_LAYER_WORLD].space) return;  // (not asked for; nothing uploaded: nothing to report)
+    uint64_t n = 0;
+    check(aic_light_changed_count(ctx_, AIC_LAYER_WORLD, &n, nullptr), "aic_light_changed_count");
+    if (!n) return;
+    const size_t at = changed_light_cubes_.size();
+    changed_light_cubes_.resize(at + (size_t)n);
+    uint32_t written = 0;
+    const int rc = aic_light_changed_take(ctx_, AIC_LAYER_WORLD, (uint32_t)n, changed_light_cubes_[at].data(), &written);
+    changed_light_cubes_.resize(at + (rc == AIC_OK ? written : 0u));
+    check(rc, "aic_light_changed_take");
+    if (written) pick_skip_stale_ = 0;  // the stale set has grown: its ranks are counted from the start again
+}
+
 aic_present_desc HipRtRenderer::present_desc(uint32_t out_width, uint32_t out_height, uint32_t flags) const {
     const Viewport vp = world_camera_.viewport();
     const GraphicsOptions &o = world_camera_.options();
@@ -1142,6 +1186,7 @@ HipRtRenderer::LightUpdateInfo HipRtRenderer::evaluate_light(int maximum_distanc
     p.lanes_per_cube = lanes_per_cube;
     aic_light_info info;
     check(aic_evaluate_light(ctx_, AIC_LAYER_WORLD, &p, &info), "aic_evaluate_light");
+    take_changed_light();
     return LightUpdateInfo{info.updates, info.batches, info.cost, info.device_ms, info.total_ms, info.queue_left, info.bundles_visited};
 }
 
@@ -1167,6 +1212,7 @@ bool HipRtRenderer::evaluate_light_done() {
 HipRtRenderer::LightUpdateInfo HipRtRenderer::evaluate_light_wait() {
     aic_light_info info;
     check(aic_evaluate_light_wait(ctx_, AIC_LAYER_WORLD, &info), "aic_evaluate_light_wait");
+    take_changed_light();  // (the update is published now)
     return LightUpdateInfo{info.updates, info.batches, info.cost, info.device_ms, info.total_ms, info.queue_left, info.bundles_visited};
 }
 

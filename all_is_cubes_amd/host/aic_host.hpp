@@ -475,6 +475,18 @@ class HipRtRenderer : public HeadlessRenderer {
                               uint32_t n, uint32_t max_stale, uint32_t flags = 0);
     void restart_stale() { pick_skip_stale_ = 0; }
     uint64_t pick_skip_stale() const { return pick_skip_stale_; }
+    // The same for a light update, and for any number of changed cubes (aic_light_changed_take, aic_pick_stale_cubes). changed_light_cubes:
+    // the cubes whose light texel the device's updater changed, taken from the library by every evaluate_light() and evaluate_light_wait() while
+    // track_light_changes is set (off by default: a loop that never asks must not pile them up) and kept
+    // until clear_changed_light_cubes() -- the loop clears them once pick_stale_cubes hands out no stale pixel any more. pick_stale_cubes: pick_stale
+    // with the stale set made on the device from changed_boxes() (grown by `expand`) and those light cubes under the current world camera; flags:
+    // AIC_STALE_DEPTH_TEST, AIC_STALE_DEPTH_BEHIND. It shares pick_stale's count of stale pixels handed out, which a light update that reported cubes
+    // also sets to 0.
+    const std::vector<std::array<int32_t, 3>> &changed_light_cubes() const { return changed_light_cubes_; }
+    bool track_light_changes = false;
+    void clear_changed_light_cubes() { changed_light_cubes_.clear(); }
+    aic_stale_cubes_info pick_stale_cubes(const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n, uint32_t max_stale,
+                                          uint32_t flags = 0, int32_t expand = 1);
     // raytrace_to_texture's per-frame presentation of its resident textures (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71, bloom.rs:41-60,
     // shaders/postprocess.wgsl:140-158 and 251-276; aic_present_split): the resident Split frame `src_device` -- of raytracer's viewport, i.e. the current
     // (size-policy-modified) viewport -- stretched with a linear filter to out_width x out_height, bloomed, tone-mapped and encoded, with bloom_intensity,
@@ -592,6 +604,8 @@ class HipRtRenderer : public HeadlessRenderer {
     uint64_t pick_cursor_ = 0, pick_skip_unknown_ = 0;  // pick_pixels
     uint64_t pick_skip_stale_ = 0;  // pick_stale
     std::vector<std::array<int32_t, 6>> changed_boxes_;  // of the last update(), world layer
+    std::vector<std::array<int32_t, 3>> changed_light_cubes_;  // what the light updates reported since clear_changed_light_cubes()
+    void take_changed_light();  // aic_light_changed_take of the world layer, appended to changed_light_cubes_
     uint32_t pick_width_ = 0, pick_height_ = 0;         // ... and the viewport they belong to
     // snapshot taken by update(): draw() must not touch the scene objects (headless.rs:33-39)
     Camera world_camera_, ui_camera_;

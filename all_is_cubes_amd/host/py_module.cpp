@@ -424,6 +424,22 @@ PYBIND11_MODULE(_host, m) {
             return d;
         }, py::arg("rects"), py::arg("frame_ptr"), py::arg("order_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("max_stale"), py::arg("flags") = 0u)
         .def("restart_stale", &HipRtRenderer::restart_stale)
+        .def("changed_light_cubes", [](const HipRtRenderer &r) { return r.changed_light_cubes(); })
+        .def("clear_changed_light_cubes", &HipRtRenderer::clear_changed_light_cubes)
+        .def_readwrite("track_light_changes", &HipRtRenderer::track_light_changes)
+        .def("pick_stale_cubes", [](HipRtRenderer &r, uintptr_t frame_ptr, uintptr_t order_ptr, uintptr_t out_ptr, uint32_t n, uint32_t max_stale, uint32_t flags, int32_t expand) {
+            // -> dict(n_stale, next_cursor, n_from_stale, n_from_order, kernel_ms, n_rects, whole_frame)
+            aic_stale_cubes_info i;
+            {
+                py::gil_scoped_release release;
+                i = r.pick_stale_cubes(reinterpret_cast<const void *>(frame_ptr), reinterpret_cast<const uint32_t *>(order_ptr), reinterpret_cast<uint32_t *>(out_ptr), n, max_stale, flags,
+                                       expand);
+            }
+            py::dict d;
+            d["n_stale"] = i.n_stale; d["next_cursor"] = i.next_cursor; d["n_from_stale"] = i.n_from_stale; d["n_from_order"] = i.n_from_order;
+            d["kernel_ms"] = i.kernel_ms; d["n_rects"] = i.n_rects; d["whole_frame"] = i.whole_frame;
+            return d;
+        }, py::arg("frame_ptr"), py::arg("order_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("max_stale"), py::arg("flags") = 0u, py::arg("expand") = 1)
         .def_property_readonly("pick_skip_stale", &HipRtRenderer::pick_skip_stale)
         .def_property_readonly("pick_cursor", &HipRtRenderer::pick_cursor)
         .def_property_readonly("pick_skip_unknown", &HipRtRenderer::pick_skip_unknown)

@@ -490,8 +490,8 @@ int aic_pick_pixels(aic_ctx *ctx, const aic_pick_desc *desc, const uint32_t *ord
  * n_rects > 0, max_stale > 0 and the depth test); NULL rects with n_rects > 0; n_rects above AIC_STALE_MAX_RECTS (a caller with more boxes merges them
  * or passes one whole-frame rectangle); a rectangle with x0 > x1, y0 > y1, x1 > width or y1 > height; a NaN dmin; unknown flag bits. n = 0 is AIC_OK,
  * writes nothing and zeroes the info.
- * Limits: LightingOption::Bounce rays go anywhere. A light update changes cubes the caller did not edit: expand = the light's maximum_distance is the
- * conservative answer, letting the light dissolve in over the picker's cycle is what happens without it. */
+ * Limits: LightingOption::Bounce rays go anywhere. A light update changes cubes the caller did not edit, and more of them than AIC_STALE_MAX_RECTS:
+ * aic_pick_stale_cubes below takes the changed light cubes themselves, any number of them. */
 #define AIC_STALE_DEPTH_TEST 1u
 #define AIC_STALE_MAX_RECTS 4096u
 typedef struct aic_stale_rect {
@@ -521,6 +521,75 @@ int aic_stale_rects(const double view_projection[16], uint32_t width, uint32_t h
                     aic_stale_rect *out /* [n] */);
 int aic_pick_stale(aic_ctx *ctx, const aic_stale_desc *desc, const void *src_device, const uint32_t *order_device, uint32_t *pixels_out_device,
                    aic_stale_info *info);
+/* Adds what the reference does not have: aic_pick_stale for any number of changed boxes and changed LIGHT cubes, projected on the device, so that a light
+ * update (hundreds to tens of thousands of changed texels) is complete in the next displayed frame too. The cost follows the rectangles' area and not
+ * pixels x rectangles. DESIGN.md 4.19 states the rule; tests/stale_cubes_ref.py is that text in NumPy.
+ *
+ * The set. S = the pixels of the resident frame inside at least one rectangle that does not keep them out.
+ *   - boxes[n_boxes][6] are changed BLOCKS: a box's rectangle is aic_stale_rects' own under view_projection, width, height and expand: x0, y0, x1, y1 and
+ *     dmin bit for bit.
+ *   - light_cubes[n_light_cubes][3] are cubes whose LIGHT texel changed with the blocks as they are. A pixel's value depends on light only at a lit
+ *     surface, through the texels within one cube of the hit cube; so a changed texel at cube q can change only pixels with a surface inside
+ *     [q - 1, q + 2): the rectangle of the box [q, q + 1) with expand = 1 (the desc's expand is not used), plus dmax = the greatest z / w of the eight
+ *     corners, plus 2^-24, rounded UP to f32; dmax = +inf where dmin is -inf.
+ *   - With AIC_STALE_DEPTH_TEST any rectangle keeps a pixel out as under aic_pick_stale: the depth texel's sign bit is clear, the alpha half is >= 1 and
+ *     depth < dmin in f32. The caller's knowledge, with the three caveats stated there.
+ *   - With AIC_STALE_DEPTH_BEHIND a LIGHT rectangle also keeps a pixel out iff the depth texel's sign bit is clear, the alpha half is > -0.5 (aic_pick_pixels'
+ *     validity test: a NaN alpha and the marker texel, whose alpha is -1, stay stale) and depth > dmax in f32. This needs only a frame traced under the camera's own depth transform, and is exact under translucency
+ *     and antialiasing: a Split frame's depth texel is the depth of the NEAREST surface of the pixel -- nearest over a ray's surfaces, glass included,
+ *     and nearest over the four samples of an antialiased pixel --, so a depth beyond the grown box's greatest depth says that every surface of every
+ *     sample lies behind the box, and the texel cannot matter. No opaque alpha is asked for. Boxes never use this test: a changed block in front of a
+ *     surface can hide it.
+ * The list is aic_pick_stale's: the ranks of order_device in S ascending; g = min(n, max_stale, max(n_stale - skip_stale, 0)); then the picker from
+ * cursor; all 64-bit. With n_boxes + n_light_cubes = 0 or max_stale = 0 nothing is looked at, n_stale, n_rects and whole_frame are 0 and the list is the
+ * picker's. There is no cap on the counts but that their sum fits 32 bits, and memory. boxes and light_cubes are host memory, copied into context
+ * scratch before the call returns. A rectangle that is the whole frame with no depth bound the flags can use (the camera inside or beside the grown box)
+ * makes every pixel stale at once: info.whole_frame is 1 and no rectangle is marked. Scratch (4 bytes per 32 pixels of a row, 40 bytes per 256 pixels,
+ * 24 a rectangle, the arrays and a 32-byte record) belongs to the context, is allocated on first use, again when a call needs more, and released in
+ * aic_destroy. The call blocks and runs on slot 0, like its siblings; src is only read, and only with a depth flag that some rectangle can use.
+ * Rejected before anything is queued, with AIC_ERR_INVALID and the context still usable: everything aic_pick_stale rejects for the arguments the two
+ * share (a NULL desc or info; a NULL pixels_out_device with n > 0; pixels_out_device or order_device off a 4-byte boundary; n > 0 with count = 0; width
+ * or height above 65535; n above 2048 x 65535; a frame still occupying slot 0; src_device off an 8-byte boundary, or NULL when it would be read: n > 0,
+ * max_stale > 0 and AIC_STALE_DEPTH_TEST with any box or cube, or AIC_STALE_DEPTH_BEHIND with a light cube; unknown flag bits); NULL boxes with
+ * n_boxes > 0; NULL light_cubes with n_light_cubes > 0; n_boxes + n_light_cubes above 2^32 - 1; a negative expand; a component of view_projection that
+ * is not finite. n = 0 is AIC_OK, writes nothing and zeroes the info.
+ * aic_probe_stale_cube_rects copies the projected rectangles back to host memory: out[n_boxes + n_light_cubes], the boxes' first, all fields 0 for a
+ * dropped one, dmax also for boxes (which never use it). It uses the desc's width, height, view_projection, expand and the two arrays, and rejects what
+ * aic_pick_stale_cubes rejects of those.
+ * Limits: LightingOption::Bounce rays go anywhere. */
+#define AIC_STALE_DEPTH_BEHIND 2u
+typedef struct aic_stale_cubes_desc {
+    uint32_t width, height;  /* the resident frame */
+    uint32_t n;              /* picks to write */
+    uint32_t max_stale;      /* at most this many of them from the stale pixels; 0: none */
+    uint64_t skip_stale;     /* stale pixels (in rank order) already handed out under these boxes and cubes */
+    uint64_t cursor;         /* pick index k of the first picker pick */
+    double view_projection[16];  /* as aic_stale_rects takes it */
+    uint32_t n_boxes;
+    int32_t expand;          /* the boxes are grown by this many cubes, as under aic_stale_rects */
+    uint32_t n_light_cubes;
+    uint32_t flags;          /* AIC_STALE_DEPTH_TEST | AIC_STALE_DEPTH_BEHIND */
+    const int32_t *boxes;        /* [n_boxes][6] {lo x, y, z, hi x, y, z}, upper bounds exclusive; host memory */
+    const int32_t *light_cubes;  /* [n_light_cubes][3]; host memory */
+} aic_stale_cubes_desc;
+typedef struct aic_stale_cubes_info {
+    uint64_t n_stale;        /* |S| (0 when nothing was looked at) */
+    uint64_t next_cursor;    /* cursor + n_from_order */
+    uint32_t n_from_stale;   /* g */
+    uint32_t n_from_order;   /* n - g */
+    float kernel_ms;         /* HIP events around the launches */
+    uint32_t reserved;
+    uint32_t n_rects;        /* boxes and cubes whose rectangle holds a pixel */
+    uint32_t whole_frame;    /* 1: a whole-frame rectangle without a usable depth bound made every pixel stale */
+} aic_stale_cubes_info;
+typedef struct aic_stale_cube_rect {
+    uint32_t x0, y0, x1, y1; /* columns [x0, x1), rows [y0, y1) */
+    float dmin;              /* nothing of the grown box is nearer than this depth; -inf: unknown */
+    float dmax;              /* nothing of the grown box is farther than this depth; +inf: unknown */
+} aic_stale_cube_rect;
+int aic_pick_stale_cubes(aic_ctx *ctx, const aic_stale_cubes_desc *desc, const void *src_device, const uint32_t *order_device,
+                         uint32_t *pixels_out_device, aic_stale_cubes_info *info);
+int aic_probe_stale_cube_rects(aic_ctx *ctx, const aic_stale_cubes_desc *desc, aic_stale_cube_rect *out /* [n_boxes + n_light_cubes] */);
 /* replaces: what raytrace_to_texture does with its resident textures every displayed frame: RaytraceToTexture::draw
  * (all-is-cubes-gpu/src/raytrace_to_texture.rs:546-568) draws rt_frame_copy_vertex / rt_frame_copy_fragment (shaders/rt-copy.wgsl:41-71) into the linear
  * scene texture -- the pipeline's linear ClampToEdge sampler stretches the frame to the viewport (the reference traces at half the nominal size,
@@ -979,6 +1048,22 @@ int aic_read_light_volume(aic_ctx *ctx, int layer, uint8_t *out);
 /* the texels of n cubes, out[n][4] (LightStorage::get, all-is-cubes/src/space/light/data.rs, over a list): served from the
  * updater's host mirror of the volume when that is current. AIC_ERR_INVALID for a cube outside the space. */
 int aic_read_light_cubes(aic_ctx *ctx, int layer, uint32_t n, const int32_t *xyz, uint8_t *out);
+/* Adds what the reference does not have: which light texels the UPDATER changed, for a caller that keeps a resident frame (aic_pick_stale_cubes takes the
+ * answer as its light_cubes). The answer is exact: a cube is reported iff its four texel bytes in the layer's published volume differ from the baseline;
+ * a texel that moved and moved back is not reported.
+ * The baseline starts as the volume of aic_upload_space and follows every texel the CALLER writes itself, which are therefore never reported:
+ * aic_update_light_volume, the `light` of aic_update_cubes, aic_compact; a take sets it to the current volume. The updater's writes are the apply step of
+ * aic_evaluate_light, the estimate of fast = 1 (a full relight: the diff against the whole baseline) and the OPAQUE texels aic_light_cubes_changed
+ * stores. The changes of an update submitted with aic_evaluate_light_submit join when it is PUBLISHED -- at aic_evaluate_light_wait or at the call that
+ * ends it --, so that frames and takes agree on the volume: until then aic_light_changed_count answers for the published volume and does not wait,
+ * and aic_light_changed_take, like every call that changes light state, ends the update first (its outcome stays for aic_evaluate_light_wait).
+ * aic_light_changed_count: *n = the number of reported cubes, bounds (may be NULL) = their bounding box {lo x, y, z, hi x, y, z}, upper bounds
+ * exclusive, all 0 when there are none; nothing is consumed.
+ * aic_light_changed_take: those cubes as xyz[n][3], ascending in the volume's cube index ((x - lo.x) * size.y + (y - lo.y)) * size.z + (z - lo.z), and
+ * *n_written = n; then the baseline becomes the current volume. capacity < n: AIC_ERR_INVALID, nothing written or consumed.
+ * AIC_ERR_INVALID: a NULL n or n_written, a NULL xyz with capacity > 0, no space uploaded for the layer. */
+int aic_light_changed_count(aic_ctx *ctx, int layer, uint64_t *n, int32_t bounds[6]);
+int aic_light_changed_take(aic_ctx *ctx, int layer, uint32_t capacity, int32_t *xyz, uint32_t *n_written);
 /* The propagation chart (chart/generator.rs): returns the node count; fills weights[n][6] and children[n][6] when both
  * are non-null, and the depth of the tree. Host-only: needs no device or context. */
 uint32_t aic_light_chart(float *weights, uint32_t *children, uint32_t *depth);

@@ -40,6 +40,7 @@ pub const AIC_TEXT_DEVICE: u32 = 1;
 pub const AIC_LINES_MAX: u32 = 1048576;
 pub const AIC_STALE_DEPTH_TEST: u32 = 1;
 pub const AIC_STALE_MAX_RECTS: u32 = 4096;
+pub const AIC_STALE_DEPTH_BEHIND: u32 = 2;
 pub const AIC_CURSOR_MAX_LINES: u32 = 28;
 pub const AIC_CURSOR_NO_BLOCK: u32 = 0xFFFF_FFFF;
 pub const AIC_EXPOSURE_SAMPLES: u32 = 100;
@@ -230,6 +231,48 @@ pub struct aic_stale_info {
     pub n_from_order: u32,
     pub kernel_ms: f32,
     pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct aic_stale_cubes_desc {
+    pub width: u32,
+    pub height: u32,
+    pub n: u32,
+    pub max_stale: u32,
+    pub skip_stale: u64,
+    pub cursor: u64,
+    pub view_projection: [f64; 16],
+    pub n_boxes: u32,
+    pub expand: i32,
+    pub n_light_cubes: u32,
+    pub flags: u32,
+    pub boxes: *const i32,
+    pub light_cubes: *const i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_stale_cubes_info {
+    pub n_stale: u64,
+    pub next_cursor: u64,
+    pub n_from_stale: u32,
+    pub n_from_order: u32,
+    pub kernel_ms: f32,
+    pub reserved: u32,
+    pub n_rects: u32,
+    pub whole_frame: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct aic_stale_cube_rect {
+    pub x0: u32,
+    pub y0: u32,
+    pub x1: u32,
+    pub y1: u32,
+    pub dmin: f32,
+    pub dmax: f32,
 }
 
 #[repr(C)]
@@ -453,6 +496,17 @@ unsafe extern "C" {
         pixels_out_device: *mut u32,
         info: *mut aic_stale_info,
     ) -> c_int;
+    pub fn aic_pick_stale_cubes(
+        ctx: *mut aic_ctx,
+        desc: *const aic_stale_cubes_desc,
+        src_device: *const c_void,
+        order_device: *const u32,
+        pixels_out_device: *mut u32,
+        info: *mut aic_stale_cubes_info,
+    ) -> c_int;
+    pub fn aic_probe_stale_cube_rects(ctx: *mut aic_ctx, desc: *const aic_stale_cubes_desc, out: *mut aic_stale_cube_rect) -> c_int;
+    pub fn aic_light_changed_count(ctx: *mut aic_ctx, layer: c_int, n: *mut u64, bounds: *mut i32) -> c_int;
+    pub fn aic_light_changed_take(ctx: *mut aic_ctx, layer: c_int, capacity: u32, xyz: *mut i32, n_written: *mut u32) -> c_int;
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;
     pub fn aic_export_split(ctx: *mut aic_ctx, desc: *const aic_export_desc, src_device: *const c_void, color_out: *mut c_void, depth_out: *mut f32, out_is_device: c_int, info: *mut aic_export_info) -> c_int;
     pub fn aic_export_size(width: u32, height: u32, max_area: f64, out: *mut u32) -> c_int;

@@ -926,6 +926,88 @@ impl HipRtRenderer {
         Ok(info)
     }
 
+    /// The cubes of the world layer whose light texel the light updater changed since the last take (`aic_light_changed_take`; not in the reference):
+    /// what [`Self::pick_stale_cubes`] takes as `light_cubes`. Exact, ascending in the volume's cube index; the caller's own light writes are never
+    /// reported. A submitted light update is ended and published first.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub fn take_changed_light_cubes(&mut self) -> Result<Vec<[i32; 3]>, RenderError> {
+        let Device::One(ctx) = self.device else { panic!("take_changed_light_cubes needs a single-device renderer") };
+        let mut written = 0u32;
+        // SAFETY: the context is live; a take of no capacity writes no cube -- it ends a submitted update, and succeeds only when nothing is reported
+        if unsafe { ffi::aic_light_changed_take(ctx.as_ptr(), ffi::AIC_LAYER_WORLD, 0, core::ptr::null_mut(), &mut written) } == 0 {
+            return Ok(Vec::new());
+        }
+        let mut n = 0u64;
+        // SAFETY: the context is live; bounds may be null
+        self.device.check(unsafe { ffi::aic_light_changed_count(ctx.as_ptr(), ffi::AIC_LAYER_WORLD, &mut n, core::ptr::null_mut()) })?;
+        let mut out = vec![[0i32; 3]; usize::try_from(n).unwrap_or(usize::MAX)];
+        // SAFETY: `out` holds `n` cubes of three coordinates
+        self.device.check(unsafe {
+            ffi::aic_light_changed_take(ctx.as_ptr(), ffi::AIC_LAYER_WORLD, u32::try_from(n).unwrap_or(u32::MAX), out.as_mut_ptr().cast(), &mut written)
+        })?;
+        out.truncate(written as usize);
+        Ok(out)
+    }
+
+    /// [`Self::pick_stale`] from the changed cubes themselves, any number of them (`aic_pick_stale_cubes`; not in the reference): `boxes` are changed
+    /// blocks `[lower, upper)`, grown by `expand` as under [`Self::stale_rects`]; `light_cubes` are cubes whose light texel changed
+    /// ([`Self::take_changed_light_cubes`]), each the box `[q, q + 1)` grown by one. The device projects them under the renderer's current world
+    /// camera and marks their rectangles, so the cost follows the rectangles' area. `ffi::AIC_STALE_DEPTH_TEST` is [`Self::pick_stale`]'s front test;
+    /// with `ffi::AIC_STALE_DEPTH_BEHIND` a light cube's rectangle keeps out a world pixel whose depth lies beyond the cube's greatest depth, which is
+    /// exact under translucency and antialiasing (the depth texel is the nearest surface's).
+    ///
+    /// # Safety
+    /// As [`Self::pick_stale`].
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn pick_stale_cubes(
+        &mut self,
+        boxes: &[[i32; 6]],
+        expand: i32,
+        light_cubes: &[[i32; 3]],
+        flags: u32,
+        src_device: *const core::ffi::c_void,
+        order_device: *const u32,
+        pixels_out_device: *mut u32,
+        n: u32,
+        max_stale: u32,
+        skip_stale: u64,
+        cursor: u64,
+    ) -> Result<ffi::aic_stale_cubes_info, RenderError> {
+        let Device::One(ctx) = self.device else { panic!("pick_stale_cubes needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let camera = &self.cameras.cameras().world;
+        let desc = ffi::aic_stale_cubes_desc {
+            width: viewport.framebuffer_size.width,
+            height: viewport.framebuffer_size.height,
+            n,
+            max_stale,
+            skip_stale,
+            cursor,
+            view_projection: camera.view_matrix().then(&camera.projection_matrix()).to_array(),
+            n_boxes: u32::try_from(boxes.len()).unwrap_or(u32::MAX),
+            expand,
+            n_light_cubes: u32::try_from(light_cubes.len()).unwrap_or(u32::MAX),
+            flags,
+            boxes: boxes.as_ptr().cast(),
+            light_cubes: light_cubes.as_ptr().cast(),
+        };
+        let mut info = ffi::aic_stale_cubes_info::default();
+        // SAFETY: the context is live; the caller vouches for the frame and the two lists; both arrays are copied before the call returns
+        self.device.check(unsafe { ffi::aic_pick_stale_cubes(ctx.as_ptr(), &desc, src_device, order_device, pixels_out_device, &mut info) })?;
+        Ok(info)
+    }
+
     /// What `raytrace_to_texture` does with its resident textures every displayed frame (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71,
     /// bloom.rs:41-60, shaders/postprocess.wgsl:140-158 and 251-276): the resident Split frame at `src_device`, of the renderer's own viewport, is
     /// stretched with a linear filter to `out_size`, bloomed with the world options' `bloom_intensity`, tone-mapped and written to `out_device` as sRGB

@@ -22,6 +22,7 @@
 #include "aic_present_lines.h"
 #include "aic_reproject.h"
 #include "aic_stale.h"
+#include "aic_stale_cubes.h"
 #include "record.h"
 
 namespace {
@@ -327,6 +328,18 @@ hipError_t launch_pick_stale(const StaleParams &p, hipStream_t stream) {
         P(p.order), P(p.out), P(p.scratch), P(p.rects), p.width, p.count, p.n, p.max_stale, p.n_rects, p.depth_test, p.skip_stale, p.cursor, S(stream));
     for (uint32_t i = 0; i < p.n_rects; i++) rec("  rect %u x0y0 %08x x1y1 %08x dmin %a reserved %u", i, p.rects[i].x0y0, p.rects[i].x1y1, p.rects[i].dmin, p.rects[i].reserved);
     return failing("launch_pick_stale") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_pick_stale_cubes(const StaleCubesParams &p, hipStream_t stream) {
+    rec("launch_pick_stale_cubes");
+    rec("  color %s depth %s order %s out %s scratch %s boxes %s light_cubes %s rects %s %ux%u n %u max_stale %u n_boxes %u n_light_cubes %u expand %d front %u behind %u skip_stale %llu cursor %llu %s",
+        P(p.color), P(p.depth), P(p.order), P(p.out), P(p.scratch), P(p.boxes), P(p.light_cubes), P(p.rects), p.width, p.height, p.n, p.max_stale, p.n_boxes, p.n_light_cubes, p.expand,
+        p.depth_front, p.depth_behind, p.skip_stale, p.cursor, S(stream));
+    return failing("launch_pick_stale_cubes") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_project_stale_cubes(const StaleCubesParams &p, hipStream_t stream) {
+    rec("launch_project_stale_cubes scratch %s boxes %s light_cubes %s rects %s %ux%u n_boxes %u n_light_cubes %u expand %d %s", P(p.scratch), P(p.boxes), P(p.light_cubes), P(p.rects), p.width,
+        p.height, p.n_boxes, p.n_light_cubes, p.expand, S(stream));
+    return failing("launch_project_stale_cubes") ? hipErrorInvalidValue : hipSuccess;
 }
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
