@@ -86,7 +86,7 @@ bool cameras_close(const double a[16], const double b[16]) {
 // What one launch traces. Whole frames (k of them: all pointers null) go through the pixel grid, the tile queues and the cost feedback; the other four replace the
 // camera (a pixel list: the pixel grid) and take none of those. A patch batch (aic_trace_patches): n NDC rectangles on the device, one per pixel of the batch's image. Orthographic views
 // (aic_render_orthographic): ortho_n views on the device. A ray batch (aic_trace_rays): n world-space rays on the device replace the camera; the space traced is
-// the launch's world layer (the caller swaps it in, as aic_render_orthographic does), labelled `layer` in first-hit records, which go to `aux_target` when the
+// the launch's world layer (Traced::world_seat names it, as for aic_render_orthographic), labelled `layer` in first-hit records, which go to `aux_target` when the
 // caller's own device buffer receives them.
 struct RayBatch {
     const double *rays;
@@ -110,6 +110,7 @@ struct Traced {
     int32_t ortho_n = 0;
     const RayBatch *rb = nullptr;
     const PixelList *px = nullptr;
+    int world_seat = AIC_LAYER_WORLD;  // the layer traced as the launch's world layer (ray batches and orthographic views: the layer that holds their space)
     bool whole_frame() const { return !patches && !rb && !px && !ortho_n; }
     DevAux *aux_target() const { return rb ? rb->aux_target : (px ? px->aux_target : nullptr); }
 };
@@ -178,7 +179,7 @@ uint32_t part_grid_tiles_per_wave(const aic_ctx *c, uint32_t slot, const DevFram
     // 0.376 -> 0.341 ms with four frames in flight, 0.338 with eight (profiles/r06_experiments.txt R). A frame submitted with nothing else in flight (the
     // first of a stream, or a host that submits slower than the device traces) still takes the whole chip; small frames keep their four tiles per wave.
     uint32_t busy_others = 0;
-    for (uint32_t i = 0; i < AIC_MAX_IN_FLIGHT; i++) busy_others += (i != slot && c->slots[i].busy) ? 1u : 0u;
+    for (uint32_t i = 0; i < AIC_MAX_IN_FLIGHT; i++) busy_others += (i != slot && c->slots[i].busy && c->slots[i].npix) ? 1u : 0u;
     const uint32_t resident_waves = (uint32_t)c->n_cus * 16u;
     const uint32_t tpw_full = (F.tiles_x * F.tiles_y + resident_waves - 1u) / resident_waves;
     if (tpw_full >= 4u && busy_others > 0u) {
@@ -193,10 +194,11 @@ void plan_geometry(const aic_ctx *c, uint32_t k, const aic_frame_desc *f, uint32
     DevFrame &F = P.F;
     DevLayer *hl = P.hl;
     std::memset(&F, 0, sizeof(F));
-    fill_dev_layer(c->layers[AIC_LAYER_WORLD], f->world, &hl[0]);
+    const Layer &seated = c->layers[what.world_seat];
+    fill_dev_layer(seated, f->world, &hl[0]);
     fill_dev_layer(c->layers[AIC_LAYER_UI], f->ui, &hl[1]);
     // AIC_FRAME_BLOOM: the frame is bloomed as the reference's GPU renderer blooms it (aic_bloom.hip); at intensity 0 the flag changes nothing
-    const aic_options &bloom_opt = c->layers[AIC_LAYER_WORLD].opt;
+    const aic_options &bloom_opt = seated.opt;
     P.bloom = (f->flags & AIC_FRAME_BLOOM) && bloom_opt.bloom_intensity > 0.0f;
     if (bloom_opt.bloom_intensity != 0.0f && !P.bloom) P.flaws |= AIC_FLAW_NO_BLOOM;  // renderer.rs:293-297
     F.width = f->width;
@@ -537,7 +539,10 @@ int submit_frames(aic_ctx *c, uint32_t k, const aic_frame_desc *frames, uint32_t
     fs.npix = P.npix;
     fs.variant = fs.tile_queues = 0;
     if (allow_aux) c->aux_records = 0;
-    if (!P.npix) return AIC_OK;
+    if (!P.npix) {  // an empty frame (a partition's part of no rows): nothing is queued, but it occupies its slot until it is waited for like any other
+        fs.busy = true;
+        return AIC_OK;
+    }
     const bool own_aux = P.want_aux && !what.aux_target();  // the first-hit records go to the context's buffer (aic_read_aux)
     hipError_t e;
     if (own_aux && (e = c->aux.ensure(P.npix)) != hipSuccess) return hip_fail(c, "alloc aux", e);
@@ -597,6 +602,7 @@ int wait_frame(aic_ctx *c, uint32_t slot, aic_frame_info *info, bool whole_strea
     for (uint32_t j = 0; infos && j < n_infos; j++) std::memset(&infos[j], 0, sizeof(infos[j]));
     float kernel_ms = 0.f;
     const uint32_t k = fs.n_sub ? fs.n_sub : 1u;
+    if (fs.busy && !fs.npix) fs.busy = false;  // an empty frame: no event was recorded for it, the report is all zeros
     if (fs.busy) {
         fs.busy = false;  // released whatever happens below: a frame that failed must not block its slot for good
         // the frame and its counters (ev2), not the slot's housekeeping behind them -- unless the caller has enqueued a copy of its own behind the frame
@@ -754,14 +760,14 @@ int finish_listed(aic_ctx *c, uint32_t n, bool to_host, aic_pixel_aux *aux, aic_
     return AIC_OK;
 }
 
-// Rays and orthographic views are traced as the WORLD layer of the launch, whatever layer holds the space: submit_frame with `layer` in that seat. (One
-// way in and one way out: nothing between the two swaps can return.)
+// Rays and orthographic views are traced as the WORLD layer of the launch, whatever layer holds the space: submit_frame with `layer` named for that seat.
+// (Until the session fuzz the two Layer objects were swapped around the submit instead. A light update running on the context's worker thread holds a
+// reference to its layer all the while -- neither call waits for it, by design -- and found the other layer's space under it: rays on the UI layer beside a
+// pending update of the world cut that update short, tests/test_gpu_trace_rays.py.)
 int submit_in_world_seat(aic_ctx *c, int layer, const aic_frame_desc *f, uint32_t *target, bool allow_aux, const Traced &what) {
-    const bool swap_layers = layer != AIC_LAYER_WORLD;
-    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
-    const int rc = submit_frame(c, f, target, 0, allow_aux, what);
-    if (swap_layers) std::swap(c->layers[AIC_LAYER_WORLD], c->layers[layer]);
-    return rc;
+    Traced seated = what;
+    seated.world_seat = layer;
+    return submit_frame(c, f, target, 0, allow_aux, seated);
 }
 
 }  // namespace

@@ -287,11 +287,13 @@ int aic_render(aic_ctx *ctx, const aic_frame_desc *frame, void *out_rgba8, int o
  * chip (a third with three others in flight, a quarter from four on), so that the frames in flight are resident side by side -- same pixels and counts,
  * a higher frame rate, a longer life of each frame; a frame submitted with nothing else in flight takes the whole chip. out_device must be a device pointer; the
  * AIC_FRAME_AUX flag is ignored here (use aic_render). Scene updates that change what a frame in flight
- * reads (aic_upload_space, aic_update_cubes, aic_replace_blocks, aic_set_options, aic_compact) wait for every
- * frame in flight first; aic_update_light_volume and aic_evaluate_light do NOT: they write the other half of the
+ * reads (aic_upload_space, aic_update_cubes, aic_replace_blocks, aic_compact) wait for every
+ * frame in flight first (aic_set_options waits for nothing: a frame carries the options it was submitted under); aic_update_light_volume and aic_evaluate_light do NOT: they write the other half of the
  * light double buffer beside the frames in flight (which keep the half they were given) and only wait for a frame
  * still reading that other half.
  * Slots 0..7 are made with the context; a higher slot gets its stream and events when it is first used.
+ * A frame of no pixels (a partition's part that has no rows) queues nothing and occupies its slot like any other until it is waited for: the wait
+ * reports zeros, and until then a second submit on the slot, and on slot 0 the work that runs there, is refused.
  * "The frame is in out_device" is all aic_render_wait (and aic_render with a device target) waits for: behind the frame the slot's
  * stream still prepares the slot's next frame (the frame's cost record becomes a tile order, counters are cleared -- microseconds of
  * work private to the slot). Work the caller orders behind the frame with aic_stream_wait_frame, or issues after the wait returns,

@@ -221,6 +221,44 @@ def test_viewport_zero(ctx):
     assert got["rgba8"].shape == (0, 0, 4) and got["info"].cubes_traced == 0
 
 
+def test_a_submitted_part_of_no_rows_occupies_its_slot_until_it_is_waited_for(ctx):
+    """Part 2 of a 9-row frame dealt in strips of 8 to three parts has no rows: nothing is queued for it, and it is a submitted frame all the same
+    (found by tests/test_gpu_session_fuzz.py). Until its wait the slot is busy -- a second submit and the work of slot 0 are refused and write nothing --
+    and the wait reports the empty frame, not whatever ran on the slot last."""
+    import torch
+
+    w, h = 17, 9
+    ctx.upload_space(abi.LAYER_WORLD, scenes.one_cube_space())
+    ctx.set_options(abi.LAYER_WORLD, abi.make_options())
+    _, _, inv = oracle.camera_matrices(90.0, 200.0, w / h, oracle.look_at_y_up((0.7, 0.9, 2.5), (0.5, 0.5, 0.5)), (0.7, 0.9, 2.5))
+    whole = ctx.make_frame(w, h, world_inv=inv)
+    want = ctx.render(whole)
+    assert want["info"].rows_rendered == h and want["info"].cubes_traced > 0
+    empty = ctx.make_frame(w, h, world_inv=inv, partition=(8, 3, 2))
+    assert ctx.partition_rows(h, (8, 3, 2)) == 0
+    out = torch.full((w * h * 4,), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    for slot in (0, 5):
+        ctx.render_submit(empty, out.data_ptr(), slot)
+        with pytest.raises(abi.AicError) as err:
+            ctx.render_submit(whole, out.data_ptr(), slot)
+        assert err.value.code == 1  # AIC_ERR_INVALID: the slot is busy
+        if slot == 0:
+            for refused in (lambda: ctx.render_to_device(whole, out.data_ptr()), lambda: ctx.trace_patches(whole, [[-0.5, -0.5, 0.5, 0.5]]),
+                            lambda: ctx.render_orthographic(abi.LAYER_WORLD, 1)):
+                with pytest.raises(abi.AicError) as err:
+                    refused()
+                assert err.value.code == 1
+        ctx.stream_wait_frame(slot, torch.cuda.current_stream().cuda_stream)  # (no event was recorded for it: nothing to wait for)
+        info = ctx.render_wait(slot)
+        assert (info.rows_rendered, info.cubes_traced, info.variant, info.tile_queues) == (0, 0, 0, 0), slot
+        assert (out.cpu().numpy() == 0xA5).all(), slot
+    again = ctx.render(whole)
+    assert (again["rgba8"] == want["rgba8"]).all() and again["info"].cubes_traced == want["info"].cubes_traced
+    ctx.render_submit(whole, out.data_ptr(), 5)
+    assert ctx.render_wait(5).rows_rendered == h and (out.cpu().numpy().reshape(h, w, 4) == want["rgba8"]).all()
+
+
 # --- seeded synthetic scenes: every option of the path vs the oracle ------------------------
 SYNTH_EYE = (14.5, 22.5, 44.0)
 

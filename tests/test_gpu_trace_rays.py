@@ -487,6 +487,43 @@ def test_a_batch_beside_streamed_frames(ctx, space):
         torch.cuda.synchronize()
 
 
+def test_rays_and_views_of_the_ui_layer_beside_a_light_update_of_the_world():
+    """Rays and orthographic views of the UI layer's space are traced in the world's seat of the launch, and neither waits for a light update that
+    runs on the context's worker thread (found by tests/test_gpu_session_fuzz.py: the two Layer objects used to be swapped around the submit, the
+    worker found the UI layer's space under its reference to the world, and an update of 2553 cubes ended after 26). An update long enough to run
+    beside twelve such calls -- a few cubes changed in a light field that is nobody's fixed point, no cap -- must come out as the blocking call
+    makes it on a second context, and every batch as it is traced with nothing else going on."""
+    world = workloads.synthetic_space(n=16, resolution=8, n_blocks=6, seed=165, light="field")
+    ui = flat.FlatSpace((0, 0, 0), (3, 2, 1))
+    ui.set_sky_uniform((1.0, 1.0, 0.5))
+    ui.add_block(flat.air())
+    ui.block_index[0, 0, 0] = ui.add_block(flat.atom((0.0, 1.0, 0.0, 1.0)))
+    ui.block_index[2, 1, 0] = ui.add_block(flat.atom((0.9, 0.2, 0.1, 0.5)))
+    rng = np.random.default_rng(11)
+    rays = np.concatenate([rng.uniform(-1.0, 4.0, (700, 3)), rng.normal(size=(700, 3))], 1)
+    xyz = np.array([[3, 9, 4], [8, 10, 8], [12, 9, 3], [5, 11, 12]], np.int32)
+    kw = dict(maximum_distance=4, fast=False, queue=[], max_updates=0, batch=256)
+    with abi.Context(0) as a, abi.Context(0) as b:
+        for c in (a, b):
+            c.upload_space(abi.LAYER_WORLD, world)
+            c.upload_space(abi.LAYER_UI, ui)
+            c.update_cubes(abi.LAYER_WORLD, xyz, np.array([1, 2, 6, 7], np.uint16))
+            c.light_cubes_changed(abi.LAYER_WORLD, xyz)
+        want_rays, want_view = b.trace_rays(abi.LAYER_UI, rays, want_aux=True), b.render_orthographic(abi.LAYER_UI, 4)
+        a.evaluate_light_submit(abi.LAYER_WORLD, **kw)
+        beside = 0
+        for _ in range(6):
+            beside += not a.evaluate_light_done(abi.LAYER_WORLD)
+            got_rays, got_view = a.trace_rays(abi.LAYER_UI, rays, want_aux=True), a.render_orthographic(abi.LAYER_UI, 4)
+            assert (got_rays["rgba8"] == want_rays["rgba8"]).all() and all((got_rays["aux"][k] == want_rays["aux"][k]).all() for k in AUX_FIELDS)
+            assert (got_view["rgba8"] == want_view["rgba8"]).all() and got_view["info"].cubes_traced == want_view["info"].cubes_traced
+        ia, ib = a.evaluate_light_wait(abi.LAYER_WORLD), b.evaluate_light(abi.LAYER_WORLD, **kw)
+        print(f"{ia.updates} updates on the worker, {ib.updates} blocking; {beside} of 6 rounds began while the update ran")
+        assert ib.updates > 100, "the update did not spread beyond the changed cubes: too short to run beside anything"
+        assert (ia.updates, ia.queue_left) == (ib.updates, ib.queue_left)
+        assert (a.read_light_volume(abi.LAYER_WORLD, world.size) == b.read_light_volume(abi.LAYER_WORLD, world.size)).all()
+
+
 # --- 6. the host mirror --------------------------------------------------------------------------------------------------------------
 def test_host_mirror_trace_rays(ctx, space):
     import all_is_cubes_amd as A
