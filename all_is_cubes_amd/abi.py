@@ -79,7 +79,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_find_block_cubes", "aic_pick_stale_blocks", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_light_changed_count", "aic_light_changed_take", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -288,6 +288,20 @@ class StaleCubesDesc(C.Structure):
 class StaleCubesInfo(C.Structure):
     _fields_ = [("n_stale", C.c_uint64), ("next_cursor", C.c_uint64), ("n_from_stale", C.c_uint32), ("n_from_order", C.c_uint32),
                 ("kernel_ms", C.c_float), ("reserved", C.c_uint32), ("n_rects", C.c_uint32), ("whole_frame", C.c_uint32)]
+
+
+class BlockCubesInfo(C.Structure):
+    _fields_ = [("n_cubes", C.c_uint64), ("n_runs", C.c_uint64), ("bounds", C.c_int32 * 6), ("n_written", C.c_uint32), ("merged", C.c_uint32),
+                ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+class StaleBlocksDesc(C.Structure):
+    _fields_ = [("cubes", StaleCubesDesc), ("layer", C.c_int32), ("n_blocks", C.c_uint32), ("block_indices", C.c_void_p), ("max_runs", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class StaleBlocksInfo(C.Structure):
+    _fields_ = [("pick", StaleCubesInfo), ("found", BlockCubesInfo)]
 
 
 STALE_CUBE_RECT_DTYPE = np.dtype([("x0", "<u4"), ("y0", "<u4"), ("x1", "<u4"), ("y1", "<u4"), ("dmin", "<f4"), ("dmax", "<f4")])
@@ -516,6 +530,8 @@ def load() -> C.CDLL:
         lib.aic_light_changed_take.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
         lib.aic_pick_stale_cubes.argtypes = [C.c_void_p, C.POINTER(StaleCubesDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StaleCubesInfo)]
         lib.aic_probe_stale_cube_rects.argtypes = [C.c_void_p, C.POINTER(StaleCubesDesc), C.c_void_p]
+        lib.aic_find_block_cubes.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(BlockCubesInfo)]
+        lib.aic_pick_stale_blocks.argtypes = [C.c_void_p, C.POINTER(StaleBlocksDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StaleBlocksInfo)]
         lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
         lib.aic_present_split_lines.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo),
                                                 C.POINTER(LinesInfo)]
@@ -1000,6 +1016,36 @@ class Context:
         self._check(self._lib.aic_pick_stale_cubes(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(order_ptr or None),
                                                    C.c_void_p(out_ptr or None), C.byref(info)))
         del keep
+        return info
+
+    def find_block_cubes(self, layer: int, indices, capacity: int):
+        """The cubes of `layer` that hold one of the block `indices`, as runs along z (aic_find_block_cubes): (boxes [n_written, 6] int32 {lo, hi
+        exclusive} sorted by a run's first cube in the grid's linear order, info). With more runs than `capacity` the one box info.bounds is written
+        instead (none with capacity 0) and info.merged is 1. What a re-evaluated block (replace_blocks) made stale: the grid does not change under
+        such a call, only what these cubes look like."""
+        idx = np.ascontiguousarray(np.asarray(indices, np.uint32).reshape(-1))
+        out = np.zeros((max(int(capacity), 1), 6), np.int32)
+        info = BlockCubesInfo()
+        self._check(self._lib.aic_find_block_cubes(self._h, int(layer), len(idx), C.c_void_p(idx.ctypes.data if len(idx) else None), int(capacity),
+                                                   C.c_void_p(out.ctypes.data if capacity else None), C.byref(info)))
+        return out[:info.n_written].copy(), info
+
+    def pick_stale_blocks(self, view_projection, width: int, height: int, n: int, boxes, light_cubes, layer: int, blocks, src_ptr: int, order_ptr: int,
+                          out_ptr: int, cursor: int = 0, max_stale: int = 0, skip_stale: int = 0, flags: int = 0, expand: int = 1,
+                          max_runs: int = 65536) -> StaleBlocksInfo:
+        """pick_stale_cubes with, behind `boxes`, the boxes find_block_cubes(layer, blocks, max_runs) gives, found and kept on the device
+        (aic_pick_stale_blocks): the pixels a re-evaluated block made stale first. info.pick is pick_stale_cubes' info, info.found the find's; with
+        n = 0 or max_stale = 0 no find runs."""
+        d = StaleBlocksDesc()
+        d.cubes, keep = self._stale_cubes_desc(view_projection, width, height, boxes, light_cubes, expand)
+        d.cubes.n, d.cubes.max_stale, d.cubes.skip_stale, d.cubes.cursor, d.cubes.flags = int(n), int(max_stale), int(skip_stale), int(cursor), int(flags)
+        idx = np.ascontiguousarray(np.asarray(blocks if blocks is not None else [], np.uint32).reshape(-1))
+        d.layer, d.n_blocks, d.max_runs = int(layer), len(idx), int(max_runs)
+        d.block_indices = idx.ctypes.data if len(idx) else None
+        info = StaleBlocksInfo()
+        self._check(self._lib.aic_pick_stale_blocks(self._h, C.byref(d), C.c_void_p(src_ptr or None), C.c_void_p(order_ptr or None),
+                                                    C.c_void_p(out_ptr or None), C.byref(info)))
+        del keep, idx
         return info
 
     def probe_stale_cube_rects(self, view_projection, width: int, height: int, boxes, light_cubes, expand: int = 1) -> np.ndarray:

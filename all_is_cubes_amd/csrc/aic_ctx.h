@@ -231,6 +231,11 @@ struct aic_ctx {
     DevBuf<unsigned char> stale_scratch;  // aic_pick_stale: the record, the scan blocks' counts and offsets, the bitmap, the rectangles (aic_stale.h)
     DevBuf<unsigned char> cursor_scratch;  // aic_cursor_raycast with host pointers: the staged rays, then the records
     DevBuf<unsigned char> stale_cubes_scratch;  // aic_pick_stale_cubes: the record, the pixel bitmap, the scan blocks' counts, offsets and ballots, the rectangles, the staged boxes and cubes (aic_stale_cubes.h)
+    // aic_find_block_cubes, aic_pick_stale_blocks: the record, the set, the workgroups' counts and offsets (aic_stale_blocks.h); the boxes a find hands to
+    // the host; the events around a pick's find, made by the first call that needs them
+    DevBuf<unsigned char> stale_blocks_scratch;
+    DevBuf<int32_t> stale_blocks_boxes;
+    hipEvent_t stale_blocks_ev[2] = {nullptr, nullptr};
 };
 
 namespace aic {

@@ -1,5 +1,5 @@
 // aic_split_ops.cpp -- the operations of the C ABI declared in include/aic_hip.h that act on a resident Split frame: reproject it (aic_reproject_split),
-// pick the next pixels to trace (aic_pick_pixels; aic_pick_stale: the pixels a scene change made stale first; aic_pick_stale_cubes: the same from any number of changed boxes and light cubes), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
+// pick the next pixels to trace (aic_pick_pixels; aic_pick_stale: the pixels a scene change made stale first; aic_pick_stale_cubes: the same from any number of changed boxes and light cubes; aic_find_block_cubes and aic_pick_stale_blocks: the same for a re-evaluated block, whose cubes the device finds), present it (aic_present_split), present it with a line list drawn in (aic_present_split_lines) and
 // with the info text laid over it (aic_present_split_text, aic_set_text_font), export it as sRGB8 colour and metric depth (aic_export_split), with the size
 // queries and host-only helpers that go with them (aic_reproject_geometry, aic_present_geometry, aic_present_lines_scratch, aic_text_geometry,
 // aic_text_layout, aic_export_size).
@@ -24,6 +24,7 @@
 #include "aic_present_lines.h"
 #include "aic_reproject.h"
 #include "aic_stale.h"
+#include "aic_stale_blocks.h"
 #include "aic_stale_cubes.h"
 
 using namespace aic;
@@ -441,12 +442,14 @@ int stale_cubes_args_invalid(aic_ctx *c, const char *who, const aic_stale_cubes_
     return 0;
 }
 
-// sizes the scratch for the desc's boxes and cubes, fills the launcher's parameters that describe them and queues their copy to the device
-int stale_cubes_stage(aic_ctx *c, const aic_stale_cubes_desc *d, StaleCubesParams &sp, hipStream_t stream) {
-    hipError_t e = c->stale_cubes_scratch.ensure(stale_cubes_scratch_bytes(d->width, d->height, d->n_boxes, d->n_light_cubes));
+// sizes the scratch for the desc's boxes and cubes and for n_found more boxes behind the desc's own (aic_pick_stale_blocks: the device writes those),
+// fills the launcher's parameters that describe them and queues the copy of the desc's to the device
+int stale_cubes_stage(aic_ctx *c, const aic_stale_cubes_desc *d, StaleCubesParams &sp, hipStream_t stream, uint32_t n_found = 0u) {
+    const uint32_t n_boxes = d->n_boxes + n_found;  // (the entry points have checked the sums)
+    hipError_t e = c->stale_cubes_scratch.ensure(stale_cubes_scratch_bytes(d->width, d->height, n_boxes, d->n_light_cubes));
     if (e != hipSuccess) return hip_fail(c, "alloc stale cubes scratch", e);
     unsigned char *s = c->stale_cubes_scratch.p;
-    const size_t in0 = stale_cubes_input_offset(d->width, d->height, (uint64_t)d->n_boxes + d->n_light_cubes), box_bytes = 24u * (size_t)d->n_boxes;
+    const size_t in0 = stale_cubes_input_offset(d->width, d->height, (uint64_t)n_boxes + d->n_light_cubes), own_bytes = 24u * (size_t)d->n_boxes, box_bytes = 24u * (size_t)n_boxes;
     sp.scratch = s;
     sp.rects = (StaleCubeRect *)(s + stale_cubes_rects_offset(d->width, d->height));
     sp.boxes = (const int32_t *)(s + in0);
@@ -454,36 +457,132 @@ int stale_cubes_stage(aic_ctx *c, const aic_stale_cubes_desc *d, StaleCubesParam
     std::memcpy(sp.m, d->view_projection, sizeof(sp.m));
     sp.width = d->width;
     sp.height = d->height;
-    sp.n_boxes = d->n_boxes;
+    sp.n_boxes = n_boxes;
     sp.n_light_cubes = d->n_light_cubes;
     sp.expand = d->expand;
-    if (d->n_boxes) HIP_TRY(c, hipMemcpyAsync(s + in0, d->boxes, box_bytes, hipMemcpyHostToDevice, stream));
+    if (d->n_boxes) HIP_TRY(c, hipMemcpyAsync(s + in0, d->boxes, own_bytes, hipMemcpyHostToDevice, stream));
     if (d->n_light_cubes) HIP_TRY(c, hipMemcpyAsync(s + in0 + box_bytes, d->light_cubes, 12u * (size_t)d->n_light_cubes, hipMemcpyHostToDevice, stream));
     return AIC_OK;
 }
 
-}  // namespace
+// A find of the cubes that hold given blocks (aic_find_block_cubes, and aic_pick_stale_blocks' part of it)
+struct BlockFind {
+    int layer;
+    uint32_t n_blocks;
+    const uint32_t *indices;
+    uint32_t capacity;
+};
 
-int aic_pick_stale_cubes(aic_ctx *c, const aic_stale_cubes_desc *d, const void *src, const uint32_t *order, uint32_t *pixels_out, aic_stale_cubes_info *info) {
-    const char *who = "aic_pick_stale_cubes";
-    if (!c || !d || !info) return reject(c, who, "bad argument");
-    std::memset(info, 0, sizeof(*info));
+// what both entry points reject of a find; 0: nothing
+int block_find_invalid(aic_ctx *c, const char *who, const BlockFind &f) {
+    if (!valid_layer(f.layer)) return reject(c, who, "a layer that is neither 0 nor 1");
+    const Layer &l = c->layers[f.layer];
+    if (!l.present) return reject(c, who, "no space uploaded for the layer");
+    if (f.n_blocks && !f.indices) return reject(c, who, "no block indices");
+    for (uint32_t i = 0; i < f.n_blocks; i++)
+        if (f.indices[i] >= l.host_blocks.size()) return reject(c, who, "a block index at or above the layer's block count");
+    if (block_cubes_groups(l.n_cubes()) > 0x7FFFFFFFull) return reject(c, who, "a grid of more than 2048 x (2^31 - 1) cubes");
+    return 0;
+}
+
+// whether the find has anything to scan
+bool block_find_scans(const aic_ctx *c, const BlockFind &f) { return f.n_blocks && c->layers[f.layer].n_cubes(); }
+
+// the events around the write of a pick's find, whose own two are taken by the pick's launches
+int block_find_events(aic_ctx *c) {
+    for (hipEvent_t &ev : c->stale_blocks_ev)
+        if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+    return AIC_OK;
+}
+
+// The count of a find that scans: the set and the record's initial value go to the scratch, the count runs, the stream is synchronised and the record
+// read: *info is complete but for the time of the write, and bp describes the grid for launch_write_block_cubes (boxes and n_runs are the caller's to
+// fill in).
+int block_find_count(aic_ctx *c, const BlockFind &f, aic_ctx::FrameSlot &fs, BlockCubesParams &bp, aic_block_cubes_info *info) {
+    const Layer &l = c->layers[f.layer];
+    const uint32_t set_words = (uint32_t)((l.host_blocks.size() + 31u) / 32u);  // at most kBlockSetWords: a table holds at most 65536 blocks
+    std::vector<uint32_t> head(sizeof(BlockCubesRecord) / 4u + set_words, 0u);  // the record, then the set
+    BlockCubesRecord rec = {};
+    rec.lo[0] = rec.lo[1] = rec.lo[2] = 0xFFFFFFFFu;
+    std::memcpy(head.data(), &rec, sizeof(rec));
+    for (uint32_t i = 0; i < f.n_blocks; i++) head[sizeof(rec) / 4u + (f.indices[i] >> 5)] |= 1u << (f.indices[i] & 31u);
+    hipError_t e = c->stale_blocks_scratch.ensure(block_cubes_scratch_bytes(set_words, l.n_cubes()));
+    if (e != hipSuccess) return hip_fail(c, "alloc stale blocks scratch", e);
+    bp = BlockCubesParams{};
+    bp.grid = l.pool.p;
+    bp.n = l.n_cubes();
+    bp.sx = (uint32_t)l.size[0];
+    bp.sy = (uint32_t)l.size[1];
+    bp.sz = (uint32_t)l.size[2];
+    bp.index_mask = l.cls_in_code ? kCubeIndexMask : 0xffffu;
+    bp.set_words = set_words;
+    for (int a = 0; a < 3; a++) bp.lo[a] = l.lo[a];
+    bp.scratch = c->stale_blocks_scratch.p;
+    HIP_TRY(c, hipMemcpyAsync(bp.scratch, head.data(), head.size() * 4u, hipMemcpyHostToDevice, fs.stream));
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    if ((e = launch_count_block_cubes(bp, fs.stream)) != hipSuccess) return hip_fail(c, "launch count block cubes", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    HIP_TRY(c, hipMemcpyAsync(&rec, bp.scratch, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    info->n_cubes = rec.n_cubes;
+    info->n_runs = rec.n_runs;
+    if (rec.n_cubes)
+        for (int a = 0; a < 3; a++) {
+            info->bounds[a] = l.lo[a] + (int32_t)rec.lo[a];
+            info->bounds[3 + a] = l.lo[a] + (int32_t)rec.hi[a];
+        }
+    info->merged = rec.n_runs > f.capacity ? 1u : 0u;
+    info->n_written = info->merged ? (f.capacity ? 1u : 0u) : (uint32_t)rec.n_runs;
+    return AIC_OK;
+}
+
+// aic_pick_stale_cubes (find == nullptr), and aic_pick_stale_blocks: the same call with the find's boxes behind the desc's own. info is zeroed.
+int pick_stale_cubes_with(aic_ctx *c, const char *who, const aic_stale_cubes_desc *d, const BlockFind *find, const void *src, const uint32_t *order, uint32_t *pixels_out,
+                          aic_stale_cubes_info *info, aic_block_cubes_info *found) {
     if (const int rc = pick_args_invalid(c, who, d->width, d->height, d->flags & ~(AIC_STALE_DEPTH_TEST | AIC_STALE_DEPTH_BEHIND), d->n, pixels_out, order)) return rc;
     if (const int rc = split_frame_rule(c, who, src)) return rc;
     const uint64_t count = (uint64_t)d->width * d->height;
     if (d->n && !count) return reject(c, who, "an empty frame has no pixel to pick");
     if (const int rc = stale_cubes_args_invalid(c, who, d)) return rc;
+    if (find) {
+        if (const int rc = block_find_invalid(c, who, *find)) return rc;
+        if ((uint64_t)d->n_boxes + find->capacity + d->n_light_cubes > 0xFFFFFFFFull) return reject(c, who, "more than 2^32 - 1 boxes, runs and light cubes");
+    }
     const bool front = (d->flags & AIC_STALE_DEPTH_TEST) != 0, behind = (d->flags & AIC_STALE_DEPTH_BEHIND) != 0;
-    const uint32_t n_total = d->n_boxes + d->n_light_cubes;
-    const bool look = d->n && n_total && d->max_stale;  // whether anything is looked at
-    const bool reads_frame = look && (front || (behind && d->n_light_cubes));
-    if (reads_frame && !src) return reject(c, who, "no frame to test the depths of");
+    // a find runs when anything can be looked at; what it finds is known only once it has run, so a frame that may be read counts as read
+    const bool finds = find && d->n && d->max_stale && block_find_scans(c, *find);
+    const bool may_look = d->n && d->max_stale && (d->n_boxes || d->n_light_cubes || finds);
+    if (may_look && (front || (behind && d->n_light_cubes)) && !src) return reject(c, who, "no frame to test the depths of");
     if (const int rc = begin(c, who)) return rc;
     if (!d->n) return AIC_OK;  // (and so count == 0)
     aic_ctx::FrameSlot &fs = c->slots[0];
+    BlockCubesParams bp = {};
+    uint32_t n_found = 0u;
+    if (finds) {
+        if (const int rc = block_find_events(c)) return rc;
+        if (const int rc = block_find_count(c, *find, fs, bp, found)) return rc;
+        n_found = found->n_written;
+    }
+    const uint32_t n_total = d->n_boxes + n_found + d->n_light_cubes;
+    const bool look = d->n && n_total && d->max_stale;  // whether anything is looked at
+    const bool reads_frame = look && (front || (behind && d->n_light_cubes));
     StaleCubesParams sp = {};
     if (look)
-        if (const int rc = stale_cubes_stage(c, d, sp, fs.stream)) return rc;
+        if (const int rc = stale_cubes_stage(c, d, sp, fs.stream, n_found)) return rc;
+    hipError_t e;
+    if (n_found) {  // the found boxes, behind the desc's own: the one box of a merged find from the host's record, else written where the pick reads them
+        int32_t *at = const_cast<int32_t *>(sp.boxes) + 6u * (size_t)d->n_boxes;
+        if (found->merged) {
+            HIP_TRY(c, hipMemcpyAsync(at, found->bounds, sizeof(found->bounds), hipMemcpyHostToDevice, fs.stream));
+        } else {
+            bp.boxes = at;
+            bp.n_runs = n_found;
+            HIP_TRY(c, hipEventRecord(c->stale_blocks_ev[0], fs.stream));
+            if ((e = launch_write_block_cubes(bp, fs.stream)) != hipSuccess) return hip_fail(c, "launch write block cubes", e);
+            HIP_TRY(c, hipEventRecord(c->stale_blocks_ev[1], fs.stream));
+        }
+    }
     sp.color = reads_frame ? (const uint2 *)src : nullptr;
     sp.depth = reads_frame ? (const float *)((const unsigned char *)src + count * 8u) : nullptr;
     sp.order = order;
@@ -496,7 +595,6 @@ int aic_pick_stale_cubes(aic_ctx *c, const aic_stale_cubes_desc *d, const void *
     sp.depth_behind = behind ? 1u : 0u;
     sp.skip_stale = d->skip_stale;
     sp.cursor = d->cursor;
-    hipError_t e;
     HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
     if ((e = launch_pick_stale_cubes(sp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick stale cubes", e);
     HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
@@ -515,6 +613,60 @@ int aic_pick_stale_cubes(aic_ctx *c, const aic_stale_cubes_desc *d, const void *
     info->n_rects = rec.n_rects;
     info->whole_frame = rec.whole_frame ? 1u : 0u;
     HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    if (n_found && !found->merged) {
+        float write_ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&write_ms, c->stale_blocks_ev[0], c->stale_blocks_ev[1]));
+        found->kernel_ms += write_ms;
+    }
+    return AIC_OK;
+}
+
+}  // namespace
+
+int aic_pick_stale_cubes(aic_ctx *c, const aic_stale_cubes_desc *d, const void *src, const uint32_t *order, uint32_t *pixels_out, aic_stale_cubes_info *info) {
+    const char *who = "aic_pick_stale_cubes";
+    if (!c || !d || !info) return reject(c, who, "bad argument");
+    std::memset(info, 0, sizeof(*info));
+    return pick_stale_cubes_with(c, who, d, nullptr, src, order, pixels_out, info, nullptr);
+}
+
+int aic_pick_stale_blocks(aic_ctx *c, const aic_stale_blocks_desc *d, const void *src, const uint32_t *order, uint32_t *pixels_out, aic_stale_blocks_info *info) {
+    const char *who = "aic_pick_stale_blocks";
+    if (!c || !d || !info) return reject(c, who, "bad argument");
+    std::memset(info, 0, sizeof(*info));
+    const BlockFind find = {d->layer, d->n_blocks, d->block_indices, d->max_runs};
+    return pick_stale_cubes_with(c, who, &d->cubes, d->n_blocks ? &find : nullptr, src, order, pixels_out, &info->pick, &info->found);
+}
+
+int aic_find_block_cubes(aic_ctx *c, int layer, uint32_t n_blocks, const uint32_t *block_indices, uint32_t capacity, int32_t *out_boxes, aic_block_cubes_info *info) {
+    const char *who = "aic_find_block_cubes";
+    if (!c || !info) return reject(c, who, "bad argument");
+    std::memset(info, 0, sizeof(*info));
+    const BlockFind find = {layer, n_blocks, block_indices, capacity};
+    if (const int rc = block_find_invalid(c, who, find)) return rc;
+    if (capacity && !out_boxes) return reject(c, who, "no boxes to write to");
+    if (const int rc = begin(c, who)) return rc;
+    if (!block_find_scans(c, find)) return AIC_OK;
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    BlockCubesParams bp = {};
+    if (const int rc = block_find_count(c, find, fs, bp, info)) return rc;
+    if (!info->n_written) return AIC_OK;
+    if (info->merged) {
+        std::memcpy(out_boxes, info->bounds, sizeof(info->bounds));
+        return AIC_OK;
+    }
+    hipError_t e = c->stale_blocks_boxes.ensure(6u * (size_t)info->n_written);
+    if (e != hipSuccess) return hip_fail(c, "alloc stale blocks boxes", e);
+    bp.boxes = c->stale_blocks_boxes.p;
+    bp.n_runs = info->n_written;
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));  // (the count's time has been read)
+    if ((e = launch_write_block_cubes(bp, fs.stream)) != hipSuccess) return hip_fail(c, "launch write block cubes", e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    HIP_TRY(c, hipMemcpyAsync(out_boxes, bp.boxes, 24u * (size_t)info->n_written, hipMemcpyDeviceToHost, fs.stream));
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    float write_ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&write_ms, fs.ev0, fs.ev1));
+    info->kernel_ms += write_ms;
     return AIC_OK;
 }
 

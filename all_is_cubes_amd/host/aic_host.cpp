@@ -555,7 +555,14 @@ bool HipRtRenderer::sync_space(int layer, const std::shared_ptr<Space> &space, c
         if (todo.everything || !todo.blocks.empty()) changed_boxes_.push_back({b.lo[0], b.lo[1], b.lo[2], b.hi[0], b.hi[1], b.hi[2]});
         else
             for (const auto &c : todo.cubes) changed_boxes_.push_back({c[0], c[1], c[2], c[0] + 1, c[1] + 1, c[2] + 1});
-        if (!changed_boxes_.empty()) pick_skip_stale_ = 0;
+        // changed_cube_boxes() and changed_blocks(): the cubes one by one also beside a re-evaluated block, whose index is recorded instead of the whole
+        // space (pick_stale_blocks finds its cubes on the device); the whole space only after a whole upload
+        if (todo.everything) changed_cube_boxes_.push_back({b.lo[0], b.lo[1], b.lo[2], b.hi[0], b.hi[1], b.hi[2]});
+        else {
+            for (const auto &c : todo.cubes) changed_cube_boxes_.push_back({c[0], c[1], c[2], c[0] + 1, c[1] + 1, c[2] + 1});
+            changed_blocks_.insert(changed_blocks_.end(), todo.blocks.begin(), todo.blocks.end());
+        }
+        if (!changed_boxes_.empty()) pick_skip_stale_ = 0;  // (a re-sent block put the whole space there: it restarts the count too)
     }
     if (todo.everything) {
         upload_full(layer, *space);
@@ -615,6 +622,8 @@ bool HipRtRenderer::update_scene(const Cursor *cursor) {  // renderer.rs:96-161
     std::memcpy(backdrop_, sc.ui.backdrop, sizeof(backdrop_));
     show_ui_ = sc.graphics_options.show_ui;
     changed_boxes_.clear();
+    changed_cube_boxes_.clear();
+    changed_blocks_.clear();
     bool changed = sync_space(AIC_LAYER_WORLD, sc.world_space, world_camera_.options());
     changed |= sync_space(AIC_LAYER_UI, show_ui_ ? sc.ui.space : nullptr, ui_camera_.options());
     return changed;
@@ -778,6 +787,50 @@ aic_stale_cubes_info HipRtRenderer::pick_stale_cubes(const void *device_frame, c
     check(aic_pick_stale_cubes(ctx_, &d, device_frame, device_order, device_pixels_out, &info), "aic_pick_stale_cubes");
     pick_cursor_ = info.next_cursor;
     pick_skip_stale_ += info.n_from_stale;
+    return info;
+}
+
+std::pair<std::vector<std::array<int32_t, 6>>, aic_block_cubes_info> HipRtRenderer::find_block_cubes(const std::vector<uint32_t> &indices, uint32_t capacity) {
+    std::vector<std::array<int32_t, 6>> boxes(capacity);
+    aic_block_cubes_info info;
+    check(aic_find_block_cubes(ctx_, AIC_LAYER_WORLD, (uint32_t)indices.size(), indices.empty() ? nullptr : indices.data(), capacity,
+                               capacity ? boxes[0].data() : nullptr, &info),
+          "aic_find_block_cubes");
+    boxes.resize(info.n_written);
+    return {std::move(boxes), info};
+}
+
+aic_stale_blocks_info HipRtRenderer::pick_stale_blocks(const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n,
+                                                       uint32_t max_stale, uint32_t flags, int32_t expand, uint32_t max_runs) {
+    const Viewport vp = world_camera_.viewport();
+    if (vp.framebuffer_width != pick_width_ || vp.framebuffer_height != pick_height_) {
+        pick_width_ = vp.framebuffer_width;
+        pick_height_ = vp.framebuffer_height;
+        pick_cursor_ = pick_skip_unknown_ = pick_skip_stale_ = 0;
+    }
+    const Mat4 m = world_camera_.view_matrix().then(world_camera_.projection_matrix());  // row-vector order: read column-major it is projection x view
+    aic_stale_blocks_desc d{};
+    d.cubes.width = pick_width_;
+    d.cubes.height = pick_height_;
+    d.cubes.n = n;
+    d.cubes.max_stale = max_stale;
+    d.cubes.skip_stale = pick_skip_stale_;
+    d.cubes.cursor = pick_cursor_;
+    std::memcpy(d.cubes.view_projection, m.m, sizeof(d.cubes.view_projection));
+    d.cubes.n_boxes = (uint32_t)changed_cube_boxes_.size();
+    d.cubes.expand = expand;
+    d.cubes.n_light_cubes = (uint32_t)changed_light_cubes_.size();
+    d.cubes.flags = flags;
+    d.cubes.boxes = changed_cube_boxes_.empty() ? nullptr : changed_cube_boxes_[0].data();
+    d.cubes.light_cubes = changed_light_cubes_.empty() ? nullptr : changed_light_cubes_[0].data();
+    d.layer = AIC_LAYER_WORLD;
+    d.n_blocks = (uint32_t)changed_blocks_.size();
+    d.block_indices = changed_blocks_.empty() ? nullptr : changed_blocks_.data();
+    d.max_runs = max_runs;
+    aic_stale_blocks_info info;
+    check(aic_pick_stale_blocks(ctx_, &d, device_frame, device_order, device_pixels_out, &info), "aic_pick_stale_blocks");
+    pick_cursor_ = info.pick.next_cursor;
+    pick_skip_stale_ += info.pick.n_from_stale;
     return info;
 }
 

@@ -487,6 +487,17 @@ class HipRtRenderer : public HeadlessRenderer {
     void clear_changed_light_cubes() { changed_light_cubes_.clear(); }
     aic_stale_cubes_info pick_stale_cubes(const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n, uint32_t max_stale,
                                           uint32_t flags = 0, int32_t expand = 1);
+    // The same for a re-evaluated block (todo.blocks, updating.rs:139-153; aic_find_block_cubes, aic_pick_stale_blocks), for which
+    // changed_boxes() can only name the whole space. changed_blocks: the block indices the last update() re-sent; changed_cube_boxes: the cubes it sent
+    // one by one, also beside a re-sent block, and the space's bounds only after a whole upload (then changed_blocks is empty). find_block_cubes: the
+    // world layer's cubes that hold one of `indices`, as runs along z, or their one bounding box when there are more than `capacity`. pick_stale_blocks:
+    // pick_stale_cubes with changed_cube_boxes(), the light cubes and, found on the device, the cubes of changed_blocks(); it keeps the picker's cursor
+    // and the count of stale pixels handed out as pick_stale_cubes does.
+    const std::vector<uint32_t> &changed_blocks() const { return changed_blocks_; }
+    const std::vector<std::array<int32_t, 6>> &changed_cube_boxes() const { return changed_cube_boxes_; }
+    std::pair<std::vector<std::array<int32_t, 6>>, aic_block_cubes_info> find_block_cubes(const std::vector<uint32_t> &indices, uint32_t capacity);
+    aic_stale_blocks_info pick_stale_blocks(const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n, uint32_t max_stale,
+                                            uint32_t flags = 0, int32_t expand = 1, uint32_t max_runs = 65536);
     // raytrace_to_texture's per-frame presentation of its resident textures (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71, bloom.rs:41-60,
     // shaders/postprocess.wgsl:140-158 and 251-276; aic_present_split): the resident Split frame `src_device` -- of raytracer's viewport, i.e. the current
     // (size-policy-modified) viewport -- stretched with a linear filter to out_width x out_height, bloomed, tone-mapped and encoded, with bloom_intensity,
@@ -604,6 +615,8 @@ class HipRtRenderer : public HeadlessRenderer {
     uint64_t pick_cursor_ = 0, pick_skip_unknown_ = 0;  // pick_pixels
     uint64_t pick_skip_stale_ = 0;  // pick_stale
     std::vector<std::array<int32_t, 6>> changed_boxes_;  // of the last update(), world layer
+    std::vector<std::array<int32_t, 6>> changed_cube_boxes_;  // of the last update(), world layer: the cubes sent one by one, or the bounds after a whole upload
+    std::vector<uint32_t> changed_blocks_;                    // ... and the block indices it re-sent
     std::vector<std::array<int32_t, 3>> changed_light_cubes_;  // what the light updates reported since clear_changed_light_cubes()
     void take_changed_light();  // aic_light_changed_take of the world layer, appended to changed_light_cubes_
     uint32_t pick_width_ = 0, pick_height_ = 0;         // ... and the viewport they belong to

@@ -440,6 +440,39 @@ PYBIND11_MODULE(_host, m) {
             d["kernel_ms"] = i.kernel_ms; d["n_rects"] = i.n_rects; d["whole_frame"] = i.whole_frame;
             return d;
         }, py::arg("frame_ptr"), py::arg("order_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("max_stale"), py::arg("flags") = 0u, py::arg("expand") = 1)
+        .def("changed_blocks", [](const HipRtRenderer &r) { return r.changed_blocks(); })
+        .def("changed_cube_boxes", [](const HipRtRenderer &r) { return r.changed_cube_boxes(); })
+        .def("find_block_cubes", [](HipRtRenderer &r, const std::vector<uint32_t> &indices, uint32_t capacity) {
+            // -> (list of boxes, dict(n_cubes, n_runs, bounds, n_written, merged, kernel_ms))
+            std::pair<std::vector<std::array<int32_t, 6>>, aic_block_cubes_info> res;
+            {
+                py::gil_scoped_release release;
+                res = r.find_block_cubes(indices, capacity);
+            }
+            const aic_block_cubes_info &i = res.second;
+            py::dict d;
+            d["n_cubes"] = i.n_cubes; d["n_runs"] = i.n_runs; d["bounds"] = std::vector<int32_t>(i.bounds, i.bounds + 6);
+            d["n_written"] = i.n_written; d["merged"] = i.merged; d["kernel_ms"] = i.kernel_ms;
+            return py::make_tuple(res.first, d);
+        }, py::arg("indices"), py::arg("capacity"))
+        .def("pick_stale_blocks", [](HipRtRenderer &r, uintptr_t frame_ptr, uintptr_t order_ptr, uintptr_t out_ptr, uint32_t n, uint32_t max_stale, uint32_t flags, int32_t expand,
+                                     uint32_t max_runs) {
+            // -> dict(pick = pick_stale_cubes' dict, found = find_block_cubes' dict)
+            aic_stale_blocks_info i;
+            {
+                py::gil_scoped_release release;
+                i = r.pick_stale_blocks(reinterpret_cast<const void *>(frame_ptr), reinterpret_cast<const uint32_t *>(order_ptr), reinterpret_cast<uint32_t *>(out_ptr), n, max_stale,
+                                        flags, expand, max_runs);
+            }
+            py::dict p, f, d;
+            p["n_stale"] = i.pick.n_stale; p["next_cursor"] = i.pick.next_cursor; p["n_from_stale"] = i.pick.n_from_stale; p["n_from_order"] = i.pick.n_from_order;
+            p["kernel_ms"] = i.pick.kernel_ms; p["n_rects"] = i.pick.n_rects; p["whole_frame"] = i.pick.whole_frame;
+            f["n_cubes"] = i.found.n_cubes; f["n_runs"] = i.found.n_runs; f["bounds"] = std::vector<int32_t>(i.found.bounds, i.found.bounds + 6);
+            f["n_written"] = i.found.n_written; f["merged"] = i.found.merged; f["kernel_ms"] = i.found.kernel_ms;
+            d["pick"] = p; d["found"] = f;
+            return d;
+        }, py::arg("frame_ptr"), py::arg("order_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("max_stale"), py::arg("flags") = 0u, py::arg("expand") = 1,
+           py::arg("max_runs") = 65536u)
         .def_property_readonly("pick_skip_stale", &HipRtRenderer::pick_skip_stale)
         .def_property_readonly("pick_cursor", &HipRtRenderer::pick_cursor)
         .def_property_readonly("pick_skip_unknown", &HipRtRenderer::pick_skip_unknown)

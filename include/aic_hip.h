@@ -592,6 +592,70 @@ typedef struct aic_stale_cube_rect {
 int aic_pick_stale_cubes(aic_ctx *ctx, const aic_stale_cubes_desc *desc, const void *src_device, const uint32_t *order_device,
                          uint32_t *pixels_out_device, aic_stale_cubes_info *info);
 int aic_probe_stale_cube_rects(aic_ctx *ctx, const aic_stale_cubes_desc *desc, aic_stale_cube_rect *out /* [n_boxes + n_light_cubes] */);
+/* Adds what the reference does not have: the third kind of scene change under a resident frame, a block DEFINITION that changed (the reference's
+ * todo.blocks, updating.rs:139-153; here aic_replace_block(s)). The cube grid does not change under such a call, only what the cubes holding that index
+ * look like; aic_find_block_cubes finds those cubes in the layer's resident grid, and aic_pick_stale_blocks is aic_pick_stale_cubes with their boxes
+ * added on the device. DESIGN.md 4.20 states the rule; tests/stale_blocks_ref.py is that text in NumPy.
+ *
+ * The rule. The layer's grid has size (sx, sy, sz) and lower corner lo; entry i = (x * sy + y) * sz + z (x, y, z from 0).
+ *   - The index of an entry is its low 14 bits when the layer's grid carries tags (a block table of at most 16384 entries), else the entry itself. A cube
+ *     the library has marked OPEN keeps its index bits and matches like any other.
+ *   - match[i]: the entry's index is one of block_indices[n_blocks]. Duplicates among them are legal.
+ *   - A run is a maximal stretch of consecutive matching entries inside one (x, y) row; runs never continue from z = sz - 1 into the next row.
+ *   - The run list is sorted by the first entry's linear index. Box k is {lo.x + x, lo.y + y, lo.z + z0, lo.x + x + 1, lo.y + y + 1, lo.z + z1}, upper
+ *     bounds exclusive, for the run z0 .. z1 - 1 of row (x, y).
+ *   - info.n_cubes is the number of matches, info.n_runs the number of runs, info.bounds the smallest box holding all matches, all 0 when there are none.
+ * What is written to out_boxes[capacity][6] (host memory):
+ *     n_runs <= capacity                 every run, in order      n_written = n_runs   merged = 0
+ *     n_runs > capacity, capacity >= 1   the one box `bounds`     n_written = 1        merged = 1
+ *     n_runs > capacity, capacity = 0    nothing                  n_written = 0        merged = 1
+ *     n_runs = 0                         nothing                  n_written = 0        merged = 0
+ * so that a block filling half the world costs one box and not gigabytes of scratch. The result is the same bytes on every run.
+ *
+ * aic_pick_stale_blocks, by composition: the list and info.pick are exactly what aic_pick_stale_cubes gives for desc.cubes with, behind its own boxes,
+ * the found.n_written boxes of aic_find_block_cubes(layer, block_indices, max_runs) -- same expand, flags, skip_stale, cursor and light cubes. The found
+ * boxes never leave the device. With n_blocks = 0 the call is aic_pick_stale_cubes itself; when nothing is looked at (cubes.n = 0 or cubes.max_stale = 0)
+ * no find runs and info.found is all 0. pick.kernel_ms covers the pick's launches and found.kernel_ms the find's.
+ *
+ * Both calls block, run on slot 0 and take its rule (no frame may occupy slot 0), like their siblings, and are ordered behind every earlier scene call
+ * (aic_upload_space, aic_update_cubes, aic_replace_block(s), aic_compact) the way a frame submitted at that point would be. They only read the grid, which
+ * the light updater never writes: they do NOT end a pending aic_evaluate_light_submit, and they are legal with frames in flight on other slots. Scratch
+ * (8 KB of set, 12 bytes per 2048 grid entries, 24 bytes a run written) belongs to the context, is allocated on first use, again when a call needs
+ * more, and released in aic_destroy.
+ * Rejected before anything is queued, with AIC_ERR_INVALID and the context still usable: a NULL info; NULL block_indices with n_blocks > 0; an index at
+ * or above the layer's block count; a layer that is not 0 or 1 or has no space; out_boxes NULL with capacity > 0; for aic_pick_stale_blocks also
+ * everything aic_pick_stale_cubes rejects and cubes.n_boxes + max_runs + cubes.n_light_cubes above 2^32 - 1. One of those rules is wider here: what a
+ * find gives is known only once it has run, so with n > 0, max_stale > 0, n_blocks > 0 and a grid that is not empty a NULL src_device is rejected under
+ * AIC_STALE_DEPTH_TEST, and under AIC_STALE_DEPTH_BEHIND when cubes.n_light_cubes > 0 (the behind test is a light cube's alone), also when the find
+ * would give no box.
+ * Limits: LightingOption::Bounce rays go anywhere. A found box is projected like any other box: one with a corner at or behind the camera plane once it
+ * is grown by expand -- a cube holding the block beside or behind the camera, as happens whenever the camera stands inside the space among such cubes --
+ * has the whole frame for its rectangle, and then every pixel is stale as before (info.pick.whole_frame = 1). The light the re-evaluated block gives off or blocks is the light updater's matter
+ * (aic_light_cubes_changed, aic_light_changed_take), not found here. */
+typedef struct aic_block_cubes_info {
+    uint64_t n_cubes, n_runs;
+    int32_t  bounds[6];      /* {lo x, y, z, hi x, y, z}, upper bounds exclusive */
+    uint32_t n_written;      /* boxes written to out */
+    uint32_t merged;         /* 1: n_runs > capacity, the runs were not written one by one */
+    float    kernel_ms;      /* HIP events around the find's launches */
+    uint32_t reserved;
+} aic_block_cubes_info;
+int aic_find_block_cubes(aic_ctx *ctx, int layer, uint32_t n_blocks, const uint32_t *block_indices /* host */, uint32_t capacity,
+                         int32_t *out_boxes /* [capacity][6], host; may be NULL when capacity = 0 */, aic_block_cubes_info *info);
+typedef struct aic_stale_blocks_desc {
+    aic_stale_cubes_desc cubes;     /* everything aic_pick_stale_cubes takes */
+    int32_t  layer;
+    uint32_t n_blocks;
+    const uint32_t *block_indices;  /* [n_blocks]; host memory */
+    uint32_t max_runs;              /* capacity of the find */
+    uint32_t reserved;
+} aic_stale_blocks_desc;
+typedef struct aic_stale_blocks_info {
+    aic_stale_cubes_info pick;
+    aic_block_cubes_info found;
+} aic_stale_blocks_info;
+int aic_pick_stale_blocks(aic_ctx *ctx, const aic_stale_blocks_desc *desc, const void *src_device, const uint32_t *order_device,
+                          uint32_t *pixels_out_device, aic_stale_blocks_info *info);
 /* replaces: what raytrace_to_texture does with its resident textures every displayed frame: RaytraceToTexture::draw
  * (all-is-cubes-gpu/src/raytrace_to_texture.rs:546-568) draws rt_frame_copy_vertex / rt_frame_copy_fragment (shaders/rt-copy.wgsl:41-71) into the linear
  * scene texture -- the pipeline's linear ClampToEdge sampler stretches the frame to the viewport (the reference traces at half the nominal size,

@@ -265,6 +265,36 @@ pub struct aic_stale_cubes_info {
 }
 
 #[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_block_cubes_info {
+    pub n_cubes: u64,
+    pub n_runs: u64,
+    pub bounds: [i32; 6],
+    pub n_written: u32,
+    pub merged: u32,
+    pub kernel_ms: f32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct aic_stale_blocks_desc {
+    pub cubes: aic_stale_cubes_desc,
+    pub layer: i32,
+    pub n_blocks: u32,
+    pub block_indices: *const u32,
+    pub max_runs: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_stale_blocks_info {
+    pub pick: aic_stale_cubes_info,
+    pub found: aic_block_cubes_info,
+}
+
+#[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct aic_stale_cube_rect {
     pub x0: u32,
@@ -505,6 +535,23 @@ unsafe extern "C" {
         info: *mut aic_stale_cubes_info,
     ) -> c_int;
     pub fn aic_probe_stale_cube_rects(ctx: *mut aic_ctx, desc: *const aic_stale_cubes_desc, out: *mut aic_stale_cube_rect) -> c_int;
+    pub fn aic_find_block_cubes(
+        ctx: *mut aic_ctx,
+        layer: c_int,
+        n_blocks: u32,
+        block_indices: *const u32,
+        capacity: u32,
+        out_boxes: *mut i32,
+        info: *mut aic_block_cubes_info,
+    ) -> c_int;
+    pub fn aic_pick_stale_blocks(
+        ctx: *mut aic_ctx,
+        desc: *const aic_stale_blocks_desc,
+        src_device: *const c_void,
+        order_device: *const u32,
+        pixels_out_device: *mut u32,
+        info: *mut aic_stale_blocks_info,
+    ) -> c_int;
     pub fn aic_light_changed_count(ctx: *mut aic_ctx, layer: c_int, n: *mut u64, bounds: *mut i32) -> c_int;
     pub fn aic_light_changed_take(ctx: *mut aic_ctx, layer: c_int, capacity: u32, xyz: *mut i32, n_written: *mut u32) -> c_int;
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;

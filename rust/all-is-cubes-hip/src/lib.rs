@@ -87,6 +87,8 @@ struct LayerSync {
     todo: listen::StoreLock<Todo>,
     listening: bool,
     n_blocks: usize,
+    /// the block indices the last `sync_layer` re-sent because their definition changed (`todo.blocks`): what `pick_stale_blocks` takes
+    resent_blocks: Vec<u32>,
 }
 
 /// Renderer-specific diagnostic information: the device's `RaytraceInfo` sums and kernel time.
@@ -438,6 +440,7 @@ impl HipRtRenderer {
                     todo: listen::StoreLock::new(Todo { everything: true, ..Todo::default() }),
                     listening: false,
                     n_blocks: 0,
+                    resent_blocks: Vec::new(),
                 });
             }
             (None, s) => {
@@ -454,6 +457,7 @@ impl HipRtRenderer {
         }
         let todo = &mut *sync.todo.lock();
         let block_data = space.block_data();
+        sync.resent_blocks.clear();
         if core::mem::take(&mut todo.everything) {
             // == SpaceRaytracer::new (sr.rs:64-88)
             let flat = FlatSpace::new(&space);
@@ -463,7 +467,9 @@ impl HipRtRenderer {
         } else {
             // appended blocks, then re-evaluated ones (updating.rs:139-153): one batched call
             let mut indices: Vec<u32> = (sync.n_blocks..block_data.len()).map(|i| i as u32).collect();
+            let appended = indices.len();
             indices.extend(todo.blocks.drain().map(u32::from).filter(|&i| (i as usize) < sync.n_blocks));
+            sync.resent_blocks.extend_from_slice(&indices[appended..]);
             if !indices.is_empty() {
                 let flat: Vec<_> = indices.iter().map(|&i| flatten_block(&block_data[i as usize])).collect();
                 let descs: Vec<_> = flat.iter().map(|b| b.desc).collect();
@@ -1005,6 +1011,103 @@ impl HipRtRenderer {
         let mut info = ffi::aic_stale_cubes_info::default();
         // SAFETY: the context is live; the caller vouches for the frame and the two lists; both arrays are copied before the call returns
         self.device.check(unsafe { ffi::aic_pick_stale_cubes(ctx.as_ptr(), &desc, src_device, order_device, pixels_out_device, &mut info) })?;
+        Ok(info)
+    }
+
+    /// The world layer's block indices whose definition the last [`Self::update_scene`] re-sent (the reference's `todo.blocks`, updating.rs:139-153):
+    /// the cube grid did not change under them, only what the cubes holding them look like. [`Self::pick_stale_blocks`] takes them as `blocks`.
+    /// Empty after a whole upload, which makes every pixel stale.
+    #[must_use]
+    pub fn changed_blocks(&self) -> &[u32] {
+        self.layers.world.as_ref().map_or(&[][..], |sync| sync.resent_blocks.as_slice())
+    }
+
+    /// The cubes of the world layer that hold one of the block indices `blocks`, as runs along z (`aic_find_block_cubes`; not in the reference): boxes
+    /// `[lower, upper)` sorted by a run's first cube in the grid's linear order. With more runs than `capacity` the one box `info.bounds` is returned
+    /// instead (none with `capacity` 0) and `info.merged` is 1.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub fn find_block_cubes(&mut self, blocks: &[u32], capacity: u32) -> Result<(Vec<[i32; 6]>, ffi::aic_block_cubes_info), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("find_block_cubes needs a single-device renderer") };
+        let mut out = vec![[0i32; 6]; capacity as usize];
+        let mut info = ffi::aic_block_cubes_info::default();
+        // SAFETY: the context is live; `blocks` holds as many indices as are passed and `out` holds `capacity` boxes of six coordinates
+        self.device.check(unsafe {
+            ffi::aic_find_block_cubes(
+                ctx.as_ptr(),
+                ffi::AIC_LAYER_WORLD,
+                u32::try_from(blocks.len()).unwrap_or(u32::MAX),
+                blocks.as_ptr(),
+                capacity,
+                if capacity == 0 { core::ptr::null_mut() } else { out.as_mut_ptr().cast() },
+                &mut info,
+            )
+        })?;
+        out.truncate(info.n_written as usize);
+        Ok((out, info))
+    }
+
+    /// [`Self::pick_stale_cubes`] with, behind `boxes`, the boxes [`Self::find_block_cubes`]`(blocks, max_runs)` gives, found and kept on the device
+    /// (`aic_pick_stale_blocks`; not in the reference): the pixels a re-evaluated block made stale first. `blocks` is [`Self::changed_blocks`] of the
+    /// update that re-sent them, kept by the caller until no stale pixel is handed out any more.
+    ///
+    /// # Safety
+    /// As [`Self::pick_stale`].
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn pick_stale_blocks(
+        &mut self,
+        boxes: &[[i32; 6]],
+        expand: i32,
+        light_cubes: &[[i32; 3]],
+        blocks: &[u32],
+        max_runs: u32,
+        flags: u32,
+        src_device: *const core::ffi::c_void,
+        order_device: *const u32,
+        pixels_out_device: *mut u32,
+        n: u32,
+        max_stale: u32,
+        skip_stale: u64,
+        cursor: u64,
+    ) -> Result<ffi::aic_stale_blocks_info, RenderError> {
+        let Device::One(ctx) = self.device else { panic!("pick_stale_blocks needs a single-device renderer") };
+        let (viewport, _) = self.frame_desc();
+        let camera = &self.cameras.cameras().world;
+        let desc = ffi::aic_stale_blocks_desc {
+            cubes: ffi::aic_stale_cubes_desc {
+                width: viewport.framebuffer_size.width,
+                height: viewport.framebuffer_size.height,
+                n,
+                max_stale,
+                skip_stale,
+                cursor,
+                view_projection: camera.view_matrix().then(&camera.projection_matrix()).to_array(),
+                n_boxes: u32::try_from(boxes.len()).unwrap_or(u32::MAX),
+                expand,
+                n_light_cubes: u32::try_from(light_cubes.len()).unwrap_or(u32::MAX),
+                flags,
+                boxes: boxes.as_ptr().cast(),
+                light_cubes: light_cubes.as_ptr().cast(),
+            },
+            layer: ffi::AIC_LAYER_WORLD,
+            n_blocks: u32::try_from(blocks.len()).unwrap_or(u32::MAX),
+            block_indices: blocks.as_ptr(),
+            max_runs,
+            reserved: 0,
+        };
+        let mut info = ffi::aic_stale_blocks_info::default();
+        // SAFETY: the context is live; the caller vouches for the frame and the two lists; the three arrays are copied before the call returns
+        self.device.check(unsafe { ffi::aic_pick_stale_blocks(ctx.as_ptr(), &desc, src_device, order_device, pixels_out_device, &mut info) })?;
         Ok(info)
     }
 

@@ -22,6 +22,7 @@
 #include "aic_present_lines.h"
 #include "aic_reproject.h"
 #include "aic_stale.h"
+#include "aic_stale_blocks.h"
 #include "aic_stale_cubes.h"
 #include "record.h"
 
@@ -340,6 +341,15 @@ hipError_t launch_project_stale_cubes(const StaleCubesParams &p, hipStream_t str
     rec("launch_project_stale_cubes scratch %s boxes %s light_cubes %s rects %s %ux%u n_boxes %u n_light_cubes %u expand %d %s", P(p.scratch), P(p.boxes), P(p.light_cubes), P(p.rects), p.width,
         p.height, p.n_boxes, p.n_light_cubes, p.expand, S(stream));
     return failing("launch_project_stale_cubes") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_count_block_cubes(const BlockCubesParams &p, hipStream_t stream) {
+    rec("launch_count_block_cubes grid %s n %llu size %u %u %u lo %d %d %d index_mask %04x set_words %u scratch %s %s", P(p.grid), p.n, p.sx, p.sy, p.sz, p.lo[0], p.lo[1], p.lo[2], p.index_mask,
+        p.set_words, P(p.scratch), S(stream));
+    return failing("launch_count_block_cubes") ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t launch_write_block_cubes(const BlockCubesParams &p, hipStream_t stream) {
+    rec("launch_write_block_cubes grid %s n %llu scratch %s boxes %s n_runs %u %s", P(p.grid), p.n, P(p.scratch), P(p.boxes), p.n_runs, S(stream));
+    return failing("launch_write_block_cubes") ? hipErrorInvalidValue : hipSuccess;
 }
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
