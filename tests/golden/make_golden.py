@@ -64,6 +64,11 @@ PNG_CASES = [
     "viewport_zero-all", "viewport_zero-2-all", "layers_none_but_text-all",
     # round 3: the info-text overlay (renderer.rs:659-683) drawn by the host mirror
     "info_text-1.0-all", "info_text-1.5-ray", "info_text-2.0-ray",
+    # the bloom chain against the reference's own image (tests/test_bloom_cpu.py)
+    "bloom-0.25-all",
+    # the Split presentation path (tests/test_present_goldens_cpu.py, tests/test_gpu_present_goldens.py): the cursor's lines under the
+    # frame's depth, and the text of the renderer that scales it with the viewport (the `-ray` images of 1.5 and 2.0 above do not)
+    "cursor_basic-all", "info_text-1.5-all", "info_text-2.0-all",
 ]
 
 

@@ -114,17 +114,22 @@ def expected_split(name: str):
     """(depth [HT, W] f64 before the transform, layer [HT, W]: +1 world, -1 UI, first_sample_depth [HT, W]) from the oracle, computed once per case."""
     world, ui, opt, _, backdrop = case(name)
     inv, ui_inv = cameras(name)
+    return split_of(world, ui, opt, inv, ui_inv, backdrop, W, HT)
+
+
+def split_of(world, ui, opt, inv, ui_inv, backdrop, width, height):
+    """expected_split of any scene, cameras and frame size (tests/test_present_goldens_cpu.py and tests/test_gpu_present_goldens.py use it too)."""
     wsp = oracle.Space(world) if world is not None else None
     usp = oracle.Space(ui) if ui is not None else None
     points = SAMPLE_POINTS if opt.antialiasing == 2 else [(0.5, 0.5)]
     has_backdrop = any(v != 0 for v in backdrop)
-    depth = np.full((HT, W), np.inf)
-    first = np.full((HT, W), np.inf)
-    layer = np.zeros((HT, W), np.int8)
-    for y in range(HT):
-        y0, y1 = -(y / HT * 2.0 - 1.0), -((y + 1) / HT * 2.0 - 1.0)
-        for x in range(W):
-            x0, x1 = x / W * 2.0 - 1.0, (x + 1) / W * 2.0 - 1.0
+    depth = np.full((height, width), np.inf)
+    first = np.full((height, width), np.inf)
+    layer = np.zeros((height, width), np.int8)
+    for y in range(height):
+        y0, y1 = -(y / height * 2.0 - 1.0), -((y + 1) / height * 2.0 - 1.0)
+        for x in range(width):
+            x0, x1 = x / width * 2.0 - 1.0, (x + 1) / width * 2.0 - 1.0
             for i, (ux, uy) in enumerate(points):
                 if len(points) == 4:
                     px, py = x0 + (x1 - x0) * ux, y0 + (y1 - y0) * uy  # point_within_patch
@@ -158,8 +163,12 @@ def expected_split(name: str):
 
 def expected_planes(name, colorbuf, zw, rows=slice(None)):
     depth, layer, _ = expected_split(name)
-    depth, layer = depth[rows], layer[rows]
-    e = np.where(layer == -1, np.float32(UI_EXPOSURE), np.where(layer == 1, np.float32(WORLD_EXPOSURE), np.float32(1.0))).astype(np.float32)
+    return planes_of(depth[rows], layer[rows], colorbuf, zw, WORLD_EXPOSURE, UI_EXPOSURE)
+
+
+def planes_of(depth, layer, colorbuf, zw, world_exposure, ui_exposure):
+    """expected_planes from split_of's depth and layer: (colour plane f16, depth plane f32)."""
+    e = np.where(layer == -1, np.float32(ui_exposure), np.where(layer == 1, np.float32(world_exposure), np.float32(1.0))).astype(np.float32)
     cb = colorbuf.astype(np.float32)
     color = np.empty(cb.shape, np.float32)
     color[..., :3] = cb[..., :3] * e[..., None]
