@@ -7,7 +7,10 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include "aic_rank_list.h"
 
 namespace aic {
 
@@ -15,11 +18,10 @@ constexpr uint32_t kPickBlock = 256;  // ranks per scan block: one per thread
 
 // What the device leaves for the host (the first 32 bytes of the scratch); written by the scan, so only by a call with max_unknown > 0.
 struct PickRecord {
-    unsigned long long n_unknown;
-    unsigned long long next_cursor;
-    uint32_t n_from_unknown, n_from_order;
+    RankListRecord head;  // the set: the unknown ranks
     uint32_t pad[2];
 };
+static_assert(sizeof(PickRecord) == 32 && offsetof(PickRecord, head) == 0 && offsetof(PickRecord, pad) == 24, "pick_scratch_words and the host's copy count on it");
 
 // The scratch, in 32-bit words: the record, then per scan block its count of unknown ranks and the count of those before it.
 inline uint32_t pick_blocks(uint64_t count) { return (uint32_t)((count + kPickBlock - 1u) / kPickBlock); }

@@ -49,6 +49,28 @@ int pick_args_invalid(aic_ctx *c, const char *who, uint32_t w, uint32_t h, uint3
     return (((uintptr_t)pixels_out | (uintptr_t)order) & 3u) ? reject(c, who, "a list starts at a 4-byte boundary") : 0;
 }
 
+// How every picker ends once its launcher's parameters are filled: ev0, what `launch` queues, ev1, the picker's 32-byte record back from the head of
+// `scratch` -- or, with scratch == nullptr, nothing was looked at and the whole list is the picker's --, one synchronise and the time between the events.
+template <class Record, class Launch>
+int pick_finish(aic_ctx *c, const char *what, Launch launch, const void *scratch, uint32_t n, unsigned long long cursor, Record &rec, float *kernel_ms) {
+    static_assert(sizeof(Record) == 32 && offsetof(Record, head) == 0, "a picker's record: aic_rank_list.h's head and two words of its own");
+    aic_ctx::FrameSlot &fs = c->slots[0];
+    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
+    const hipError_t e = launch(fs.stream);
+    if (e != hipSuccess) return hip_fail(c, what, e);
+    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
+    rec = Record{};
+    if (scratch) {
+        HIP_TRY(c, hipMemcpyAsync(&rec, scratch, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
+    } else {
+        rec.head.n_from_order = n;
+        rec.head.next_cursor = cursor + n;
+    }
+    HIP_TRY(c, hipStreamSynchronize(fs.stream));
+    HIP_TRY(c, hipEventElapsedTime(kernel_ms, fs.ev0, fs.ev1));
+    return AIC_OK;
+}
+
 // What every operation opens with once its arguments are checked: slot 0's stream is the one it queues on. `who` is the entry point the message names.
 int begin(aic_ctx *c, const char *who) {
     HIP_TRY(c, hipSetDevice(c->device));
@@ -336,7 +358,6 @@ int aic_pick_pixels(aic_ctx *c, const aic_pick_desc *d, const uint32_t *order, u
         return fail(c, AIC_ERR_INVALID, "aic_pick_pixels: max_unknown needs the context's last successful aic_reproject_split to be of this size");
     hipError_t e;
     if (d->max_unknown && (e = c->pick_scratch.ensure(pick_scratch_words(count))) != hipSuccess) return hip_fail(c, "alloc pick scratch", e);
-    aic_ctx::FrameSlot &fs = c->slots[0];
     PickParams pp;
     pp.R = d->max_unknown ? (const uint2 *)(c->reproject_scratch.p + reproject_geometry(d->width, d->height).keys_bytes()) : nullptr;
     pp.order = order;
@@ -347,22 +368,12 @@ int aic_pick_pixels(aic_ctx *c, const aic_pick_desc *d, const uint32_t *order, u
     pp.max_unknown = d->max_unknown;
     pp.skip_unknown = d->skip_unknown;
     pp.cursor = d->cursor;
-    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
-    if ((e = launch_pick(pp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick", e);
-    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
-    PickRecord rec = {};
-    if (d->max_unknown) {
-        HIP_TRY(c, hipMemcpyAsync(&rec, c->pick_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
-    } else {  // nothing was looked at: the whole list is the picker's
-        rec.n_from_order = d->n;
-        rec.next_cursor = d->cursor + d->n;
-    }
-    HIP_TRY(c, hipStreamSynchronize(fs.stream));
-    info->n_unknown = rec.n_unknown;
-    info->next_cursor = rec.next_cursor;
-    info->n_from_unknown = rec.n_from_unknown;
-    info->n_from_order = rec.n_from_order;
-    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    PickRecord rec;
+    if (const int rc = pick_finish(c, "launch pick", [&](hipStream_t s) { return launch_pick(pp, s); }, pp.scratch, d->n, d->cursor, rec, &info->kernel_ms)) return rc;
+    info->n_unknown = rec.head.n_set;
+    info->next_cursor = rec.head.next_cursor;
+    info->n_from_unknown = rec.head.n_from_set;
+    info->n_from_order = rec.head.n_from_order;
     return AIC_OK;
 }
 
@@ -409,22 +420,12 @@ int aic_pick_stale(aic_ctx *c, const aic_stale_desc *d, const void *src, const u
     sp.skip_stale = d->skip_stale;
     sp.cursor = d->cursor;
     if (look) HIP_TRY(c, hipMemcpyAsync(c->stale_scratch.p + stale_rects_offset(count), rects.data(), sizeof(aic_stale_rect) * (size_t)n_rects, hipMemcpyHostToDevice, fs.stream));
-    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
-    if ((e = launch_pick_stale(sp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick stale", e);
-    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
-    StaleRecord rec = {};
-    if (look) {
-        HIP_TRY(c, hipMemcpyAsync(&rec, c->stale_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
-    } else {  // nothing was looked at: the whole list is the picker's
-        rec.n_from_order = d->n;
-        rec.next_cursor = d->cursor + d->n;
-    }
-    HIP_TRY(c, hipStreamSynchronize(fs.stream));  // (`rects` goes out of scope)
-    info->n_stale = rec.n_stale;
-    info->next_cursor = rec.next_cursor;
-    info->n_from_stale = rec.n_from_stale;
-    info->n_from_order = rec.n_from_order;
-    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
+    StaleRecord rec;  // (pick_finish synchronises before `rects` goes out of scope)
+    if (const int rc = pick_finish(c, "launch pick stale", [&](hipStream_t s) { return launch_pick_stale(sp, s); }, sp.scratch, d->n, d->cursor, rec, &info->kernel_ms)) return rc;
+    info->n_stale = rec.head.n_set;
+    info->next_cursor = rec.head.next_cursor;
+    info->n_from_stale = rec.head.n_from_set;
+    info->n_from_order = rec.head.n_from_order;
     return AIC_OK;
 }
 
@@ -595,24 +596,14 @@ int pick_stale_cubes_with(aic_ctx *c, const char *who, const aic_stale_cubes_des
     sp.depth_behind = behind ? 1u : 0u;
     sp.skip_stale = d->skip_stale;
     sp.cursor = d->cursor;
-    HIP_TRY(c, hipEventRecord(fs.ev0, fs.stream));
-    if ((e = launch_pick_stale_cubes(sp, fs.stream)) != hipSuccess) return hip_fail(c, "launch pick stale cubes", e);
-    HIP_TRY(c, hipEventRecord(fs.ev1, fs.stream));
-    StaleCubesRecord rec = {};
-    if (look) {
-        HIP_TRY(c, hipMemcpyAsync(&rec, c->stale_cubes_scratch.p, sizeof(rec), hipMemcpyDeviceToHost, fs.stream));
-    } else {  // nothing was looked at: the whole list is the picker's
-        rec.n_from_order = d->n;
-        rec.next_cursor = d->cursor + d->n;
-    }
-    HIP_TRY(c, hipStreamSynchronize(fs.stream));
-    info->n_stale = rec.n_stale;
-    info->next_cursor = rec.next_cursor;
-    info->n_from_stale = rec.n_from_stale;
-    info->n_from_order = rec.n_from_order;
+    StaleCubesRecord rec;
+    if (const int rc = pick_finish(c, "launch pick stale cubes", [&](hipStream_t s) { return launch_pick_stale_cubes(sp, s); }, sp.scratch, d->n, d->cursor, rec, &info->kernel_ms)) return rc;
+    info->n_stale = rec.head.n_set;
+    info->next_cursor = rec.head.next_cursor;
+    info->n_from_stale = rec.head.n_from_set;
+    info->n_from_order = rec.head.n_from_order;
     info->n_rects = rec.n_rects;
     info->whole_frame = rec.whole_frame ? 1u : 0u;
-    HIP_TRY(c, hipEventElapsedTime(&info->kernel_ms, fs.ev0, fs.ev1));
     if (n_found && !found->merged) {
         float write_ms = 0.f;
         HIP_TRY(c, hipEventElapsedTime(&write_ms, c->stale_blocks_ev[0], c->stale_blocks_ev[1]));

@@ -3,12 +3,15 @@
 //
 // aic_pick_stale is aic_pick_pixels with the unknown set replaced by the stale set S of a resident Split frame: the pixels inside at least one of the
 // caller's screen rectangles that does not keep them out (with AIC_STALE_DEPTH_TEST a rectangle keeps out an opaque world pixel whose depth lies in front
-// of it). The exact rule is in DESIGN.md 4.17; tests/stale_ref.py is that text in NumPy. The three phases are aic_pick.hip's (count, scan, write), copied
-// and not shared, so that aic_pick.o stays what it was.
+// of it). The exact rule is in DESIGN.md 4.17; tests/stale_ref.py is that text in NumPy. The three phases are aic_pick.hip's (count, scan, write); what
+// the pickers share of them is aic_rank_list.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include "aic_rank_list.h"
 
 namespace aic {
 
@@ -24,11 +27,10 @@ struct StaleRect {
 
 // What the device leaves for the host (the first 32 bytes of the scratch); written by the scan.
 struct StaleRecord {
-    unsigned long long n_stale;
-    unsigned long long next_cursor;
-    uint32_t n_from_stale, n_from_order;
+    RankListRecord head;  // the set: the stale ranks
     uint32_t pad[2];
 };
+static_assert(sizeof(StaleRecord) == 32 && offsetof(StaleRecord, head) == 0 && offsetof(StaleRecord, pad) == 24, "the scratch layout and the host's copy count on it");
 
 // The scratch, in bytes: the record; per scan block its count of stale ranks and the count of those before it (32 bits each); per wave of a scan block
 // the ballot of its stale ranks (64 bits: the rank-indexed bitmap); the rectangles.

@@ -4,12 +4,14 @@
 // aic_pick_stale_cubes is aic_pick_stale for any number of changed boxes and light cubes: the device projects them (aic_stale_rect_math.h, the arithmetic
 // of aic_stale_rects), marks every rectangle's pixels in a pixel-indexed bitmap -- one wave a rectangle, so the cost follows the rectangles' area and
 // not pixels x rectangles --, and compacts the ranks whose pixel's bit is set. The exact rule is in DESIGN.md 4.19; tests/stale_cubes_ref.py is that
-// text in NumPy. The compaction (count, scan, write) is aic_stale.hip's with another predicate, copied and not shared, so that aic_stale.o stays what it
-// was.
+// text in NumPy. The compaction (count, scan, write) is aic_stale.hip's with another predicate; what the two share of it is aic_rank_list.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include "aic_rank_list.h"
 
 namespace aic {
 
@@ -25,12 +27,13 @@ struct StaleCubeRect {
 // What the device leaves for the host (the first 32 bytes of the scratch). n_rects and whole_frame are zeroed in the stream and raised by the projection;
 // the rest is written by the scan.
 struct StaleCubesRecord {
-    unsigned long long n_stale;
-    unsigned long long next_cursor;
-    uint32_t n_from_stale, n_from_order;
+    RankListRecord head;   // the set: the stale ranks
     uint32_t n_rects;      // rectangles that hold a pixel
     uint32_t whole_frame;  // not 0: a rectangle was the whole frame with no usable depth bound: every pixel is stale
 };
+
+static_assert(sizeof(StaleCubesRecord) == 32 && offsetof(StaleCubesRecord, head) == 0 && offsetof(StaleCubesRecord, n_rects) == 24 && offsetof(StaleCubesRecord, whole_frame) == 28,
+              "the scratch layout, the projection's atomics and the host's copy count on it");
 
 // The scratch, in bytes: the record; the pixel bitmap (height rows of ceil(width / 32) words: a row never shares a word with the next) -- the two are
 // zeroed by one memset --; per scan block its count of stale ranks and the count of those before it (32 bits each); per wave of a scan block the ballot

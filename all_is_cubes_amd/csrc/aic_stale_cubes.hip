@@ -9,8 +9,8 @@
 //    set already; with a depth flag it then reads depth and alpha of the pixels still wanted -- up to 32, consecutive along the row -- and drops those the
 //    rectangle keeps out; what is left goes in with one atomicOr. OR is order-free: the bitmap is the same on every run. A rectangle the projection
 //    flagged as the whole frame is left out, and under that flag every wave leaves at once.
-//  * Count / scan / write: aic_stale.hip's compaction, copied; rank r is stale when the bit of pixel order[r] is set, or, under the whole-frame flag, when
-//    order[r] is a pixel at all. The scan keeps the record's two projection counters.
+//  * Count / scan / write: aic_stale.hip's compaction, which both take from aic_rank_list.h; rank r is stale when the bit of pixel order[r] is set, or,
+//    under the whole-frame flag, when order[r] is a pixel at all. The scan keeps the record's two projection counters.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,13 +18,11 @@
 #include "aic_stale_cubes.h"
 #include "aic_stale_rect_math.h"
 
-#ifndef AIC_DEV
-#define AIC_DEV __device__ __forceinline__
-#endif
-
 namespace aic {
 
 namespace {
+
+static_assert(kStaleCubesBlock == kRankBlock, "aic_rank_list.h's scan block");
 
 AIC_DEV StaleCubesRecord *cubes_record(const StaleCubesParams &p) { return reinterpret_cast<StaleCubesRecord *>(p.scratch); }
 AIC_DEV uint32_t *cubes_pixmap(const StaleCubesParams &p) { return reinterpret_cast<uint32_t *>(p.scratch + sizeof(StaleCubesRecord)); }
@@ -36,9 +34,6 @@ AIC_DEV uint32_t *cubes_counts(const StaleCubesParams &p) {
 AIC_DEV uint32_t *cubes_offsets(const StaleCubesParams &p, uint32_t nb) { return cubes_counts(p) + nb; }
 // word [block * 4 + wave]
 AIC_DEV unsigned long long *cubes_ballots(const StaleCubesParams &p, uint32_t nb) { return reinterpret_cast<unsigned long long *>(cubes_counts(p) + 2u * (size_t)nb); }
-
-AIC_DEV uint32_t rank_pixel(const StaleCubesParams &p, uint32_t r) { return p.order ? p.order[r] : r; }
-AIC_DEV uint32_t lanes_before(unsigned long long b) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u)); }
 
 // which of a rectangle's two depth bounds can keep a pixel out under the call's flags
 AIC_DEV bool front_usable(const StaleCubesParams &p, float dmin) { return p.depth_front && dmin > -__builtin_inff(); }
@@ -117,95 +112,30 @@ __global__ void __launch_bounds__(256) stale_cubes_mark_kernel(StaleCubesParams 
 }
 
 __global__ void __launch_bounds__(256) stale_cubes_count_kernel(StaleCubesParams p, uint32_t nb) {
-    __shared__ uint32_t wave_n[4];
     const uint32_t count = p.width * p.height;
     const uint32_t r = blockIdx.x * kStaleCubesBlock + threadIdx.x;  // (count rounded up to whole blocks is still below 2^32)
-    const uint32_t px = r < count ? rank_pixel(p, r) : 0xFFFFFFFFu;
+    const uint32_t px = r < count ? rank_pixel(p.order, r) : 0xFFFFFFFFu;
     bool stale = px < count;  // an entry that is no pixel is never stale
     if (stale && !cubes_record(p)->whole_frame) {
         const uint32_t x = px % p.width, y = px / p.width;
         stale = (cubes_pixmap(p)[(size_t)y * cubes_row_words(p) + (x >> 5)] >> (x & 31u)) & 1u;
     }
-    const unsigned long long b = __ballot(stale);
-    if ((threadIdx.x & 63u) == 0u) {
-        wave_n[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-        cubes_ballots(p, nb)[blockIdx.x * (kStaleCubesBlock / 64u) + (threadIdx.x >> 6)] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0u) cubes_counts(p)[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    block_count(__ballot(stale), cubes_counts(p), cubes_ballots(p, nb));
 }
 
 __global__ void __launch_bounds__(1024) stale_cubes_scan_kernel(StaleCubesParams p, uint32_t nb) {
-    __shared__ uint32_t wave_sum[16];
-    const uint32_t *counts = cubes_counts(p);
-    uint32_t *offsets = cubes_offsets(p, nb);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t carry = 0u;  // stale ranks before this round's blocks; at most count
-    for (uint32_t base = 0u; base < nb; base += 1024u) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < nb ? counts[i] : 0u;
-        uint32_t s = v;  // inclusive over the wave
-        for (uint32_t d = 1u; d < 64u; d <<= 1) {
-            const uint32_t t = __shfl_up(s, d);
-            if (lane >= d) s += t;
-        }
-        if (lane == 63u) wave_sum[wave] = s;
-        __syncthreads();
-        uint32_t before = 0u, total = 0u;
-        for (uint32_t w = 0u; w < 16u; w++) {
-            const uint32_t x = wave_sum[w];
-            if (w < wave) before += x;
-            total += x;
-        }
-        if (i < nb) offsets[i] = carry + before + (s - v);
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0u) {
-        const unsigned long long n_stale = carry;
-        const unsigned long long left = n_stale > p.skip_stale ? n_stale - p.skip_stale : 0ull;
-        unsigned long long g = p.n < p.max_stale ? p.n : p.max_stale;
-        if (left < g) g = left;
-        StaleCubesRecord *rec = cubes_record(p);  // (n_rects and whole_frame stay the projection's)
-        rec->n_stale = n_stale;
-        rec->next_cursor = p.cursor + (unsigned long long)(p.n - (uint32_t)g);
-        rec->n_from_stale = (uint32_t)g;
-        rec->n_from_order = p.n - (uint32_t)g;
-    }
-}
-
-// pick k of PixelPicker's sequence as a rank (include/aic_hip.h under aic_pixel_order); all 64-bit
-AIC_DEV uint32_t pick_rank(unsigned long long k, uint32_t count) {
-    const uint32_t quarter = count / 4u, central = quarter < 60000u ? quarter : 60000u;
-    if (central == 0u) return (uint32_t)(k % count);
-    const unsigned long long h = k >> 1;
-    return (k & 1ull) ? central + (uint32_t)(h % (count - central)) : (uint32_t)(h % central);
+    const uint32_t n_stale = scan_block_counts(cubes_counts(p), cubes_offsets(p, nb), nb);
+    // (the head alone: n_rects and whole_frame stay the projection's)
+    if (threadIdx.x == 0u) cubes_record(p)->head = rank_list_record(n_stale, p.n, p.max_stale, p.skip_stale, p.cursor);
 }
 
 // blocks [0, nbc): the stale ranks (nbc = 0: nothing was looked at, the record is not read, g = 0); blocks from nbc on: the picker picks
 __global__ void __launch_bounds__(256) stale_cubes_write_kernel(StaleCubesParams p, uint32_t nbc) {
-    const uint32_t g = nbc ? cubes_record(p)->n_from_stale : 0u;  // <= n
-    if (blockIdx.x < nbc) {
-        if (g == 0u) return;
-        const unsigned long long lo = p.skip_stale, hi = lo + g;  // g > 0: skip < n_stale < 2^32
-        const unsigned long long b0 = cubes_offsets(p, nbc)[blockIdx.x], bn = cubes_counts(p)[blockIdx.x];
-        if (b0 >= hi || b0 + bn <= lo) return;  // the whole workgroup alike
-        const unsigned long long *words = cubes_ballots(p, nbc) + (size_t)blockIdx.x * (kStaleCubesBlock / 64u);
-        const uint32_t wave = threadIdx.x >> 6;
-        uint32_t wave_off = 0u;
-        for (uint32_t w = 0u; w < kStaleCubesBlock / 64u - 1u; w++)
-            if (w < wave) wave_off += (uint32_t)__popcll(words[w]);
-        const unsigned long long b = words[wave];
-        if (!((b >> (threadIdx.x & 63u)) & 1ull)) return;  // (a set bit: r < count and order[r] < count)
-        const unsigned long long pos = b0 + wave_off + lanes_before(b);
-        if (pos >= lo && pos < hi) p.out[pos - lo] = rank_pixel(p, blockIdx.x * kStaleCubesBlock + threadIdx.x);  // pos - lo < g <= n
-        return;
-    }
-    const uint32_t j = (blockIdx.x - nbc) * kStaleCubesBlock + threadIdx.x;  // (n is at most 2048 x 65535)
-    if (j >= p.n - g) return;
-    const uint32_t count = p.width * p.height;
-    const uint32_t r = pick_rank(p.cursor + j, count);  // < count
-    p.out[g + j] = rank_pixel(p, r);                    // g + j < n
+    const uint32_t g = nbc ? cubes_record(p)->head.n_from_set : 0u;  // <= n
+    if (blockIdx.x < nbc)
+        write_set_ranks(p.order, p.out, cubes_counts(p), cubes_offsets(p, nbc), cubes_ballots(p, nbc), p.skip_stale, g);
+    else
+        write_picks(p.order, p.out, p.width * p.height, p.n, g, p.cursor, (blockIdx.x - nbc) * kStaleCubesBlock + threadIdx.x);
 }
 
 uint32_t total_of(const StaleCubesParams &p) { return p.n_boxes + p.n_light_cubes; }  // the host has checked the sum

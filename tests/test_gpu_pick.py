@@ -3,7 +3,9 @@ the picker's order, then PixelPicker's sequence from a cursor.
 
 Yardstick: tests/pick_ref.py, the restatement of DESIGN.md 4.12 in NumPy and Python integers, on the splat image of tests/reproject_ref.py. Whole uint32
 lists are compared, every info field, and the guard words behind pixels_out[n); there is no tolerance anywhere. Sizes: 1 x 1 (central = 0), 3 x 5,
-17 x 9 (one scan block, not full), 64 x 48 (12 scan blocks of 256 ranks) and 257 x 129 (130 scan blocks, a partial last one; a multiple of nothing). The
+17 x 9 (one scan block, not full), 64 x 48 (12 scan blocks of 256 ranks) and 257 x 129 (130 scan blocks, a partial last one; a multiple of nothing). No
+size here has more than 1024 scan blocks: the scan's second round, with its carry, is the code of csrc/aic_rank_list.h that all pickers share, and the
+523 x 503 frames (1028 scan blocks) of tests/test_gpu_stale.py and tests/test_gpu_stale_cubes.py cover it for aic_pick_pixels too. The
 restatement of a (size, matrix) pair and every picker list are computed once and shared.
 
 The first test needs no device: it shows from the restatement alone that the cases are not vacuous."""

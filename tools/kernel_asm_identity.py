@@ -1,13 +1,13 @@
 """Per-kernel comparison of two device listings: has a change that was meant to leave the code object alone done so?
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wall --cuda-device-only -S aic_trace.hip -o new.s   (the Makefile's flags; the same for the other tree)
-  python tools/kernel_asm_identity.py parent.s new.s      (exit 0: every kernel identical)
+  python tools/kernel_asm_identity.py parent.s new.s      (exit 0: at least one kernel, and every kernel identical)
 Kernels are matched by symbol, so their order in the file does not matter. A kernel's text runs from its `.protected <sym> ; -- Begin function` line
-through its instructions, its .amdhsa_kernel descriptor and the `; Kernel info:` resource comments. The function index in .LBB<n>_ / .Lfunc_end<n> labels
+(`.globl <sym> ; -- Begin function` for a kernel in an anonymous namespace) through its instructions, its .amdhsa_kernel descriptor and the `; Kernel info:` resource comments. The function index in .LBB<n>_ / .Lfunc_end<n> labels
 is normalised (it only counts the functions ahead of this one in the file)."""
 import re, sys
 def kernels(path):
     lines = open(path).read().split("\n")
-    starts = [i for i, l in enumerate(lines) if re.match(r"\s*\.protected\s+\S+\s*; -- Begin function", l)]
+    starts = [i for i, l in enumerate(lines) if re.match(r"\s*\.(protected|globl)\s+\S+\s*; -- Begin function", l)]
     end_all = next(i for i, l in enumerate(lines) if ".AMDGPU.gpr_maximums" in l)
     out = {}
     for a, b in zip(starts, starts[1:] + [end_all]):
@@ -32,4 +32,5 @@ for k in b:
     if k not in a: print("extra:", k)
 n_trace = sum("trace_image_kernel" in k for k in a)
 print(f"{len(a)} kernels ({n_trace} trace_image_kernel instantiations) in {sys.argv[1]}, {len(b)} in {sys.argv[2]}; identical: {len(same)} / {len(a)}")
-sys.exit(0 if len(same) == len(a) == len(b) else 1)
+if not a: print("no kernel found in", sys.argv[1])
+sys.exit(0 if a and len(same) == len(a) == len(b) else 1)
