@@ -79,7 +79,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_find_block_cubes", "aic_pick_stale_blocks", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_find_block_cubes", "aic_pick_stale_blocks", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_light_rays", "aic_light_rays_bound", "aic_light_rays_wireframe", "aic_light_rays_cursor_lines", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_light_changed_count", "aic_light_changed_take", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -440,6 +440,41 @@ def cursor_wireframe(cube, face_entered: int, face_selected: int, point_entered,
     return out[:2 * n.value].copy()
 
 
+# aic_light_cube_info (32 bytes) and aic_light_ray (40 bytes): what aic_light_rays answers per cube and per pushed record
+LIGHT_CUBE_INFO_DTYPE = np.dtype([("cube", "<i4", (3,)), ("result", "u1", (4,)), ("cost", "<u4"), ("n_rays", "<u4"), ("first_ray", "<u4"), ("flags", "<u4")])
+LIGHT_RAY_DTYPE = np.dtype([("trigger_cube", "<i4", (3,)), ("value_cube", "<i4", (3,)), ("value", "u1", (4,)), ("light_from_struck_face", "<f4", (3,))])
+LIGHT_RAYS_DEVICE = 1                           # AIC_LIGHT_RAYS_DEVICE: rays and lines are device pointers
+LIGHT_CUBE_STORED, LIGHT_CUBE_OUTSIDE = 1, 2    # aic_light_cube_info.flags
+LIGHT_RAYS_MAX_CUBES = 1 << 16
+LIGHT_RAY_BOX_LINES, LIGHT_RAY_LINES = 12, 29   # lines of a cube's box; lines of one record (its value cube's box and the arrow's 17)
+
+
+def light_rays_bound(maximum_distance: int) -> int:
+    """The most records one cube can produce with this maximum_distance (aic_light_rays_bound), counted in the chart. Host-only."""
+    lib = load()
+    lib.aic_light_rays_bound.restype = C.c_uint32
+    lib.aic_light_rays_bound.argtypes = [C.c_int32]
+    return int(lib.aic_light_rays_bound(int(maximum_distance)))
+
+
+def light_rays_wireframe(info, rays) -> np.ndarray:
+    """The lines of one cube (aic_light_rays_wireframe; impl Wireframe for LightUpdateCubeInfo, light/debug.rs:50-95) from its LIGHT_CUBE_INFO_DTYPE
+    record and its own n_rays LIGHT_RAY_DTYPE records: [2 * (12 + 29 n_rays)] LINE_VERTEX_DTYPE records. Host-only."""
+    lib = load()
+    lib.aic_light_rays_wireframe.restype = C.c_int
+    lib.aic_light_rays_wireframe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    i = np.ascontiguousarray(info, LIGHT_CUBE_INFO_DTYPE).reshape(1)
+    r = np.ascontiguousarray(rays, LIGHT_RAY_DTYPE).reshape(-1)
+    if len(r) != int(i["n_rays"][0]):
+        raise ValueError("light_rays_wireframe: info.n_rays records wanted")
+    out = np.zeros(2 * (LIGHT_RAY_BOX_LINES + LIGHT_RAY_LINES * len(r)), LINE_VERTEX_DTYPE)
+    n = C.c_uint32(0)
+    rc = lib.aic_light_rays_wireframe(_ptr(i), _ptr(r) if len(r) else None, _ptr(out), C.byref(n))
+    if rc != 0:
+        raise AicError(rc, "aic_light_rays_wireframe")
+    return out[:2 * n.value]
+
+
 def text_geometry(nominal_size, cell=(9, 18, 1), origin_px=(5.0, 5.0)):
     """The info text's character grid and texture-coordinate transform for a viewport of `nominal_size` = (width, height) nominal pixels and a font
     `cell` = (cell_width, cell_height, cell_margin) (aic_text_geometry; character_texture_size, text.rs:20-52, and PostprocessUniforms::new,
@@ -541,6 +576,7 @@ def load() -> C.CDLL:
         lib.aic_export_split.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ExportInfo)]
         lib.aic_sample_luminance.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.aic_cursor_raycast.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_double, C.c_uint32, C.c_void_p]
+        lib.aic_light_rays.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.aic_export_size.restype = C.c_int
         lib.aic_export_size.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -896,6 +932,40 @@ class Context:
         boundaries: no staging, no read-back. Returns once the records are there."""
         self._check(self._lib.aic_cursor_raycast(self._h, int(layer), int(n), C.c_void_p(rays_ptr or None), float(maximum_distance), RAYS_DEVICE,
                                                  C.c_void_p(out_ptr or None)))
+
+    def light_rays(self, layer: int, cubes, maximum_distance: int, capacity=None, want_lines: bool = True):
+        """Space::compute_light::<LightUpdateCubeInfo> of each of the cubes [n,3] against the layer's published light volume (aic_light_rays): returns
+        (infos [n] LIGHT_CUBE_INFO_DTYPE, rays LIGHT_RAY_DTYPE, lines [2 * n_lines] LINE_VERTEX_DTYPE or None, totals (rays, lines)). capacity None
+        asks twice: once for the totals alone, then with room for exactly what the batch produces (the call stages a host list at the size it is given, and
+        n * light_rays_bound is far more than a batch needs). rays and lines hold what was stored. Legal with frames in flight."""
+        cu = np.ascontiguousarray(cubes, np.int32).reshape(-1, 3)
+        n = len(cu)
+        if capacity is None and n:
+            first = np.zeros(2, np.uint64)
+            self._check(self._lib.aic_light_rays(self._h, int(layer), n, _ptr(cu), int(maximum_distance), 0, 0, None, None, None, _ptr(first)))
+            capacity = int(first[0])
+        cap = int(capacity or 0)
+        infos = np.zeros(n, LIGHT_CUBE_INFO_DTYPE)
+        rays = np.zeros(max(cap, 1), LIGHT_RAY_DTYPE)
+        lines = np.zeros(2 * (LIGHT_RAY_BOX_LINES * n + LIGHT_RAY_LINES * cap) + 2, LINE_VERTEX_DTYPE) if want_lines else None
+        totals = np.zeros(2, np.uint64)
+        self._check(self._lib.aic_light_rays(self._h, int(layer), n, _ptr(cu) if n else None, int(maximum_distance), 0, cap, _ptr(infos), _ptr(rays),
+                                             _ptr(lines) if want_lines else None, _ptr(totals)))
+        stored = infos[(infos["flags"] & LIGHT_CUBE_STORED) != 0]
+        n_rays = int(stored["n_rays"].sum())
+        n_lines = LIGHT_RAY_BOX_LINES * len(stored) + LIGHT_RAY_LINES * n_rays
+        return infos, rays[:n_rays], (lines[:2 * n_lines] if want_lines else None), (int(totals[0]), int(totals[1]))
+
+    def light_rays_device(self, layer: int, cubes, maximum_distance: int, capacity: int, rays_ptr: int, lines_ptr: int):
+        """The same with the records ([capacity] of 40 bytes) and the lines ([2 * (12 n + 29 capacity)] vertices of 28 bytes) in HBM on the context's
+        device (AIC_LIGHT_RAYS_DEVICE), either pointer 0 for none: nothing of them is staged or read back, and present_split_lines takes the lines as
+        they stand. Returns (infos, totals)."""
+        cu = np.ascontiguousarray(cubes, np.int32).reshape(-1, 3)
+        infos = np.zeros(len(cu), LIGHT_CUBE_INFO_DTYPE)
+        totals = np.zeros(2, np.uint64)
+        self._check(self._lib.aic_light_rays(self._h, int(layer), len(cu), _ptr(cu) if len(cu) else None, int(maximum_distance), LIGHT_RAYS_DEVICE, int(capacity),
+                                             _ptr(infos), C.c_void_p(rays_ptr or None), C.c_void_p(lines_ptr or None), _ptr(totals)))
+        return infos, (int(totals[0]), int(totals[1]))
 
     def trace_pixels(self, frame: FrameDesc, pixels, want_aux: bool = False):
         """The listed pixels of `frame` (indices y * width + x, host memory), each traced exactly as render() traces it, results in list order

@@ -2,7 +2,7 @@
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
 // aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater) and
-// aic_ray_queries.cpp (the luminance sampler's call and the cursor raycast's) only (all five are written inside `using namespace aic`, and so is this header). Whatever one of the
+// aic_ray_queries.cpp (the luminance sampler's call and the cursor raycast's) and aic_light_rays_host.cpp (the light-ray records' call) only (all six are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
 #pragma once
@@ -236,6 +236,14 @@ struct aic_ctx {
     DevBuf<unsigned char> stale_blocks_scratch;
     DevBuf<int32_t> stale_blocks_boxes;
     hipEvent_t stale_blocks_ev[2] = {nullptr, nullptr};
+    // aic_light_rays (aic_light_rays_host.cpp): the effective tree of light_rays_distance (tree, children's weights, children's entries); the derived
+    // properties of the blocks of light_rays_layer at its version light_rays_version; the call's scratch (staged cubes, counts, offsets, results, infos,
+    // totals, record positions, the records and lines of a host list, the walk's slots and queues)
+    DevBuf<unsigned char> light_rays_tree, light_rays_derived, light_rays_scratch;
+    DevBuf<unsigned char> light_rays_list;  // aic_light_rays_cursor_lines: the caller's lines and the cube's behind them, as aic_present_split_lines takes them
+    int light_rays_distance = -1, light_rays_layer = -1;
+    uint32_t light_rays_n_tree = 0, light_rays_bound = 0;
+    uint64_t light_rays_version = 0;
 };
 
 namespace aic {

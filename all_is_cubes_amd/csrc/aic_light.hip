@@ -6,7 +6,7 @@
 // the texel the reference computes: the walk of the ray-bundle tree is a depth-first recursion there
 // (walk_ray_tree, updater.rs:427-530) and an explicit stack here, visiting the bundles in the same order and
 // adding into the same accumulators. PackedLight::scalar_in's log2 (data.rs:214-218) is the correctly-rounded-table
-// log2f of glibc/musl/Rust's std on Linux, restated below and pinned to the host's libm by a test.
+// log2f of glibc/musl/Rust's std on Linux, restated in aic_light_arith.h and pinned to the host's libm by a test.
 //
 // Bound: this is a pointer-chasing tree walk (48-byte chart nodes, 2-byte cube lookups, 128-byte block records),
 // latency- and issue-bound like the trace kernel, not a bandwidth kernel: the chart (5.5 MB) and the scene's
@@ -14,68 +14,11 @@
 // that lanes at the same depth touch neighbouring addresses.
 
 #include "aic_light.h"
+#include "aic_bit_gather.h"
+#include "aic_light_arith.h"
 
 namespace aic {
 namespace {
-
-// ---- PositiveSign / ZeroOne arithmetic (math/restricted_number.rs:240-326) ----
-__device__ __forceinline__ float ps_new_clamped(float v) { return v > 0.f ? v : 0.f; }
-__device__ __forceinline__ float ps_mul(float a, float b) {
-    const float v = a * b;
-    return (v != v) ? 0.f : v;
-}
-
-// ---- log2f: the table-driven routine of ARM optimized-routines as shipped in glibc >= 2.27 and musl
-// (what f32::log2 calls on Linux): 16-entry table of 1/c and log2(c), degree-4 polynomial, double arithmetic.
-__device__ const double kLog2Tab[16][2] = {
-    {0x1.661ec79f8f3bep+0, -0x1.efec65b963019p-2}, {0x1.571ed4aaf883dp+0, -0x1.b0b6832d4fca4p-2},
-    {0x1.49539f0f010bp+0, -0x1.7418b0a1fb77bp-2},  {0x1.3c995b0b80385p+0, -0x1.39de91a6dcf7bp-2},
-    {0x1.30d190c8864a5p+0, -0x1.01d9bf3f2b631p-2}, {0x1.25e227b0b8eap+0, -0x1.97c1d1b3b7afp-3},
-    {0x1.1bb4a4a1a343fp+0, -0x1.2f9e393af3c9fp-3}, {0x1.12358f08ae5bap+0, -0x1.960cbbf788d5cp-4},
-    {0x1.0953f419900a7p+0, -0x1.a6f9db6475fcep-5}, {0x1p+0, 0x0p+0},
-    {0x1.e608cfd9a47acp-1, 0x1.338ca9f24f53dp-4},  {0x1.ca4b31f026aap-1, 0x1.476a9543891bap-3},
-    {0x1.b2036576afce6p-1, 0x1.e840b4ac4e4d2p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.40645f0c6651cp-2},
-    {0x1.886e6037841edp-1, 0x1.88e9c2c1b9ff8p-2},  {0x1.767dcf5534862p-1, 0x1.ce0a44eb17bccp-2}};
-
-__device__ float log2f_exact(float x) {
-    uint32_t ix = __float_as_uint(x);
-    if (ix == 0x3f800000u) return 0.f;
-    if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {
-        if (ix * 2u == 0u) return -__builtin_inff();
-        if (ix == 0x7f800000u) return x;
-        if ((ix & 0x80000000u) || ix * 2u >= 0xff000000u) return __builtin_nanf("");
-        ix = __float_as_uint(x * 0x1p23f);  // subnormal: normalise
-        ix -= 23u << 23;
-    }
-    const uint32_t tmp = ix - 0x3f330000u;
-    const int i = (int)((tmp >> 19) % 16u);
-    const uint32_t top = tmp & 0xff800000u;
-    const uint32_t iz = ix - top;
-    const int k = (int32_t)tmp >> 23;
-    const double invc = kLog2Tab[i][0], logc = kLog2Tab[i][1];
-    const double z = (double)__uint_as_float(iz);
-    const double r = z * invc - 1.0;
-    const double y0 = logc + (double)k;
-    const double r2 = r * r;
-    double y = -0x1.712b6f70a7e4dp-2 * r2 + (0x1.ecabf496832ep-2 * r + -0x1.715479ffae3dep-1);
-    const double p = 0x1.715475f35c8b8p0 * r + y0;
-    y = y * r2 + p;
-    return (float)y;
-}
-
-// data.rs:214-218 PackedLight::scalar_in: (log2(v) * 10 + 144).round() as u8 (saturating, NaN -> 0)
-__device__ __forceinline__ uint32_t packed_scalar_in(float value) {
-    const float x = roundf(log2f_exact(value) * 10.0f + 144.0f);
-    if (x != x) return 0u;
-    if (x <= 0.f) return 0u;
-    if (x >= 255.f) return 255u;
-    return (uint32_t)x;
-}
-
-__device__ __forceinline__ void normal_of(int f, int n[3]) {  // f: 0 nx 1 ny 2 nz 3 px 4 py 5 pz
-    n[0] = n[1] = n[2] = 0;
-    n[f >= 3 ? f - 3 : f] = f >= 3 ? 1 : -1;
-}
 
 struct Ctx {
     const LightJob &J;
@@ -424,7 +367,6 @@ __global__ void __launch_bounds__(64) compute_light_kernel(const LightJob J) {
 #define AIC_LIGHT_CHUNK 1
 #endif
 constexpr uint32_t kLdsFlags = 1024u;   // DevDerived.flags of the first blocks, cached in LDS
-constexpr uint32_t kOrderCap = 2048u;   // set bits gathered per pass of the ordered reduction
 constexpr uint32_t kLightBlock = 256u;  // most threads a cube's block may have (1 or 4 waves)
 
 // The walk's loop uses a dozen fields of the job; with ~100 scalar registers already spoken for, the compiler re-reads them from the kernel-argument
@@ -639,48 +581,6 @@ struct WaveCtx {
         return alive && end > k + 1u;
     }
 };
-
-// Gathers set bits of bits[*word_io, n_words) into order[] in ascending order -- all of them if they fit kOrderCap, else
-// the longest prefix of words that does -- and advances *word_io. All threads of the block take part (no divergence
-// around the call): each counts and then writes out a contiguous stretch of words; `s_scan` (>= 4 words) carries the
-// waves' counts. Returns the number gathered; 0 = nothing left; 0xffffffff = this span was empty but words remain.
-__device__ uint32_t gather_set_bits(const uint32_t *bits, uint32_t n_words, uint32_t *word_io, uint32_t *order, uint32_t tid, uint32_t nt, uint32_t *s_scan) {
-    const uint32_t w0 = *word_io;
-    if (w0 >= n_words) return 0u;
-    const uint32_t wl = tid & 63u, wid = tid >> 6, nw = nt >> 6;
-    uint32_t span = n_words - w0, a, e, count, incl, total, base;
-    for (;;) {
-        const uint32_t per = (span + nt - 1u) / nt;
-        a = min(w0 + tid * per, w0 + span);
-        e = min(a + per, w0 + span);
-        count = 0u;
-        for (uint32_t w = a; w < e; w++) count += __popc(bits[w]);
-        incl = count;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d, 64);
-            if ((int)wl >= d) incl += up;
-        }
-        if (wl == 63u) s_scan[wid] = incl;
-        __syncthreads();
-        base = 0u; total = 0u;
-        for (uint32_t q = 0u; q < nw; q++) {
-            const uint32_t t = s_scan[q];
-            if (q < wid) base += t;
-            total += t;
-        }
-        __syncthreads();
-        if (total <= kOrderCap || span <= kOrderCap / 32u) break;
-        span = max(kOrderCap / 32u, span / 2u);
-    }
-    uint32_t at = base + incl - count;
-    for (uint32_t w = a; w < e; w++) {
-        uint32_t v = bits[w];
-        while (v) { const uint32_t bpos = __ffs(v) - 1u; v &= v - 1u; order[at++] = w * 32u + bpos; }
-    }
-    __syncthreads();
-    *word_io = w0 + span;
-    return total == 0u ? 0xffffffffu : total;
-}
 
 // SESSION: the same walk, but the launch stays on the device for a whole aic_evaluate_light call and is handed one small batch
 // after another through a page of pinned host memory (LightMailbox, aic_light.h) instead of being launched once per batch:

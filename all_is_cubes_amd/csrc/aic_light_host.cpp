@@ -26,6 +26,7 @@
 
 #include "aic_ctx.h"
 #include "aic_light.h"
+#include "aic_light_rays.h"
 
 using namespace aic;
 
@@ -1657,6 +1658,58 @@ int light_visible_bits(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<uin
     bits->assign(kVisibleBitsWords, 0u);
     for (size_t i = 0; i < l.host_blocks.size() && i < 32u * kVisibleBitsWords; i++)
         if (derived_visible_h(hb, l.host_blocks[i])) (*bits)[i >> 5] |= 1u << (i & 31u);
+    return AIC_OK;
+}
+
+// What aic_light_rays (aic_light_rays_host.cpp) takes from here. The effective tree of a maximum_distance with its children's weights and entries
+// (the entry's first word is the child's position; the rest of it is the updater's own); the bound counts the bundles within the distance, the root
+// apart, that have no child within it: a record ends its bundle (updater.rs:838-853), so no two of a cube's records lie on one root path, and those
+// are the most positions no two of which do.
+void light_rays_tree(int maximum_distance, LightRaysTree *out) {
+    std::vector<uint32_t> child_pos;
+    out->tree = build_light_tree(maximum_distance, nullptr, &out->child_w, &child_pos);
+    out->child_ent.resize(child_pos.size());
+    for (size_t q = 0; q < child_pos.size(); q++) out->child_ent[q] = child_pos[q] ? make_uint2(child_pos[q], out->tree[child_pos[q]].offset) : make_uint2(0u, 0u);
+    out->bound = 0;
+    for (size_t k = 1; k < out->tree.size(); k++) {
+        if (out->tree[k].info & 8u) continue;
+        bool child_within = false;
+        for (int f = 0; f < 6; f++) {
+            const uint32_t cp = child_pos[k * 6 + (size_t)f];
+            child_within = child_within || (cp != 0u && !(out->tree[cp].info & 8u));
+        }
+        if (!child_within) out->bound++;
+    }
+}
+uint32_t light_rays_bound(int maximum_distance) {
+    static std::mutex mu;
+    static int64_t known[256];
+    static bool init = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!init) { for (auto &k : known) k = -1; init = true; }
+    if (known[maximum_distance] < 0) {
+        LightRaysTree t;
+        light_rays_tree(maximum_distance, &t);
+        known[maximum_distance] = t.bound;
+    }
+    return (uint32_t)known[maximum_distance];
+}
+int light_rays_derived(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<DevDerived> *out) {
+    const size_t n = l.n_cubes();
+    HostBlocks hb;
+    hb.blocks = &l.host_blocks;
+    hb.n_cubes = n;
+    bool any_voxels = false;
+    for (const DevBlock &b : l.host_blocks) any_voxels = any_voxels || (b.kind & 255u) != 0u;
+    if (any_voxels) {
+        hb.vox.resize(l.pool.n > n ? l.pool.n - n : 0);
+        hb.pal.resize(l.palette.n);
+        if (!hb.vox.empty()) HIP_TRY(c, hipMemcpyAsync(hb.vox.data(), l.pool.p + n, hb.vox.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, stream));
+        if (!hb.pal.empty()) HIP_TRY(c, hipMemcpyAsync(hb.pal.data(), l.palette.p, hb.pal.size() * sizeof(DevPaletteEntry), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(c, hipStreamSynchronize(stream));
+    }
+    out->resize(l.host_blocks.size());
+    for (size_t i = 0; i < l.host_blocks.size(); i++) (*out)[i] = compute_derived_h(hb, l.host_blocks[i]);
     return AIC_OK;
 }
 }  // namespace aic

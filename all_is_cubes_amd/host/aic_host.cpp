@@ -612,6 +612,7 @@ bool HipRtRenderer::update_scene(const Cursor *cursor) {  // renderer.rs:96-161
     std::vector<aic_line_vertex> lines = cursor ? cursor->wireframe() : std::vector<aic_line_vertex>();  // (throws before anything has changed)
     had_cursor_ = cursor != nullptr;
     cursor_lines_ = std::move(lines);
+    cursor_light_cube_ = cursor && cursor->layer == AIC_LAYER_WORLD ? std::optional<std::array<int32_t, 3>>(cursor->preceding_cube_or_cube()) : std::nullopt;
     const StandardCameras &sc = *cameras_;
     const Viewport vp = modified_viewport();
     world_camera_ = Camera(sc.graphics_options, vp);
@@ -933,13 +934,25 @@ std::vector<aic_line_vertex> Cursor::wireframe() const {
     return v;
 }
 
-aic_lines_desc HipRtRenderer::lines_desc(const std::vector<aic_line_vertex> *lines) const {
+std::array<int32_t, 3> Cursor::preceding_cube_or_cube() const {
+    std::array<int32_t, 3> c = {cube[0], cube[1], cube[2]};
+    if (face_entered >= 1 && face_entered <= 6) c[(size_t)(face_entered - 1) % 3] += face_entered <= 3 ? -1 : 1;
+    return c;
+}
+
+aic_lines_desc HipRtRenderer::lines_desc(const std::vector<aic_line_vertex> *lines) {
     const std::vector<aic_line_vertex> &v = lines ? *lines : cursor_lines_;
     aic_lines_desc l{};
     const Mat4 m = world_camera_.view_matrix().then(world_camera_.projection_matrix());  // (row-vector order: WGSL's projection * view, column-major)
     for (int i = 0; i < 16; i++) l.view_projection[i] = (float)m.m[i];
     l.n_lines = (uint32_t)(v.size() / 2);
     l.vertices = v.empty() ? nullptr : v.data();
+    if (!lines && cursor_light_cube_ && cameras_->graphics_options.debug_light_rays_at_cursor && layers_[AIC_LAYER_WORLD].space) {
+        // gather_debug_lines (debug_lines.rs:47-63) behind the cursor's own lines (everything.rs:446-476): one list, made where it is drawn
+        check(aic_light_rays_cursor_lines(ctx_, AIC_LAYER_WORLD, cursor_light_cube_->data(), light_rays_maximum_distance, l.vertices, l.n_lines, nullptr, &l.vertices, &l.n_lines),
+              "aic_light_rays_cursor_lines");
+        l.flags = AIC_LINES_DEVICE;
+    }
     return l;
 }
 
@@ -1295,6 +1308,7 @@ std::vector<std::optional<Cursor>> HipRtRenderer::cursor_raycast(int layer, cons
         c.face_entered = h.cursor.face_entered; c.face_selected = h.cursor.face_selected;
         c.distance_to_point = h.cursor.distance_to_point;
         c.resolution = h.cursor.resolution;
+        c.layer = layer;
         c.block_index = h.block_index;
         c.light = PackedLight{h.light_hit[0], h.light_hit[1], h.light_hit[2], h.light_hit[3]};
         if (h.has_preceding) {
@@ -1307,6 +1321,28 @@ std::vector<std::optional<Cursor>> HipRtRenderer::cursor_raycast(int layer, cons
 }
 std::optional<Cursor> HipRtRenderer::cursor_raycast(int layer, const Ray &ray, double maximum_distance) {
     return cursor_raycast(layer, std::vector<Ray>{ray}, maximum_distance)[0];
+}
+std::vector<aic_line_vertex> HipRtRenderer::LightCubeInfo::wireframe() const {
+    std::vector<aic_line_vertex> v(2 * (12 + 29 * rays.size()));
+    uint32_t n = 0;
+    if (info.n_rays != rays.size() || aic_light_rays_wireframe(&info, rays.empty() ? nullptr : rays.data(), v.data(), &n) != AIC_OK)
+        throw std::invalid_argument("LightCubeInfo::wireframe: rays are not the cube's n_rays records");
+    return v;
+}
+std::vector<HipRtRenderer::LightCubeInfo> HipRtRenderer::light_rays(int layer, const std::vector<std::array<int32_t, 3>> &cubes, int maximum_distance) {
+    static_assert(sizeof(std::array<int32_t, 3>) == 12, "a cube is the ABI's three ints");
+    const uint64_t capacity = (uint64_t)cubes.size() * aic_light_rays_bound(maximum_distance);
+    if (cubes.size() > AIC_LIGHT_RAYS_MAX_CUBES || capacity > 0xffffffffull) throw RenderError(AIC_ERR_INVALID, "light_rays: more than 1 << 16 cubes in one call");
+    std::vector<aic_light_cube_info> infos(cubes.size());
+    std::vector<aic_light_ray> rays((size_t)capacity);
+    check(aic_light_rays(ctx_, layer, (uint32_t)cubes.size(), cubes.empty() ? nullptr : cubes[0].data(), maximum_distance, 0u, (uint32_t)capacity, infos.data(),
+                         rays.empty() ? nullptr : rays.data(), nullptr, nullptr), "aic_light_rays");
+    std::vector<LightCubeInfo> out(cubes.size());
+    for (size_t i = 0; i < out.size(); i++) {
+        out[i].info = infos[i];
+        out[i].rays.assign(rays.begin() + infos[i].first_ray, rays.begin() + infos[i].first_ray + infos[i].n_rays);
+    }
+    return out;
 }
 std::optional<Cursor> HipRtRenderer::project_cursor(double ndc_x, double ndc_y) {  // stdcam.rs:357-389
     if (layers_[AIC_LAYER_UI].space) {

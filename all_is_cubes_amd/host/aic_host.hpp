@@ -91,6 +91,7 @@ struct GraphicsOptions {
     AntialiasingOption antialiasing = AntialiasingOption::None;
     bool debug_info_text = true;
     bool debug_pixel_cost = false;
+    bool debug_light_rays_at_cursor = false;  // the lines pass draws compute_light's ray records at cursor.preceding_cube() (HipRtRenderer::present_split)
     static GraphicsOptions unaltered_colors();  // UNALTERED_COLORS
     GraphicsOptions repair() const;             // clamps fov_y to 1..189, view_distance to 1..10000
     aic_options to_abi() const;
@@ -347,6 +348,10 @@ struct Cursor {
     // Cursor::preceding: the cube the ray was in before, unless it started in the hit cube (face_entered Within), and Space::get_light there
     std::optional<std::array<int32_t, 3>> preceding_cube;
     std::optional<PackedLight> preceding_light;
+    // Cursor::space(): the layer whose space the cursor is in (cursor_raycast sets it; debug_light_rays_at_cursor draws for a cursor in the world space only)
+    int32_t layer = AIC_LAYER_WORLD;
+    // Cursor::preceding_cube() (cursor.rs:163-168): cube + face_entered's normal, the cube itself for Within
+    std::array<int32_t, 3> preceding_cube_or_cube() const;
     std::vector<aic_line_vertex> wireframe() const;
 };
 
@@ -577,6 +582,20 @@ class HipRtRenderer : public HeadlessRenderer {
     // block the ray strikes within maximum_distance (infinity is legal), or nothing. Legal with frames in flight. The batch form is one launch.
     std::optional<Cursor> cursor_raycast(int layer, const Ray &ray, double maximum_distance);
     std::vector<std::optional<Cursor>> cursor_raycast(int layer, const std::vector<Ray> &rays, double maximum_distance);
+    // Space::compute_light::<LightUpdateCubeInfo> (all-is-cubes/src/space/light/updater.rs:368-417, light/debug.rs; aic_light_rays) for cubes of one layer's
+    // space against its published light volume: per cube the texel and cost compute_light returns and the ray records it pushes, in the reference's
+    // order. Legal with frames in flight. wireframe() is impl Wireframe for LightUpdateCubeInfo (aic_light_rays_wireframe).
+    struct LightCubeInfo {
+        aic_light_cube_info info{};
+        std::vector<aic_light_ray> rays;
+        std::vector<aic_line_vertex> wireframe() const;
+    };
+    std::vector<LightCubeInfo> light_rays(int layer, const std::vector<std::array<int32_t, 3>> &cubes, int maximum_distance);
+    // GraphicsOptions::debug_light_rays_at_cursor (all-is-cubes-gpu/src/common/debug_lines.rs:47-63): with the option on and the cursor of the last
+    // update() in the world space, every present_split that draws the cursor's lines (`lines` == nullptr) draws them and then the lines of
+    // compute_light at cursor.preceding_cube(), from one list made on the device (aic_light_rays_cursor_lines): the records never visit the host.
+    // The distance is the world space's LightPhysics::Rays { maximum_distance }, which the application states here as it does for evaluate_light.
+    int light_rays_maximum_distance = 30;
     // StandardCameras::project_cursor (all-is-cubes-render/src/camera/stdcam.rs:357-389) through the cameras of the last update(): the UI space, if
     // there is one, at any distance; else, or if nothing is struck there, the world at 6.0. The result goes straight into update(cursor).
     std::optional<Cursor> project_cursor(double ndc_x, double ndc_y);
@@ -607,7 +626,8 @@ class HipRtRenderer : public HeadlessRenderer {
     float cam_override_exposure_ = 1.0f;
     bool had_cursor_ = false;
     std::vector<aic_line_vertex> cursor_lines_;  // the wireframe of the cursor of the last update()
-    aic_lines_desc lines_desc(const std::vector<aic_line_vertex> *lines) const;
+    std::optional<std::array<int32_t, 3>> cursor_light_cube_;  // ... and its preceding_cube(), if it is in the world space
+    aic_lines_desc lines_desc(const std::vector<aic_line_vertex> *lines);
     bool text_font_set_ = false;
     std::vector<uint8_t> text_codes_;  // the character grid of the last presentation with text
     aic_text_desc text_desc(const std::string &info_text);

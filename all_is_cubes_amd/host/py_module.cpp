@@ -55,7 +55,8 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("view_distance", &GraphicsOptions::view_distance).def_readwrite("lighting_display", &GraphicsOptions::lighting_display)
         .def_readwrite("transparency", &GraphicsOptions::transparency).def_readwrite("show_ui", &GraphicsOptions::show_ui)
         .def_readwrite("antialiasing", &GraphicsOptions::antialiasing).def_readwrite("debug_info_text", &GraphicsOptions::debug_info_text)
-        .def_readwrite("debug_pixel_cost", &GraphicsOptions::debug_pixel_cost);
+        .def_readwrite("debug_pixel_cost", &GraphicsOptions::debug_pixel_cost)
+        .def_readwrite("debug_light_rays_at_cursor", &GraphicsOptions::debug_light_rays_at_cursor);
 
     py::class_<Viewport>(m, "Viewport")
         .def(py::init<>())
@@ -273,6 +274,8 @@ PYBIND11_MODULE(_host, m) {
                       [](Cursor &c, std::array<int32_t, 3> v) { std::copy(v.begin(), v.end(), c.voxel_size); })
         .def_readwrite("resolution", &Cursor::resolution)
         .def_readwrite("block_index", &Cursor::block_index)
+        .def_readwrite("layer", &Cursor::layer)
+        .def("preceding_cube_or_cube", &Cursor::preceding_cube_or_cube)
         .def_property("voxel", [](const Cursor &c) { return std::array<int32_t, 3>{c.voxel[0], c.voxel[1], c.voxel[2]}; },
                       [](Cursor &c, std::array<int32_t, 3> v) { std::copy(v.begin(), v.end(), c.voxel); })
         .def_property("light", [](const Cursor &c) { return std::array<uint8_t, 4>{c.light.r, c.light.g, c.light.b, c.light.status}; },
@@ -344,6 +347,27 @@ PYBIND11_MODULE(_host, m) {
             if (rays.ndim() == 1) return py::cast(res[0]);
             return py::cast(res);
         }, py::arg("layer"), py::arg("rays"), py::arg("maximum_distance"))
+        .def("light_rays", [](HipRtRenderer &r, int layer, py::array_t<int32_t, py::array::c_style | py::array::forcecast> cubes, int maximum_distance) {
+            // cubes [n, 3] -> a list of (info bytes [32] u8 -- view it as abi.LIGHT_CUBE_INFO_DTYPE --, rays [n_rays, 40] u8 -- abi.LIGHT_RAY_DTYPE --, lines [2 n_lines, 7] f32)
+            if (cubes.size() % 3 != 0) throw std::invalid_argument("cubes: [n, 3] ints");
+            std::vector<std::array<int32_t, 3>> v((size_t)cubes.size() / 3);
+            if (!v.empty()) std::memcpy(v.data(), cubes.data(), v.size() * 12);
+            std::vector<HipRtRenderer::LightCubeInfo> res;
+            { py::gil_scoped_release rel; res = r.light_rays(layer, v, maximum_distance); }
+            py::list out;
+            for (const auto &c : res) {
+                py::array_t<uint8_t> info((py::ssize_t)sizeof(aic_light_cube_info));
+                std::memcpy(info.mutable_data(), &c.info, sizeof(aic_light_cube_info));
+                py::array_t<uint8_t> rays({(py::ssize_t)c.rays.size(), (py::ssize_t)sizeof(aic_light_ray)});
+                if (!c.rays.empty()) std::memcpy(rays.mutable_data(), c.rays.data(), c.rays.size() * sizeof(aic_light_ray));
+                const std::vector<aic_line_vertex> w = c.wireframe();
+                py::array_t<float> lines({(py::ssize_t)w.size(), (py::ssize_t)7});
+                std::memcpy(lines.mutable_data(), w.data(), w.size() * sizeof(aic_line_vertex));
+                out.append(py::make_tuple(info, rays, lines));
+            }
+            return out;
+        }, py::arg("layer"), py::arg("cubes"), py::arg("maximum_distance"))
+        .def_readwrite("light_rays_maximum_distance", &HipRtRenderer::light_rays_maximum_distance)
         .def("project_cursor", [](HipRtRenderer &r, double ndc_x, double ndc_y) {
             std::optional<Cursor> c;
             { py::gil_scoped_release rel; c = r.project_cursor(ndc_x, ndc_y); }

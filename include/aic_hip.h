@@ -1151,6 +1151,69 @@ int aic_multi_evaluate_light(aic_multi *m, int layer, const aic_light_params *pa
  * all devices always trace the same light volume; if that hand-over fails, the whole volume goes over at the next
  * aic_multi_evaluate_light or aic_multi_render, whichever comes first. */
 int aic_multi_light_cubes_changed(aic_multi *m, int layer, uint32_t n, const int32_t *xyz, int queue_order);
+/* replaces: Space::compute_light::<LightUpdateCubeInfo> (all-is-cubes/src/space/mod.rs, light/updater.rs:368-417, light/debug.rs) for n cubes against
+ * the layer's published light volume -- what GraphicsOptions::debug_light_rays_at_cursor draws for cursor.preceding_cube() (all-is-cubes-gpu
+ * common/debug_lines.rs:47-63) -- and impl Wireframe for LightUpdateCubeInfo as a line list; DESIGN.md 4.21, tests/light_rays_ref.py is this text in
+ * Python. Nothing is written to the volume and no cube is queued: the call asks, it does not update.
+ * Per cube one aic_light_cube_info: `result` and `cost` are what compute_light returns for it (the texel r, g, b, status and ComputedLight::cost),
+ * n_rays the records it pushed, first_ray the records of the cubes before it in the batch. Per D::push_ray (updater.rs:844-853: the hit of an opaque
+ * face that ends a ray bundle) one aic_light_ray: trigger_cube = hit.cube, value_cube = hit.adjacent(), value = the stored texel read there,
+ * light_from_struck_face = emission + clamped face colour reflecting that texel's value, f32 in the reference's order. A cube's records are in the
+ * order the reference pushes them: walk_ray_tree's depth-first order, children in the order nx ny nz px py pz.
+ * An opaque cube walks nothing: 0 rays, result and cost as the reference's (updater.rs:385-389). A cube outside the space (a cursor's preceding_cube
+ * may be one) is ours to decide: AIC_LIGHT_CUBE_OUTSIDE, 0 rays, result and cost 0.
+ * capacity: the records `rays` can hold. Cube k's records are stored, at rays[first_ray], iff first_ray + n_rays <= capacity, and then its flags carry
+ * AIC_LIGHT_CUBE_STORED: whole cubes only, and the stored cubes are a prefix of the batch. totals[0] = all records of the batch, stored or not,
+ * totals[1] = all its lines, 12 n + 29 totals[0].
+ * lines: the wireframe of every STORED cube, as wireframe_vertices(v, Rgba(0.8, 0.8, 1.0, 1.0), &info) makes it: cube k's 12 + 29 n_rays lines start at
+ * line 12 k + 29 first_ray (two vertices a line), so `lines` holds 2 * (12 n + 29 min(capacity, totals[0])) vertices at most. The 12 edges of
+ * cube.aab().expand(0.1) in Aab::wireframe_points' order; then per record the 12 edges of value_cube.aab().expand(0.01) in that colour and the 17 lines
+ * of Ray::wireframe_points (all-is-cubes-base raycast/ray.rs:115-158) for Ray::new(cube.center(), hit_point - cube.center()), hit_point the midpoint of
+ * the trigger and value cubes' centres, coloured light_from_struck_face with alpha 1. All of it f64 with one rounding per operation (length =
+ * sqrt(x*x + y*y + z*z) summed left to right, cross = (y*o.z - z*o.y, z*o.x - x*o.z, x*o.y - y*o.x)), the sines and cosines of k * TAU / 8 from the host's C
+ * library, positions cast to f32 last. aic_light_rays_wireframe is the same text on the host for one cube: the device's lines equal it byte for byte.
+ * flags: AIC_LIGHT_RAYS_DEVICE or 0 -- `rays` and `lines` are device pointers on the context's device (4-byte aligned), nothing of them is staged or
+ * read back: aic_present_split_lines takes such `lines` with AIC_LINES_DEVICE. cubes, infos and totals are host memory always; each of infos, rays,
+ * lines and totals may be NULL. The call returns when everything is there. Like aic_cursor_raycast it runs beside frames in flight and disturbs none of
+ * them, finishes a pending aic_evaluate_light_submit first and sees every scene and light write issued before it.
+ * AIC_ERR_INVALID, before anything is queued, the context still usable: NULL cubes with n > 0, unknown flag bits, a layer without a space,
+ * maximum_distance outside 0..255, n above 1 << 16, misaligned device pointers. n == 0 is AIC_OK and does nothing (totals, if given, are zeroed).
+ * An aic_multi replicates the scene and the light: a host of one asks through the context of its first device. */
+typedef struct aic_light_cube_info {
+    int32_t cube[3];
+    uint8_t result[4];   /* PackedLight r, g, b, status */
+    uint32_t cost;
+    uint32_t n_rays;
+    uint32_t first_ray;  /* exclusive prefix sum of n_rays over the batch */
+    uint32_t flags;      /* AIC_LIGHT_CUBE_* */
+} aic_light_cube_info;
+typedef struct aic_light_ray {
+    int32_t trigger_cube[3];
+    int32_t value_cube[3];
+    uint8_t value[4];
+    float light_from_struck_face[3];
+} aic_light_ray;
+#define AIC_LIGHT_RAYS_DEVICE 1u  /* `rays` and `lines` are device pointers */
+#define AIC_LIGHT_CUBE_STORED 1u  /* the cube's records are in `rays` (and its lines in `lines`) */
+#define AIC_LIGHT_CUBE_OUTSIDE 2u /* the cube lies outside the space */
+#define AIC_LIGHT_RAYS_MAX_CUBES 65536u
+int aic_light_rays(aic_ctx *ctx, int layer, uint32_t n, const int32_t *cubes /* [n][3] */, int32_t maximum_distance, uint32_t flags, uint32_t capacity,
+                   aic_light_cube_info *infos /* [n] */, aic_light_ray *rays /* [capacity] */, aic_line_vertex *lines, uint64_t totals[2]);
+/* host-only: the most records one cube can produce with this maximum_distance, whatever the space holds. A record ends its ray bundle, so no two
+ * records of a cube lie on one path from the chart's root: the bound is the number of bundles within the distance, the root apart, that have no child
+ * within the distance -- counted in the chart, 602 (its rays) once the distance reaches the chart's. 0 for a maximum_distance outside 0..255. */
+uint32_t aic_light_rays_bound(int32_t maximum_distance);
+/* host-only: the lines of one cube from its info and its n_rays records, out[2 * (12 + 29 * n_rays)]; *n_lines = 12 + 29 * n_rays. A NULL pointer
+ * (rays may be NULL when n_rays is 0): AIC_ERR_INVALID. */
+int aic_light_rays_wireframe(const aic_light_cube_info *info, const aic_light_ray *rays, aic_line_vertex *out, uint32_t *n_lines);
+/* What gather_debug_lines hands the lines pass when debug_light_rays_at_cursor is on (all-is-cubes-gpu common/debug_lines.rs:47-63, everything.rs:446-476):
+ * the caller's n_first lines (host memory: the cursor's own wireframe, drawn first) and behind them the lines of `cube` -- cursor.preceding_cube() --
+ * as aic_light_rays makes them, in ONE list in device memory the context owns. *device_lines and *n_lines are what aic_present_split_lines takes with
+ * AIC_LINES_DEVICE; the list stays valid until the next call of this function or aic_destroy. The records and their lines never visit the host; info,
+ * if not NULL, is the cube's. Everything aic_light_rays says of streams, pending light updates and rejections holds; also AIC_ERR_INVALID: a NULL cube,
+ * device_lines or n_lines, NULL first with n_first > 0, more than AIC_LINES_MAX lines in all. */
+int aic_light_rays_cursor_lines(aic_ctx *ctx, int layer, const int32_t *cube /* [3] */, int32_t maximum_distance, const aic_line_vertex *first, uint32_t n_first,
+                                aic_light_cube_info *info, const aic_line_vertex **device_lines, uint32_t *n_lines);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,10 @@ pub const AIC_STALE_MAX_RECTS: u32 = 4096;
 pub const AIC_STALE_DEPTH_BEHIND: u32 = 2;
 pub const AIC_CURSOR_MAX_LINES: u32 = 28;
 pub const AIC_CURSOR_NO_BLOCK: u32 = 0xFFFF_FFFF;
+pub const AIC_LIGHT_RAYS_DEVICE: u32 = 1;
+pub const AIC_LIGHT_CUBE_STORED: u32 = 1;
+pub const AIC_LIGHT_CUBE_OUTSIDE: u32 = 2;
+pub const AIC_LIGHT_RAYS_MAX_CUBES: u32 = 65536;
 pub const AIC_EXPOSURE_SAMPLES: u32 = 100;
 pub const AIC_EXPOSURE_RAYS: u32 = 10;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
@@ -426,6 +430,28 @@ pub struct aic_cursor_hit {
     pub reserved_hit: u32,
 }
 
+/// What `aic_light_rays` answers per cube: 32 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct aic_light_cube_info {
+    pub cube: [i32; 3],
+    pub result: [u8; 4],
+    pub cost: u32,
+    pub n_rays: u32,
+    pub first_ray: u32,
+    pub flags: u32,
+}
+
+/// One `LightUpdateRayInfo` of `aic_light_rays`: 40 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct aic_light_ray {
+    pub trigger_cube: [i32; 3],
+    pub value_cube: [i32; 3],
+    pub value: [u8; 4],
+    pub light_from_struck_face: [f32; 3],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct aic_pixel_aux {
@@ -566,6 +592,10 @@ unsafe extern "C" {
     pub fn aic_present_lines_scratch(src_w: u32, src_h: u32, out_w: u32, out_h: u32, n_lines: u32, bytes: *mut u64) -> c_int;
     pub fn aic_cursor_wireframe(cursor: *const aic_cursor_desc, out: *mut aic_line_vertex, n_lines: *mut u32) -> c_int;
     pub fn aic_cursor_raycast(ctx: *mut aic_ctx, layer: c_int, n: u32, rays: *const f64, maximum_distance: f64, flags: u32, out: *mut aic_cursor_hit) -> c_int;
+    pub fn aic_light_rays(ctx: *mut aic_ctx, layer: c_int, n: u32, cubes: *const i32, maximum_distance: i32, flags: u32, capacity: u32, infos: *mut aic_light_cube_info, rays: *mut aic_light_ray, lines: *mut aic_line_vertex, totals: *mut u64) -> c_int;
+    pub fn aic_light_rays_bound(maximum_distance: i32) -> u32;
+    pub fn aic_light_rays_wireframe(info: *const aic_light_cube_info, rays: *const aic_light_ray, out: *mut aic_line_vertex, n_lines: *mut u32) -> c_int;
+    pub fn aic_light_rays_cursor_lines(ctx: *mut aic_ctx, layer: c_int, cube: *const i32, maximum_distance: i32, first: *const aic_line_vertex, n_first: u32, info: *mut aic_light_cube_info, device_lines: *mut *const aic_line_vertex, n_lines: *mut u32) -> c_int;
     pub fn aic_set_text_font(ctx: *mut aic_ctx, atlas_rgba8: *const u8, cell_width: u32, cell_height: u32, cell_margin: u32) -> c_int;
     pub fn aic_text_geometry(nominal_width: f64, nominal_height: f64, cell_width: u32, cell_height: u32, cell_margin: u32, origin_px: *const f64, cols: *mut u32, rows: *mut u32, scale: *mut f32, origin: *mut f32) -> c_int;
     pub fn aic_text_layout(utf8: *const c_char, len: u64, cols: u32, rows: u32, codes: *mut u8, used: *mut u32) -> c_int;

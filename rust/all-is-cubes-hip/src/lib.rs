@@ -287,6 +287,21 @@ pub fn cursor_wireframe(cursor: &ffi::aic_cursor_desc) -> Option<Vec<[ffi::aic_l
     Some(out)
 }
 
+/// `impl Wireframe for LightUpdateCubeInfo` (all-is-cubes/src/space/light/debug.rs:50-95) as the line list [`HipRtRenderer::present_split_lines`]
+/// draws, under `wireframe_vertices(v, Rgba::new(0.8, 0.8, 1.0, 1.0), ..)`: the cube's box, then per record its value cube's box and the arrow from the
+/// cube's centre, coloured `light_from_struck_face`. `12 + 29 * rays.len()` lines. Host-only. `None`: `rays` is not the cube's `n_rays` records.
+#[must_use]
+pub fn light_rays_wireframe(info: &ffi::aic_light_cube_info, rays: &[ffi::aic_light_ray]) -> Option<Vec<[ffi::aic_line_vertex; 2]>> {
+    if rays.len() != info.n_rays as usize {
+        return None;
+    }
+    let mut out = vec![[ffi::aic_line_vertex::default(); 2]; 12 + 29 * rays.len()];
+    let mut n = 0u32;
+    // SAFETY: `out` holds 2 * (12 + 29 * n_rays) vertices, what the call writes; `rays` holds n_rays records
+    let rc = unsafe { ffi::aic_light_rays_wireframe(info, rays.as_ptr(), out.as_mut_ptr().cast(), &mut n) };
+    (rc == 0 && n as usize == out.len()).then_some(out)
+}
+
 /// Cell width, height and margin of [`font_atlas`]: `FONT_SYSTEM_16`'s 7 x 16 character cell and an outline of one.
 const FONT_CELL: [u32; 3] = [9, 18, 1];
 
@@ -711,6 +726,32 @@ impl HipRtRenderer {
         // SAFETY: the context is live; both buffers hold `n` elements and outlive the call, which returns when the records are there
         self.device.check(unsafe { ffi::aic_cursor_raycast(self.device.first_ctx(), layer, n, rays.as_ptr().cast(), maximum_distance, 0, out.as_mut_ptr()) })?;
         Ok(out.into_iter().map(|h| (h.hit != 0).then_some(h)).collect())
+    }
+
+    /// `Space::compute_light::<LightUpdateCubeInfo>` (all-is-cubes/src/space/light/updater.rs:368-417, light/debug.rs) for a batch of cubes against
+    /// the published light volume of `layer`, on the device: what `GraphicsOptions::debug_light_rays_at_cursor` draws for `cursor.preceding_cube()`.
+    /// Per cube its info (the texel and cost `compute_light` returns, its number of records) and its records in the order the reference pushes them;
+    /// everything the batch produces is returned. [`light_rays_wireframe`] turns one cube's answer into lines. Legal while frames are in flight. A
+    /// multi-device renderer asks its first device: the scene and the light are replicated.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures.
+    ///
+    /// # Panics
+    /// On a layer without a space, or more than `1 << 16` cubes.
+    pub fn light_rays(&mut self, layer: core::ffi::c_int, cubes: &[[i32; 3]], maximum_distance: u8) -> Result<Vec<(ffi::aic_light_cube_info, Vec<ffi::aic_light_ray>)>, RenderError> {
+        let n = u32::try_from(cubes.len()).expect("more than u32::MAX cubes");
+        // SAFETY: host-only, no pointers
+        let bound = unsafe { ffi::aic_light_rays_bound(i32::from(maximum_distance)) };
+        let capacity = n.checked_mul(bound).expect("more records than u32::MAX");
+        let mut infos = vec![ffi::aic_light_cube_info::default(); cubes.len()];
+        let mut rays = vec![ffi::aic_light_ray::default(); capacity as usize];
+        let mut totals = [0u64; 2];
+        // SAFETY: the context is live; `infos` holds `n` records and `rays` `capacity`, both outlive the call, which returns when the records are there
+        self.device.check(unsafe {
+            ffi::aic_light_rays(self.device.first_ctx(), layer, n, cubes.as_ptr().cast(), i32::from(maximum_distance), 0, capacity, infos.as_mut_ptr(), rays.as_mut_ptr(), core::ptr::null_mut(), totals.as_mut_ptr())
+        })?;
+        Ok(infos.into_iter().map(|i| (i, rays[i.first_ray as usize..(i.first_ray + i.n_rays) as usize].to_vec())).collect())
     }
 
     /// `StandardCameras::project_cursor` (all-is-cubes-render/src/camera/stdcam.rs:357-389) through the cameras of the last `update`: the UI space,

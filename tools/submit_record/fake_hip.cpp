@@ -18,6 +18,7 @@
 #include "aic_device.h"
 #include "aic_exposure.h"
 #include "aic_launch.h"
+#include "aic_light_rays.h"
 #include "aic_pick.h"
 #include "aic_present_lines.h"
 #include "aic_reproject.h"
@@ -219,13 +220,14 @@ hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { FAKE("hi
 
 // ---- the kernel launchers and the light updater's hooks
 struct aic_ctx;
+int (*fake_light_job_finish)(aic_ctx *) = nullptr;  // (record.h: a program that wants to see the call sets it; nobody else's record changes)
 namespace aic {
 
 struct LightState;
 struct Layer;
 void light_state_free(LightState *) {}
 void light_state_cubes_updated(LightState *, uint64_t, uint64_t, uint32_t, const int32_t *, const uint16_t *, const uint8_t *) {}
-int light_job_finish(aic_ctx *) { return 0; }
+int light_job_finish(aic_ctx *c) { return fake_light_job_finish ? fake_light_job_finish(c) : 0; }
 // (the luminance sampler's bitmap, kVisibleBitsWords words: a fixed pattern; can be made to fail like a runtime call)
 int light_visible_bits(aic_ctx *, Layer &, hipStream_t stream, std::vector<uint32_t> *bits) {
     rec("light_visible_bits %s", S(stream));
@@ -350,6 +352,57 @@ hipError_t launch_count_block_cubes(const BlockCubesParams &p, hipStream_t strea
 hipError_t launch_write_block_cubes(const BlockCubesParams &p, hipStream_t stream) {
     rec("launch_write_block_cubes grid %s n %llu scratch %s boxes %s n_runs %u %s", P(p.grid), p.n, P(p.scratch), P(p.boxes), p.n_runs, S(stream));
     return failing("launch_write_block_cubes") ? hipErrorInvalidValue : hipSuccess;
+}
+// (the light-ray records, aic_light_rays_host.cpp. The tree is a stand-in of ten positions with a bound of three; the scan answers two records a cube
+// and stores the cubes the capacity holds; the emitters write every byte they may, so that the sanitizer sees a buffer that is too small)
+void light_rays_tree(int maximum_distance, LightRaysTree *out) {
+    rec("light_rays_tree %d", maximum_distance);
+    out->tree.assign(10, DevTreePos{});
+    out->child_w.assign(10 * 36, 0.f);
+    out->child_ent.assign(10 * 6, make_uint2(0u, 0u));
+    out->bound = 3;
+}
+uint32_t light_rays_bound(int) { return 3; }
+int light_rays_derived(aic_ctx *, Layer &, hipStream_t stream, std::vector<DevDerived> *out) {
+    rec("light_rays_derived %s", S(stream));
+    if (failing("light_rays_derived")) return AIC_ERR_DEVICE;
+    out->assign(4, DevDerived{});
+    return AIC_OK;
+}
+hipError_t launch_light_rays_walk(const LightRaysParams &p, uint32_t workgroups, hipStream_t stream) {
+    rec("launch_light_rays_walk groups %u n %u n_tree %u bound %u capacity %u cubes %s results %s counts %s positions %s slots %s queue %s %s", workgroups, p.n, p.n_tree, p.bound,
+        p.capacity, P(p.cubes), P(p.results), P(p.counts), P(p.positions), P(p.slots), P(p.queue), S(stream));
+    rec("  grid %s light %s derived %s lut %s tree %s child_w %s child_ent %s index_mask %u", P(p.grid), P(p.light), P(p.derived), P(p.lut), P(p.tree), P(p.child_w), P(p.child_ent),
+        p.index_mask);
+    rec_words("  lo size", p.lo, 6);
+    rec_words("  block_sky", p.block_sky, 7);
+    if (failing("launch_light_rays_walk")) return hipErrorInvalidValue;
+    std::memset(p.positions, 0x33, (size_t)p.n * p.bound * 4);
+    std::memset(p.slots, 0x44, (size_t)workgroups * p.n_tree * 64);
+    std::memset(p.queue, 0x55, (size_t)workgroups * p.n_tree * 8);
+    return hipSuccess;
+}
+hipError_t launch_light_rays_scan(const LightRaysParams &p, hipStream_t stream) {
+    rec("launch_light_rays_scan n %u capacity %u counts %s offsets %s infos %s totals %s %s", p.n, p.capacity, P(p.counts), P(p.offsets), P(p.infos), P(p.totals), S(stream));
+    if (failing("launch_light_rays_scan")) return hipErrorInvalidValue;
+    uint32_t stored = 0;
+    for (uint32_t i = 0; i < p.n; i++) {
+        p.counts[i] = 2; p.offsets[i] = 2 * i;
+        aic_light_cube_info info = {};
+        for (int a = 0; a < 3; a++) info.cube[a] = p.cubes[3 * i + a];
+        info.n_rays = 2; info.first_ray = 2 * i;
+        if ((uint64_t)2 * i + 2 <= p.capacity) { info.flags = AIC_LIGHT_CUBE_STORED; stored++; }
+        p.infos[i] = info;
+    }
+    p.totals[0] = 2ull * p.n; p.totals[1] = stored; p.totals[2] = 2ull * stored; p.totals[3] = 0;
+    return hipSuccess;
+}
+hipError_t launch_light_rays_emit(const LightRaysParams &p, hipStream_t stream) {
+    rec("launch_light_rays_emit n_stored %u n_stored_rays %u rays %s lines %s %s", p.n_stored, p.n_stored_rays, P(p.rays), P(p.lines), S(stream));
+    if (failing("launch_light_rays_emit")) return hipErrorInvalidValue;
+    std::memset((void *)p.rays, 0x11, (size_t)p.n_stored_rays * sizeof(aic_light_ray));
+    if (p.lines) std::memset((void *)p.lines, 0x22, ((size_t)12 * p.n_stored + (size_t)29 * p.n_stored_rays) * 2 * sizeof(aic_line_vertex));
+    return hipSuccess;
 }
 void launch_probe_powf(const float *, const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_powf"); }
 void launch_probe_expf(const float *, float *, uint32_t, hipStream_t) { rec("launch_probe_expf"); }
