@@ -38,6 +38,13 @@ LINES_DEVICE = 1  # AIC_LINES_DEVICE: the line vertices are a device pointer
 LINES_MAX = 1 << 20  # AIC_LINES_MAX
 CURSOR_MAX_LINES = 28  # AIC_CURSOR_MAX_LINES
 TEXT_DEVICE = 1  # AIC_TEXT_DEVICE: the character codes are a device pointer
+# terminal frames (aic_image_cells, aic_render_cells, aic_cells_ansi): CharacterMode, ColorMode, the flags and a cell's colour kinds
+CELLS_NAMES, CELLS_SHADES, CELLS_SPLIT, CELLS_SHAPES, CELLS_BRAILLE = 0, 1, 2, 3, 4
+CELLS_COLOR_NONE, CELLS_COLOR_256, CELLS_COLOR_RGB = 0, 1, 2
+CELLS_IMAGE_DEVICE, CELLS_OUT_DEVICE, CELLS_IMAGE_F16, CELLS_POSTPROCESSED = 1, 2, 4, 8
+CELLS_ANSI_IN_RECT = 1
+CELL_GLYPH_BLOCK = 0x80000000  # AIC_CELL_GLYPH_BLOCK | layer << 16 | block_index: the text of that block of that layer
+CELL_COLOR_NONE, CELL_COLOR_RESET, CELL_COLOR_BLACK, CELL_COLOR_ANSI, CELL_COLOR_RGB = 0, 1, 2, 3, 4
 # aic_frame_desc.tuning / aic_frame_info.variant (include/aic_hip.h)
 TUNE_QUEUES_SHIFT, TUNE_SUPER_SHIFT, TUNE_VARIANT_SHIFT = 0, 4, 9
 VARIANT_AUTO, VARIANT_PLAIN, VARIANT_EXCHANGING, VARIANT_RECORDING = 0, 1, 2, 3
@@ -79,7 +86,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_find_block_cubes", "aic_pick_stale_blocks", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_light_rays", "aic_light_rays_bound", "aic_light_rays_wireframe", "aic_light_rays_cursor_lines", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_find_block_cubes", "aic_pick_stale_blocks", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_light_rays", "aic_light_rays_bound", "aic_light_rays_wireframe", "aic_light_rays_cursor_lines", "aic_cells_geometry", "aic_image_cells", "aic_render_cells", "aic_cells_ansi", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_light_changed_count", "aic_light_changed_take", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -506,6 +513,69 @@ def text_layout(text, cols: int, rows: int):
     return codes, (used[0], used[1])
 
 
+CELL_DTYPE = np.dtype([("glyph", "<u4"), ("fg", "<u4"), ("bg", "<u4")])  # aic_cell: 12 bytes
+
+
+class CellsDesc(C.Structure):
+    _fields_ = [("cols", C.c_uint32), ("rows", C.c_uint32), ("characters", C.c_int32), ("colors", C.c_int32), ("exposure", C.c_float),
+                ("tone_mapping", C.c_int32), ("maximum_intensity", C.c_float), ("flags", C.c_uint32)]
+
+
+class CellsInfo(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("n_cells", "n_full", "n_upper", "n_lower", "n_text", "n_space", "n_shade", "n_rising", "n_falling", "n_equal",
+                                          "n_unequal", "n_names", "n_braille", "n_gray", "n_cube", "n_rgb")] + [("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+    def counters(self) -> dict:
+        """The branch counters by name, as tests/cells_ref.py counts them."""
+        return {k: int(getattr(self, k)) for k, _ in self._fields_[1:16]}
+
+
+class CellsText(C.Structure):
+    _fields_ = [("names", C.POINTER(C.c_char_p) * 2), ("widths", C.POINTER(C.c_uint8) * 2), ("n_names", C.c_uint32 * 2), ("origin", C.c_uint16 * 2),
+                ("reserved", C.c_uint32)]
+
+
+def cells_geometry(cols: int, rows: int, characters: int):
+    """TerminalOptions::viewport_from_terminal_size (aic_cells_geometry): ((width, height) of the framebuffer, (nominal width, height))."""
+    w, h, nominal = C.c_uint32(), C.c_uint32(), (C.c_double * 2)()
+    rc = load().aic_cells_geometry(int(cols), int(rows), int(characters), C.byref(w), C.byref(h), nominal)
+    if rc != AIC_OK:
+        raise AicError(rc, f"aic_cells_geometry({cols}, {rows}, characters {characters})")
+    return (w.value, h.value), (nominal[0], nominal[1])
+
+
+def cells_ansi(cells, names=None, widths=None, in_rect: bool = False, origin=(0, 0), capacity: Optional[int] = None) -> bytes:
+    """write_frame as a byte stream (aic_cells_ansi). cells: [rows][cols] of CELL_DTYPE. names / widths: per layer (world, ui) a list of str (None
+    entries allowed) / of column widths, or None. `capacity`: the buffer to offer (default: exactly what the stream needs)."""
+    cells = np.ascontiguousarray(cells, CELL_DTYPE)
+    rows, cols = cells.shape
+    text = CellsText()
+    keep = []
+    for layer in (0, 1):
+        table = names[layer] if names else None
+        if table is not None:
+            arr = (C.c_char_p * max(len(table), 1))(*[None if t is None else t.encode() for t in table])
+            keep.append(arr)
+            text.names[layer] = C.cast(arr, C.POINTER(C.c_char_p))
+            text.n_names[layer] = len(table)
+            if widths and widths[layer] is not None:
+                wa = (C.c_uint8 * max(len(table), 1))(*[int(v) for v in widths[layer]])
+                keep.append(wa)
+                text.widths[layer] = C.cast(wa, C.POINTER(C.c_uint8))
+    text.origin[0], text.origin[1] = int(origin[0]), int(origin[1])
+    lib = load()
+    flags = CELLS_ANSI_IN_RECT if in_rect else 0
+    length = C.c_uint64()
+    if capacity is None:
+        lib.aic_cells_ansi(_ptr(cells) if cells.size else None, cols, rows, C.byref(text), flags, None, 0, C.byref(length))
+        capacity = length.value
+    buf = C.create_string_buffer(max(int(capacity), 1))
+    rc = lib.aic_cells_ansi(_ptr(cells) if cells.size else None, cols, rows, C.byref(text), flags, buf, int(capacity), C.byref(length))
+    if rc != AIC_OK:
+        raise AicError(rc, f"aic_cells_ansi: the stream needs {length.value} bytes, capacity {capacity}")
+    return buf.raw[:length.value]
+
+
 PIXEL_AUX_DTYPE = np.dtype(
     [("hit", "<i4"), ("cube", "<i4", (3,)), ("voxel", "<i4", (3,)), ("resolution", "<i4"), ("face", "<i4"),
      ("block_index", "<i4"), ("cubes_traced", "<u4"), ("layer", "<u4"), ("t_distance", "<f8")],
@@ -577,6 +647,10 @@ def load() -> C.CDLL:
         lib.aic_sample_luminance.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.aic_cursor_raycast.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_double, C.c_uint32, C.c_void_p]
         lib.aic_light_rays.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.aic_cells_geometry.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+        lib.aic_cells_ansi.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(CellsText), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.aic_image_cells.argtypes = [C.c_void_p, C.POINTER(CellsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CellsInfo)]
+        lib.aic_render_cells.argtypes = [C.c_void_p, C.POINTER(FrameDesc), C.POINTER(CellsDesc), C.c_void_p, C.c_int, C.POINTER(FrameInfo), C.POINTER(CellsInfo)]
         lib.aic_export_size.restype = C.c_int
         lib.aic_export_size.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
         lib.aic_assemble_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -1145,6 +1219,43 @@ class Context:
         image = np.zeros((d.out_height, d.out_width, 4), np.uint16 if flags & PRESENT_OUT_F16 else np.uint8)
         self._check(self._lib.aic_present_split(self._h, C.byref(d), C.c_void_p(src_ptr or None), image.ctypes.data_as(C.c_void_p), 0, C.byref(info)))
         return image, info
+
+    def image_cells(self, image, aux, cols: int, rows: int, characters: int, colors: int, exposure: float = 1.0, tone_mapping: int = 0,
+                    maximum_intensity: float = float("inf"), postprocessed: bool = False, f16: bool = False, image_device: bool = False,
+                    out_device: Optional[int] = None):
+        """image_patch_to_character for every cell of an image (aic_image_cells). image: [height][width][4] float32 (or, f16, float16 / uint16 bit
+        patterns) of cells_geometry's framebuffer and aux: [height][width] of PIXEL_AUX_DTYPE or None -- or, image_device, two device pointers
+        (aux 0: none). Returns (cells [rows][cols] of CELL_DTYPE, info), cells None when `out_device`, a device pointer they are written to, is given."""
+        d = CellsDesc(int(cols), int(rows), int(characters), int(colors), float(exposure), int(tone_mapping), float(maximum_intensity), 0)
+        d.flags = (CELLS_POSTPROCESSED if postprocessed else 0) | (CELLS_IMAGE_F16 if f16 else 0) | (CELLS_IMAGE_DEVICE if image_device else 0)
+        if image_device:
+            img_p, aux_p = C.c_void_p(int(image) or None), C.c_void_p(int(aux or 0) or None)
+        else:
+            image = np.ascontiguousarray(image, (image.dtype if f16 else np.float32))
+            if f16 and image.dtype.itemsize != 2:
+                raise ValueError("an f16 image is float16 or uint16 bit patterns")
+            aux = None if aux is None else np.ascontiguousarray(aux, PIXEL_AUX_DTYPE)
+            img_p, aux_p = _ptr(image), (None if aux is None else _ptr(aux))
+        info = CellsInfo()
+        if out_device is not None:
+            d.flags |= CELLS_OUT_DEVICE
+            self._check(self._lib.aic_image_cells(self._h, C.byref(d), img_p, aux_p, C.c_void_p(out_device or None), C.byref(info)))
+            return None, info
+        out = np.zeros((max(int(rows), 1), max(int(cols), 1)), CELL_DTYPE)
+        self._check(self._lib.aic_image_cells(self._h, C.byref(d), img_p, aux_p, _ptr(out), C.byref(info)))
+        return out, info
+
+    def render_cells(self, frame: FrameDesc, cols: int, rows: int, characters: int, colors: int, out_device: Optional[int] = None):
+        """One frame of the terminal renderer (aic_render_cells): `frame`, of cells_geometry's size, is traced into context scratch and turned into
+        cells on the device. Returns (cells [rows][cols] of CELL_DTYPE or None with `out_device`, frame info, cells info)."""
+        d = CellsDesc(int(cols), int(rows), int(characters), int(colors), 1.0, 0, float("inf"), 0)
+        fi, ci = FrameInfo(), CellsInfo()
+        if out_device is not None:
+            self._check(self._lib.aic_render_cells(self._h, C.byref(frame), C.byref(d), C.c_void_p(out_device or None), 1, C.byref(fi), C.byref(ci)))
+            return None, fi, ci
+        out = np.zeros((max(int(rows), 1), max(int(cols), 1)), CELL_DTYPE)
+        self._check(self._lib.aic_render_cells(self._h, C.byref(frame), C.byref(d), _ptr(out), 0, C.byref(fi), C.byref(ci)))
+        return out, fi, ci
 
     def export_split(self, src, src_size, out_size, inverse_projection_zw, color: bool = True, depth: bool = True, device_outs=None):
         """A resident Split frame exported as sRGB8 colour and metric depth (aic_export_split): the colour is what present_split gives at `out_size`

@@ -382,6 +382,7 @@ void aic_destroy(aic_ctx *c) {
     c->lut.release(); c->srgb_thr.release(); c->srgb_buckets.release(); c->out.release(); c->aux.release(); c->staging.release(); c->ortho_views.release(); c->reproject_scratch.release(); c->pick_scratch.release(); c->stale_scratch.release(); c->stale_cubes_scratch.release(); c->stale_blocks_scratch.release(); c->stale_blocks_boxes.release(); c->present_scratch.release(); c->lines_scratch.release();
     c->text_atlas.release(); c->text_codes.release(); c->export_counts.release(); c->exposure_scratch.release(); c->cursor_scratch.release();
     c->light_rays_tree.release(); c->light_rays_derived.release(); c->light_rays_scratch.release(); c->light_rays_list.release();
+    c->cells_scratch.release(); c->cells_frame.release();
     for (hipEvent_t ev : c->stale_blocks_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (c->dump) std::fclose(c->dump);

@@ -244,6 +244,10 @@ struct aic_ctx {
     int light_rays_distance = -1, light_rays_layer = -1;
     uint32_t light_rays_n_tree = 0, light_rays_bound = 0;
     uint64_t light_rays_version = 0;
+    // aic_image_cells, aic_render_cells (aic_cells_host.cpp): the branch counters, then the staged image, records and cells of a call with host pointers;
+    // the linear frame aic_render_cells traces into (its first-hit records go to `aux`)
+    DevBuf<unsigned char> cells_scratch;
+    DevBuf<float4> cells_frame;
 };
 
 namespace aic {

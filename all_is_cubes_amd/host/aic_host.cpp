@@ -1191,6 +1191,130 @@ std::string HipRtRenderer::draw_text(const std::string &line_ending) {
     return out;
 }
 
+// --- the terminal (all-is-cubes-desktop/src/terminal.rs, terminal/options.rs) ---------------------------------------------------------------------------
+TerminalColorMode TerminalOptions::cycle(TerminalColorMode m) {
+    switch (m) {
+        case TerminalColorMode::None: return TerminalColorMode::TwoFiftySix;
+        case TerminalColorMode::TwoFiftySix: return TerminalColorMode::Rgb;
+        default: return TerminalColorMode::None;
+    }
+}
+TerminalCharacterMode TerminalOptions::cycle(TerminalCharacterMode m) {
+    switch (m) {
+        case TerminalCharacterMode::Names: return TerminalCharacterMode::Shades;
+        case TerminalCharacterMode::Shades: return TerminalCharacterMode::Split;
+        case TerminalCharacterMode::Split: return TerminalCharacterMode::Shapes;
+        case TerminalCharacterMode::Shapes: return TerminalCharacterMode::Braille;
+        default: return TerminalCharacterMode::Names;
+    }
+}
+Viewport TerminalOptions::viewport_from_terminal_size(uint32_t cols, uint32_t rows) const {
+    Viewport v;
+    double nominal[2];
+    if (aic_cells_geometry(cols, rows, (int32_t)characters, &v.framebuffer_width, &v.framebuffer_height, nominal) != AIC_OK)
+        throw std::invalid_argument("viewport_from_terminal_size: cols or rows above 65535");
+    v.nominal_width = nominal[0];
+    v.nominal_height = nominal[1];
+    return v;
+}
+
+// the grid whose framebuffer under `characters` is w x h; throws if there is none
+static void cells_grid_of(uint32_t w, uint32_t h, TerminalCharacterMode characters, uint32_t *cols, uint32_t *rows) {
+    uint32_t rw = 0, rh = 0;
+    (void)aic_cells_geometry(1, 1, (int32_t)characters, &rw, &rh, nullptr);  // rays per character
+    if (!rw || !rh || !w || !h || w % rw || h % rh) throw std::invalid_argument("the viewport is not viewport_from_terminal_size of a grid under this CharacterMode");
+    *cols = w / rw;
+    *rows = h / rh;
+}
+
+CellsRendering HipRtRenderer::draw_cells(const TerminalOptions &options) {
+    const aic_frame_desc f = make_frame();
+    CellsRendering r;
+    cells_grid_of(f.width, f.height, options.characters, &r.cols, &r.rows);
+    r.cells.assign((size_t)r.cols * r.rows, aic_cell{0, 0, 0});
+    aic_cells_desc d{};
+    d.cols = r.cols;
+    d.rows = r.rows;
+    d.characters = (int32_t)options.characters;
+    d.colors = (int32_t)options.colors;
+    aic_frame_info fi;
+    check(aic_render_cells(ctx_, &f, &d, r.cells.data(), 0, &fi, &r.cells_info), "aic_render_cells");
+    r.info = to_info(fi, f.width, f.height);
+    return r;
+}
+
+HipRtRenderer::TerminalNames HipRtRenderer::terminal_names() const {
+    TerminalNames t;
+    for (int layer = 0; layer < 2; layer++) {
+        const std::shared_ptr<Space> &space = layers_[layer].space;
+        for (size_t i = 0; space && i < space->n_blocks(); i++) {
+            const std::string &name = space->block((uint32_t)i).display_name;
+            if (name.empty()) { t.names[layer].push_back("#"); t.widths[layer].push_back(1); continue; }
+            // first UTF-8 scalar, as draw_text cuts it
+            size_t len = 1;
+            const unsigned char c0 = (unsigned char)name[0];
+            if (c0 >= 0xf0) len = 4; else if (c0 >= 0xe0) len = 3; else if (c0 >= 0xc0) len = 2;
+            len = std::min(len, name.size());
+            uint32_t v = len == 1 ? c0 : (len == 2 ? (c0 & 0x1fu) : (len == 3 ? (c0 & 0x0fu) : (c0 & 0x07u)));
+            for (size_t k = 1; k < len; k++) v = (v << 6) | ((unsigned char)name[k] & 0x3fu);
+            const bool wide = (v >= 0x1100u && v <= 0x115fu) || (v >= 0x2e80u && v <= 0xa4cfu) || (v >= 0xac00u && v <= 0xd7a3u) || (v >= 0xf900u && v <= 0xfaffu) ||
+                              (v >= 0xfe30u && v <= 0xfe6fu) || (v >= 0xff00u && v <= 0xff60u) || (v >= 0xffe0u && v <= 0xffe6u) || (v >= 0x1f300u && v <= 0x1faffu) ||
+                              (v >= 0x20000u && v <= 0x3fffdu);
+            const bool combining = (v >= 0x300u && v <= 0x36fu) || (v >= 0x200bu && v <= 0x200fu);
+            t.names[layer].push_back(name.substr(0, len));
+            t.widths[layer].push_back(wide ? 2 : (combining ? 0 : 1));
+        }
+    }
+    return t;
+}
+
+std::string HipRtRenderer::cells_to_ansi(const CellsRendering &frame, bool in_rect, uint16_t origin_x, uint16_t origin_y) const {
+    const TerminalNames t = terminal_names();
+    std::vector<const char *> ptrs[2];
+    aic_cells_text text{};
+    for (int layer = 0; layer < 2; layer++) {
+        for (const std::string &s : t.names[layer]) ptrs[layer].push_back(s.c_str());
+        text.names[layer] = ptrs[layer].empty() ? nullptr : ptrs[layer].data();
+        text.widths[layer] = t.widths[layer].empty() ? nullptr : t.widths[layer].data();
+        text.n_names[layer] = (uint32_t)ptrs[layer].size();
+    }
+    text.origin[0] = origin_x;
+    text.origin[1] = origin_y;
+    const uint32_t flags = in_rect ? AIC_CELLS_ANSI_IN_RECT : 0u;
+    uint64_t length = 0;
+    (void)aic_cells_ansi(frame.cells.data(), frame.cols, frame.rows, &text, flags, nullptr, 0, &length);  // (measures: too small a capacity by design)
+    std::string out((size_t)length, '\0');
+    if (aic_cells_ansi(frame.cells.data(), frame.cols, frame.rows, &text, flags, out.data(), length, &length) != AIC_OK)
+        throw RenderError(AIC_ERR_INVALID, "aic_cells_ansi failed");
+    return out;
+}
+
+std::string HipRtRenderer::draw_terminal(const TerminalOptions &options, bool in_rect, uint16_t origin_x, uint16_t origin_y) {
+    return cells_to_ansi(draw_cells(options), in_rect, origin_x, origin_y);
+}
+
+CellsRendering HipRtRenderer::present_split_cells(const void *src_device, void *scratch_device, uint32_t cols, uint32_t rows, const TerminalOptions &options) {
+    if (options.characters == TerminalCharacterMode::Names) throw std::invalid_argument("present_split_cells: Names needs first-hit records, which a Split frame has not got");
+    const Viewport target = options.viewport_from_terminal_size(cols, rows);
+    aic_present_info pi;
+    const aic_present_desc pd = present_desc(target.framebuffer_width, target.framebuffer_height, AIC_PRESENT_OUT_F16);
+    check(aic_present_split(ctx_, &pd, src_device, scratch_device, 1, &pi), "aic_present_split");
+    CellsRendering r;
+    r.cols = cols ? cols : 1u;
+    r.rows = rows ? rows : 1u;
+    r.cells.assign((size_t)r.cols * r.rows, aic_cell{0, 0, 0});
+    aic_cells_desc d{};
+    d.cols = cols;
+    d.rows = rows;
+    d.characters = (int32_t)options.characters;
+    d.colors = (int32_t)options.colors;
+    d.exposure = 1.0f;
+    d.maximum_intensity = INFINITY;
+    d.flags = AIC_CELLS_IMAGE_F16 | AIC_CELLS_POSTPROCESSED | AIC_CELLS_IMAGE_DEVICE;
+    check(aic_image_cells(ctx_, &d, scratch_device, nullptr, r.cells.data(), &r.cells_info), "aic_image_cells");
+    return r;
+}
+
 uint32_t HipRtRenderer::partition_rows(uint32_t strip_rows, uint32_t n_parts, uint32_t part) const {
     aic_partition p{strip_rows, n_parts, part, 0};
     return aic_partition_rows(world_camera_.viewport().framebuffer_height, &p);

@@ -301,6 +301,26 @@ struct Rendering {  // headless.rs:52-67
     ImageInfo info;
 };
 
+// TerminalOptions (all-is-cubes-desktop/src/terminal/options.rs:15-185): what the terminal's frames are made of. The enumerators carry the C ABI's values
+// (AIC_CELLS_COLOR_*, AIC_CELLS_*).
+enum class TerminalColorMode : int32_t { None = 0, TwoFiftySix = 1, Rgb = 2 };
+enum class TerminalCharacterMode : int32_t { Names = 0, Shades = 1, Split = 2, Shapes = 3, Braille = 4 };
+struct TerminalOptions {
+    TerminalColorMode colors = TerminalColorMode::TwoFiftySix;        // options.rs:41-48
+    TerminalCharacterMode characters = TerminalCharacterMode::Split;
+    // the "next" option for purposes of UI stepping (options.rs:61-68, 166-175)
+    static TerminalColorMode cycle(TerminalColorMode m);
+    static TerminalCharacterMode cycle(TerminalCharacterMode m);
+    // viewport_from_terminal_size (options.rs:25-38; aic_cells_geometry): the viewport to raytrace for a drawing area of cols x rows characters
+    Viewport viewport_from_terminal_size(uint32_t cols, uint32_t rows) const;
+};
+struct CellsRendering {  // a frame of the terminal: [rows][cols] cells (aic_cell), the trace's ImageInfo (zero for a presentation) and the branch counters
+    uint32_t cols = 0, rows = 0;
+    std::vector<aic_cell> cells;
+    ImageInfo info;
+    aic_cells_info cells_info{};
+};
+
 // The info-text overlay (renderer.rs:659-683 `draw_info_text`): `text` drawn with Builtin::FontSystem16 by
 // FontDef::draw_str_monospaced (all-is-cubes/src/text/font.rs:178-203) at offset (5, 5) into an RGBA8 image of width x
 // height, outline pixels in `outline`, glyph pixels in `foreground`, in the reference's call order (a later glyph's outline
@@ -430,6 +450,26 @@ class HipRtRenderer : public HeadlessRenderer {
     // pixel centre; the first block hit shows the first character of its display name ('#' if it has none), a ray that
     // entered the space and hit nothing ' ', one that never entered it '.', one that ran out of steps 'X'
     std::string draw_text(const std::string &line_ending = "\n");
+    // One frame of the terminal renderer (all-is-cubes-desktop/src/terminal.rs:119-137; aic_render_cells): the current viewport -- which must be
+    // TerminalOptions::viewport_from_terminal_size of some grid under options.characters, std::invalid_argument otherwise -- traced and turned into
+    // character cells on the device.
+    CellsRendering draw_cells(const TerminalOptions &options);
+    // The names table aic_cells_ansi takes for block glyphs, made from each layer's blocks' display_name as draw_text cuts it: the first scalar, "#"
+    // when empty. Widths: 2 for the East Asian wide and fullwidth ranges, 0 for combining marks, else 1 (the reference measures by cursor read-back and
+    // falls back to unicode_width, chars.rs:229-300).
+    struct TerminalNames {
+        std::vector<std::string> names[2];
+        std::vector<uint8_t> widths[2];
+    };
+    TerminalNames terminal_names() const;
+    // TerminalWindow::write_frame (terminal/ui.rs:300-360; aic_cells_ansi) of `frame` with terminal_names(): the byte stream for the terminal
+    std::string cells_to_ansi(const CellsRendering &frame, bool in_rect = false, uint16_t origin_x = 0, uint16_t origin_y = 0) const;
+    // draw_cells and cells_to_ansi in one
+    std::string draw_terminal(const TerminalOptions &options, bool in_rect = false, uint16_t origin_x = 0, uint16_t origin_y = 0);
+    // A terminal target for the resident interactive frame: aic_present_split with AIC_PRESENT_OUT_F16 of `src_device` (a Split frame of the current
+    // viewport) into `scratch_device` -- device memory of the caller's, 8 bytes per pixel of the cells' framebuffer for cols x rows --, then
+    // aic_image_cells on it (f16, already post-processed, on the device). Every mode but Names, which needs first-hit records a Split frame has not got.
+    CellsRendering present_split_cells(const void *src_device, void *scratch_device, uint32_t cols, uint32_t rows, const TerminalOptions &options);
     // SpaceRaytracer::trace_ray (sr.rs:113-120) for a batch of world-space rays against one layer's space as last updated (aic_trace_rays): no camera, no
     // layering, one ray per result. `colors[i]` is the ColorBuf trace_ray leaves in its accumulator (light r, g, b and transmittance), `hits[i]` the first-hit
     // record (hit == 0: none; t_distance in units of the ray's direction, which is taken as given).

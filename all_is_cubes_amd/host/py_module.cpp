@@ -232,6 +232,29 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("n_hits", &ImageInfo::n_hits).def_readonly("n_light", &ImageInfo::n_light).def_readonly("kernel_ms", &ImageInfo::kernel_ms)
         .def_readonly("total_ms", &ImageInfo::total_ms).def_readonly("width", &ImageInfo::width).def_readonly("height", &ImageInfo::height)
         .def_readonly("rows_rendered", &ImageInfo::rows_rendered).def("status_text", &ImageInfo::status_text);
+    py::enum_<TerminalColorMode>(m, "TerminalColorMode").value("None_", TerminalColorMode::None).value("TwoFiftySix", TerminalColorMode::TwoFiftySix)
+        .value("Rgb", TerminalColorMode::Rgb);
+    py::enum_<TerminalCharacterMode>(m, "TerminalCharacterMode").value("Names", TerminalCharacterMode::Names).value("Shades", TerminalCharacterMode::Shades)
+        .value("Split", TerminalCharacterMode::Split).value("Shapes", TerminalCharacterMode::Shapes).value("Braille", TerminalCharacterMode::Braille);
+    py::class_<TerminalOptions>(m, "TerminalOptions")
+        .def(py::init<>())
+        .def_readwrite("colors", &TerminalOptions::colors).def_readwrite("characters", &TerminalOptions::characters)
+        .def("cycle_colors", [](TerminalOptions &o) { o.colors = TerminalOptions::cycle(o.colors); })
+        .def("cycle_characters", [](TerminalOptions &o) { o.characters = TerminalOptions::cycle(o.characters); })
+        .def("viewport_from_terminal_size", &TerminalOptions::viewport_from_terminal_size, py::arg("cols"), py::arg("rows"));
+    py::class_<CellsRendering>(m, "CellsRendering")
+        .def_readonly("cols", &CellsRendering::cols).def_readonly("rows", &CellsRendering::rows).def_readonly("info", &CellsRendering::info)
+        .def_property_readonly("cells", [](const CellsRendering &r) {  // [rows, cols, 3] u32: glyph, fg, bg -- view it as abi.CELL_DTYPE
+            py::array_t<uint32_t> a({(py::ssize_t)r.rows, (py::ssize_t)r.cols, (py::ssize_t)3});
+            if (!r.cells.empty()) std::memcpy(a.mutable_data(), r.cells.data(), r.cells.size() * sizeof(aic_cell));
+            return a;
+        })
+        .def_property_readonly("counters", [](const CellsRendering &r) {
+            py::array_t<uint32_t> a((py::ssize_t)16);  // n_cells, then the fifteen branch counters in aic_cells_info's order
+            std::memcpy(a.mutable_data(), &r.cells_info, 16 * 4);
+            return a;
+        })
+        .def_property_readonly("kernel_ms", [](const CellsRendering &r) { return r.cells_info.kernel_ms; });
     py::class_<Rendering>(m, "Rendering")
         .def_readonly("width", &Rendering::width).def_readonly("height", &Rendering::height).def_readonly("flaws", &Rendering::flaws)
         .def_readonly("info", &Rendering::info)
@@ -320,6 +343,31 @@ PYBIND11_MODULE(_host, m) {
         }, py::arg("cursor") = py::none())
         .def("draw", [](HipRtRenderer &r, const std::string &t) { py::gil_scoped_release rel; return r.draw(t); }, py::arg("info_text") = "")
         .def("draw_text", [](HipRtRenderer &r, const std::string &le) { py::gil_scoped_release rel; return r.draw_text(le); }, py::arg("line_ending") = "\n")
+        .def("draw_cells", [](HipRtRenderer &r, const TerminalOptions &o) { py::gil_scoped_release rel; return r.draw_cells(o); }, py::arg("options"))
+        .def("draw_terminal", [](HipRtRenderer &r, const TerminalOptions &o, bool in_rect, std::array<uint16_t, 2> origin) {
+            std::string s;
+            { py::gil_scoped_release rel; s = r.draw_terminal(o, in_rect, origin[0], origin[1]); }
+            return py::bytes(s);
+        }, py::arg("options"), py::arg("in_rect") = false, py::arg("origin") = std::array<uint16_t, 2>{0, 0})
+        .def("cells_to_ansi", [](HipRtRenderer &r, const CellsRendering &frame, bool in_rect, std::array<uint16_t, 2> origin) {
+            return py::bytes(r.cells_to_ansi(frame, in_rect, origin[0], origin[1]));
+        }, py::arg("frame"), py::arg("in_rect") = false, py::arg("origin") = std::array<uint16_t, 2>{0, 0})
+        .def("terminal_names", [](HipRtRenderer &r) {  // ((world names, ui names), (world widths, ui widths)): what abi.cells_ansi takes
+            const HipRtRenderer::TerminalNames t = r.terminal_names();
+            py::list names, widths;
+            for (int layer = 0; layer < 2; layer++) {
+                py::list n, w;
+                for (const std::string &s : t.names[layer]) n.append(py::str(s));
+                for (uint8_t v : t.widths[layer]) w.append((int)v);
+                names.append(n);
+                widths.append(w);
+            }
+            return py::make_tuple(names, widths);
+        })
+        .def("present_split_cells", [](HipRtRenderer &r, uintptr_t src_ptr, uintptr_t scratch_ptr, uint32_t cols, uint32_t rows, const TerminalOptions &o) {
+            py::gil_scoped_release rel;
+            return r.present_split_cells(reinterpret_cast<const void *>(src_ptr), reinterpret_cast<void *>(scratch_ptr), cols, rows, o);
+        }, py::arg("src_ptr"), py::arg("scratch_ptr"), py::arg("cols"), py::arg("rows"), py::arg("options"))
         .def("trace_rays", [](HipRtRenderer &r, int layer, py::array_t<double, py::array::c_style | py::array::forcecast> rays, bool include_sky) {
             // rays [n, 6] = origin xyz, direction xyz -> dict(colorbuf [n, 4] f32, hits [n, sizeof(aic_pixel_aux)] u8 -- view it as abi.PIXEL_AUX_DTYPE --, info)
             if (rays.size() % 6 != 0) throw std::invalid_argument("rays: [n, 6] doubles");

@@ -1214,6 +1214,102 @@ int aic_light_rays_wireframe(const aic_light_cube_info *info, const aic_light_ra
  * device_lines or n_lines, NULL first with n_first > 0, more than AIC_LINES_MAX lines in all. */
 int aic_light_rays_cursor_lines(aic_ctx *ctx, int layer, const int32_t *cube /* [3] */, int32_t maximum_distance, const aic_line_vertex *first, uint32_t n_first,
                                 aic_light_cube_info *info, const aic_line_vertex **device_lines, uint32_t *n_lines);
+/* Terminal frames -- replaces: the `terminal` graphics mode of the desktop program (all-is-cubes-desktop/src/terminal.rs:101-140): the raytracer with the
+ * ColorCharacterBuf accumulator -- per pixel the first hit block's text and camera.post_process_color of Rgba::from of the ColorBuf (terminal.rs:341-366) --,
+ * then image_patch_to_character (terminal/chars.rs:18-173), which turns each patch of 1x1, 1x2 or 2x4 pixels into one character and a colour pair under
+ * TerminalOptions { colors, characters } (terminal/options.rs:15-185), and write_frame (terminal/ui.rs:300-360), which writes them as text and colour
+ * escapes. Here the patch rule runs on the device, one lane per character cell, behind the trace: a frame leaves the device as 12 bytes per cell.
+ * DESIGN.md 4.22 restates every operation; tests/cells_ref.py is that text in NumPy and the device equals it cell for cell, all three words.
+ *
+ * A cell: glyph is a Unicode scalar value (' ', '.', 'X', U+2580..U+259B, U+2800 + the Braille index) or AIC_CELL_GLYPH_BLOCK | layer << 16 | block_index,
+ * "the text of that block of that layer" (the library knows no names, as it knows no font). fg and bg are kind << 24 | payload:
+ *   kind 0  no colour: the Colors field is None, nothing is emitted     kind 1  Color::Reset     kind 2  Color::Black
+ *   kind 3  Color::AnsiValue(n), payload n                               kind 4  Color::Rgb, payload r << 16 | g << 8 | b
+ * A pixel's text follows its aic_pixel_aux record as the text renderer reads it: hit == 1 gives the block reference; else cubes_traced > 1000 'X' (an
+ * approximation of Exception::Incomplete), cubes_traced > 0 ' ', else '.'. Under antialiasing the record is the first sample's, where CharacterBuf::mean
+ * takes the first sample that has a hit: colours are exact under antialiasing, text at AntialiasingOption::None, the reference's default. */
+#define AIC_CELLS_NAMES 0    /* CharacterMode::Names: the block's text, 1 x 1 rays per character */
+#define AIC_CELLS_SHADES 1   /* CharacterMode::Shades: " ░▒▓█" by luminance, 1 x 1 */
+#define AIC_CELLS_SPLIT 2    /* CharacterMode::Split: half blocks, 1 x 2 */
+#define AIC_CELLS_SHAPES 3   /* CharacterMode::Shapes: eighth blocks without colour, Split's rule with, 1 x 2 */
+#define AIC_CELLS_BRAILLE 4  /* CharacterMode::Braille: dot patterns, 2 x 4 */
+#define AIC_CELLS_COLOR_NONE 0  /* ColorMode::None */
+#define AIC_CELLS_COLOR_256 1   /* ColorMode::TwoFiftySix */
+#define AIC_CELLS_COLOR_RGB 2   /* ColorMode::Rgb */
+#define AIC_CELL_GLYPH_BLOCK 0x80000000u
+#define AIC_CELL_COLOR_NONE 0u
+#define AIC_CELL_COLOR_RESET 1u
+#define AIC_CELL_COLOR_BLACK 2u
+#define AIC_CELL_COLOR_ANSI 3u
+#define AIC_CELL_COLOR_RGB 4u
+typedef struct aic_cell {
+    uint32_t glyph, fg, bg;
+} aic_cell;
+/* replaces: TerminalOptions::viewport_from_terminal_size (terminal/options.rs:25-38), host-only: cols and rows are raised to 1 (`size.max(size2(1, 1))`),
+ * the framebuffer is cells x rays per character, the nominal size (cols * 0.5, rows * 1.0). Any output may be NULL. AIC_ERR_INVALID: cols or rows above
+ * 65535 (the reference's u16), characters outside 0..4. */
+int aic_cells_geometry(uint32_t cols, uint32_t rows, int32_t characters, uint32_t *width, uint32_t *height, double nominal[2]);
+#define AIC_CELLS_IMAGE_DEVICE 1u    /* `image` and `aux` are device pointers on the context's device (16-byte / 8-byte aligned; f16 image 8-byte) */
+#define AIC_CELLS_OUT_DEVICE 2u      /* `out` is a device pointer on the context's device (4-byte aligned) */
+#define AIC_CELLS_IMAGE_F16 4u       /* the image holds four f16 per pixel (what aic_present_split writes with AIC_PRESENT_OUT_F16) instead of four f32 */
+#define AIC_CELLS_POSTPROCESSED 8u   /* the image is already exposed and tone-mapped: post_process_color is skipped */
+typedef struct aic_cells_desc {
+    uint32_t cols, rows;        /* the grid; the image is aic_cells_geometry's framebuffer of max(cols, 1) x max(rows, 1) cells */
+    int32_t characters, colors; /* AIC_CELLS_* / AIC_CELLS_COLOR_* */
+    float exposure;             /* Camera::exposure() of post_process_color (camera_struct.rs:376-382); not NaN, not negative */
+    int32_t tone_mapping;       /* 0 Clamp, 1 Reinhard */
+    float maximum_intensity;    /* may be +inf: no tone mapping */
+    uint32_t flags;             /* AIC_CELLS_* flags */
+} aic_cells_desc;
+/* cells per branch of image_patch_to_character taken, and colour conversions per branch of ColorMode::convert (up to two a cell) */
+typedef struct aic_cells_info {
+    uint32_t n_cells;
+    uint32_t n_full, n_upper, n_lower, n_text, n_space;  /* Split without colour: the five arms (n_text: the `lum2 > 0.2` arm, with or without aux) */
+    uint32_t n_shade;                                    /* Shades; Shapes without colour when |lum1 - lum2| < 0.05 */
+    uint32_t n_rising, n_falling;                        /* Shapes without colour: lum1 < lum2, and the rest */
+    uint32_t n_equal, n_unequal;                         /* Split and Shapes with colour: the two converted colours equal or not */
+    uint32_t n_names, n_braille;
+    uint32_t n_gray, n_cube, n_rgb;                      /* conversions: TwoFiftySix grey ramp, TwoFiftySix colour cube, Rgb */
+    float kernel_ms;                                     /* HIP events around the cells kernel */
+    uint32_t reserved;
+} aic_cells_info;
+/* replaces: image_patch_to_character for every cell of an image the caller has. image = [height][width] of four f32 (linear r, g, b, a: what
+ * AIC_FRAME_OUT_LINEAR writes) or with AIC_CELLS_IMAGE_F16 four f16; alpha is never read (every pixel is Some(colour); Rgba::luminance and to_srgb8's colour
+ * channels ignore it). aux = [height][width] first-hit records where the image lives, or NULL: Names is then AIC_ERR_INVALID and Split without colours
+ * writes ' ' where it would have written the text. out = [rows][cols] cells (of the raised grid). The call blocks and runs on slot 0's stream.
+ * AIC_ERR_INVALID, before anything is queued and with the context still usable: a NULL desc, image or out; characters or colors out of range; cols or rows
+ * above 65535; unknown flag bits; tone_mapping other than 0 or 1; exposure NaN or negative; maximum_intensity NaN or negative; a misaligned device pointer;
+ * a frame still occupying slot 0. */
+int aic_image_cells(aic_ctx *ctx, const aic_cells_desc *desc, const void *image, const aic_pixel_aux *aux, aic_cell *out, aic_cells_info *info);
+/* replaces: one frame of the terminal renderer (terminal.rs:119-137): traces `frame` as aic_render does with AIC_FRAME_OUT_LINEAR | AIC_FRAME_AUX into
+ * scratch the context owns (16 + 56 bytes a pixel, kept until aic_destroy), then runs the cells kernel behind it on the context's stream. frame->width and
+ * height must be aic_cells_geometry's of desc. desc->exposure, tone_mapping and maximum_intensity are NOT used: every pixel, UI pixels included, is
+ * post-processed with frame->world.exposure and the world layer's options, as the reference does (terminal.rs:120-123). desc->flags must be 0;
+ * out_is_device as in aic_render. The library sets no AIC_FRAME_PIXEL_CENTERS: the terminal draws through the image path. It accepts and refuses what
+ * aic_render accepts and refuses, and refuses also AIC_FRAME_AUX, AIC_FRAME_OUT_LINEAR, AIC_FRAME_OUT_COLORBUF and AIC_FRAME_OUT_SPLIT set by the caller
+ * and a frame size that is not the geometry's (AIC_ERR_INVALID), a partition with n_parts > 1 and AIC_FRAME_BLOOM (AIC_ERR_UNSUPPORTED). Either info may be
+ * NULL. */
+int aic_render_cells(aic_ctx *ctx, const aic_frame_desc *frame, const aic_cells_desc *desc, aic_cell *out, int out_is_device, aic_frame_info *frame_info,
+                     aic_cells_info *cells_info);
+/* replaces: TerminalWindow::write_frame with write_colored_and_measure (terminal/ui.rs:300-360, terminal/chars.rs:205-296) as a byte stream, host-only.
+ * The escape text is this project's own statement (DESIGN.md 4.22 writes the format out), not a copy of what the reference's terminal library emits.
+ * text (may be NULL): per layer a table of NUL-terminated UTF-8 strings and their column widths for block glyphs; a NULL table, an index beyond it or a
+ * NULL string gives "#" of width 1; NULL widths mean 1 each. Every other glyph has width 1. A glyph of width w advances max(w, 1) cells and is written
+ * only if w fits what is left of the row; its colour escape is written first either way, and only when the pair differs from the last one written.
+ * Without AIC_CELLS_ANSI_IN_RECT a row ends with the attribute reset and "\r\n" and the colour memory is cleared; with it a row starts with a cursor
+ * move to (origin[0], origin[1] + row), zero-based. The stream starts with cursor-hide and the attribute reset and ends with the reset.
+ * *length is always the length needed; nothing is written past capacity; when capacity is too small the call returns AIC_ERR_INVALID and writes nothing.
+ * AIC_ERR_INVALID also: NULL cells with cols * rows > 0, a NULL length, NULL out with capacity > 0, unknown flag bits. */
+#define AIC_CELLS_ANSI_IN_RECT 1u
+typedef struct aic_cells_text {
+    const char *const *names[2];  /* per layer (AIC_LAYER_WORLD, AIC_LAYER_UI): [n_names] strings */
+    const uint8_t *widths[2];     /* per layer: [n_names] column widths */
+    uint32_t n_names[2];
+    uint16_t origin[2];           /* AIC_CELLS_ANSI_IN_RECT: the rectangle's corner, column and row */
+    uint32_t reserved;
+} aic_cells_text;
+int aic_cells_ansi(const aic_cell *cells, uint32_t cols, uint32_t rows, const aic_cells_text *text, uint32_t flags, char *out, uint64_t capacity,
+                   uint64_t *length);
 
 #ifdef __cplusplus
 }

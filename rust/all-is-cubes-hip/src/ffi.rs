@@ -47,6 +47,25 @@ pub const AIC_LIGHT_RAYS_DEVICE: u32 = 1;
 pub const AIC_LIGHT_CUBE_STORED: u32 = 1;
 pub const AIC_LIGHT_CUBE_OUTSIDE: u32 = 2;
 pub const AIC_LIGHT_RAYS_MAX_CUBES: u32 = 65536;
+pub const AIC_CELLS_NAMES: i32 = 0;
+pub const AIC_CELLS_SHADES: i32 = 1;
+pub const AIC_CELLS_SPLIT: i32 = 2;
+pub const AIC_CELLS_SHAPES: i32 = 3;
+pub const AIC_CELLS_BRAILLE: i32 = 4;
+pub const AIC_CELLS_COLOR_NONE: i32 = 0;
+pub const AIC_CELLS_COLOR_256: i32 = 1;
+pub const AIC_CELLS_COLOR_RGB: i32 = 2;
+pub const AIC_CELL_GLYPH_BLOCK: u32 = 0x8000_0000;
+pub const AIC_CELL_COLOR_NONE: u32 = 0;
+pub const AIC_CELL_COLOR_RESET: u32 = 1;
+pub const AIC_CELL_COLOR_BLACK: u32 = 2;
+pub const AIC_CELL_COLOR_ANSI: u32 = 3;
+pub const AIC_CELL_COLOR_RGB: u32 = 4;
+pub const AIC_CELLS_IMAGE_DEVICE: u32 = 1;
+pub const AIC_CELLS_OUT_DEVICE: u32 = 2;
+pub const AIC_CELLS_IMAGE_F16: u32 = 4;
+pub const AIC_CELLS_POSTPROCESSED: u32 = 8;
+pub const AIC_CELLS_ANSI_IN_RECT: u32 = 1;
 pub const AIC_EXPOSURE_SAMPLES: u32 = 100;
 pub const AIC_EXPOSURE_RAYS: u32 = 10;
 pub const AIC_MAX_IN_FLIGHT: u32 = 32;
@@ -452,6 +471,64 @@ pub struct aic_light_ray {
     pub light_from_struck_face: [f32; 3],
 }
 
+/// One character cell of a terminal frame (`aic_image_cells`, `aic_render_cells`): 12 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct aic_cell {
+    pub glyph: u32,
+    pub fg: u32,
+    pub bg: u32,
+}
+
+/// `TerminalOptions` and the grid, with the post-processing `aic_image_cells` applies.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_cells_desc {
+    pub cols: u32,
+    pub rows: u32,
+    pub characters: i32,
+    pub colors: i32,
+    pub exposure: f32,
+    pub tone_mapping: i32,
+    pub maximum_intensity: f32,
+    pub flags: u32,
+}
+
+/// Cells per branch of `image_patch_to_character`, colour conversions per branch of `ColorMode::convert`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aic_cells_info {
+    pub n_cells: u32,
+    pub n_full: u32,
+    pub n_upper: u32,
+    pub n_lower: u32,
+    pub n_text: u32,
+    pub n_space: u32,
+    pub n_shade: u32,
+    pub n_rising: u32,
+    pub n_falling: u32,
+    pub n_equal: u32,
+    pub n_unequal: u32,
+    pub n_names: u32,
+    pub n_braille: u32,
+    pub n_gray: u32,
+    pub n_cube: u32,
+    pub n_rgb: u32,
+    pub kernel_ms: f32,
+    pub reserved: u32,
+}
+
+/// The names tables and the rectangle's corner `aic_cells_ansi` takes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct aic_cells_text {
+    pub names: [*const *const c_char; 2],
+    pub widths: [*const u8; 2],
+    pub n_names: [u32; 2],
+    pub origin: [u16; 2],
+    pub reserved: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct aic_pixel_aux {
@@ -596,6 +673,10 @@ unsafe extern "C" {
     pub fn aic_light_rays_bound(maximum_distance: i32) -> u32;
     pub fn aic_light_rays_wireframe(info: *const aic_light_cube_info, rays: *const aic_light_ray, out: *mut aic_line_vertex, n_lines: *mut u32) -> c_int;
     pub fn aic_light_rays_cursor_lines(ctx: *mut aic_ctx, layer: c_int, cube: *const i32, maximum_distance: i32, first: *const aic_line_vertex, n_first: u32, info: *mut aic_light_cube_info, device_lines: *mut *const aic_line_vertex, n_lines: *mut u32) -> c_int;
+    pub fn aic_cells_geometry(cols: u32, rows: u32, characters: i32, width: *mut u32, height: *mut u32, nominal: *mut f64) -> c_int;
+    pub fn aic_image_cells(ctx: *mut aic_ctx, desc: *const aic_cells_desc, image: *const c_void, aux: *const aic_pixel_aux, out: *mut aic_cell, info: *mut aic_cells_info) -> c_int;
+    pub fn aic_render_cells(ctx: *mut aic_ctx, frame: *const aic_frame_desc, desc: *const aic_cells_desc, out: *mut aic_cell, out_is_device: c_int, frame_info: *mut aic_frame_info, cells_info: *mut aic_cells_info) -> c_int;
+    pub fn aic_cells_ansi(cells: *const aic_cell, cols: u32, rows: u32, text: *const aic_cells_text, flags: u32, out: *mut c_char, capacity: u64, length: *mut u64) -> c_int;
     pub fn aic_set_text_font(ctx: *mut aic_ctx, atlas_rgba8: *const u8, cell_width: u32, cell_height: u32, cell_margin: u32) -> c_int;
     pub fn aic_text_geometry(nominal_width: f64, nominal_height: f64, cell_width: u32, cell_height: u32, cell_margin: u32, origin_px: *const f64, cols: *mut u32, rows: *mut u32, scale: *mut f32, origin: *mut f32) -> c_int;
     pub fn aic_text_layout(utf8: *const c_char, len: u64, cols: u32, rows: u32, codes: *mut u8, used: *mut u32) -> c_int;

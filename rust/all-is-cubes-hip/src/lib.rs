@@ -302,6 +302,77 @@ pub fn light_rays_wireframe(info: &ffi::aic_light_cube_info, rays: &[ffi::aic_li
     (rc == 0 && n as usize == out.len()).then_some(out)
 }
 
+/// `TerminalOptions` of the desktop program's terminal mode (all-is-cubes-desktop/src/terminal/options.rs:15-185), with the C ABI's values
+/// (`ffi::AIC_CELLS_COLOR_*`, `ffi::AIC_CELLS_*`). The defaults are the reference's: `TwoFiftySix`, `Split`.
+#[derive(Clone, Copy, Debug, Eq, Hash, PartialEq)]
+pub struct TerminalOptions {
+    pub colors: i32,
+    pub characters: i32,
+}
+
+impl Default for TerminalOptions {
+    fn default() -> Self {
+        Self { colors: ffi::AIC_CELLS_COLOR_256, characters: ffi::AIC_CELLS_SPLIT }
+    }
+}
+
+impl TerminalOptions {
+    /// `ColorMode::cycle` (options.rs:61-68).
+    pub fn cycle_colors(&mut self) {
+        self.colors = (self.colors + 1) % 3;
+    }
+
+    /// `CharacterMode::cycle` (options.rs:166-175).
+    pub fn cycle_characters(&mut self) {
+        self.characters = (self.characters + 1) % 5;
+    }
+
+    /// `viewport_from_terminal_size` (options.rs:25-38; `aic_cells_geometry`): framebuffer width and height, nominal width and height. `None`: a
+    /// dimension above 65535.
+    #[must_use]
+    pub fn viewport_from_terminal_size(&self, cols: u32, rows: u32) -> Option<([u32; 2], [f64; 2])> {
+        let (mut w, mut h, mut nominal) = (0u32, 0u32, [0f64; 2]);
+        // SAFETY: host-only; the three out-pointers are valid
+        let rc = unsafe { ffi::aic_cells_geometry(cols, rows, self.characters, &mut w, &mut h, nominal.as_mut_ptr()) };
+        (rc == 0).then_some(([w, h], nominal))
+    }
+}
+
+/// `TerminalWindow::write_frame` (all-is-cubes-desktop/src/terminal/ui.rs:300-360; `aic_cells_ansi`) as a byte stream: `cells` is `[rows][cols]`,
+/// `names[layer]` the text and column width of each block of that layer (a block beyond the table shows `#`), `origin` the corner of the rectangle to
+/// draw into (`None`: rows end with a newline). Host-only. `None`: `cells` is not `cols * rows` long, or a name holds a NUL.
+#[must_use]
+pub fn cells_ansi(cells: &[ffi::aic_cell], cols: u32, rows: u32, names: [&[(&str, u8)]; 2], origin: Option<[u16; 2]>) -> Option<Vec<u8>> {
+    if cells.len() != (cols as usize) * (rows as usize) {
+        return None;
+    }
+    let mut strings: [Vec<std::ffi::CString>; 2] = [Vec::new(), Vec::new()];
+    let mut pointers: [Vec<*const core::ffi::c_char>; 2] = [Vec::new(), Vec::new()];
+    let mut widths: [Vec<u8>; 2] = [Vec::new(), Vec::new()];
+    for layer in 0..2 {
+        for (name, width) in names[layer] {
+            strings[layer].push(std::ffi::CString::new(*name).ok()?);
+            widths[layer].push(*width);
+        }
+        pointers[layer] = strings[layer].iter().map(|s| s.as_ptr()).collect();
+    }
+    let text = ffi::aic_cells_text {
+        names: [pointers[0].as_ptr(), pointers[1].as_ptr()],
+        widths: [widths[0].as_ptr(), widths[1].as_ptr()],
+        n_names: [pointers[0].len() as u32, pointers[1].len() as u32],
+        origin: origin.unwrap_or([0, 0]),
+        reserved: 0,
+    };
+    let flags = if origin.is_some() { ffi::AIC_CELLS_ANSI_IN_RECT } else { 0 };
+    let mut length = 0u64;
+    // SAFETY: host-only; a capacity of 0 writes nothing and reports the length needed (the call's refusal of the capacity is expected)
+    let _ = unsafe { ffi::aic_cells_ansi(cells.as_ptr(), cols, rows, &text, flags, core::ptr::null_mut(), 0, &mut length) };
+    let mut out = vec![0u8; length as usize];
+    // SAFETY: `out` holds `length` bytes, the tables outlive the call
+    let rc = unsafe { ffi::aic_cells_ansi(cells.as_ptr(), cols, rows, &text, flags, out.as_mut_ptr().cast(), length, &mut length) };
+    (rc == 0).then_some(out)
+}
+
 /// Cell width, height and margin of [`font_atlas`]: `FONT_SYSTEM_16`'s 7 x 16 character cell and an outline of one.
 const FONT_CELL: [u32; 3] = [9, 18, 1];
 
@@ -591,6 +662,49 @@ impl HipRtRenderer {
         let color = planes[..n].iter().map(|t| [*t as u16, (*t >> 16) as u16, (*t >> 32) as u16, (*t >> 48) as u16]).collect();
         let depth = (0..n).map(|i| f32::from_bits((planes[n + i / 2] >> (32 * (i % 2))) as u32)).collect();
         Ok((color, depth))
+    }
+
+    /// One frame of the terminal renderer (all-is-cubes-desktop/src/terminal.rs:119-137; `aic_render_cells`): the current viewport -- which must be
+    /// [`TerminalOptions::viewport_from_terminal_size`] of `cols` x `rows` -- traced and turned into `[rows][cols]` character cells on the device.
+    /// [`cells_ansi`] writes them out.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures, and when the viewport is not the grid's.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub fn draw_cells(&mut self, cols: u32, rows: u32, options: TerminalOptions) -> Result<(Vec<ffi::aic_cell>, ffi::aic_cells_info), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("draw_cells needs a single-device renderer") };
+        let (_, frame) = self.frame_desc();
+        let desc = ffi::aic_cells_desc { cols, rows, characters: options.characters, colors: options.colors, ..Default::default() };
+        let mut cells = vec![ffi::aic_cell::default(); (cols.max(1) as usize) * (rows.max(1) as usize)];
+        let mut frame_info = ffi::aic_frame_info::default();
+        let mut cells_info = ffi::aic_cells_info::default();
+        // SAFETY: the context is live; `cells` holds the raised grid the call writes and outlives it
+        self.device.check(unsafe { ffi::aic_render_cells(ctx.as_ptr(), &frame, &desc, cells.as_mut_ptr(), 0, &mut frame_info, &mut cells_info) })?;
+        Ok((cells, cells_info))
+    }
+
+    /// `image_patch_to_character` (terminal/chars.rs:18-173; `aic_image_cells`) for every cell of an image in device memory, e.g. the f16 presentation
+    /// of a resident Split frame (`flags`: `AIC_CELLS_IMAGE_DEVICE | AIC_CELLS_IMAGE_F16 | AIC_CELLS_POSTPROCESSED`).
+    ///
+    /// # Safety
+    /// `image_device` (and `aux_device`, unless null) must hold the framebuffer of `desc` on the renderer's device, laid out as `desc.flags` says.
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures and rejected arguments.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub unsafe fn image_cells_device(&mut self, desc: &ffi::aic_cells_desc, image_device: *const core::ffi::c_void, aux_device: *const ffi::aic_pixel_aux) -> Result<(Vec<ffi::aic_cell>, ffi::aic_cells_info), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("image_cells_device needs a single-device renderer") };
+        let mut desc = *desc;
+        desc.flags = (desc.flags | ffi::AIC_CELLS_IMAGE_DEVICE) & !ffi::AIC_CELLS_OUT_DEVICE;
+        let mut cells = vec![ffi::aic_cell::default(); (desc.cols.max(1) as usize) * (desc.rows.max(1) as usize)];
+        let mut info = ffi::aic_cells_info::default();
+        // SAFETY: the context is live; the caller vouches for the device pointers; `cells` holds the raised grid
+        self.device.check(unsafe { ffi::aic_image_cells(ctx.as_ptr(), &desc, image_device, aux_device, cells.as_mut_ptr(), &mut info) })?;
+        Ok((cells, info))
     }
 
     /// The finished pixels as the trait's `Rendering`: info text, flaws, info.
