@@ -86,7 +86,7 @@ def tuning(queues=None, super_shift=None, variant=None) -> int:
 ABI_SYMBOLS = [
     "aic_abi_version", "aic_create", "aic_destroy", "aic_last_error", "aic_device_name", "aic_upload_space",
     "aic_clear_space", "aic_update_cubes", "aic_update_light_volume", "aic_replace_block", "aic_replace_blocks", "aic_compact", "aic_set_options", "aic_set_depth_transform",
-    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_find_block_cubes", "aic_pick_stale_blocks", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_light_rays", "aic_light_rays_bound", "aic_light_rays_wireframe", "aic_light_rays_cursor_lines", "aic_cells_geometry", "aic_image_cells", "aic_render_cells", "aic_cells_ansi", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
+    "aic_render", "aic_render_submit", "aic_render_wait", "aic_render_submit_batch", "aic_render_wait_batch", "aic_trace_patches", "aic_trace_rays", "aic_trace_pixels", "aic_pixel_order", "aic_reproject_split", "aic_reproject_geometry", "aic_pick_pixels", "aic_stale_rects", "aic_pick_stale", "aic_pick_stale_cubes", "aic_probe_stale_cube_rects", "aic_find_block_cubes", "aic_pick_stale_blocks", "aic_replace_cube_grid", "aic_copy_cube_grid", "aic_update_light_volume_device", "aic_present_split", "aic_present_geometry", "aic_present_split_lines", "aic_present_lines_scratch", "aic_cursor_wireframe", "aic_cursor_raycast", "aic_light_rays", "aic_light_rays_bound", "aic_light_rays_wireframe", "aic_light_rays_cursor_lines", "aic_cells_geometry", "aic_image_cells", "aic_render_cells", "aic_cells_ansi", "aic_set_text_font", "aic_text_geometry", "aic_text_layout", "aic_present_split_text", "aic_export_split", "aic_export_size", "aic_exposure_init", "aic_exposure_rays", "aic_sample_luminance", "aic_exposure_advance", "aic_partition_rows", "aic_assemble_strips", "aic_assemble_strips_async", "aic_assemble_strips_on", "aic_read_aux", "aic_synchronize", "aic_stream", "aic_wait_event", "aic_stream_wait_frame",
     "aic_probe_raycast", "aic_probe_light_lut", "aic_probe_powf", "aic_probe_expf", "aic_probe_bloom",
     "aic_ortho_image_size", "aic_render_orthographic",
     "aic_evaluate_light", "aic_evaluate_light_submit", "aic_evaluate_light_wait", "aic_evaluate_light_poll", "aic_light_cubes_changed", "aic_light_changed_count", "aic_light_changed_take", "aic_read_light_volume", "aic_read_light_cubes", "aic_light_chart", "aic_probe_derived", "aic_probe_log2f", "aic_probe_cube_grid",
@@ -636,6 +636,9 @@ def load() -> C.CDLL:
         lib.aic_pick_stale_cubes.argtypes = [C.c_void_p, C.POINTER(StaleCubesDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StaleCubesInfo)]
         lib.aic_probe_stale_cube_rects.argtypes = [C.c_void_p, C.POINTER(StaleCubesDesc), C.c_void_p]
         lib.aic_find_block_cubes.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(BlockCubesInfo)]
+        lib.aic_replace_cube_grid.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(BlockCubesInfo)]
+        lib.aic_copy_cube_grid.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.aic_update_light_volume_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.aic_pick_stale_blocks.argtypes = [C.c_void_p, C.POINTER(StaleBlocksDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StaleBlocksInfo)]
         lib.aic_present_split.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo)]
         lib.aic_present_split_lines.argtypes = [C.c_void_p, C.POINTER(PresentDesc), C.POINTER(LinesDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PresentInfo),
@@ -752,11 +755,38 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None or a.size == 0 else a.ctypes.data
 
 
+def device_array_ptr(a, dtypes, count: int, what: str, device_index: Optional[int] = None) -> int:
+    """The address of an array in device memory, for the calls that take one (replace_cube_grid, copy_cube_grid, update_light_volume_device): a raw
+    pointer (an int) as it is, or a torch tensor -- checked here, before the call: its dtype is one of `dtypes` (names of torch dtypes of one element
+    size, e.g. ("uint16", "int16"): the bits are taken as they are), it has `count` elements, is contiguous and lives on the GPU `device_index`
+    (None: any GPU; the library looks at the pointer itself as well)."""
+    if a is None:
+        return 0
+    if isinstance(a, (int, np.integer)):
+        return int(a)
+    if not (hasattr(a, "data_ptr") and hasattr(a, "is_contiguous")):
+        raise TypeError(f"{what}: a torch tensor on the device or a raw device pointer, not {type(a).__name__}")
+    name = str(a.dtype).replace("torch.", "")
+    if name not in dtypes:
+        raise ValueError(f"{what}: dtype {name}, not {' or '.join(dtypes)}")
+    if int(a.numel()) != int(count):
+        raise ValueError(f"{what}: {int(a.numel())} elements, not the layer's {int(count)}")
+    if not a.is_contiguous():
+        raise ValueError(f"{what}: the tensor is not contiguous")
+    if a.device.type != "cuda":
+        raise ValueError(f"{what}: the tensor is on {a.device}, not in device memory")
+    if device_index is not None and a.device.index != device_index:
+        raise ValueError(f"{what}: the tensor is on device {a.device.index}, the context on device {device_index}")
+    return int(a.data_ptr())
+
+
 class Context:
     """One device-resident renderer state = `RtRenderer` minus cameras."""
 
     def __init__(self, device_id: int = -1):
         self._lib = load()
+        self._device_id = int(device_id) if device_id >= 0 else None  # (None: whatever device was current; the library checks device pointers itself)
+        self._layer_cubes = {}  # layer -> cubes of the space uploaded through this object: what a device array is measured against
         st = C.c_int(0)
         self._h = self._lib.aic_create(device_id, C.byref(st))
         if not self._h:
@@ -822,9 +852,11 @@ class Context:
     def upload_space(self, layer: int, flat_space) -> None:
         d, _keep = self._space_desc(flat_space)
         self._check(self._lib.aic_upload_space(self._h, layer, C.byref(d)))
+        self._layer_cubes[int(layer)] = int(d.size[0]) * int(d.size[1]) * int(d.size[2])
 
     def clear_space(self, layer: int) -> None:
         self._check(self._lib.aic_clear_space(self._h, layer))
+        self._layer_cubes.pop(int(layer), None)
 
     def update_cubes(self, layer: int, xyz, block_index=None, light=None) -> None:
         xyz = np.ascontiguousarray(xyz, np.int32).reshape(-1, 3)
@@ -835,6 +867,40 @@ class Context:
     def update_light_volume(self, layer: int, light: np.ndarray) -> None:
         lt = np.ascontiguousarray(light, np.uint8)
         self._check(self._lib.aic_update_light_volume(self._h, layer, _ptr(lt)))
+
+    def _device_arrays(self, layer: int, index_array, light_array, names):
+        """The addresses of a layer's index array and light array in device memory (device_array_ptr's checks, against the space uploaded here)."""
+        n = self._layer_cubes.get(int(layer))
+        if n is None:
+            raise AicError(1, f"no space uploaded for layer {layer} through this context")
+        return (device_array_ptr(index_array, ("uint16", "int16"), n, names[0], self._device_id),
+                device_array_ptr(light_array, ("uint8",), 4 * n, names[1], self._device_id))
+
+    def replace_cube_grid(self, layer: int, block_index, light=None, capacity: int = 4096):
+        """The block index of every cube of `layer` from device memory (aic_replace_cube_grid): `block_index` is a torch tensor of the layer's
+        cubes as uint16 (or int16, bits as they are) on the context's device, Z-major plain indices, or a raw device pointer; `light`, if given,
+        cubes x 4 uint8 texels. Returns (boxes [n_written, 6] int32 {lo, hi exclusive} -- the runs of changed cubes along z, as find_block_cubes
+        gives them, ready for pick_stale_cubes; the one box `bounds` when there are more runs than `capacity` --, info as a dict: n_cubes, n_runs,
+        bounds, n_written, merged, kernel_ms). The tensors must be complete (their stream synchronised, or ordered with wait_event) and are free
+        again on return."""
+        bi, lt = self._device_arrays(layer, block_index, light, ("block_index", "light"))
+        out = np.zeros((max(int(capacity), 1), 6), np.int32)
+        info = BlockCubesInfo()
+        self._check(self._lib.aic_replace_cube_grid(self._h, int(layer), C.c_void_p(bi or None), C.c_void_p(lt or None), int(capacity),
+                                                    C.c_void_p(out.ctypes.data if capacity else None), C.byref(info)))
+        return out[:info.n_written].copy(), dict(n_cubes=int(info.n_cubes), n_runs=int(info.n_runs), bounds=[int(v) for v in info.bounds],
+                                                 n_written=int(info.n_written), merged=int(info.merged), kernel_ms=float(info.kernel_ms))
+
+    def copy_cube_grid(self, layer: int, out=None, light_out=None) -> None:
+        """The layer's grid into device memory as plain indices, tags stripped (`out`: uint16 / int16, one per cube), and its published light
+        volume (`light_out`: cubes x 4 uint8) (aic_copy_cube_grid): how a device simulation starts from an uploaded scene. Tensors or raw pointers."""
+        o, lo = self._device_arrays(layer, out, light_out, ("out", "light_out"))
+        self._check(self._lib.aic_copy_cube_grid(self._h, int(layer), C.c_void_p(o or None), C.c_void_p(lo or None)))
+
+    def update_light_volume_device(self, layer: int, light) -> None:
+        """update_light_volume with the texels in device memory (aic_update_light_volume_device): cubes x 4 uint8, a tensor or a raw pointer."""
+        _, lt = self._device_arrays(layer, None, light, ("", "light"))
+        self._check(self._lib.aic_update_light_volume_device(self._h, int(layer), C.c_void_p(lt or None)))
 
     def replace_block(self, layer: int, index: int, block) -> None:
         from . import flat

@@ -383,7 +383,10 @@ void aic_destroy(aic_ctx *c) {
     c->text_atlas.release(); c->text_codes.release(); c->export_counts.release(); c->exposure_scratch.release(); c->cursor_scratch.release();
     c->light_rays_tree.release(); c->light_rays_derived.release(); c->light_rays_scratch.release(); c->light_rays_list.release();
     c->cells_scratch.release(); c->cells_frame.release();
+    c->grid_replace_scratch.release(); c->grid_replace_boxes.release();
     for (hipEvent_t ev : c->stale_blocks_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : c->grid_replace_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (c->dump) std::fclose(c->dump);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);

@@ -2,7 +2,7 @@
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
 // aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater) and
-// aic_ray_queries.cpp (the luminance sampler's call and the cursor raycast's) and aic_light_rays_host.cpp (the light-ray records' call) only (all six are written inside `using namespace aic`, and so is this header). Whatever one of the
+// aic_ray_queries.cpp (the luminance sampler's call and the cursor raycast's) and aic_light_rays_host.cpp (the light-ray records' call), aic_cells_host.cpp (the terminal's cells) and aic_grid_replace_host.cpp (scene inputs from device memory) only (all of them are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
 #pragma once
@@ -248,6 +248,11 @@ struct aic_ctx {
     // the linear frame aic_render_cells traces into (its first-hit records go to `aux`)
     DevBuf<unsigned char> cells_scratch;
     DevBuf<float4> cells_frame;
+    // aic_replace_cube_grid (aic_grid_replace_host.cpp): the record, the workgroups' counts, offsets and changes (aic_grid_replace.h); the boxes it hands
+    // to the host
+    DevBuf<unsigned char> grid_replace_scratch;
+    DevBuf<int32_t> grid_replace_boxes;
+    hipEvent_t grid_replace_ev[2] = {nullptr, nullptr};  // around its launches (a frame in flight on a slot keeps that slot's events), made by the first call
 };
 
 namespace aic {
@@ -269,7 +274,7 @@ inline bool valid_layer(int l) { return l == AIC_LAYER_WORLD || l == AIC_LAYER_U
 // aic_abi.cpp
 aic_options default_options();
 // the call recorder (AIC_DUMP): appends one record {tag, layer, bytes, payload} to the context's dump file, if it has one
-enum DumpTag : uint32_t { DUMP_UPLOAD = 1, DUMP_CLEAR = 2, DUMP_CUBES = 3, DUMP_LIGHT = 4, DUMP_BLOCK = 5, DUMP_OPTIONS = 6, DUMP_FRAME = 7 };
+enum DumpTag : uint32_t { DUMP_UPLOAD = 1, DUMP_CLEAR = 2, DUMP_CUBES = 3, DUMP_LIGHT = 4, DUMP_BLOCK = 5, DUMP_OPTIONS = 6, DUMP_FRAME = 7, DUMP_GRID = 8 };
 struct DumpPart { const void *p; size_t n; };
 void dump_record(aic_ctx *c, uint32_t tag, uint32_t layer, std::initializer_list<DumpPart> parts);
 int take_light_spare(aic_ctx *c, Layer &l, int layer, size_t n, int *index);

@@ -801,6 +801,21 @@ std::pair<std::vector<std::array<int32_t, 6>>, aic_block_cubes_info> HipRtRender
     return {std::move(boxes), info};
 }
 
+aic_block_cubes_info HipRtRenderer::replace_cube_grid_device(int layer, const uint16_t *device_block_index, const uint8_t *device_light, uint32_t max_runs) {
+    std::vector<std::array<int32_t, 6>> boxes(max_runs);
+    aic_block_cubes_info info;
+    check(aic_replace_cube_grid(ctx_, layer, device_block_index, device_light, max_runs, max_runs ? boxes[0].data() : nullptr, &info), "aic_replace_cube_grid");
+    boxes.resize(info.n_written);
+    if (layer == AIC_LAYER_WORLD) {
+        if (info.merged && !info.n_written) boxes.push_back({info.bounds[0], info.bounds[1], info.bounds[2], info.bounds[3], info.bounds[4], info.bounds[5]});  // (max_runs = 0)
+        changed_boxes_ = boxes;
+        changed_cube_boxes_ = std::move(boxes);
+        changed_blocks_.clear();
+        if (!changed_boxes_.empty()) pick_skip_stale_ = 0;
+    }
+    return info;
+}
+
 aic_stale_blocks_info HipRtRenderer::pick_stale_blocks(const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n,
                                                        uint32_t max_stale, uint32_t flags, int32_t expand, uint32_t max_runs) {
     const Viewport vp = world_camera_.viewport();

@@ -541,6 +541,12 @@ class HipRtRenderer : public HeadlessRenderer {
     const std::vector<uint32_t> &changed_blocks() const { return changed_blocks_; }
     const std::vector<std::array<int32_t, 6>> &changed_cube_boxes() const { return changed_cube_boxes_; }
     std::pair<std::vector<std::array<int32_t, 6>>, aic_block_cubes_info> find_block_cubes(const std::vector<uint32_t> &indices, uint32_t capacity);
+    // A scene made on the device (aic_replace_cube_grid): the block index of every cube of `layer` from device_block_index[n cubes] (and
+    // the light from device_light[n cubes][4], or nullptr), on the device the renderer runs on. The runs of changed cubes -- the one bounding box past
+    // max_runs of them -- become what changed_boxes() and changed_cube_boxes() return next, for the world layer, and the count of stale pixels handed
+    // out restarts: after update(), the loop of pick_stale_cubes, trace_pixels_into and present_split goes on unchanged. The Space object the renderer
+    // listens to is not told: its cubes are the caller's to keep in step, or to leave behind.
+    aic_block_cubes_info replace_cube_grid_device(int layer, const uint16_t *device_block_index, const uint8_t *device_light, uint32_t max_runs = 4096);
     aic_stale_blocks_info pick_stale_blocks(const void *device_frame, const uint32_t *device_order, uint32_t *device_pixels_out, uint32_t n, uint32_t max_stale,
                                             uint32_t flags = 0, int32_t expand = 1, uint32_t max_runs = 65536);
     // raytrace_to_texture's per-frame presentation of its resident textures (raytrace_to_texture.rs:546-568, shaders/rt-copy.wgsl:41-71, bloom.rs:41-60,

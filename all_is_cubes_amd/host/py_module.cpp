@@ -527,6 +527,18 @@ PYBIND11_MODULE(_host, m) {
             d["n_written"] = i.n_written; d["merged"] = i.merged; d["kernel_ms"] = i.kernel_ms;
             return py::make_tuple(res.first, d);
         }, py::arg("indices"), py::arg("capacity"))
+        .def("replace_cube_grid_device", [](HipRtRenderer &r, int layer, uintptr_t ptr, uintptr_t light_ptr, uint32_t max_runs) {
+            // -> dict(n_cubes, n_runs, bounds, n_written, merged, kernel_ms); the boxes are changed_boxes()
+            aic_block_cubes_info i;
+            {
+                py::gil_scoped_release release;
+                i = r.replace_cube_grid_device(layer, reinterpret_cast<const uint16_t *>(ptr), reinterpret_cast<const uint8_t *>(light_ptr), max_runs);
+            }
+            py::dict d;
+            d["n_cubes"] = i.n_cubes; d["n_runs"] = i.n_runs; d["bounds"] = std::vector<int32_t>(i.bounds, i.bounds + 6);
+            d["n_written"] = i.n_written; d["merged"] = i.merged; d["kernel_ms"] = i.kernel_ms;
+            return d;
+        }, py::arg("layer"), py::arg("ptr"), py::arg("light_ptr") = (uintptr_t)0, py::arg("max_runs") = 4096u)
         .def("pick_stale_blocks", [](HipRtRenderer &r, uintptr_t frame_ptr, uintptr_t order_ptr, uintptr_t out_ptr, uint32_t n, uint32_t max_stale, uint32_t flags, int32_t expand,
                                      uint32_t max_runs) {
             // -> dict(pick = pick_stale_cubes' dict, found = find_block_cubes' dict)

@@ -21,7 +21,7 @@ import numpy as np
 from . import flat
 
 MAGIC = b"AICDUMP1"
-UPLOAD, CLEAR, CUBES, LIGHT, BLOCK, OPTIONS, FRAME = 1, 2, 3, 4, 5, 6, 7
+UPLOAD, CLEAR, CUBES, LIGHT, BLOCK, OPTIONS, FRAME, GRID = 1, 2, 3, 4, 5, 6, 7, 8
 
 _UPLOAD_HDR = np.dtype([("lo", "<i4", 3), ("size", "<i4", 3), ("n_blocks", "<u4"), ("sky_kind", "<i4"), ("n_voxels", "<u8"),
                         ("n_palette", "<u8"), ("sky", "<f4", (8, 3)), ("block_sky", "u1", (7, 4))], align=True)
@@ -75,6 +75,10 @@ def _parse(tag: int, payload: memoryview) -> Dict[str, object]:
         return {"options": take(_OPTIONS, 1)[0]}
     if tag == FRAME:
         return {"frame": take(_FRAME, 1)[0]}
+    if tag == GRID:  # aic_replace_cube_grid: the device arrays as the call saw them, copied back
+        n = int(take("<u8", 1)[0])
+        has_light, capacity = (int(v) for v in take("<u4", 2))
+        return {"block_index": take("<u2", n), "light": take("u1", n * 4).reshape(n, 4) if has_light else None, "capacity": capacity}
     raise ValueError(f"unknown dump record tag {tag}")
 
 
@@ -137,6 +141,11 @@ class DumpWriter:
     def update_light_volume(self, layer: int, light) -> None:
         light = np.asarray(light, np.uint8).reshape(-1, 4)
         self._rec(LIGHT, layer, np.array([len(light)], "<u8"), light)
+
+    def replace_cube_grid(self, layer: int, block_index, light=None, capacity: int = 4096) -> None:
+        bi = np.asarray(block_index, "<u2").reshape(-1)
+        self._rec(GRID, layer, np.array([len(bi)], "<u8"), np.array([light is not None, capacity], "<u4"), bi,
+                  None if light is None else np.asarray(light, np.uint8).reshape(-1, 4))
 
     def replace_block(self, layer: int, index: int, block: flat.BlockDef) -> None:
         desc, vox, pal = flat.pack_block(block)
@@ -206,6 +215,11 @@ class SceneState:
         elif r.tag == LIGHT:
             sp = self.spaces[r.layer]
             sp.light[...] = d["light"].reshape(sp.light.shape)
+        elif r.tag == GRID:
+            sp = self.spaces[r.layer]
+            sp.block_index[...] = d["block_index"].reshape(sp.block_index.shape)
+            if d["light"] is not None:
+                sp.light[...] = d["light"].reshape(sp.light.shape)
         elif r.tag == BLOCK:
             sp = self.spaces[r.layer]
             b = _block_from_desc(d["desc"], d["voxels"], d["palette"])
@@ -236,6 +250,14 @@ def replay(path, ctx=None, device_id: int = -1) -> List[np.ndarray]:
                 ctx.update_cubes(r.layer, d["xyz"], d["block_index"], d["light"])
             elif r.tag == LIGHT:
                 ctx.update_light_volume(r.layer, d["light"])
+            elif r.tag == GRID:  # (the arrays are staged through torch tensors on the context's device)
+                import torch
+
+                dev = torch.device("cuda", ctx._device_id if ctx._device_id is not None else torch.cuda.current_device())
+                bi = torch.from_numpy(d["block_index"].view(np.int16)).to(dev)
+                lt = None if d["light"] is None else torch.from_numpy(np.ascontiguousarray(d["light"]).reshape(-1)).to(dev)
+                torch.cuda.synchronize(dev)
+                ctx.replace_cube_grid(r.layer, bi, lt, capacity=d["capacity"])
             elif r.tag == BLOCK:
                 ctx.replace_block(r.layer, d["index"], _block_from_desc(d["desc"], d["voxels"], d["palette"]))
             elif r.tag == OPTIONS:

@@ -656,6 +656,44 @@ typedef struct aic_stale_blocks_info {
 } aic_stale_blocks_info;
 int aic_pick_stale_blocks(aic_ctx *ctx, const aic_stale_blocks_desc *desc, const void *src_device, const uint32_t *order_device,
                           uint32_t *pixels_out_device, aic_stale_blocks_info *info);
+/* Adds what the reference does not have: a cube grid that was MADE on the device -- by a cellular automaton, a falling-sand or fluid step, a model that
+ * emits voxels, any torch code -- becomes the layer's scene without a trip through the host, and the call says which cubes changed, which is what
+ * aic_pick_stale_cubes and aic_light_cubes_changed want to know. DESIGN.md 4.23 states the rule and the passes; tests/grid_replace_ref.py is that text in
+ * NumPy.
+ *
+ * aic_replace_cube_grid. The layer's bounds, block table, voxel pool, palette and sky stay. The block index of every cube is replaced by
+ * block_index_device[n_cubes]: plain indices in device memory on the context's device, entry (x * sy + y) * sz + z as in aic_upload_space. With
+ * light_device ([n_cubes][4], PackedLight texels) the light volume is replaced too; NULL leaves it as it is.
+ *   - Afterwards the grid holds, byte for byte, what aic_upload_space of the same space with that block_index leaves there: with a block table of at most
+ *     16384 entries index | (class + 1) << 14, and 0 in the tag of an OPEN cube (aic_probe_cube_grid); past 16384 blocks plain indices.
+ *     Nothing at or past entry n_cubes of the pool is written: the voxel volumes start there.
+ *   - The change report is aic_find_block_cubes' rule and info with another match: match[i] = the new index differs from the index the entry held (the low
+ *     14 bits of a tagged entry: tags and OPEN never count as change). Runs, their order, the boxes (upper bounds exclusive, straight into
+ *     aic_stale_cubes_desc.boxes), n_cubes, n_runs, bounds, n_written and merged follow that call's table; everything is 0 when nothing changed.
+ *     kernel_ms: HIP events around the call's launches.
+ *   - The call blocks. Like aic_update_cubes it first waits for every frame in flight and ends a pending aic_evaluate_light_submit; it bumps the layer's
+ *     version, so the light updater reads the new grid before its next step. Texels the caller replaced are the caller's own and are never reported by
+ *     aic_light_changed_*. The caller's arrays must be complete before the call -- its stream synchronised, or ordered with aic_wait_event -- and are
+ *     free again when it returns.
+ * Rejected with AIC_ERR_INVALID, with grid, light and context untouched and usable: an index at or above the layer's block count anywhere in the array
+ * (the count pass finds the largest before anything is written); a NULL info or array; a layer that is not 0 or 1 or has no space; an array that does not
+ * start at a 16-byte boundary (light_device: 4-byte); out_boxes NULL with capacity > 0. An empty grid is AIC_OK with a zero info.
+ *
+ * aic_copy_cube_grid. out_device[n_cubes] = the layer's grid as plain indices, tags stripped; light_out_device[n_cubes][4] = the published light volume
+ * as it stands. Either may be NULL. How a device simulation starts from an uploaded scene. It only reads: legal with frames in flight on other slots,
+ * like aic_find_block_cubes, whose slot rule it takes (no frame may occupy slot 0); a pending aic_evaluate_light_submit is published first when the light
+ * is asked for. out_device starts at a 16-byte boundary, light_out_device at a 4-byte one. Blocks.
+ *
+ * aic_update_light_volume_device. aic_update_light_volume with the source in device memory (4-byte aligned, on the context's device): double-buffered
+ * into a spare volume, on the upload stream, behind a finished light job; frames in flight are not waited for. Blocks until the copy is done.
+ *
+ * Scratch (16 bytes per 2048 grid entries, 24 bytes a run written) belongs to the context, is allocated on first use, again when a call needs
+ * more, and released in aic_destroy. */
+int aic_replace_cube_grid(aic_ctx *ctx, int layer, const uint16_t *block_index_device /* [n_cubes], Z-major, plain indices */,
+                          const uint8_t *light_device /* [n_cubes][4] or NULL */, uint32_t capacity,
+                          int32_t *out_boxes /* [capacity][6], host; NULL iff capacity = 0 */, aic_block_cubes_info *info);
+int aic_copy_cube_grid(aic_ctx *ctx, int layer, uint16_t *out_device /* [n_cubes] or NULL */, uint8_t *light_out_device /* [n_cubes][4] or NULL */);
+int aic_update_light_volume_device(aic_ctx *ctx, int layer, const uint8_t *light_device);
 /* replaces: what raytrace_to_texture does with its resident textures every displayed frame: RaytraceToTexture::draw
  * (all-is-cubes-gpu/src/raytrace_to_texture.rs:546-568) draws rt_frame_copy_vertex / rt_frame_copy_fragment (shaders/rt-copy.wgsl:41-71) into the linear
  * scene texture -- the pipeline's linear ClampToEdge sampler stretches the frame to the viewport (the reference traces at half the nominal size,

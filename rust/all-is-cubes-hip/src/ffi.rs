@@ -655,6 +655,17 @@ unsafe extern "C" {
         pixels_out_device: *mut u32,
         info: *mut aic_stale_blocks_info,
     ) -> c_int;
+    pub fn aic_replace_cube_grid(
+        ctx: *mut aic_ctx,
+        layer: c_int,
+        block_index_device: *const u16,
+        light_device: *const u8,
+        capacity: u32,
+        out_boxes: *mut i32,
+        info: *mut aic_block_cubes_info,
+    ) -> c_int;
+    pub fn aic_copy_cube_grid(ctx: *mut aic_ctx, layer: c_int, out_device: *mut u16, light_out_device: *mut u8) -> c_int;
+    pub fn aic_update_light_volume_device(ctx: *mut aic_ctx, layer: c_int, light_device: *const u8) -> c_int;
     pub fn aic_light_changed_count(ctx: *mut aic_ctx, layer: c_int, n: *mut u64, bounds: *mut i32) -> c_int;
     pub fn aic_light_changed_take(ctx: *mut aic_ctx, layer: c_int, capacity: u32, xyz: *mut i32, n_written: *mut u32) -> c_int;
     pub fn aic_present_split(ctx: *mut aic_ctx, desc: *const aic_present_desc, src_device: *const c_void, out: *mut c_void, out_is_device: c_int, info: *mut aic_present_info) -> c_int;

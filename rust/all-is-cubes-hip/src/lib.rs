@@ -1206,6 +1206,45 @@ impl HipRtRenderer {
         Ok((out, info))
     }
 
+    /// The block index of every cube of the world layer from `block_index_device` (and the light from `light_device`, unless null), arrays in device
+    /// memory on the renderer's device (`aic_replace_cube_grid`; not in the reference): a world made on the device becomes the scene without a trip
+    /// through the host. Returns the runs of changed cubes along z as boxes `[lower, upper)`, as [`Self::find_block_cubes`] gives them -- with more
+    /// runs than `capacity` the one box `info.bounds` --, ready for [`Self::pick_stale_cubes`]. The `Space` the renderer listens to is not told.
+    ///
+    /// # Safety
+    /// `block_index_device` points to one `u16` per cube of the world space, 16-byte aligned, and `light_device` is null or points to four bytes per
+    /// cube, both in device memory and complete (their stream synchronised).
+    ///
+    /// # Errors
+    /// As [`HeadlessRenderer::draw`] for device failures; an index at or above the block count is refused with the scene untouched.
+    ///
+    /// # Panics
+    /// On a multi-device renderer.
+    pub unsafe fn replace_cube_grid_device(
+        &mut self,
+        block_index_device: *const u16,
+        light_device: *const u8,
+        capacity: u32,
+    ) -> Result<(Vec<[i32; 6]>, ffi::aic_block_cubes_info), RenderError> {
+        let Device::One(ctx) = self.device else { panic!("replace_cube_grid_device needs a single-device renderer") };
+        let mut out = vec![[0i32; 6]; capacity as usize];
+        let mut info = ffi::aic_block_cubes_info::default();
+        // SAFETY: the context is live; the caller vouches for the device arrays and `out` holds `capacity` boxes of six coordinates
+        self.device.check(unsafe {
+            ffi::aic_replace_cube_grid(
+                ctx.as_ptr(),
+                ffi::AIC_LAYER_WORLD,
+                block_index_device,
+                light_device,
+                capacity,
+                if capacity == 0 { core::ptr::null_mut() } else { out.as_mut_ptr().cast() },
+                &mut info,
+            )
+        })?;
+        out.truncate(info.n_written as usize);
+        Ok((out, info))
+    }
+
     /// [`Self::pick_stale_cubes`] with, behind `boxes`, the boxes [`Self::find_block_cubes`]`(blocks, max_runs)` gives, found and kept on the device
     /// (`aic_pick_stale_blocks`; not in the reference): the pixels a re-evaluated block made stale first. `blocks` is [`Self::changed_blocks`] of the
     /// update that re-sent them, kept by the caller until no stale pixel is handed out any more.
