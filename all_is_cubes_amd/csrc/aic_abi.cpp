@@ -6,7 +6,7 @@
 // aic_trace.hip (aic_launch.h) on a private HIP stream. No CPU rendering path exists here: every entry
 // point fails with AIC_ERR_NO_DEVICE / AIC_ERR_DEVICE when HIP is unusable.
 // Here: the context, scene upload and update, options, strip assembly, synchronisation and the probes. The frame path -- everything that submits or
-// waits for a trace -- is aic_frame.cpp, what acts on a resident Split frame aic_split_ops.cpp, the light updater aic_light_host.cpp.
+// waits for a trace -- is aic_frame.cpp, what acts on a resident Split frame aic_split_ops.cpp, the light updater aic_light_host.cpp and the units beside it (aic_light_host.h).
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,7 @@
 #include "aic_device.h"
 #include "aic_encode.h"
 #include "aic_launch.h"
+#include "aic_light_host.h"
 
 using namespace aic;
 
@@ -45,7 +46,7 @@ constexpr uint64_t kMaxLightTexels = 0x3ffffff0ull; // cubes of a space: the SHA
 
 }  // namespace
 
-// What the frame path (aic_frame.cpp) and the light host code (aic_light_host.cpp) use too: declared in aic_ctx.h.
+// What the frame path (aic_frame.cpp) and the light host code (aic_light_host.cpp, aic_light_entry.cpp) use too: declared in aic_ctx.h.
 namespace aic {
 
 aic_options default_options() {

@@ -1,7 +1,7 @@
 // aic_ctx.h -- what the translation units of the C ABI's host side share: the context behind the opaque `aic_ctx` of
 // include/aic_hip.h, its layers and device buffers, the error helpers and the call recorder. Internal: included by aic_abi.cpp
 // (context, scene, options, strips, probes), aic_frame.cpp (the frame path: submit, wait and the entry points that trace),
-// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), aic_light_host.cpp (the light updater) and
+// aic_split_ops.cpp (reprojection, picking, presentation and export of a resident Split frame), the light updater's units (through aic_light_host.h, which declares what they share and offer) and
 // aic_ray_queries.cpp (the luminance sampler's call and the cursor raycast's) and aic_light_rays_host.cpp (the light-ray records' call), aic_cells_host.cpp (the terminal's cells) and aic_grid_replace_host.cpp (scene inputs from device memory) only (all of them are written inside `using namespace aic`, and so is this header). Whatever one of the
 // files uses alone stays in that file's anonymous namespace; what is declared here lives in namespace aic, like the kernel
 // launchers they call.
@@ -55,11 +55,8 @@ struct DevBuf {
     }
 };
 
-struct LightState;                       // aic_light_host.cpp
+struct LightState;                       // aic_light_host.h, with everything else the light host code offers; a Layer only owns one
 void light_state_free(LightState *s);
-// keeps the light updater's host mirrors in step with an aic_update_cubes call (no-op if they were not current)
-void light_state_cubes_updated(LightState *s, uint64_t version_before, uint64_t version_after, uint32_t n, const int32_t *xyz, const uint16_t *block_index,
-                               const uint8_t *light);
 
 struct Layer {
     bool present = false;
@@ -279,9 +276,5 @@ struct DumpPart { const void *p; size_t n; };
 void dump_record(aic_ctx *c, uint32_t tag, uint32_t layer, std::initializer_list<DumpPart> parts);
 int take_light_spare(aic_ctx *c, Layer &l, int layer, size_t n, int *index);
 int quiesce(aic_ctx *c);
-// aic_light_host.cpp
-int light_job_finish(aic_ctx *c);
-constexpr uint32_t kVisibleBitsWords = 2048;  // 65536 block indices x 1 bit
-int light_visible_bits(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<uint32_t> *bits);
 
 }  // namespace aic

@@ -11,7 +11,7 @@
 //   nothing returned                                     -> sky.sample(d).luminance()
 //
 // The Raycaster is the trace kernels' own (aic_raycast.h, pinned to the reference's step tables by aic_probe_raycast); "visible" is one bit per block
-// index made by the host from compute_derived (aic_light_host.cpp) -- NOT the cube's class bits, which say "recursive" for a block whose voxels are all
+// index made by the host from compute_derived (aic_light_derived.cpp) -- NOT the cube's class bits, which say "recursive" for a block whose voxels are all
 // invisible. Wave64, no LDS: a step of automatic exposure is 10 rays, so the launch is one wave and what it costs is the launch and the latency of some
 // tens of dependent lookups.
 #include <hip/hip_runtime.h>

@@ -11,6 +11,7 @@
 #include "aic_ctx.h"
 #include "aic_grid_replace.h"
 #include "aic_launch.h"
+#include "aic_light_host.h"
 
 namespace {
 

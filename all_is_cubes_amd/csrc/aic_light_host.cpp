@@ -1,236 +1,30 @@
-// aic_light_host.cpp -- the host half of the light updater. Of aic_abi.cpp it uses what aic_ctx.h declares.
+// aic_light_host.cpp -- the host half of the light updater: the update itself. Of aic_abi.cpp it uses what aic_ctx.h declares; what
+// it shares with the light updater's other units (the chart, compute_derived, the entry points) and gives the rest of the library is aic_light_host.h.
 //
 // What runs where (see aic_light.h): the priority queue, fast_evaluate_light and apply_light_update are sequential
 // by definition and run here; compute_light -- the ray-bundle tree walk, all of the arithmetic -- runs on the
 // device for a batch of queue entries at a time (aic_light.hip). Follows
-//   all-is-cubes/src/space/light/chart/generator.rs   the chart
-//   all-is-cubes/src/space/light/queue.rs             LightUpdateQueue
+//   all-is-cubes/src/space/light/queue.rs             LightUpdateQueue (aic_light_queue.h)
 //   all-is-cubes/src/space/light/updater.rs:181-361   update_light_from_queue, apply_light_update
 //   all-is-cubes/src/space/light/updater.rs:537-581   fast_evaluate_light
-//   all-is-cubes/src/block/eval/derived.rs:78-240     compute_derived (face colours, opacity, visibility)
-//   all-is-cubes/src/space.rs:1496-1540               Mutation::{evaluate_light, fast_evaluate_light}
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <mutex>
-#include <thread>
 #include <vector>
 
-#include "aic_ctx.h"
-#include "aic_light.h"
-#include "aic_light_rays.h"
+#include "aic_light_host.h"
 
 using namespace aic;
 
 namespace {
 
-using I3h = std::array<int32_t, 3>;
-inline I3h face_normal_h(int f) {  // 0 nx 1 ny 2 nz 3 px 4 py 5 pz
-    I3h n = {0, 0, 0};
-    n[(size_t)(f >= 3 ? f - 3 : f)] = f >= 3 ? 1 : -1;
-    return n;
-}
-
-// ------------------------------------------------------------------------------------
-// chart/generator.rs: rays towards every cell of the surface of an 11x11x11 cube (602 of them), stepped through the
-// grid from the centre of the origin cube up to distance 127, merged into a tree by shared prefixes, then flattened in
-// post-order from the end so that the root is node 0.
-
-struct LightChart {
-    std::vector<DevLightNode> nodes;
-    uint32_t depth = 0;  // the deepest chain of bundles: what the tree walk's stack must hold
-};
-
-LightChart generate_light_chart() {
-    struct TreeNode {
-        int32_t cube[3];
-        int32_t children[6];
-        float weight[6];
-    };
-    std::vector<TreeNode> tree;
-    {
-        TreeNode root;
-        for (int a = 0; a < 3; a++) root.cube[a] = 0;
-        for (int f = 0; f < 6; f++) { root.children[f] = -1; root.weight[f] = 0.f; }
-        tree.push_back(root);
-    }
-    const int STEP = 5;  // RAY_DIRECTION_STEP (generator.rs)
-    std::vector<I3h> steps;
-    for (int x = -STEP; x <= STEP; x++)
-        for (int y = -STEP; y <= STEP; y++)
-            for (int z = -STEP; z <= STEP; z++) {
-                if (!(std::abs(x) == STEP || std::abs(y) == STEP || std::abs(z) == STEP)) continue;
-                const float fx = (float)x, fy = (float)y, fz = (float)z;
-                const float len = std::sqrt(fx * fx + fy * fy + fz * fz);
-                const float d[3] = {fx / len, fy / len, fz / len};  // Vector3D::normalize
-                float cosw[6];
-                for (int f = 0; f < 6; f++) {
-                    const I3h n = face_normal_h(f);
-                    const float dotv = (float)n[0] * d[0] + (float)n[1] * d[1] + (float)n[2] * d[2];
-                    cosw[f] = dotv > 0.0f ? dotv : 0.0f;
-                }
-                // Ray::new([0.5; 3], direction).cast().take_while(|step| step.t_distance() <= 127.0): the raycaster of
-                // math/raycast.rs from the cube centre -- t_max = 0.5 / |d| per moving axis, the smallest strictly-less
-                // t_max steps, ties to the later axis (raycast.rs:577-626)
-                double t_max[3], t_delta[3];
-                int stepdir[3];
-                for (int a = 0; a < 3; a++) {
-                    const double da = (double)d[a];
-                    stepdir[a] = da > 0.0 ? 1 : (da < 0.0 ? -1 : 0);
-                    t_delta[a] = 1.0 / std::fabs(da);
-                    t_max[a] = da == 0.0 ? INFINITY : (1.0 - 0.5) / std::fabs(da);
-                }
-                steps.clear();
-                I3h cube = {0, 0, 0};
-                double t = 0.0;
-                while (t <= 127.0) {
-                    steps.push_back(cube);
-                    int axis;
-                    if (t_max[0] < t_max[1]) axis = (t_max[0] < t_max[2]) ? 0 : 2;
-                    else axis = (t_max[1] < t_max[2]) ? 1 : 2;
-                    t = t_max[axis];
-                    cube[(size_t)axis] += stepdir[axis];
-                    t_max[axis] += t_delta[axis];
-                }
-                // tree.insert(&steps[1..], weight)
-                int node = 0;
-                for (int f = 0; f < 6; f++) tree[0].weight[f] += cosw[f];
-                for (size_t k = 1; k < steps.size(); k++) {
-                    const I3h c = steps[k];
-                    int dir = -1;
-                    for (int f = 0; f < 6; f++) {
-                        const I3h n = face_normal_h(f);
-                        if (tree[(size_t)node].cube[0] + n[0] == c[0] && tree[(size_t)node].cube[1] + n[1] == c[1] && tree[(size_t)node].cube[2] + n[2] == c[2]) dir = f;
-                    }
-                    if (dir < 0) break;
-                    int child = tree[(size_t)node].children[dir];
-                    if (child < 0) {
-                        TreeNode n;
-                        for (int a = 0; a < 3; a++) n.cube[a] = c[(size_t)a];
-                        for (int f = 0; f < 6; f++) { n.children[f] = -1; n.weight[f] = 0.f; }
-                        child = (int)tree.size();
-                        tree.push_back(n);
-                        tree[(size_t)node].children[dir] = child;
-                    }
-                    node = child;
-                    for (int f = 0; f < 6; f++) tree[(size_t)node].weight[f] += cosw[f];
-                }
-            }
-    LightChart chart;
-    chart.nodes.resize(tree.size());
-    std::vector<uint32_t> flat_index(tree.size(), 0);
-    uint32_t next_index = (uint32_t)tree.size() - 1;
-    struct Frame { int node; int child; };
-    std::vector<Frame> stack;
-    stack.push_back(Frame{0, 0});
-    while (!stack.empty()) {
-        chart.depth = std::max(chart.depth, (uint32_t)stack.size());
-        Frame &fr = stack.back();
-        if (fr.child < 6) {
-            const int c = tree[(size_t)fr.node].children[fr.child++];
-            if (c >= 0) stack.push_back(Frame{c, 0});
-            continue;
-        }
-        const int n = fr.node;
-        stack.pop_back();
-        const uint32_t this_index = next_index;
-        if (this_index != 0) next_index -= 1;
-        flat_index[(size_t)n] = this_index;
-        DevLightNode fn;
-        for (int f = 0; f < 6; f++) {
-            fn.weight[f] = tree[(size_t)n].weight[f];
-            fn.child[f] = tree[(size_t)n].children[f] >= 0 ? flat_index[(size_t)tree[(size_t)n].children[f]] : 0u;
-        }
-        chart.nodes[this_index] = fn;
-    }
-    return chart;
-}
-
-const LightChart &light_chart() {
-    static const LightChart chart = generate_light_chart();
-    return chart;
-}
-
-// The part of the chart a walk with the given maximum_distance can reach, in pre-order with children in face order:
-// a bundle whose cube centre is farther than maximum_distance from the origin's ends the ray (updater.rs:456-462), so it
-// is a leaf here. What the wave-per-cube kernel walks (aic_light.h).
-std::vector<DevTreePos> build_light_tree(int maximum_distance, uint32_t *depth_out, std::vector<float> *child_w, std::vector<uint32_t> *child_pos) {
-    const LightChart &ch = light_chart();
-    std::vector<DevTreePos> out;
-    struct Frame { uint32_t node, pos; int32_t off[3]; int next_face; };
-    std::vector<Frame> stack;
-    const double max2 = (double)maximum_distance * (double)maximum_distance;
-    uint32_t depth = 0;
-    auto push = [&](uint32_t node, uint32_t parent_pos, const int32_t off[3], uint32_t fe) {
-        DevTreePos t;
-        for (int f = 0; f < 6; f++) t.weight[f] = ch.nodes[node].weight[f];
-        t.end = 0;
-        t.parent = parent_pos;
-        t.offset = (uint32_t)(off[0] + 256) | ((uint32_t)(off[1] + 256) << 10) | ((uint32_t)(off[2] + 256) << 20);
-        const double d2 = (double)off[0] * off[0] + (double)off[1] * off[1] + (double)off[2] * off[2];
-        const bool far_ = d2 > max2;
-        t.info = fe | (far_ ? 8u : 0u) | ((uint32_t)stack.size() << 8);  // depth = number of ancestors
-        const uint32_t pos = (uint32_t)out.size();
-        out.push_back(t);
-        Frame fr;
-        fr.node = node; fr.pos = pos; fr.next_face = far_ ? 6 : 0;
-        for (int a = 0; a < 3; a++) fr.off[a] = off[a];
-        stack.push_back(fr);
-    };
-    const int32_t zero[3] = {0, 0, 0};
-    push(0, 0, zero, 7u);
-    while (!stack.empty()) {
-        depth = std::max(depth, (uint32_t)stack.size());
-        Frame &fr = stack.back();
-        if (fr.next_face < 6) {
-            const int f = fr.next_face++;
-            const uint32_t c = ch.nodes[fr.node].child[f];
-            if (c != 0u) {
-                const I3h n = face_normal_h(f);
-                const int32_t off[3] = {fr.off[0] + n[0], fr.off[1] + n[1], fr.off[2] + n[2]};
-                const uint32_t parent_pos = fr.pos;
-                if (child_w) {
-                    if (child_w->size() < ((size_t)parent_pos + 1) * 36) child_w->resize(((size_t)parent_pos + 1) * 36, 0.f);
-                    for (int g = 0; g < 6; g++) (*child_w)[(size_t)parent_pos * 36 + (size_t)f * 6 + (size_t)g] = ch.nodes[c].weight[g];
-                }
-                if (child_pos) {
-                    if (child_pos->size() < ((size_t)parent_pos + 1) * 6) child_pos->resize(((size_t)parent_pos + 1) * 6, 0u);
-                    (*child_pos)[(size_t)parent_pos * 6 + (size_t)f] = (uint32_t)out.size();
-                }
-                push(c, parent_pos, off, (uint32_t)(f >= 3 ? f - 3 : f + 3));  // entered through the opposite face
-            }
-            continue;
-        }
-        out[fr.pos].end = (uint32_t)out.size();
-        stack.pop_back();
-    }
-    if (depth_out) *depth_out = depth;
-    if (child_w) child_w->resize(out.size() * 36, 0.f);
-    if (child_pos) child_pos->resize(out.size() * 6, 0u);
-    return out;
-}
-
-// ------------------------------------------------------------------------------------
-// restricted_number.rs / color.rs / raytracer_components.rs arithmetic used by compute_derived
-
-inline float h_ps_new_clamped(float v) { return v > 0.f ? v : 0.f; }
-inline float h_zo_new_clamped(float v) {
-    if (v > 0.f && v <= 1.f) return v;
-    if (v <= 0.f) return 0.f;
-    return 1.f;
-}
-inline float h_ps_mul(float a, float b) {
-    const float v = a * b;
-    return (v != v) ? 0.f : v;
-}
 // data.rs:214-218 PackedLight::scalar_in (f32::log2 is libm's log2f)
 inline uint32_t h_scalar_in(float value) {
     const float x = std::round(std::log2(value) * 10.0f + 144.0f);
@@ -239,597 +33,12 @@ inline uint32_t h_scalar_in(float value) {
     if (x >= 255.f) return 255u;
     return (uint32_t)x;
 }
-
-struct HostVoxel { float color[4]; float emission[3]; };
-
-// The flattened block data as the device holds it (aic_device.h), read back once per scene version.
-struct HostBlocks {
-    const std::vector<DevBlock> *blocks = nullptr;
-    std::vector<uint16_t> vox;       // pool past the cube grid
-    std::vector<DevPaletteEntry> pal;
-    size_t n_cubes = 0;
-    bool get(const DevBlock &b, const I3h &c, HostVoxel *out) const {  // voxel_storage.rs:731-733 get_opt_evoxel
-        const uint32_t res = b.kind & 255u;
-        if (res == 0u) {
-            if (c[0] == 0 && c[1] == 0 && c[2] == 0) {
-                for (int k = 0; k < 4; k++) out->color[k] = b.color[k];
-                for (int k = 0; k < 3; k++) out->emission[k] = b.emission[k];
-                return true;
-            }
-            return false;
-        }
-        const uint32_t vlo[3] = {b.vlo_packed & 255u, (b.vlo_packed >> 8) & 255u, (b.vlo_packed >> 16) & 255u};
-        const uint32_t vs[3] = {b.vsize_packed & 255u, (b.vsize_packed >> 8) & 255u, (b.vsize_packed >> 16) & 255u};
-        const uint32_t dx = (uint32_t)c[0] - vlo[0], dy = (uint32_t)c[1] - vlo[1], dz = (uint32_t)c[2] - vlo[2];
-        if ((dx >= vs[0]) | (dy >= vs[1]) | (dz >= vs[2])) return false;
-        const size_t i = ((size_t)dx * vs[1] + dy) * vs[2] + dz;
-        const DevPaletteEntry &pe = pal[(size_t)b.pal_off + vox[(size_t)b.vox_off - n_cubes + i]];
-        for (int k = 0; k < 4; k++) out->color[k] = pe.color[k];
-        for (int k = 0; k < 3; k++) out->emission[k] = pe.emission[k];
-        return true;
-    }
-};
-
-// raytracer_components.rs:215-258 apply_transmittance
-inline void h_apply_transmittance(const float color[4], float thickness, float out_color[4], float *out_coeff) {
-    thickness = std::fmax(thickness, 0.0f);
-    if (thickness == 0.0f) {
-        if (color[3] == 1.0f) { for (int k = 0; k < 4; k++) out_color[k] = color[k]; *out_coeff = 1.0f; }
-        else { for (int k = 0; k < 4; k++) out_color[k] = 0.f; *out_coeff = 0.0f; }
-        return;
-    }
-    const float unit_transmittance = 1.0f - color[3];
-    const float depth_transmittance = std::pow(unit_transmittance, thickness);
-    const float alpha = h_zo_new_clamped(1.0f - depth_transmittance);
-    out_color[0] = color[0]; out_color[1] = color[1]; out_color[2] = color[2]; out_color[3] = alpha;
-    float emission_coeff;
-    if (unit_transmittance == 1.0f) emission_coeff = thickness;
-    else emission_coeff = (depth_transmittance - 1.f) / (unit_transmittance - 1.f);
-    *out_coeff = std::fmax(emission_coeff, 0.0f);
-}
-
-// raytracer_components.rs:174-201 trace_for_eval: one axis-aligned ray through the block's voxels
-inline void h_trace_for_eval(const HostBlocks &hb, const DevBlock &b, I3h cube, int direction_face, int resolution, float out_color[4], float out_emission[3]) {
-    const float thickness = 1.0f / (float)resolution;
-    const I3h step = face_normal_h(direction_face);
-    float light[3] = {0.f, 0.f, 0.f}, transmittance = 1.0f;  // ColorBuf (raytracer_components.rs:20-39)
-    float emission[3] = {0.f, 0.f, 0.f};
-    HostVoxel v;
-    while (hb.get(b, cube, &v)) {
-        float adjusted[4], coeff;
-        h_apply_transmittance(v.color, thickness, adjusted, &coeff);
-        const float c = h_ps_new_clamped(coeff);
-        for (int i = 0; i < 3; i++) emission[i] += h_ps_mul(v.emission[i], c) * transmittance;
-        // ColorBuf::from(Rgba) then add_color_internal (raytracer_components.rs:87-92, 149-163)
-        for (int i = 0; i < 3; i++) light[i] += (adjusted[i] * adjusted[3]) * transmittance;
-        transmittance *= 1.0f - adjusted[3];
-        if (transmittance < 1.0f / 256.0f) break;
-        for (size_t a = 0; a < 3; a++) cube[a] += step[a];
-    }
-    // Rgba::from(ColorBuf) (raytracer_components.rs:122-147)
-    if (transmittance >= 1.0f) { for (int k = 0; k < 4; k++) out_color[k] = 0.f; }
-    else {
-        const float color_alpha = 1.0f - transmittance;
-        float c3[3];
-        bool ok = true;
-        for (int i = 0; i < 3; i++) {
-            const float q = light[i] / color_alpha;
-            if (q > 0.f) c3[i] = q;
-            else if (q == 0.f) c3[i] = 0.f;
-            else ok = false;
-        }
-        if (ok) { out_color[0] = c3[0]; out_color[1] = c3[1]; out_color[2] = c3[2]; }
-        else { out_color[0] = 1.0f; out_color[1] = 0.0f; out_color[2] = 0.0f; }
-        if (color_alpha > 0.f && color_alpha <= 1.f) out_color[3] = color_alpha;
-        else if (color_alpha == 0.f) out_color[3] = 0.f;
-        else out_color[3] = 1.0f;
-    }
-    for (int i = 0; i < 3; i++) out_emission[i] = emission[i];
-}
-
-// derived.rs:241-292 VoxSum
-struct HVoxSum {
-    float color_sum[3] = {0.f, 0.f, 0.f}, alpha_sum = 0.f, emission_sum[3] = {0.f, 0.f, 0.f};
-    size_t count = 0;
-    void add(const float color[4], const float emission[3]) {
-        const float alpha = color[3];
-        for (int i = 0; i < 3; i++) color_sum[i] += color[i] * alpha;
-        alpha_sum += alpha;
-        for (int i = 0; i < 3; i++) emission_sum[i] += emission[i];
-        count += 1;
-    }
-    void add(const HVoxSum &o) {
-        for (int i = 0; i < 3; i++) { color_sum[i] += o.color_sum[i]; emission_sum[i] += o.emission_sum[i]; }
-        alpha_sum += o.alpha_sum;
-        count += o.count;
-    }
-    void color(float surface_area, float out[4]) const {
-        if (!(alpha_sum > 0.0f)) { out[0] = out[1] = out[2] = out[3] = 0.f; return; }
-        for (int i = 0; i < 3; i++) out[i] = h_ps_new_clamped(color_sum[i] / alpha_sum);
-        out[3] = h_zo_new_clamped(alpha_sum / surface_area);
-    }
-    void emission(float surface_area, float out[3]) const {
-        if (count == 0) { out[0] = out[1] = out[2] = 0.f; return; }
-        for (int i = 0; i < 3; i++) out[i] = h_ps_new_clamped(emission_sum[i] / surface_area);
-    }
-};
-
-// EvaluatedBlock::visible() as compute_derived decides it (derived.rs:78-240): a single voxel that is not fully transparent or emits, a voxel volume with
-// one such voxel. The one copy of the property: compute_derived_h's kDerivedVisible and the luminance sampler's bitmap (light_visible_bits) both ask here.
-bool derived_visible_h(const HostBlocks &hb, const DevBlock &b) {
-    if ((b.kind & 255u) == 0u) {
-        const bool emits = !(b.emission[0] == 0.f && b.emission[1] == 0.f && b.emission[2] == 0.f);
-        return !(b.color[3] <= 0.0f) || emits;
-    }
-    const int lo[3] = {(int)(b.vlo_packed & 255u), (int)((b.vlo_packed >> 8) & 255u), (int)((b.vlo_packed >> 16) & 255u)};
-    const int sz[3] = {(int)(b.vsize_packed & 255u), (int)((b.vsize_packed >> 8) & 255u), (int)((b.vsize_packed >> 16) & 255u)};
-    for (int x = lo[0]; x < lo[0] + sz[0]; x++)
-        for (int y = lo[1]; y < lo[1] + sz[1]; y++)
-            for (int z = lo[2]; z < lo[2] + sz[2]; z++) {
-                HostVoxel v;
-                std::memset(&v, 0, sizeof(v));
-                hb.get(b, I3h{x, y, z}, &v);
-                if (!(v.color[3] == 0.f && v.emission[0] == 0.f && v.emission[1] == 0.f && v.emission[2] == 0.f)) return true;
-            }
-    return false;
-}
-
-// derived.rs:78-240 compute_derived, on the flattened block
-DevDerived compute_derived_h(const HostBlocks &hb, const DevBlock &b) {
-    DevDerived d;
-    std::memset(&d, 0, sizeof(d));
-    const int res = (int)(b.kind & 255u);
-    if (res == 0) {  // Evoxels::single_voxel(): every face is the voxel
-        for (int k = 0; k < 4; k++) d.color[k] = b.color[k];
-        for (int f = 0; f < 6; f++) for (int k = 0; k < 4; k++) d.face[f][k] = b.color[k];
-        for (int k = 0; k < 3; k++) d.emission[k] = b.emission[k];
-        if (b.color[3] >= 1.0f) d.flags |= 63u;
-        if (derived_visible_h(hb, b)) d.flags |= kDerivedVisible;
-        return d;
-    }
-    const int lo[3] = {(int)(b.vlo_packed & 255u), (int)((b.vlo_packed >> 8) & 255u), (int)((b.vlo_packed >> 16) & 255u)};
-    const int sz[3] = {(int)(b.vsize_packed & 255u), (int)((b.vsize_packed >> 8) & 255u), (int)((b.vsize_packed >> 16) & 255u)};
-    const int hi[3] = {lo[0] + sz[0], lo[1] + sz[1], lo[2] + sz[2]};
-    HVoxSum all;
-    for (int f = 0; f < 6; f++) {
-        const int axis = f % 3;
-        const bool positive = f >= 3;
-        const int opposite = positive ? f - 3 : f + 3;
-        const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
-        HVoxSum fs;
-        if (sz[0] > 0 && sz[1] > 0 && sz[2] > 0) {
-            for (int v = lo[a2]; v < hi[a2]; v++)
-                for (int u = lo[a1]; u < hi[a1]; u++) {
-                    I3h c;
-                    c[(size_t)axis] = positive ? hi[axis] - 1 : lo[axis];
-                    c[(size_t)a1] = u; c[(size_t)a2] = v;
-                    float col[4], em[3];
-                    h_trace_for_eval(hb, b, c, opposite, res, col, em);
-                    fs.add(col, em);
-                }
-        }
-        all.add(fs);
-        fs.color((float)res * (float)res, d.face[f]);
-    }
-    const float surface_area = (float)(6.0 * (double)res * (double)res);
-    all.color(surface_area, d.color);
-    all.emission(surface_area, d.emission);
-    if (derived_visible_h(hb, b)) d.flags |= kDerivedVisible;
-    for (int f = 0; f < 6; f++) {
-        const int axis = f % 3;
-        const bool positive = f >= 3;
-        int llo[3] = {0, 0, 0}, lhi[3] = {res, res, res};
-        if (positive) llo[axis] = res - 1; else lhi[axis] = 1;
-        bool covered = true;  // the layer of voxels just inside the face lies wholly within the stored volume ...
-        for (int a = 0; a < 3; a++) covered = covered && lo[a] <= llo[a] && hi[a] >= lhi[a];
-        bool all_opaque = covered;
-        if (covered)
-            for (int x = llo[0]; x < lhi[0] && all_opaque; x++)
-                for (int y = llo[1]; y < lhi[1] && all_opaque; y++)
-                    for (int z = llo[2]; z < lhi[2]; z++) {
-                        HostVoxel v;
-                        std::memset(&v, 0, sizeof(v));
-                        hb.get(b, I3h{x, y, z}, &v);
-                        if (!(v.color[3] >= 1.0f)) { all_opaque = false; break; }  // ... and is fully opaque
-                    }
-        if (all_opaque) d.flags |= 1u << f;
-    }
-    return d;
-}
-
-inline bool d_all_opaque(const DevDerived &d) { return (d.flags & 63u) == 63u; }
-inline bool d_emits(const DevDerived &d) { return !(d.emission[0] == 0.f && d.emission[1] == 0.f && d.emission[2] == 0.f); }
-inline bool d_visible(const DevDerived &d) { return (d.flags & kDerivedVisible) != 0u; }
-inline bool d_opaque_for_light(const DevDerived &d) { return d_all_opaque(d) && !d_emits(d); }  // updater.rs:1031-1033
-
-struct LightGeom {
-    int32_t lo[3] = {0, 0, 0}, size[3] = {0, 0, 0};
-    I3h cube_of(size_t idx) const {
-        const size_t sz = (size_t)size[2], sy = (size_t)size[1];
-        return I3h{lo[0] + (int32_t)(idx / (sy * sz)), lo[1] + (int32_t)((idx / sz) % sy), lo[2] + (int32_t)(idx % sz)};
-    }
-    bool index(const I3h &c, size_t *out) const {
-        const uint32_t dx = (uint32_t)c[0] - (uint32_t)lo[0], dy = (uint32_t)c[1] - (uint32_t)lo[1], dz = (uint32_t)c[2] - (uint32_t)lo[2];
-        if ((dx >= (uint32_t)size[0]) | (dy >= (uint32_t)size[1]) | (dz >= (uint32_t)size[2])) return false;
-        *out = ((size_t)dx * (size_t)size[1] + dy) * (size_t)size[2] + dz;
-        return true;
-    }
-};
-
-// ------------------------------------------------------------------------------------
-// queue.rs. The reference keeps one hashbrown::HashTable<Cube> per priority, hashed with rustc_hash::FxBuildHasher,
-// and pops "an arbitrary element": the first full bucket in table order (queue.rs:236-243). The last unit of the
-// converged 8-bit texels depends on that order, so it is reproduced: FxHasher 2.x (multiply by 0xf1357aea2e62a9c5,
-// finish = rotate_left(26)) over Cube's Hash (x | y << 32 as one u64, then z), and hashbrown's open-addressing table
-// (group-wise triangular probing, growth at 7/8 load in bucket order, in-place rehash, tombstones on erase).
-// `W` is hashbrown's Group::WIDTH: 16 with SSE2 (x86-64), 8 elsewhere; 0 selects plain first-in-first-out.
-
-inline uint64_t fx_hash_cube(const I3h &c) {
-    const uint64_t K = 0xf1357aea2e62a9c5ull;
-    uint64_t h = 0;
-    h = (h + ((uint64_t)(uint32_t)c[0] ^ ((uint64_t)(uint32_t)c[1] << 32))) * K;
-    h = (h + (uint64_t)(uint32_t)c[2]) * K;
-    return (h << 26) | (h >> 38);
-}
-
-struct HbTable {
-    static const uint8_t EMPTY = 0xff, DELETED = 0x80;
-    int W = 16;
-    std::vector<uint8_t> ctrl;      // buckets + W control bytes (the last W mirror the first W)
-    std::vector<uint32_t> val;      // element per bucket
-    std::vector<uint64_t> hashes;   // its hash
-    size_t bucket_mask = 0, items = 0, growth_left = 0;
-    bool singleton = true;          // the shared empty table of HashTable::new()
-
-    size_t buckets() const { return bucket_mask + 1; }
-    static size_t cap_of(size_t mask) { return mask < 8 ? mask : ((mask + 1) / 8) * 7; }
-    static size_t capacity_to_buckets(size_t cap) {
-        if (cap < 15) return cap < 4 ? 4 : (cap < 8 ? 8 : 16);
-        size_t adjusted = cap * 8 / 7, p = 1;
-        while (p < adjusted) p <<= 1;
-        return p;
-    }
-    uint8_t ctrl_at(size_t i) const { return singleton ? EMPTY : ctrl[i]; }
-    void set_ctrl(size_t index, uint8_t c) {
-        const size_t index2 = ((index - (size_t)W) & bucket_mask) + (size_t)W;
-        ctrl[index] = c;
-        ctrl[index2] = c;
-    }
-    static uint8_t h2(uint64_t hash) { return (uint8_t)((hash >> 57) & 0x7f); }
-    // first EMPTY/DELETED byte of the group at pos, or -1
-    int first_special(size_t pos) const {
-        for (int k = 0; k < W; k++) if (ctrl_at(pos + k) & 0x80) return k;
-        return -1;
-    }
-    size_t find_insert_slot(uint64_t hash) const {
-        size_t pos = (size_t)hash & bucket_mask, stride = 0;
-        for (;;) {
-            const int bit = first_special(pos);
-            if (bit >= 0) {
-                size_t index = (pos + (size_t)bit) & bucket_mask;
-                if (!(ctrl_at(index) & 0x80)) index = (size_t)first_special(0);  // tables smaller than a group: fix_insert_slot
-                return index;
-            }
-            stride += (size_t)W;
-            pos = (pos + stride) & bucket_mask;
-        }
-    }
-    void resize(size_t capacity) {
-        HbTable n;
-        n.W = W;
-        n.singleton = false;
-        const size_t nb = capacity_to_buckets(capacity);
-        n.bucket_mask = nb - 1;
-        n.ctrl.assign(nb + (size_t)W, EMPTY);
-        n.val.assign(nb, 0);
-        n.hashes.assign(nb, 0);
-        n.items = items;
-        n.growth_left = cap_of(n.bucket_mask) - items;
-        if (!singleton)
-            for (size_t i = 0; i < buckets(); i++)
-                if (!(ctrl[i] & 0x80)) {
-                    const size_t idx = n.find_insert_slot(hashes[i]);
-                    n.set_ctrl(idx, h2(hashes[i]));
-                    n.val[idx] = val[i];
-                    n.hashes[idx] = hashes[i];
-                }
-        *this = std::move(n);
-    }
-    void rehash_in_place() {
-        const size_t nb = buckets();
-        // full -> DELETED, special -> EMPTY, then restore the mirror bytes
-        for (size_t i = 0; i < nb; i++) ctrl[i] = (ctrl[i] & 0x80) ? EMPTY : DELETED;
-        if (nb < (size_t)W) { for (size_t i = 0; i < nb; i++) ctrl[(size_t)W + i] = ctrl[i]; }
-        else { for (size_t i = 0; i < (size_t)W; i++) ctrl[nb + i] = ctrl[i]; }
-        for (size_t i = 0; i < nb; i++) {
-            if (ctrl[i] != DELETED) continue;
-            for (;;) {
-                const uint64_t hash = hashes[i];
-                const size_t new_i = find_insert_slot(hash);
-                const size_t start = (size_t)hash & bucket_mask;
-                if (((i - start) & bucket_mask) / (size_t)W == ((new_i - start) & bucket_mask) / (size_t)W) {
-                    set_ctrl(i, h2(hash));
-                    break;
-                }
-                const uint8_t prev = ctrl[new_i];
-                set_ctrl(new_i, h2(hash));
-                if (prev == EMPTY) {
-                    set_ctrl(i, EMPTY);
-                    val[new_i] = val[i]; hashes[new_i] = hashes[i];
-                    break;
-                }
-                std::swap(val[new_i], val[i]);
-                std::swap(hashes[new_i], hashes[i]);
-            }
-        }
-        growth_left = cap_of(bucket_mask) - items;
-    }
-    void insert(uint64_t hash, uint32_t v) {
-        size_t slot = find_insert_slot(hash);
-        uint8_t old = ctrl_at(slot);
-        if (growth_left == 0 && (old & 1)) {
-            const size_t new_items = items + 1, full = singleton ? 0 : cap_of(bucket_mask);
-            if (new_items <= full / 2) rehash_in_place();
-            else resize(std::max(new_items, full + 1));
-            slot = find_insert_slot(hash);
-            old = ctrl[slot];
-        }
-        growth_left -= (old & 1) ? 1 : 0;
-        set_ctrl(slot, h2(hash));
-        val[slot] = v;
-        hashes[slot] = hash;
-        items++;
-    }
-    void erase(size_t index) {
-        const size_t before = (index - (size_t)W) & bucket_mask;
-        int lead = 0, trail = 0;  // empty_before.leading_zeros(), empty_after.trailing_zeros()
-        for (int k = W - 1; k >= 0 && ctrl[before + (size_t)k] != EMPTY; k--) lead++;
-        for (int k = 0; k < W && ctrl[index + (size_t)k] != EMPTY; k++) trail++;
-        uint8_t c;
-        if (lead + trail >= W) c = DELETED;
-        else { growth_left++; c = EMPTY; }
-        set_ctrl(index, c);
-        items--;
-    }
-    bool find(uint64_t hash, uint32_t v, size_t *out) const {
-        if (singleton) return false;
-        size_t pos = (size_t)hash & bucket_mask, stride = 0;
-        const uint8_t tag = h2(hash);
-        for (;;) {
-            bool any_empty = false;
-            for (int k = 0; k < W; k++) {
-                const uint8_t c = ctrl[pos + (size_t)k];
-                if (c == tag) {
-                    const size_t idx = (pos + (size_t)k) & bucket_mask;
-                    if (val[idx] == v) { *out = idx; return true; }
-                }
-                if (c == EMPTY) any_empty = true;
-            }
-            if (any_empty) return false;
-            stride += (size_t)W;
-            pos = (pos + stride) & bucket_mask;
-        }
-    }
-    bool first_full(size_t *out) const {  // RawIter order: ascending bucket index
-        if (singleton) return false;
-        for (size_t i = 0; i < buckets(); i++) if (!(ctrl[i] & 0x80)) { *out = i; return true; }
-        return false;
-    }
-    void clear() {
-        if (!singleton) std::fill(ctrl.begin(), ctrl.end(), EMPTY);
-        items = 0;
-        growth_left = singleton ? 0 : cap_of(bucket_mask);
-    }
-};
-
-struct LightQueue {
-    int hb_width;  // 0: first-in-first-out within a priority; 8 / 16: hashbrown table order (see above)
-    // FIFO mode: priority -> queue of cube indices; by_cube: priority+1, or 0 = absent
-    std::vector<std::deque<uint32_t>> by_priority;
-    std::vector<HbTable> tables;
-    std::vector<uint16_t> by_cube;
-    const LightGeom *geom = nullptr;
-    int highest = -1;
-    size_t len = 0;
-    LightQueue(size_t n_cubes, int width) : hb_width(width), by_priority(width ? 0 : 256), tables(width ? 256 : 0), by_cube(n_cubes, 0) {
-        for (auto &t : tables) t.W = width;
-    }
-    void clear() {
-        for (auto &q : by_priority) q.clear();
-        for (auto &t : tables) t.clear();
-        std::fill(by_cube.begin(), by_cube.end(), 0);
-        highest = -1;
-        len = 0;
-    }
-    uint64_t hash_of(uint32_t cube) const { return fx_hash_cube(geom->cube_of(cube)); }
-    void insert(uint32_t cube, int priority) {  // queue.rs:264-290: keeps the higher priority
-        const int old = (int)by_cube[cube] - 1;
-        if (old >= priority) return;
-        if (old < 0) len++;
-        by_cube[cube] = (uint16_t)(priority + 1);
-        if (hb_width) {
-            const uint64_t h = hash_of(cube);
-            if (old >= 0) {
-                size_t idx = 0;
-                if (tables[old].find(h, cube, &idx)) tables[old].erase(idx);
-            }
-            tables[priority].insert(h, cube);
-        } else {
-            by_priority[priority].push_back(cube);  // a stale entry of the old priority is skipped when popped
-        }
-        if (highest < priority) highest = priority;
-    }
-    bool remove(uint32_t cube) {
-        if (by_cube[cube] == 0) return false;
-        if (hb_width) {
-            const int p = (int)by_cube[cube] - 1;
-            size_t idx = 0;
-            if (tables[p].find(hash_of(cube), cube, &idx)) tables[p].erase(idx);
-        }
-        by_cube[cube] = 0;
-        len--;
-        return true;
-    }
-    void settle() {
-        while (highest >= 0) {
-            if (hb_width) {
-                if (tables[highest].items) return;
-            } else {
-                auto &q = by_priority[highest];
-                while (!q.empty() && (int)by_cube[q.front()] - 1 != highest) q.pop_front();
-                if (!q.empty()) return;
-            }
-            highest--;
-        }
-    }
-    bool pop(uint32_t *cube) {
-        settle();
-        if (highest < 0) return false;
-        if (hb_width) {
-            size_t idx = 0;
-            tables[highest].first_full(&idx);
-            *cube = tables[highest].val[idx];
-            tables[highest].erase(idx);
-        } else {
-            *cube = by_priority[highest].front();
-            by_priority[highest].pop_front();
-        }
-        by_cube[*cube] = 0;
-        len--;
-        return true;
-    }
-    int peek_priority() { settle(); return highest < 0 ? 0 : highest; }
-};
-const int kPriorityUninit = 210, kPriorityEstimated = 200;  // queue.rs Priority::{UNINIT, ESTIMATED}
-inline int priority_from_difference(int d) { return d / 2 + 1; }
-
 inline uint32_t texel_guess(const float v[3]) { return h_scalar_in(v[0]) | (h_scalar_in(v[1]) << 8) | (h_scalar_in(v[2]) << 16); }  // data.rs guess(): status Uninitialized
-const uint32_t kTexelOpaque = 128u << 24, kTexelNoRays = 1u << 24, kTexelUninit = 0u;
-// data.rs:186-211
-inline int texel_difference(uint32_t a, uint32_t b) {
-    int diff = 0;
-    for (int s = 0; s < 24; s += 8) {
-        const int x = (int)((a >> s) & 255u), y = (int)((b >> s) & 255u);
-        diff = std::max(diff, x > y ? x - y : y - x);
-    }
-    if ((a >> 24) != (b >> 24)) diff = std::min(255, diff + 255 / 4);
-    return diff;
-}
 
 }  // namespace
 
 namespace aic {
 
-// Per-layer state of the light updater: host mirrors of what the sequential half reads, and the device scratch.
-struct LightState {
-    uint64_t version = ~0ull;  // Layer::version the mirrors were taken at
-    LightGeom geom;
-    std::vector<uint16_t> grid;     // block index per cube
-    std::vector<uint32_t> light;    // texels; kept equal to the device's volume
-    std::vector<DevDerived> derived;
-    float lut[256];
-    DevBuf<DevDerived> d_derived;
-    DevBuf<DevLightNode> d_chart;
-    DevBuf<uint32_t> d_cubes, d_dep_pool, d_stack, d_scatter;
-    // wave-per-cube kernel: the effective tree of one maximum_distance, and per-wave scratch
-    int tree_distance = -1;
-    uint32_t tree_depth = 0, tree_size = 0;
-    DevBuf<DevTreePos> d_tree;
-    DevBuf<float> d_child_w;
-    DevBuf<float4> d_terms;
-    DevBuf<uint32_t> d_cands;
-    DevBuf<uint2> d_child_ent;
-    DevBuf<uint4> d_front, d_node;
-    DevBuf<float> d_valpha;
-    uint32_t n_front = 0, root_meta = 0;
-    std::vector<uint32_t> h_res;  // what a batch brings back: counters, per-cube results, dependency chunks
-    uint32_t *h_pin = nullptr;    // the same for small batches, pinned: the kernel writes its results here itself
-    size_t h_pin_words = 0;
-    // The update queue lives as long as the uploaded space does (as the reference's Space keeps its LightUpdateQueue):
-    // aic_light_cubes_changed adds to it, aic_evaluate_light drains it, possibly over several calls.
-    LightQueue *queue = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // device time of a batch
-    // Sessions (small batches: one launch per call, batches handed over through `mailbox`; aic_light.h)
-    LightMailbox *mailbox = nullptr;  // pinned, coherent
-    DevBuf<uint32_t> d_session;       // LightJob::session_word
-    uint32_t session_seq = 0;         // the last sequence number posted; never reused within a context
-    double wall_clock_khz = 0.0;
-    int queue_width = -1;
-    uint64_t upload_serial = ~0ull;  // Layer::upload_serial the queue belongs to
-    // What aic_light_changed_count / _take answer from (include/aic_hip.h): `baseline` is the volume the report is measured against -- the mirror as
-    // first read, then following the caller's own texels and every take --, `cand` the cubes the updater wrote since (each once: `cand_bits`, a bit
-    // per cube; `cand_all`: fast = 1 wrote them all). A cube is reported iff it is a candidate and light[i] != baseline[i]: exact, and the apply loop
-    // gets no work per update -- deliver_changed() hands over what a batch changed, which it has sorted already.
-    std::vector<uint32_t> baseline, cand;
-    std::vector<uint64_t> cand_bits;
-    bool cand_all = false;
-    bool reread_own = false;          // the mirrors were marked stale by a failed update, not by the caller: the next re-read keeps every candidate
-    uint64_t report_serial = ~0ull;   // Layer::upload_serial the baseline belongs to
-    std::vector<uint32_t> published;  // while a submitted update runs: the answer for the published volume, taken at the submit (the worker owns the rest)
-    void cand_add(uint32_t i) {
-        if (cand_all) return;
-        uint64_t &w = cand_bits[i >> 6];
-        const uint64_t b = 1ull << (i & 63u);
-        if (w & b) return;
-        w |= b;
-        cand.push_back(i);
-    }
-    void cand_clear() {
-        for (uint32_t i : cand) cand_bits[i >> 6] = 0;
-        if (cand_all) std::fill(cand_bits.begin(), cand_bits.end(), 0);
-        cand.clear();
-        cand_all = false;
-    }
-    // the reported cubes, ascending
-    void changed_list(std::vector<uint32_t> *out) const {
-        out->clear();
-        if (cand_all) {
-            for (size_t i = 0; i < light.size(); i++)
-                if (light[i] != baseline[i]) out->push_back((uint32_t)i);
-        } else {
-            for (uint32_t i : cand)
-                if (light[i] != baseline[i]) out->push_back(i);
-            std::sort(out->begin(), out->end());
-        }
-    }
-    // The mirror `light` has just been read again from the device, `before` is what it held (empty: nothing was pending). A new space starts the
-    // report afresh. Otherwise whoever replaced texels owns them -- the baseline follows, their candidates go --, and a candidate whose texel the
-    // re-read did not move keeps its pending report.
-    void report_reread(uint64_t serial, const std::vector<uint32_t> &before) {
-        const size_t n = light.size();
-        const bool keep = report_serial == serial && baseline.size() == n && before.size() == n;
-        std::vector<std::pair<uint32_t, uint32_t>> kept;  // (cube, its baseline)
-        if (keep) {
-            auto consider = [&](uint32_t i) {
-                if (before[i] != baseline[i] && (reread_own ? light[i] != baseline[i] : light[i] == before[i])) kept.emplace_back(i, baseline[i]);
-            };
-            if (cand_all) for (size_t i = 0; i < n; i++) consider((uint32_t)i);
-            else for (uint32_t i : cand) consider(i);
-        }
-        baseline = light;
-        cand_bits.assign((n + 63) / 64, 0);
-        cand.clear();
-        cand_all = false;
-        for (const auto &k : kept) { baseline[k.first] = k.second; cand_add(k.first); }
-        reread_own = false;
-        report_serial = serial;
-    }
-    void release() {
-        delete queue;
-        queue = nullptr;
-        if (h_pin) (void)hipHostFree(h_pin);
-        h_pin = nullptr;
-        h_pin_words = 0;
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        ev0 = ev1 = nullptr;
-        if (mailbox) (void)hipHostFree(mailbox);
-        mailbox = nullptr;
-        d_session.release();
-        d_derived.release(); d_chart.release(); d_cubes.release(); d_dep_pool.release();
-        d_stack.release(); d_scatter.release(); d_tree.release(); d_child_w.release(); d_terms.release(); d_cands.release(); d_child_ent.release(); d_front.release(); d_node.release(); d_valpha.release();
-    }
-};
 void light_state_cubes_updated(LightState *s, uint64_t version_before, uint64_t version_after, uint32_t n, const int32_t *xyz, const uint16_t *block_index,
                                const uint8_t *light) {
     if (!s || s->version != version_before) return;  // mirrors absent or already stale: light_prepare will re-read everything
@@ -839,7 +48,7 @@ void light_state_cubes_updated(LightState *s, uint64_t version_before, uint64_t 
         if (block_index) s->grid[idx] = block_index[k];
         if (light) {
             s->light[idx] = (uint32_t)light[4 * k] | ((uint32_t)light[4 * k + 1] << 8) | ((uint32_t)light[4 * k + 2] << 16) | ((uint32_t)light[4 * k + 3] << 24);
-            if (s->baseline.size() == s->light.size()) s->baseline[idx] = s->light[idx];  // the caller's own texel is never reported (aic_light_changed_count)
+            s->report.caller_wrote(s->light, (uint32_t)idx);
         }
     }
     s->version = version_after;
@@ -935,7 +144,11 @@ int apply_light_update_h(LightRun &R, uint32_t ci, uint32_t new_texel, const uin
     return diff;
 }
 
-int light_prepare(aic_ctx *c, Layer &l, LightState &S, const uint32_t *vol = nullptr) {  // vol: the device volume to mirror (default: the layer's current one)
+}  // namespace
+
+namespace aic {
+
+int light_prepare(aic_ctx *c, Layer &l, LightState &S, const uint32_t *vol) {
     if (!vol) vol = l.light.p;
     hipError_t e;
     const size_t n = l.n_cubes();
@@ -948,8 +161,8 @@ int light_prepare(aic_ctx *c, Layer &l, LightState &S, const uint32_t *vol = nul
     if (S.version == l.version) return AIC_OK;
     for (int a = 0; a < 3; a++) { S.geom.lo[a] = l.lo[a]; S.geom.size[a] = l.size[a]; }
     S.grid.resize(n);
-    std::vector<uint32_t> before;  // the mirror as it was, if the light report has something pending (LightState::report_reread)
-    if (S.report_serial == l.upload_serial && S.light.size() == n && (S.cand_all || !S.cand.empty())) before = S.light;
+    std::vector<uint32_t> before;  // the mirror as it was, if the light report has something pending (LightReport::report_reread)
+    if (S.report.report_serial == l.upload_serial && S.light.size() == n && (S.report.cand_all || !S.report.cand.empty())) before = S.light;
     S.light.resize(n);
     if (n) {
         HIP_TRY(c, hipMemcpy(S.grid.data(), l.pool.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
@@ -957,18 +170,10 @@ int light_prepare(aic_ctx *c, Layer &l, LightState &S, const uint32_t *vol = nul
         if (l.cls_in_code)
             for (size_t i = 0; i < n; i++) S.grid[i] &= (uint16_t)kCubeIndexMask;
     }
-    HostBlocks hb;
-    hb.blocks = &l.host_blocks;
-    hb.n_cubes = n;
-    hb.vox.resize(l.pool.n > n ? l.pool.n - n : 0);
-    hb.pal.resize(l.palette.n);
-    if (!hb.vox.empty()) HIP_TRY(c, hipMemcpy(hb.vox.data(), l.pool.p + n, hb.vox.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    if (!hb.pal.empty()) HIP_TRY(c, hipMemcpy(hb.pal.data(), l.palette.p, hb.pal.size() * sizeof(DevPaletteEntry), hipMemcpyDeviceToHost));
-    S.derived.resize(l.host_blocks.size());
-    for (size_t i = 0; i < l.host_blocks.size(); i++) S.derived[i] = compute_derived_h(hb, l.host_blocks[i]);
+    { const int rc = light_prepare_derived(c, l, &S.derived); if (rc != AIC_OK) return rc; }
     if ((e = S.d_derived.ensure(std::max<size_t>(S.derived.size(), 1))) != hipSuccess) return hip_fail(c, "alloc derived", e);
     if (!S.derived.empty()) HIP_TRY(c, hipMemcpy(S.d_derived.p, S.derived.data(), S.derived.size() * sizeof(DevDerived), hipMemcpyHostToDevice));
-    S.report_reread(l.upload_serial, before);
+    S.report.report_reread(S.light, l.upload_serial, before);
     S.version = l.version;
     return AIC_OK;
 }
@@ -984,28 +189,16 @@ void light_queue_for(Layer &l, LightState &S, int width) {
     S.queue->geom = &S.geom;
 }
 
+void light_update_failed(LightState &S, std::initializer_list<LightOwed> owed) {
+    S.version = ~0ull;
+    S.report.reread_own = true;
+    for (const LightOwed &list : owed)
+        for (size_t k = 0; k < list.n; k++) S.queue->insert(list.cubes[k], kPriorityNewlyVisible);
+}
 
-// argument checks shared by aic_evaluate_light and aic_evaluate_light_submit
-int light_check_args(aic_ctx *c, int layer, const aic_light_params *p) {
-    if (!c || !valid_layer(layer) || !p) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light: bad argument");
-    Layer &l = c->layers[layer];
-    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light: no space uploaded for this layer");
-    if (p->maximum_distance < 0 || p->maximum_distance > 255) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light: maximum_distance is a u8");
-    if (p->queue_order != 0 && p->queue_order != 8 && p->queue_order != 16) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light: queue_order must be 0, 8 or 16");
-    if (p->lanes_per_cube != 0 && p->lanes_per_cube != 1 && p->lanes_per_cube != 64 && p->lanes_per_cube != 256)
-        return fail(c, AIC_ERR_INVALID, "aic_evaluate_light: lanes_per_cube must be 0, 1, 64 or 256");
-    if (p->n_queue > 0 && (!p->queue_cubes || !p->queue_priorities)) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light: queue arrays are null");
-    for (int32_t k = 0; k < p->n_queue; k++)
-        if (p->queue_priorities[k] < 0 || p->queue_priorities[k] > 255) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light: priorities are u8");
-    return AIC_OK;
-}
-// Nothing to do -- no fast pass, no new entries, and the layer's own queue (kept since its upload) is empty: the light is as it stands. (A sim + render
-// loop calls once per frame with a budget; most frames find the queue drained, and until round 6 each of them still copied the volume, swapped
-// and waited for a frame in flight.)
-bool light_nothing_to_do(const Layer &l, const aic_light_params *p) {
-    return !p->fast && p->n_queue == 0 && l.lstate && l.lstate->queue && l.lstate->queue->len == 0 && l.lstate->queue_width == p->queue_order &&
-           l.lstate->upload_serial == l.upload_serial && l.lstate->queue->by_cube.size() == l.n_cubes();
-}
+}  // namespace aic
+
+namespace {
 
 // ------------------------------------------------------------------------------------
 // One update call, step by step: evaluate_light_on (below) is the batch loop, LightCall owns what its steps share.
@@ -1126,21 +319,16 @@ struct LightCall {
     }
     // Every way out ends the session (a kernel left waiting would end itself, but only after its patience), and that BEFORE the
     // stream is synchronised below. Then every error return leaves through the rest: the host mirrors may be
-    // ahead of the device (texels applied but not yet scattered) and a popped batch may be lost, so the mirrors are marked
-    // stale -- light_prepare re-reads the device's volume on the next call -- and the cubes whose results never reached the
-    // device go back into the queue: the popped batch (until it is applied), `changed`, and prep's pending scatter.
+    // ahead of the device (texels applied but not yet scattered) and a popped batch may be lost, so the failure rule applies
+    // (light_update_failed) to the cubes whose results never reached the device: the popped batch (until it is applied),
+    // `changed`, and prep's pending scatter.
     ~LightCall() {
         (void)session_end();
         if (ok) return;
         // (the new half of the double buffer may still be the target of copies / scatters / walks queued on `ls`: frames submitted next read it
         //  from their own streams, which do not wait for `ls` -- ADVICE r04)
         (void)hipStreamSynchronize(ls);
-        S.version = ~0ull;
-        S.reread_own = true;
-        const int kRequeue = 250;  // Priority::NEWLY_VISIBLE (all of them: after a failure the order of these updates is no longer the reference's)
-        for (uint32_t idx : cubes) R.queue.insert(idx, kRequeue);
-        for (uint32_t idx : changed) R.queue.insert(idx, kRequeue);
-        for (uint32_t k = 0; k < prep.n_scatter; k++) R.queue.insert(prep.scatter_index[k], kRequeue);
+        light_update_failed(S, {{cubes.data(), cubes.size()}, {changed.data(), changed.size()}, {prep.scatter_index, prep.n_scatter}});
     }
 
     // What the call adds to the layer's queue: Mutation::fast_evaluate_light, or the caller's entries (n_queue < 0: every uninitialised cube).
@@ -1148,8 +336,8 @@ struct LightCall {
         const size_t n = l.n_cubes();
         if (p->fast) {
             fast_evaluate_light_h(R, l.block_sky);
-            S.cand_clear();  // every texel was written: a full relight is measured against the whole baseline
-            S.cand_all = true;
+            S.report.cand_clear();  // every texel was written: a full relight is measured against the whole baseline
+            S.report.cand_all = true;
             if (n) HIP_TRY(c, hipMemcpyAsync(vol, S.light.data(), n * 4, hipMemcpyHostToDevice, ls));
         } else {
             if (p->n_queue < 0)
@@ -1537,7 +725,7 @@ struct LightCall {
             std::sort(changed.begin(), changed.end());
             changed.erase(std::unique(changed.begin(), changed.end()), changed.end());
             const size_t m = changed.size();
-            for (uint32_t idx : changed) S.cand_add(idx);  // what aic_light_changed_count may report
+            for (uint32_t idx : changed) S.report.cand_add(idx);  // what aic_light_changed_count may report
             if (m <= kLightPrepMax) {
                 prep.n_scatter = (uint32_t)m;
                 for (size_t k = 0; k < m; k++) { prep.scatter_index[k] = changed[k]; prep.scatter_texel[k] = S.light[changed[k]]; }
@@ -1563,6 +751,10 @@ struct LightCall {
         return AIC_OK;
     }
 };
+
+}  // namespace
+
+namespace aic {
 
 // The update itself, against the device volume `vol` (the layer's current one, or the spare a submitted update works on).
 int evaluate_light_on(aic_ctx *c, int layer, const aic_light_params *p, aic_light_info *info, uint32_t *vol) {
@@ -1618,9 +810,7 @@ void light_worker_main(aic_ctx *c) {
         J.cv.notify_all();
     }
 }
-}  // namespace
 
-namespace aic {
 // Ends a submitted light update, if there is one, and PUBLISHES it: the spare volume it worked on becomes the layer's. Called by aic_evaluate_light_wait and by
 // every call that needs the scene or the light still (quiesce, the light entry points, aic_destroy). Its outcome stays with the job for aic_evaluate_light_wait.
 int light_job_finish(aic_ctx *c) {
@@ -1638,380 +828,4 @@ int light_job_finish(aic_ctx *c) {
     return AIC_OK;
 }
 
-// The luminance sampler's bitmap (aic_exposure.h): bit i of `bits` = derived_visible_h of block i, kVisibleBitsWords words whatever the table's size. The
-// voxel and palette pools are read back only if a block has voxels, and on `stream` -- the caller's, which runs beside the frames in flight: nothing
-// here waits for a frame or goes through the null stream.
-int light_visible_bits(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<uint32_t> *bits) {
-    const size_t n = l.n_cubes();
-    HostBlocks hb;
-    hb.blocks = &l.host_blocks;
-    hb.n_cubes = n;
-    bool any_voxels = false;
-    for (const DevBlock &b : l.host_blocks) any_voxels = any_voxels || (b.kind & 255u) != 0u;
-    if (any_voxels) {
-        hb.vox.resize(l.pool.n > n ? l.pool.n - n : 0);
-        hb.pal.resize(l.palette.n);
-        if (!hb.vox.empty()) HIP_TRY(c, hipMemcpyAsync(hb.vox.data(), l.pool.p + n, hb.vox.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, stream));
-        if (!hb.pal.empty()) HIP_TRY(c, hipMemcpyAsync(hb.pal.data(), l.palette.p, hb.pal.size() * sizeof(DevPaletteEntry), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(c, hipStreamSynchronize(stream));
-    }
-    bits->assign(kVisibleBitsWords, 0u);
-    for (size_t i = 0; i < l.host_blocks.size() && i < 32u * kVisibleBitsWords; i++)
-        if (derived_visible_h(hb, l.host_blocks[i])) (*bits)[i >> 5] |= 1u << (i & 31u);
-    return AIC_OK;
-}
-
-// What aic_light_rays (aic_light_rays_host.cpp) takes from here. The effective tree of a maximum_distance with its children's weights and entries
-// (the entry's first word is the child's position; the rest of it is the updater's own); the bound counts the bundles within the distance, the root
-// apart, that have no child within it: a record ends its bundle (updater.rs:838-853), so no two of a cube's records lie on one root path, and those
-// are the most positions no two of which do.
-void light_rays_tree(int maximum_distance, LightRaysTree *out) {
-    std::vector<uint32_t> child_pos;
-    out->tree = build_light_tree(maximum_distance, nullptr, &out->child_w, &child_pos);
-    out->child_ent.resize(child_pos.size());
-    for (size_t q = 0; q < child_pos.size(); q++) out->child_ent[q] = child_pos[q] ? make_uint2(child_pos[q], out->tree[child_pos[q]].offset) : make_uint2(0u, 0u);
-    out->bound = 0;
-    for (size_t k = 1; k < out->tree.size(); k++) {
-        if (out->tree[k].info & 8u) continue;
-        bool child_within = false;
-        for (int f = 0; f < 6; f++) {
-            const uint32_t cp = child_pos[k * 6 + (size_t)f];
-            child_within = child_within || (cp != 0u && !(out->tree[cp].info & 8u));
-        }
-        if (!child_within) out->bound++;
-    }
-}
-uint32_t light_rays_bound(int maximum_distance) {
-    static std::mutex mu;
-    static int64_t known[256];
-    static bool init = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!init) { for (auto &k : known) k = -1; init = true; }
-    if (known[maximum_distance] < 0) {
-        LightRaysTree t;
-        light_rays_tree(maximum_distance, &t);
-        known[maximum_distance] = t.bound;
-    }
-    return (uint32_t)known[maximum_distance];
-}
-int light_rays_derived(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<DevDerived> *out) {
-    const size_t n = l.n_cubes();
-    HostBlocks hb;
-    hb.blocks = &l.host_blocks;
-    hb.n_cubes = n;
-    bool any_voxels = false;
-    for (const DevBlock &b : l.host_blocks) any_voxels = any_voxels || (b.kind & 255u) != 0u;
-    if (any_voxels) {
-        hb.vox.resize(l.pool.n > n ? l.pool.n - n : 0);
-        hb.pal.resize(l.palette.n);
-        if (!hb.vox.empty()) HIP_TRY(c, hipMemcpyAsync(hb.vox.data(), l.pool.p + n, hb.vox.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, stream));
-        if (!hb.pal.empty()) HIP_TRY(c, hipMemcpyAsync(hb.pal.data(), l.palette.p, hb.pal.size() * sizeof(DevPaletteEntry), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(c, hipStreamSynchronize(stream));
-    }
-    out->resize(l.host_blocks.size());
-    for (size_t i = 0; i < l.host_blocks.size(); i++) (*out)[i] = compute_derived_h(hb, l.host_blocks[i]);
-    return AIC_OK;
-}
 }  // namespace aic
-
-extern "C" {
-
-uint32_t aic_light_chart(float *weights, uint32_t *children, uint32_t *depth) {
-    const LightChart &ch = light_chart();
-    if (weights && children)
-        for (size_t i = 0; i < ch.nodes.size(); i++)
-            for (int f = 0; f < 6; f++) { weights[6 * i + (size_t)f] = ch.nodes[i].weight[f]; children[6 * i + (size_t)f] = ch.nodes[i].child[f]; }
-    if (depth) *depth = ch.depth;
-    return (uint32_t)ch.nodes.size();
-}
-
-int aic_evaluate_light(aic_ctx *c, int layer, const aic_light_params *p, aic_light_info *info) {
-    { const int rc = light_check_args(c, layer, p); if (rc != AIC_OK) return rc; }
-    Layer &l = c->layers[layer];
-    HIP_TRY(c, hipSetDevice(c->device));
-    { const int rc = light_job_finish(c); if (rc != AIC_OK) return rc; }
-    if (light_nothing_to_do(l, p)) {
-        if (info) std::memset(info, 0, sizeof(*info));
-        return AIC_OK;
-    }
-    // The updater runs on the context's second stream, beside the frames in flight (until round 4 it waited for every one of them:
-    // in a sim + render loop the trace and the light update then took turns -- VERDICT r03 weak 11 / next 4). Frames in flight read
-    // the light volume the updater is about to change, so it works on a SPARE volume: the current volume is copied there on the device,
-    // the two swap, the frames in flight go on reading what they were given (FrameSlot::light_used) and every frame submitted after this
-    // call returns reads the updated volume.
-    hipStream_t ls = c->upload_stream;
-    {
-        bool in_flight = false;
-        for (uint32_t i = 0; i < AIC_MAX_IN_FLIGHT; i++) in_flight = in_flight || c->slots[i].busy;
-        const size_t nc = l.n_cubes();
-        if (in_flight && nc) {
-            int spare = 0;
-            { const int rc = take_light_spare(c, l, layer, nc, &spare); if (rc != AIC_OK) return rc; }  // (a volume no frame in flight reads: no waiting for frames)
-            HIP_TRY(c, hipMemcpyAsync(l.light_spare[spare].p, l.light.p, nc * 4, hipMemcpyDeviceToDevice, ls));
-            // The copy must have landed before anything reads the new half from another stream: light_prepare refills a stale host
-            // mirror with a blocking null-stream copy, and `ls` is a non-blocking stream the null stream does not wait for.
-            HIP_TRY(c, hipStreamSynchronize(ls));
-            std::swap(l.light, l.light_spare[spare]);
-        }
-    }
-    return evaluate_light_on(c, layer, p, info, l.light.p);
-}
-
-int aic_evaluate_light_submit(aic_ctx *c, int layer, const aic_light_params *p) {
-    { const int rc = light_check_args(c, layer, p); if (rc != AIC_OK) return rc; }
-    Layer &l = c->layers[layer];
-    HIP_TRY(c, hipSetDevice(c->device));
-    { const int rc = light_job_finish(c); if (rc != AIC_OK) return rc; }
-    aic_ctx::LightJob &J = c->ljob;
-    if (J.result_ready) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light_submit: the previous update has not been collected (aic_evaluate_light_wait it first)");
-    J.layer = layer;
-    J.rc = AIC_OK;
-    std::memset(&J.info, 0, sizeof(J.info));
-    if (light_nothing_to_do(l, p)) {  // (no thread, no copy: the wait reports an update of nothing)
-        J.result_ready = true;
-        return AIC_OK;
-    }
-    // the update works on a spare volume, a copy of the current one; frames submitted while it runs read the current one
-    const size_t nc = l.n_cubes();
-    int spare = 0;
-    { const int rc = take_light_spare(c, l, layer, nc, &spare); if (rc != AIC_OK) return rc; }
-    if (nc) HIP_TRY(c, hipMemcpyAsync(l.light_spare[spare].p, l.light.p, nc * 4, hipMemcpyDeviceToDevice, c->upload_stream));
-    HIP_TRY(c, hipStreamSynchronize(c->upload_stream));
-    // aic_light_changed_count answers for the PUBLISHED volume while the worker owns the mirrors: its answer is taken now
-    if (!l.lstate) l.lstate = new LightState();
-    { const int rc = light_prepare(c, l, *l.lstate); if (rc != AIC_OK) return rc; }
-    l.lstate->changed_list(&l.lstate->published);
-    J.params = *p;
-    J.queue_cubes.assign(p->n_queue > 0 ? p->queue_cubes : nullptr, p->n_queue > 0 ? p->queue_cubes + 3 * (size_t)p->n_queue : nullptr);
-    J.queue_priorities.assign(p->n_queue > 0 ? p->queue_priorities : nullptr, p->n_queue > 0 ? p->queue_priorities + (size_t)p->n_queue : nullptr);
-    J.spare = spare;
-    if (!J.worker.joinable()) J.worker = std::thread(light_worker_main, c);
-    {
-        std::lock_guard<std::mutex> lk(J.mu);
-        J.has_work = true;
-    }
-    J.pending = true;
-    J.cv.notify_all();
-    return AIC_OK;
-}
-
-int aic_evaluate_light_poll(aic_ctx *c, int layer, int *done) {
-    if (!c || !valid_layer(layer) || !done) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light_poll: bad argument");
-    aic_ctx::LightJob &J = c->ljob;
-    *done = 1;
-    if (J.pending && J.layer == layer) {
-        std::lock_guard<std::mutex> lk(J.mu);
-        *done = (!J.has_work && !J.running) ? 1 : 0;
-    }
-    return AIC_OK;
-}
-
-int aic_evaluate_light_wait(aic_ctx *c, int layer, aic_light_info *info) {
-    if (!c || !valid_layer(layer)) return fail(c, AIC_ERR_INVALID, "aic_evaluate_light_wait: bad argument");
-    if (info) std::memset(info, 0, sizeof(*info));
-    HIP_TRY(c, hipSetDevice(c->device));
-    { const int rc = light_job_finish(c); if (rc != AIC_OK) return rc; }
-    aic_ctx::LightJob &J = c->ljob;
-    if (!J.result_ready || J.layer != layer) return AIC_OK;  // nothing was submitted for this layer
-    J.result_ready = false;
-    if (J.rc != AIC_OK) { c->err = J.err; return J.rc; }
-    if (info) *info = J.info;
-    return AIC_OK;
-}
-
-int aic_read_light_volume(aic_ctx *c, int layer, uint8_t *out) {
-    if (!c || !valid_layer(layer) || !out) return fail(c, AIC_ERR_INVALID, "aic_read_light_volume: bad argument");
-    Layer &l = c->layers[layer];
-    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_read_light_volume: no space uploaded for this layer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    { int qrc = quiesce(c); if (qrc != AIC_OK) return qrc; }
-    const size_t n = l.n_cubes();
-    if (n) HIP_TRY(c, hipMemcpy(out, l.light.p, n * 4, hipMemcpyDeviceToHost));
-    return AIC_OK;
-}
-
-// The texels of some cubes (LightStorage::get, light/data.rs, for a list): what a caller that keeps a copy of the volume elsewhere
-// -- aic_multi: one copy per device -- needs after aic_light_cubes_changed. From the host mirror when it is current (no device
-// trip), else gathered from the device volume.
-int aic_read_light_cubes(aic_ctx *c, int layer, uint32_t n_cubes, const int32_t *xyz, uint8_t *out) {
-    if (!c || !valid_layer(layer) || (n_cubes && (!xyz || !out))) return fail(c, AIC_ERR_INVALID, "aic_read_light_cubes: bad argument");
-    Layer &l = c->layers[layer];
-    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_read_light_cubes: no space uploaded for this layer");
-    if (!n_cubes) return AIC_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    { int qrc = quiesce(c); if (qrc != AIC_OK) return qrc; }
-    if (!l.lstate) l.lstate = new LightState();
-    LightState &S = *l.lstate;
-    { int rc = light_prepare(c, l, S); if (rc != AIC_OK) return rc; }
-    for (uint32_t k = 0; k < n_cubes; k++) {
-        size_t idx;
-        if (!S.geom.index(I3h{xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]}, &idx)) return fail(c, AIC_ERR_INVALID, "aic_read_light_cubes: cube outside the space");
-        const uint32_t t = S.light[idx];
-        out[4 * k] = (uint8_t)t; out[4 * k + 1] = (uint8_t)(t >> 8); out[4 * k + 2] = (uint8_t)(t >> 16); out[4 * k + 3] = (uint8_t)(t >> 24);
-    }
-    return AIC_OK;
-}
-
-// LightStorage::modified_cube_needs_update (updater.rs:135-173) for cubes whose block was just changed with
-// aic_update_cubes: a cube that is now opaque for light gets PackedLight::OPAQUE at once and leaves the queue, any other is
-// queued at Priority::NEWLY_VISIBLE, and so is every neighbour that is not opaque towards it.
-int aic_light_cubes_changed(aic_ctx *c, int layer, uint32_t n_cubes, const int32_t *xyz, int queue_order) {
-    if (!c || !valid_layer(layer) || (n_cubes && !xyz)) return fail(c, AIC_ERR_INVALID, "aic_light_cubes_changed: bad argument");
-    if (queue_order != 0 && queue_order != 8 && queue_order != 16) return fail(c, AIC_ERR_INVALID, "aic_light_cubes_changed: queue_order must be 0, 8 or 16");
-    Layer &l = c->layers[layer];
-    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_light_cubes_changed: no space uploaded for this layer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    { int qrc = quiesce(c); if (qrc != AIC_OK) return qrc; }
-    if (!l.lstate) l.lstate = new LightState();
-    LightState &S = *l.lstate;
-    { int rc = light_prepare(c, l, S); if (rc != AIC_OK) return rc; }
-    light_queue_for(l, S, queue_order);
-    LightRun R(S);
-    std::vector<uint32_t> scatter_idx;
-    const int kNewlyVisible = 250;  // queue.rs Priority::NEWLY_VISIBLE
-    for (uint32_t k = 0; k < n_cubes; k++) {  // validate everything before anything is changed
-        size_t idx;
-        if (!S.geom.index(I3h{xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]}, &idx)) return fail(c, AIC_ERR_INVALID, "aic_light_cubes_changed: cube outside the space");
-    }
-    // a device failure after this point: the OPAQUE texels below may not have reached the device, so the mirrors are marked
-    // stale (re-read on the next call) and those cubes are queued to be written again
-    struct Unwind {
-        LightState &S;
-        LightRun &R;
-        const std::vector<uint32_t> &owed;
-        bool ok = false;
-        ~Unwind() {
-            if (ok) return;
-            S.version = ~0ull;
-            S.reread_own = true;
-            for (uint32_t idx : owed) R.queue.insert(idx, 250);
-        }
-    } unwind{S, R, scatter_idx};
-    for (uint32_t k = 0; k < n_cubes; k++) {
-        const I3h cube = {xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]};
-        size_t idx;
-        if (!S.geom.index(cube, &idx)) continue;  // (validated above)
-        const DevDerived &ev = S.derived[S.grid[idx]];
-        if (d_opaque_for_light(ev)) {
-            S.light[idx] = kTexelOpaque;
-            S.cand_add((uint32_t)idx);  // the updater's write: aic_light_changed_count may report it
-            scatter_idx.push_back((uint32_t)idx);
-            R.queue.remove((uint32_t)idx);
-        } else {
-            R.queue.insert((uint32_t)idx, kNewlyVisible);
-        }
-        for (int f = 0; f < 6; f++) {
-            const I3h nrm = face_normal_h(f);
-            const I3h nb = {cube[0] + nrm[0], cube[1] + nrm[1], cube[2] + nrm[2]};
-            size_t ni;
-            if (!S.geom.index(nb, &ni)) continue;
-            const int opposite = f >= 3 ? f - 3 : f + 3;
-            if (!((S.derived[S.grid[ni]].flags >> opposite) & 1u)) R.queue.insert((uint32_t)ni, kNewlyVisible);
-        }
-    }
-    if (!scatter_idx.empty()) {
-        const size_t m = scatter_idx.size();
-        hipError_t e;
-        if ((e = S.d_scatter.ensure(2 * m)) != hipSuccess) return hip_fail(c, "alloc light scatter", e);
-        std::vector<uint32_t> buf(2 * m);
-        for (size_t k = 0; k < m; k++) { buf[k] = scatter_idx[k]; buf[m + k] = kTexelOpaque; }
-        HIP_TRY(c, hipMemcpyAsync(S.d_scatter.p, buf.data(), 2 * m * 4, hipMemcpyHostToDevice, c->stream));
-        launch_scatter_light(l.light.p, S.d_scatter.p, S.d_scatter.p + m, (uint32_t)m, c->stream);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    unwind.ok = true;
-    return AIC_OK;
-}
-
-// The cubes whose light texel the updater changed (include/aic_hip.h). While a submitted update runs the worker thread owns the layer's mirrors, and its
-// changes are not published: the count answers from LightState::published, the take ends the update first, as every call that changes light state does.
-int aic_light_changed_count(aic_ctx *c, int layer, uint64_t *n, int32_t bounds[6]) {
-    if (!c || !valid_layer(layer) || !n) return fail(c, AIC_ERR_INVALID, "aic_light_changed_count: bad argument");
-    Layer &l = c->layers[layer];
-    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_light_changed_count: no space uploaded for this layer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!l.lstate) l.lstate = new LightState();
-    LightState &S = *l.lstate;
-    std::vector<uint32_t> fresh;
-    const std::vector<uint32_t> *list = &S.published;
-    if (!(c->ljob.pending && c->ljob.layer == layer)) {
-        { int rc = light_prepare(c, l, S); if (rc != AIC_OK) return rc; }
-        S.changed_list(&fresh);
-        list = &fresh;
-    }
-    *n = list->size();
-    if (bounds) {
-        for (int a = 0; a < 6; a++) bounds[a] = 0;
-        bool first = true;
-        for (uint32_t idx : *list) {
-            const I3h q = S.geom.cube_of(idx);
-            for (int a = 0; a < 3; a++) {
-                if (first || q[a] < bounds[a]) bounds[a] = q[a];
-                if (first || q[a] + 1 > bounds[3 + a]) bounds[3 + a] = q[a] + 1;
-            }
-            first = false;
-        }
-    }
-    return AIC_OK;
-}
-
-int aic_light_changed_take(aic_ctx *c, int layer, uint32_t capacity, int32_t *xyz, uint32_t *n_written) {
-    if (!c || !valid_layer(layer) || !n_written || (capacity && !xyz)) return fail(c, AIC_ERR_INVALID, "aic_light_changed_take: bad argument");
-    Layer &l = c->layers[layer];
-    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_light_changed_take: no space uploaded for this layer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    { const int rc = light_job_finish(c); if (rc != AIC_OK) return rc; }
-    if (!l.lstate) l.lstate = new LightState();
-    LightState &S = *l.lstate;
-    { int rc = light_prepare(c, l, S); if (rc != AIC_OK) return rc; }
-    std::vector<uint32_t> list;
-    S.changed_list(&list);
-    if (list.size() > capacity) return fail(c, AIC_ERR_INVALID, "aic_light_changed_take: capacity is below the count (aic_light_changed_count)");
-    for (size_t k = 0; k < list.size(); k++) {
-        const I3h q = S.geom.cube_of(list[k]);
-        xyz[3 * k] = q[0]; xyz[3 * k + 1] = q[1]; xyz[3 * k + 2] = q[2];
-    }
-    *n_written = (uint32_t)list.size();
-    // the baseline becomes the current volume
-    if (S.cand_all) S.baseline = S.light;
-    else for (uint32_t i : S.cand) S.baseline[i] = S.light[i];
-    S.cand_clear();
-    return AIC_OK;
-}
-
-int aic_probe_derived(aic_ctx *c, int layer, float *out, uint8_t *out_opaque) {
-    if (!c || !valid_layer(layer) || !out || !out_opaque) return fail(c, AIC_ERR_INVALID, "aic_probe_derived: bad argument");
-    Layer &l = c->layers[layer];
-    if (!l.present) return fail(c, AIC_ERR_INVALID, "aic_probe_derived: no space uploaded for this layer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    { int qrc = quiesce(c); if (qrc != AIC_OK) return qrc; }
-    if (!l.lstate) l.lstate = new LightState();
-    { int rc = light_prepare(c, l, *l.lstate); if (rc != AIC_OK) return rc; }
-    const std::vector<DevDerived> &dv = l.lstate->derived;
-    for (size_t i = 0; i < dv.size(); i++) {
-        float *o = out + 32 * i;
-        for (int k = 0; k < 4; k++) o[k] = dv[i].color[k];
-        for (int f = 0; f < 6; f++) for (int k = 0; k < 4; k++) o[4 + 4 * f + k] = dv[i].face[f][k];
-        for (int k = 0; k < 3; k++) o[28 + k] = dv[i].emission[k];
-        o[31] = (dv[i].flags & kDerivedVisible) ? 1.f : 0.f;
-        for (int f = 0; f < 6; f++) out_opaque[6 * i + (size_t)f] = (uint8_t)((dv[i].flags >> f) & 1u);
-    }
-    return AIC_OK;
-}
-
-int aic_probe_log2f(aic_ctx *c, const float *x, uint32_t n, float *out) {
-    if (!c || !x || !out) return fail(c, AIC_ERR_INVALID, "aic_probe_log2f: bad argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipError_t e = c->staging.ensure((size_t)n * 8 + 64);
-    if (e != hipSuccess) return hip_fail(c, "alloc staging", e);
-    float *dx = (float *)c->staging.p, *dout = dx + n;
-    HIP_TRY(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    launch_probe_log2f(dx, dout, n, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return AIC_OK;
-}
-
-}  // extern "C"

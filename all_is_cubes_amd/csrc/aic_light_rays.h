@@ -1,18 +1,13 @@
 // aic_light_rays.h -- the light-ray records of include/aic_hip.h's aic_light_rays: the kernarg of its kernels, their launchers
-// (aic_light_rays.hip), and what the context's side (aic_light_rays_host.cpp) takes from the light updater's host code (aic_light_host.cpp): the
-// effective tree of a maximum_distance and the derived properties of the layer's blocks. The kernarg is this file's own: aic_light.o does not change with it.
+// (aic_light_rays.hip). What the context's side (aic_light_rays_host.cpp) takes from the light updater's host code -- the effective tree of a
+// maximum_distance and the derived properties of the layer's blocks -- is declared in aic_light_host.h. The kernarg is this file's own: aic_light.o does
+// not change with it.
 #pragma once
-
-#include <vector>
 
 #include "aic_light.h"
 #include "aic_light_rays_lines.h"
 
-struct aic_ctx;
-
 namespace aic {
-
-struct Layer;
 
 // what a cube's walk leaves for the scan
 struct LightRayResult {
@@ -61,17 +56,5 @@ constexpr uint32_t kLightRaysBlock = 256;
 hipError_t launch_light_rays_walk(const LightRaysParams &p, uint32_t workgroups, hipStream_t stream);
 hipError_t launch_light_rays_scan(const LightRaysParams &p, hipStream_t stream);
 hipError_t launch_light_rays_emit(const LightRaysParams &p, hipStream_t stream);
-
-// aic_light_host.cpp
-struct LightRaysTree {
-    std::vector<DevTreePos> tree;
-    std::vector<float> child_w;
-    std::vector<uint2> child_ent;
-    uint32_t bound = 0;  // aic_light_rays_bound
-};
-void light_rays_tree(int maximum_distance, LightRaysTree *out);
-uint32_t light_rays_bound(int maximum_distance);
-// compute_derived of every block of the layer; the voxel and palette pools are read back on `stream` only if a block has voxels
-int light_rays_derived(aic_ctx *c, Layer &l, hipStream_t stream, std::vector<DevDerived> *out);
 
 }  // namespace aic

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "aic_ctx.h"
+#include "aic_light_host.h"
 #include "aic_light_rays.h"
 
 static_assert(sizeof(aic_light_cube_info) == 32 && sizeof(aic_light_ray) == 40 && sizeof(aic_line_vertex) == 28, "the records of aic_light_rays");

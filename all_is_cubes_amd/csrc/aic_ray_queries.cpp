@@ -13,6 +13,7 @@
 #include "aic_ctx.h"
 #include "aic_cursor_raycast.h"
 #include "aic_exposure.h"
+#include "aic_light_host.h"
 
 static_assert(sizeof(aic_cursor_desc) == 88 && sizeof(aic_cursor_hit) == 144 && sizeof(aic_cursor_hit) % 8 == 0, "aic_cursor_hit: 144 bytes, lists of it 8-byte aligned");
 

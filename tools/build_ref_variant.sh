@@ -33,7 +33,7 @@ if [ -f $C/aic_reproject.hip ]; then  # (revisions from the reprojection post-pr
   /opt/rocm/bin/hipcc $F -c $C/aic_reproject.hip -o $D/reproject.o &
   OBJS="$OBJS $D/reproject.o"
 fi
-for part in present_lines.hip cursor.cpp pick.hip split_ops.cpp; do  # (the later post-processes, the cursor's host code; from the Split operations' own translation unit on, aic_split_ops.cpp)
+for part in present_lines.hip cursor.cpp pick.hip split_ops.cpp light_chart.cpp light_derived.cpp light_entry.cpp; do  # (the later post-processes, the cursor's host code; from the Split operations' own translation unit on, aic_split_ops.cpp; from the light host code's division by subject on, the chart, compute_derived and the entry points)
   if [ -f $C/aic_$part ]; then
     /opt/rocm/bin/hipcc $F -x hip -c $C/aic_$part -o $D/${part%.*}.o &
     OBJS="$OBJS $D/${part%.*}.o"

@@ -38,7 +38,7 @@ for spec in "$@"; do
       OBJS="$OBJS variants/reproject_$name.o"
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -c $C/aic_reproject.hip -o variants/reproject_$name.o
     fi &&
-    for part in present_lines.hip cursor.cpp pick.hip split_ops.cpp; do  # (the later post-processes, the cursor's and the Split operations' host code; an AIC_PATCH tree of an older revision has none)
+    for part in present_lines.hip cursor.cpp pick.hip split_ops.cpp light_chart.cpp light_derived.cpp light_entry.cpp; do  # (the later post-processes, the cursor's and the Split operations' host code, the units split off aic_light_host.cpp; an AIC_PATCH tree of an older revision has none)
       if [ -f $C/aic_$part ]; then
         OBJS="$OBJS variants/${part%.*}_$name.o"
         /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $flags -x hip -c $C/aic_$part -o variants/${part%.*}_$name.o || exit 1

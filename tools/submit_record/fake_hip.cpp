@@ -18,6 +18,7 @@
 #include "aic_device.h"
 #include "aic_exposure.h"
 #include "aic_launch.h"
+#include "aic_light_host.h"
 #include "aic_light_rays.h"
 #include "aic_pick.h"
 #include "aic_present_lines.h"
@@ -223,8 +224,6 @@ struct aic_ctx;
 int (*fake_light_job_finish)(aic_ctx *) = nullptr;  // (record.h: a program that wants to see the call sets it; nobody else's record changes)
 namespace aic {
 
-struct LightState;
-struct Layer;
 void light_state_free(LightState *) {}
 void light_state_cubes_updated(LightState *, uint64_t, uint64_t, uint32_t, const int32_t *, const uint16_t *, const uint8_t *) {}
 int light_job_finish(aic_ctx *c) { return fake_light_job_finish ? fake_light_job_finish(c) : 0; }
